@@ -14,7 +14,16 @@ log-mel → encoder → cross-KV → 128-token greedy decode over one batch of `
 PCM already resident in HBM.
 
 Prints ONE JSON line (rank 0).  `value` = audio seconds transcribed per wall second by the whole
-job (the "× real time" figure of BASELINE.json, rtfx = 1/rtf with rtf = src/main.rs:1191).
+job (the "× real time" figure of BASELINE.json, rtfx = 1/rtf with rtf = src/main.rs:1191);
+`ms_per_step` = wall milliseconds of one timed step.
+
+A plain run sets up, warms up, times exactly K steps (no HIP events in them: the decode replays its
+hipGraph) and prints the line.  `--full` adds what the line carried before: the untimed identity
+checks, the profiled pass and the sampled kernel events of the timed steps (roofline, kernel
+groups), the side measurements (batch 1 / 64 / 256 / 1024, host-resident clips, the in-tolerance
+and fp8 precisions, strong scaling) and the CPU baseline.  `--dump-outputs DIR` writes the token
+rows of the last timed step as DIR/tokens.npy and DIR/n_tokens.npy (float32); the weights and
+clips are seeded, so the same arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -151,6 +160,16 @@ def init_group(rank: int, world: int, prefer_nccl: bool, local_rank: int):
     return dist, "gloo", err
 
 
+def dump_outputs(path: str, rows, width: int) -> None:
+    """--dump-outputs: the token rows the timed entry returned in its last step, as float32 (token ids < 2^24 are exact)."""
+    os.makedirs(path, exist_ok=True)
+    tok = np.full((len(rows), width), -1.0, np.float32)
+    for i, t in enumerate(rows):
+        tok[i, :len(t)] = t
+    np.save(os.path.join(path, "tokens.npy"), tok)
+    np.save(os.path.join(path, "n_tokens.npy"), np.asarray([len(t) for t in rows], np.float32))
+
+
 def self_launch(n: int) -> int:
     """One process per GPU: start n copies of this script as children with RANK / LOCAL_RANK /
     WORLD_SIZE / MASTER_* set, relay rank 0's stdout (the JSON line), return non-zero if any rank fails.
@@ -227,17 +246,24 @@ def main() -> None:
     ap.add_argument("--precision", default="bf16", choices=["bf16", "f32", "fp8", "f16x3"])
     ap.add_argument("--max-new-tokens", type=int, default=128)
     ap.add_argument("--seed", type=int, default=1234)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-batch1", action="store_true", help="skip the untimed side measurements: batch-1 latency, 64- / 256- / 1024-clip batches, host-resident clips, "
-                                                              "in-tolerance precisions, strong scaling (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the untimed identity checks, the profiled pass and the sampled kernel events of the "
+                         "timed steps (roofline, per-group figures), the side measurements and the CPU baseline.  Without it a run sets up, "
+                         "warms up, times --steps steps, writes --dump-outputs and prints the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32): tokens "
+                         "[clips][prompt + max_new_tokens] (-1 past a clip's end) and n_tokens [clips]; with more GPUs, every rank's clips in clip-id order")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-batch1", action="store_true", help="with --full: skip the untimed side measurements: batch-1 latency, 64- / 256- / 1024-clip batches, "
+                                                              "host-resident clips, in-tolerance precisions, strong scaling (profiling runs)")
     ap.add_argument("--no-row-check", action="store_true",
-                    help="skip the untimed one-clip / pipelined-vs-plain identity checks (profiling runs: their launches would dilute per-kernel averages)")
+                    help="with --full: skip the untimed one-clip / pipelined-vs-plain identity checks (profiling runs: their launches would dilute per-kernel averages)")
     ap.add_argument("--test-single-device", action="store_true",
                     help="rehearsal on a one-GPU box: every rank uses device 0 and the gather goes over gloo")
     ap.add_argument("--force-dist", action="store_true", help="initialise the process group even for world size 1")
     ap.add_argument("--graph-timed", action="store_true",
-                    help="experiment: no HIP events in the timed region (decode replays its hipGraph); roofline then comes from the profiled pass")
-    ap.add_argument("--profile-all", action="store_true", help="event-time every kernel group in the timed region")
+                    help="with --full: no HIP events in the timed region (decode replays its hipGraph, as in a run without --full); roofline then comes from the profiled pass")
+    ap.add_argument("--profile-all", action="store_true", help="with --full: event-time every kernel group in the timed region")
     ap.add_argument("--launch-check", action="store_true",
                     help="no GPU work: every rank joins a gloo group, gathers one dummy record and rank 0 prints what it saw "
                          "(CPU test of the launcher and the rendezvous)")
@@ -250,6 +276,8 @@ def main() -> None:
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         # plain `python bench.py --gpus N`: this process becomes the launcher.  It has not touched HIP (the
         # binding loads libwhisper_hip.so lazily) and never will: it starts one child per GPU and relays rank 0.
@@ -372,7 +400,7 @@ def main() -> None:
         res = list(pool.map(one, range(a.streams)))
         return [t for r in res for t in r]
 
-    # untimed: warmup + one fully profiled pass to find the dominant kernel group
+    # untimed: warmup (+ with --full: one fully profiled pass to find the dominant kernel group)
     toks = None
     for _ in range(max(1, a.warmup)):
         toks = run_step(prefetch=False)
@@ -380,7 +408,7 @@ def main() -> None:
     # parity of the timed entry (wh_transcribe_batch_device*, a full device batch) with a one-clip call on the same
     # context: rows 0 and 3 must be identical — a clip decodes the same alone or in a batch
     row_check = None
-    if rank == 0 and not a.no_row_check:
+    if rank == 0 and a.full and not a.no_row_check:
         step_no[0] = 0
         full = run_step(prefetch=False)                 # batch 0 again, unpipelined
         for r in (0, min(3, a.clips - 1)):
@@ -397,14 +425,17 @@ def main() -> None:
         row_check = "rows 0 and 3 of the device batch == one-clip calls on the same context" + (
             "; pipelined == plain call on both batches" if a.pipeline else "")
     step_no[0] = 0
+    breakdown = None
+    if a.full:
+        for cx in ctxs:
+            cx.profile_enable(True)
+        run_step(prefetch=False)
+        breakdown = {k: {"ms": sum(cx.profile_get()[k]["ms"] for cx in ctxs) / a.streams,
+                         "launches": sum(cx.profile_get()[k]["launches"] for cx in ctxs)} for k in wb.KG_NAMES}
+    # timed region: with --full only the dominant kernel (decoder cross-attention) is bracketed by HIP events; without it
+    # no events at all (the decode replays its hipGraph at every position after the prompt)
     for cx in ctxs:
-        cx.profile_enable(True)
-    run_step(prefetch=False)
-    breakdown = {k: {"ms": sum(cx.profile_get()[k]["ms"] for cx in ctxs) / a.streams,
-                     "launches": sum(cx.profile_get()[k]["launches"] for cx in ctxs)} for k in wb.KG_NAMES}
-    # timed region: only the dominant kernel (decoder cross-attention) is bracketed by HIP events
-    for cx in ctxs:
-        if a.graph_timed:
+        if a.graph_timed or not a.full:
             cx.profile_enable(False)
         elif a.profile_all:
             cx.profile_enable(True)
@@ -437,9 +468,10 @@ def main() -> None:
             tm = cx.timings()
             for k in stage:
                 stage[k] += tm[k] / a.streams
-            pg = cx.profile_get()["dec_cross_attn"]
-            live["ms"] += pg["ms"]
-            live["launches"] += pg["launches"]
+            if a.full:
+                pg = cx.profile_get()["dec_cross_attn"]
+                live["ms"] += pg["ms"]
+                live["launches"] += pg["launches"]
     barrier()
     elapsed = time.perf_counter() - t0
     cross_es_mode = ctxs[0].cross_mode == 1
@@ -453,14 +485,19 @@ def main() -> None:
         allrec = sharding.gather_records(dist, rec, dev_t)
         n_results = len(sharding.unpack_records(allrec))
         assert n_results == world * a.clips
+        rows = [t for _, t in sharding.unpack_records(allrec)]
     else:
         n_results = len(toks)
+        rows = toks
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, rows, len(prompt) + a.max_new_tokens)
     # (the untimed side measurements below — one GPU only: with more ranks the others would sit in the process group's teardown meanwhile —
     # run AFTER the timed region: run before it, the dominant kernel read 265 instead of 250 us per launch in the
     # timed steps)
+    side = a.full and not a.no_batch1
     # BASELINE configs[1] (batch = 1 clip on one GPU): per-clip end-to-end latency, untimed extra
     b1_ms = []
-    if rank == 0 and world == 1 and not a.no_batch1:
+    if rank == 0 and world == 1 and side:
         ctx1 = wb.Context(model, 1)
         for i in range(6):
             t1 = time.perf_counter()
@@ -470,7 +507,7 @@ def main() -> None:
         ctx1.close()
     # BASELINE configs[2] at its own 8-GPU shard size (512 clips / 8 = 64 per GPU) as ONE 64-clip batch: untimed extra
     b64 = None
-    if rank == 0 and world == 1 and not a.no_batch1 and a.clips >= 64 and a.clips != 64:
+    if rank == 0 and world == 1 and side and a.clips >= 64 and a.clips != 64:
         ctx64 = wb.Context(model, 64)
         t64 = []
         for i in range(4):
@@ -483,7 +520,7 @@ def main() -> None:
                "note": "BASELINE configs[2]'s 8-GPU shard (64 clips) as one batch on one GPU; p95 per clip = the batch time"}
     # the 256-clip device batch rounds 1 and 2 quoted as the headline, for round-to-round comparison: untimed extra
     b256 = None
-    if rank == 0 and world == 1 and not a.no_batch1 and a.clips > 256:
+    if rank == 0 and world == 1 and side and a.clips > 256:
         ctx256 = wb.Context(model, 256)
         t256 = []
         for i in range(4):
@@ -496,7 +533,7 @@ def main() -> None:
                 "note": "one 256-clip device batch per call (the per-step workload of the round-1/2 lines)"}
     # ... and the 1024-clip device batch of the round-2 / round-3 lines
     b1024 = None
-    if rank == 0 and world == 1 and not a.no_batch1 and a.clips > 1024:
+    if rank == 0 and world == 1 and side and a.clips > 1024:
         ctx1024 = wb.Context(model, 1024)
         t1024 = []
         for i in range(3):
@@ -511,7 +548,7 @@ def main() -> None:
     # ---- the same clips from page-locked HOST memory (the reference's end_to_end_s counts the load, src/main.rs:1190): wh_transcribe_batch_next
     # copies batch i + 1 to the device on a copy stream beside batch i's work, so a step pays what is left of its own copy
     host_res = None
-    if rank == 0 and world == 1 and not a.no_batch1 and not a.pipeline and a.streams == 1:
+    if rank == 0 and world == 1 and side and not a.pipeline and a.streams == 1:
         try:
             hbuf = hip.host_alloc((a.clips, 480000), np.float32)
             with ThreadPoolExecutor(max_workers=max(1, min(16, cpu_budget()))) as gen:
@@ -539,7 +576,7 @@ def main() -> None:
             host_res = {"error": f"{type(e).__name__}: {e}"}
     # ---- BASELINE configs[2]'s own reading of scaling: a FIXED job of 512 clips dealt to the ranks (strong scaling), beside the weak-scaling headline
     strong = None
-    if scaling == "weak" and not a.no_batch1 and not a.pipeline and (512 % world) == 0 and 512 // world <= a.clips:
+    if scaling == "weak" and side and not a.pipeline and (512 % world) == 0 and 512 // world <= a.clips:
         cs = 512 // world
         ctx_s = wb.Context(model, cs)
         ctx_s.transcribe_batch_device(d_pcm, cs, params)
@@ -559,7 +596,7 @@ def main() -> None:
     # BASELINE's bf16, which does not (tests/test_hip_parity.py bounds it at 0.16); these are measured in the same run, after the main context
     # has given its memory back
     in_tol = None
-    if rank == 0 and world == 1 and not a.no_batch1 and prec in (wb.WH_PREC_BF16, wb.WH_PREC_FP8) and a.preset == "base":
+    if rank == 0 and world == 1 and side and prec in (wb.WH_PREC_BF16, wb.WH_PREC_FP8) and a.preset == "base":
         try:
             for cx in ctxs:
                 cx.close()
@@ -597,7 +634,7 @@ def main() -> None:
             in_tol = {"error": f"{type(e).__name__}: {e}"}
     # ---- BASELINE configs[4]'s precision on the same clips, in the same run (bf16 headline only): e4m3 weights, MX activations, cross-attention on e4m3 encoder states
     fp8_side = None
-    if rank == 0 and world == 1 and not a.no_batch1 and prec == wb.WH_PREC_BF16 and a.preset == "base":
+    if rank == 0 and world == 1 and side and prec == wb.WH_PREC_BF16 and a.preset == "base":
         try:
             for cx in ctxs:
                 cx.close()
@@ -622,76 +659,8 @@ def main() -> None:
 
     if rank == 0:
         cross_es = cross_es_mode
-        # bytes per element of what the cross-attention streams: e4m3 (fp8 mode), fp16 + e4m3 remainder (split-fp16 mode on the encoder states, unless WH_ES3=0), else the compute dtype
-        es3 = cross_es and prec == wb.WH_PREC_F16X3 and os.environ.get("WH_ES3", "1") != "0"
-        work = algorithmic_work(dims, per_stream, len(prompt), a.max_new_tokens, 1 if prec == wb.WH_PREC_FP8 else 3 if es3 else esz, cross_es)
         audio_s = 30.0 * a.clips * a.steps * world
         ms_per_step = elapsed / a.steps * 1e3
-        # Roofline of the dominant kernel (the decoder cross-attention: largest single-kernel share in every rocprofv3 --stats
-        # summary under profiles/).  `achieved` = the algorithmic bytes of one launch — the encoder states of every clip of the launch
-        # once (k_dec_cross_attn_es*), or K and V of one decoder layer (k_dec_cross_attn*) — ÷ the average launch duration
-        # measured with HIP events on the launch stream over the TIMED region.
-        tot_ms = sum(v["ms"] for v in breakdown.values())
-        if a.graph_timed:
-            live = {"ms": breakdown["dec_cross_attn"]["ms"] * a.streams, "launches": breakdown["dec_cross_attn"]["launches"]}
-        avg_s = live["ms"] * 1e-3 / max(1, live["launches"])
-        ach = work["cross_attn_bytes_per_launch"] / avg_s / 1e9
-        traffic = None
-        traffic_stamp = None
-        # the dominant kernel's variants: e4m3 cache (fp8 mode), one workgroup per 256-column group (wide models), all heads per workgroup
-        dom_kernel = ("k_dec_cross_attn_es3" if es3 else "k_dec_cross_attn_es2" if (cross_es and prec == wb.WH_PREC_F16X3) else "k_dec_cross_attn_es8" if (cross_es and prec == wb.WH_PREC_FP8) else
-                      "k_dec_cross_attn_es" if cross_es else "k_dec_cross_attn8" if prec == wb.WH_PREC_FP8 else
-                      "k_dec_cross_attn_cg" if (prec == wb.WH_PREC_BF16 and dims.d_model > 512 and dims.d_model % 256 == 0) else "k_dec_cross_attn")
-        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tpath):   # HBM bytes per launch from rocprofv3 --pmc passes (see profiles/README.md)
-            tj = json.load(open(tpath))
-            key = f"{a.preset}_{a.precision}_b{per_stream}"
-            traffic = tj.get(dom_kernel, {}).get(key)
-            traffic_stamp = tj.get("_collected_at", {}).get(key)
-        roofline = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                    "traffic": traffic, "traffic_source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, profiles/pmc_traffic.json (profiles/collect.sh); "
-                                                          "NOT measured in this run — counters of the build named in traffic_collected_at",
-                    "traffic_collected_at": traffic_stamp,
-                    "kernel": dom_kernel, "avg_launch_us": avg_s * 1e6,
-                    "launches_timed": live["launches"], "alg_bytes_per_launch": work["cross_attn_bytes_per_launch"],
-                    "streams": ("the encoder states [clips][1500][d] once per launch (cross-attention on the encoder states; the projected K + V "
-                                "form of the same attention reads twice these bytes)" if cross_es else "K and V of one decoder layer for every clip of the launch"),
-                    "share_of_kernel_time": breakdown["dec_cross_attn"]["ms"] / tot_ms}
-        d_, F_, T_, Le_ = dims.d_model, dims.ffn, dims.n_audio_ctx, dims.enc_layers
-        attn_flop = Le_ * 2 * 2 * T_ * T_ * d_ * a.clips
-        gemm_flop = work["enc_flop_per_clip"] * a.clips - attn_flop
-        # TFLOP/s dense bf16 / fp16; exact-f32 MFMA is 1/16 of it; the split-fp16 mode spends three fp16 MFMAs per product
-        mfma_peak = {wb.WH_PREC_F32: 2500.0 / 16.0, wb.WH_PREC_F16X3: 2500.0 / 3.0}.get(prec, 2500.0)
-
-        def sec(bound, work_units, ms, peak, unit, note):
-            ach = work_units / (ms * 1e-3) / (1e12 if unit == "TFLOP/s" else 1e9) if ms > 0 else 0.0
-            return {"bound": bound, "achieved": ach, "peak": peak, "unit": unit, "frac": ach / peak, "ms_per_step": ms, "note": note}
-        secondary = {
-            "enc_attn": sec("mfma", attn_flop, breakdown["enc_attn"]["ms"], mfma_peak, "TFLOP/s",
-                            "k_enc_attn; VALU-bound below the MFMA roof (one v_exp_f32 per 256 MFMA flops at head_dim 64)"),
-            "enc_gemm": sec("mfma", gemm_flop, breakdown["enc_gemm"]["ms"], mfma_peak, "TFLOP/s",
-                            "k_gemm8 / k_gemm8_mx (Conv1d-as-GEMM, QK, V^T, out-proj, fc1, fc2); the group's time also holds the 13 encoder LayerNorm launches"),
-            "mel": sec("hbm", work["mel_bytes_per_clip"] * a.clips, breakdown["mel"]["ms"], HBM_PEAK_GBS, "GB/s",
-                       "k_mel_stft (mixed-radix FFT in LDS + f32-MFMA filterbank) + k_mel_tokens; latency-bound per 16-frame workgroup"),
-        }
-        # rocprof-reported MFMA utilisation of the same configuration (profiles/collect_mfma.sh: SQ_VALU_MFMA_BUSY_CYCLES over
-        # GRBM_GUI_ACTIVE, i.e. matrix-pipe busy cycles over the SIMD cycles that actually elapsed — the shader clock under
-        # these kernels is 2.0-2.2 GHz, not the 2.4 GHz behind the 2.5 PFLOP/s peak; a calibration loop of nothing but MFMAs
-        # reads 0.91-0.98 at 1.9-2.0 GHz, profiles/r02_mfma_util_calibration.txt)
-        upath = os.path.join(ROOT, "profiles", "mfma_util.json")
-        if os.path.exists(upath):
-            ujall = json.load(open(upath))
-            ukey = f"{a.preset}_{a.precision}_b{per_stream}"
-            uj = ujall.get(ukey, {})
-            ustamp = ujall.get("_collected_at", {}).get(ukey)
-            def grp(prefixes):
-                ks = [k for k in uj if k.startswith(prefixes) and uj[k].get("shader_clock_GHz")]
-                busy = sum(uj[k]["mfma_util"] * uj[k]["total_ms_under_pmc"] * uj[k]["shader_clock_GHz"] for k in ks)
-                cyc = sum(uj[k]["total_ms_under_pmc"] * uj[k]["shader_clock_GHz"] for k in ks)
-                return {"mfma_util": busy / cyc, "kernels": {k: uj[k]["mfma_util"] for k in ks},
-                        "collected_at": ustamp, "note": "counter pass of the build named in collected_at, not of this run"} if cyc > 0 else None
-            secondary["enc_attn"]["rocprof"] = grp(("k_enc_attn",))
-            secondary["enc_gemm"]["rocprof"] = grp(("k_gemm8", "k_gemm<"))
         out = {
             "metric": f"rtfx: audio seconds transcribed per wall second (whisper-{a.preset}, 30 s clips, greedy {a.max_new_tokens} new tokens)",
             "value": audio_s / elapsed, "unit": "x real time", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -711,31 +680,104 @@ def main() -> None:
             "rtf": elapsed / audio_s,   # reference definition: latency / duration (src/main.rs:1191)
             "clips_per_s": a.clips * a.steps * world / elapsed,
             "p95_ms_per_clip": float(np.percentile(np.asarray(lat) * 1e3, 95)),  # every clip of a batch completes with its batch
-            "batch1": ({"p95_ms_per_clip": float(np.percentile(b1_ms, 95)), "median_ms_per_clip": float(np.median(b1_ms)),
-                        "rtfx": 30e3 / float(np.median(b1_ms)), "note": "BASELINE configs[1]: one clip per call on one GPU"}
-                       if b1_ms else None),
-            "batch64": b64,
-            "batch256": b256,
-            "batch1024": b1024,
-            "host_resident": host_res,
             "workspace_placement": placement,
-            "in_tolerance": in_tol,
-            "fp8": fp8_side,
             "scaling_weak": {"clips_per_gpu": a.clips, "total_clips_per_step": a.clips * world, "ms_per_step": ms_per_step, "value": audio_s / elapsed} if scaling == "weak" else None,
-            "scaling_strong": strong if scaling == "weak" else {"total_clips_per_step": a.clips * world, "clips_per_gpu": a.clips, "ms_per_step": ms_per_step, "value": audio_s / elapsed},
+            "scaling_strong": None if scaling == "weak" else {"total_clips_per_step": a.clips * world, "clips_per_gpu": a.clips, "ms_per_step": ms_per_step, "value": audio_s / elapsed},
             "stage_ms_per_step": {k: v / a.steps * 1e3 for k, v in stage.items()},
-            "kernel_group_ms_per_step": {k: round(v["ms"], 3) for k, v in breakdown.items()},
-            "kernel_group_launches": {k: v["launches"] for k, v in breakdown.items()},
-            "kernel_time_frac_of_step": tot_ms / ms_per_step,
-            "roofline": roofline,
-            # the other kernel groups against their own roofs (event-timed in the untimed profiled pass; SURVEY §8d:
-            # MFMA utilisation of the encoder attention / GEMMs, HBM rate of the log-mel path)
-            "secondary_rooflines": secondary,
         }
-        if world == 1 and not a.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(dims, a.seed, prompt, eot, a.max_new_tokens)
-            out["cpu_baseline"]["note"] = ("the reference's Rust/ONNX Runtime binary cannot be built or run here (no Rust, "
-                                           "no ORT, no network); published: 14.03 s model time for 12 windows on 4 EPYC-9654 cores")
+        if a.full:
+            # bytes per element of what the cross-attention streams: e4m3 (fp8 mode), fp16 + e4m3 remainder (split-fp16 mode on the encoder states, unless WH_ES3=0), else the compute dtype
+            es3 = cross_es and prec == wb.WH_PREC_F16X3 and os.environ.get("WH_ES3", "1") != "0"
+            work = algorithmic_work(dims, per_stream, len(prompt), a.max_new_tokens, 1 if prec == wb.WH_PREC_FP8 else 3 if es3 else esz, cross_es)
+            # Roofline of the dominant kernel (the decoder cross-attention: largest single-kernel share in every rocprofv3 --stats
+            # summary under profiles/).  `achieved` = the algorithmic bytes of one launch — the encoder states of every clip of the launch
+            # once (k_dec_cross_attn_es*), or K and V of one decoder layer (k_dec_cross_attn*) — ÷ the average launch duration
+            # measured with HIP events on the launch stream over the TIMED region.
+            tot_ms = sum(v["ms"] for v in breakdown.values())
+            if a.graph_timed:
+                live = {"ms": breakdown["dec_cross_attn"]["ms"] * a.streams, "launches": breakdown["dec_cross_attn"]["launches"]}
+            avg_s = live["ms"] * 1e-3 / max(1, live["launches"])
+            ach = work["cross_attn_bytes_per_launch"] / avg_s / 1e9
+            traffic = None
+            traffic_stamp = None
+            # the dominant kernel's variants: e4m3 cache (fp8 mode), one workgroup per 256-column group (wide models), all heads per workgroup
+            dom_kernel = ("k_dec_cross_attn_es3" if es3 else "k_dec_cross_attn_es2" if (cross_es and prec == wb.WH_PREC_F16X3) else "k_dec_cross_attn_es8" if (cross_es and prec == wb.WH_PREC_FP8) else
+                          "k_dec_cross_attn_es" if cross_es else "k_dec_cross_attn8" if prec == wb.WH_PREC_FP8 else
+                          "k_dec_cross_attn_cg" if (prec == wb.WH_PREC_BF16 and dims.d_model > 512 and dims.d_model % 256 == 0) else "k_dec_cross_attn")
+            tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(tpath):   # HBM bytes per launch from rocprofv3 --pmc passes (see profiles/README.md)
+                tj = json.load(open(tpath))
+                key = f"{a.preset}_{a.precision}_b{per_stream}"
+                traffic = tj.get(dom_kernel, {}).get(key)
+                traffic_stamp = tj.get("_collected_at", {}).get(key)
+            roofline = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                        "traffic": traffic, "traffic_source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, profiles/pmc_traffic.json (profiles/collect.sh); "
+                                                              "NOT measured in this run — counters of the build named in traffic_collected_at",
+                        "traffic_collected_at": traffic_stamp,
+                        "kernel": dom_kernel, "avg_launch_us": avg_s * 1e6,
+                        "launches_timed": live["launches"], "alg_bytes_per_launch": work["cross_attn_bytes_per_launch"],
+                        "streams": ("the encoder states [clips][1500][d] once per launch (cross-attention on the encoder states; the projected K + V "
+                                    "form of the same attention reads twice these bytes)" if cross_es else "K and V of one decoder layer for every clip of the launch"),
+                        "share_of_kernel_time": breakdown["dec_cross_attn"]["ms"] / tot_ms}
+            d_, F_, T_, Le_ = dims.d_model, dims.ffn, dims.n_audio_ctx, dims.enc_layers
+            attn_flop = Le_ * 2 * 2 * T_ * T_ * d_ * a.clips
+            gemm_flop = work["enc_flop_per_clip"] * a.clips - attn_flop
+            # TFLOP/s dense bf16 / fp16; exact-f32 MFMA is 1/16 of it; the split-fp16 mode spends three fp16 MFMAs per product
+            mfma_peak = {wb.WH_PREC_F32: 2500.0 / 16.0, wb.WH_PREC_F16X3: 2500.0 / 3.0}.get(prec, 2500.0)
+
+            def sec(bound, work_units, ms, peak, unit, note):
+                ach = work_units / (ms * 1e-3) / (1e12 if unit == "TFLOP/s" else 1e9) if ms > 0 else 0.0
+                return {"bound": bound, "achieved": ach, "peak": peak, "unit": unit, "frac": ach / peak, "ms_per_step": ms, "note": note}
+            secondary = {
+                "enc_attn": sec("mfma", attn_flop, breakdown["enc_attn"]["ms"], mfma_peak, "TFLOP/s",
+                                "k_enc_attn; VALU-bound below the MFMA roof (one v_exp_f32 per 256 MFMA flops at head_dim 64)"),
+                "enc_gemm": sec("mfma", gemm_flop, breakdown["enc_gemm"]["ms"], mfma_peak, "TFLOP/s",
+                                "k_gemm8 / k_gemm8_mx (Conv1d-as-GEMM, QK, V^T, out-proj, fc1, fc2); the group's time also holds the 13 encoder LayerNorm launches"),
+                "mel": sec("hbm", work["mel_bytes_per_clip"] * a.clips, breakdown["mel"]["ms"], HBM_PEAK_GBS, "GB/s",
+                           "k_mel_stft (mixed-radix FFT in LDS + f32-MFMA filterbank) + k_mel_tokens; latency-bound per 16-frame workgroup"),
+            }
+            # rocprof-reported MFMA utilisation of the same configuration (profiles/collect_mfma.sh: SQ_VALU_MFMA_BUSY_CYCLES over
+            # GRBM_GUI_ACTIVE, i.e. matrix-pipe busy cycles over the SIMD cycles that actually elapsed — the shader clock under
+            # these kernels is 2.0-2.2 GHz, not the 2.4 GHz behind the 2.5 PFLOP/s peak; a calibration loop of nothing but MFMAs
+            # reads 0.91-0.98 at 1.9-2.0 GHz, profiles/r02_mfma_util_calibration.txt)
+            upath = os.path.join(ROOT, "profiles", "mfma_util.json")
+            if os.path.exists(upath):
+                ujall = json.load(open(upath))
+                ukey = f"{a.preset}_{a.precision}_b{per_stream}"
+                uj = ujall.get(ukey, {})
+                ustamp = ujall.get("_collected_at", {}).get(ukey)
+                def grp(prefixes):
+                    ks = [k for k in uj if k.startswith(prefixes) and uj[k].get("shader_clock_GHz")]
+                    busy = sum(uj[k]["mfma_util"] * uj[k]["total_ms_under_pmc"] * uj[k]["shader_clock_GHz"] for k in ks)
+                    cyc = sum(uj[k]["total_ms_under_pmc"] * uj[k]["shader_clock_GHz"] for k in ks)
+                    return {"mfma_util": busy / cyc, "kernels": {k: uj[k]["mfma_util"] for k in ks},
+                            "collected_at": ustamp, "note": "counter pass of the build named in collected_at, not of this run"} if cyc > 0 else None
+                secondary["enc_attn"]["rocprof"] = grp(("k_enc_attn",))
+                secondary["enc_gemm"]["rocprof"] = grp(("k_gemm8", "k_gemm<"))
+            out.update({
+                "batch1": ({"p95_ms_per_clip": float(np.percentile(b1_ms, 95)), "median_ms_per_clip": float(np.median(b1_ms)),
+                            "rtfx": 30e3 / float(np.median(b1_ms)), "note": "BASELINE configs[1]: one clip per call on one GPU"}
+                           if b1_ms else None),
+                "batch64": b64,
+                "batch256": b256,
+                "batch1024": b1024,
+                "host_resident": host_res,
+                "in_tolerance": in_tol,
+                "fp8": fp8_side,
+                "kernel_group_ms_per_step": {k: round(v["ms"], 3) for k, v in breakdown.items()},
+                "kernel_group_launches": {k: v["launches"] for k, v in breakdown.items()},
+                "kernel_time_frac_of_step": tot_ms / ms_per_step,
+                "roofline": roofline,
+                # the other kernel groups against their own roofs (event-timed in the untimed profiled pass; SURVEY §8d:
+                # MFMA utilisation of the encoder attention / GEMMs, HBM rate of the log-mel path)
+                "secondary_rooflines": secondary,
+            })
+            if scaling == "weak":
+                out["scaling_strong"] = strong
+            if world == 1 and not a.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(dims, a.seed, prompt, eot, a.max_new_tokens)
+                out["cpu_baseline"]["note"] = ("the reference's Rust/ONNX Runtime binary cannot be built or run here (no Rust, "
+                                               "no ORT, no network); published: 14.03 s model time for 12 windows on 4 EPYC-9654 cores")
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -17,7 +17,7 @@ export DEBUG_CLR_GRAPH_PACKET_CAPTURE=0
 # flight) or restricted to one kernel (profiles/README.md, round-3 triage).  The switch changes no kernel, only when the host waits.
 [ "$PRESET" = "large-v3" ] && export WH_SYNC_EVERY_POS=1
 export WH_COLLECT_STAMP="${WH_COLLECT_STAMP:-$(cat $R/profiles/.stamp 2>/dev/null || echo unstamped)}"
-ARGS="$R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-batch1 --no-row-check --graph-timed --precision $PREC --clips $CLIPS --preset $PRESET"
+ARGS="$R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-batch1 --no-row-check --graph-timed --precision $PREC --clips $CLIPS --preset $PRESET"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 $ARGS > "$OUT/trace.log" 2>&1
 python3 $R/profiles/summarize_kernel_stats.py "$(ls $OUT/trace/*/*kernel_stats.csv | head -1)" 4 > "$OUT/kernel_stats.txt"
 cp "$(ls $OUT/trace/*/*kernel_stats.csv | head -1)" "$OUT/kernel_stats.csv"
