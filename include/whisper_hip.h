@@ -162,6 +162,26 @@ int wh_ctx_cross_mode(const wh_ctx* c);
  * kernel's launch time depends on where the workspace lies).  Returns the number of workspaces timed (0: step not taken; WH_PLACE=0 disables it), and the
  * microseconds per launch on the first and on the kept workspace.  No counterpart in the reference (ONNX Runtime owns its arena). */
 int wh_ctx_placement(const wh_ctx* c, float* first_us, float* kept_us);
+/* Whisper's timestamp rules in the greedy token loop (openai-whisper's ApplyTimestampRules; HF generate(return_timestamps=True)).
+ * No reference entry corresponds: the reference has the --timestamps flag (src/main.rs:852-855: <|notimestamps|> left out of the
+ * prompt) but keeps plain argmax.  With rules set, every decode entry of the ctx (wh_decode_greedy*, wh_transcribe_batch*, the device /
+ * pipelined entries, wh_transcribe_longform) applies, after the suppress masks and at every generated position:
+ *   1. no_timestamps is suppressed;
+ *   2. after two timestamps in a row no timestamp, after a single one no id below eot;
+ *   3. no timestamp below the last one emitted (below it + 1 unless the last token is a single timestamp);
+ *   4. the first generated token is a timestamp, at most timestamp_begin + max_initial_timestamp_index (< 0: no bound);
+ *   5. if the log-sum-exp of the allowed timestamp logits exceeds the largest allowed text logit, only timestamps remain;
+ *   6. the argmax of what remains (ties to the lowest id, NaN never wins, nothing left: 0).
+ * The history is the row's fed tokens (with wh_decode_params.forced: the forced ones).  Logits are the same as without rules.
+ * Refused with WH_ERR_ARG (the ctx unchanged): a wrong struct_size; at decode time a timestamp_begin outside (eot, vocab) or a prompt
+ * that holds no_timestamps.  r == NULL turns the rules off (the default). */
+typedef struct {
+    size_t struct_size;                  /* sizeof(wh_timestamp_rules) */
+    int64_t timestamp_begin;             /* id of <|0.00|>; ids >= it are timestamps, 0.02 s apart */
+    int64_t no_timestamps;               /* <|notimestamps|>, suppressed at every step; -1: none */
+    int32_t max_initial_timestamp_index; /* 50 = 1.0 s; < 0: unbounded */
+} wh_timestamp_rules;
+int wh_ctx_set_timestamp_rules(wh_ctx* c, const wh_timestamp_rules* r);
 const char* wh_last_error(const wh_ctx* c); /* c == NULL: last load/create error of this thread */
 int wh_get_timings(const wh_ctx* c, wh_timing* out);
 

@@ -34,7 +34,7 @@ EXPORTS = ("wh_model_load", "wh_model_create", "wh_model_free", "wh_model_get_di
            "wh_mel_frames", "wh_log_mel", "wh_encode", "wh_decode_greedy", "wh_decode_greedy_batch", "wh_decode_greedy_rows", "wh_transcribe_batch",
            "wh_transcribe_batch_next", "wh_transcribe_batch_device", "wh_transcribe_batch_device_next", "wh_longform_plan", "wh_transcribe_longform", "wh_profile_enable",
            "wh_profile_get", "wh_synthetic_weights", "wh_e4m3_quantize", "wh_e4m3_dequantize", "wh_abi_version",
-           "wh_device_count")
+           "wh_device_count", "wh_ctx_set_timestamp_rules")
 
 
 class WhisperHipError(RuntimeError):
@@ -67,6 +67,11 @@ class WhCtxOpts(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("max_batch", C.c_int), ("flags", C.c_int),
                 ("enc_cu_mask", C.POINTER(C.c_uint32)), ("enc_cu_mask_words", C.c_size_t),
                 ("dec_cu_mask", C.POINTER(C.c_uint32)), ("dec_cu_mask_words", C.c_size_t)]
+
+
+class WhTimestampRules(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("timestamp_begin", C.c_int64), ("no_timestamps", C.c_int64),
+                ("max_initial_timestamp_index", C.c_int32)]
 
 
 WH_CTX_TWO_STREAMS = 1
@@ -136,6 +141,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.wh_e4m3_quantize.restype = None
     L.wh_e4m3_dequantize.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, f32p]
     L.wh_e4m3_dequantize.restype = None
+    L.wh_ctx_set_timestamp_rules.argtypes = [vp, C.POINTER(WhTimestampRules)]
     _lib = L
     return L
 
@@ -263,6 +269,15 @@ class Context:
         a, b = C.c_float(0), C.c_float(0)
         n = int(self.lib.wh_ctx_placement(self.h, C.byref(a), C.byref(b)))
         return {"workspaces_timed": n, "first_us_per_launch": float(a.value), "kept_us_per_launch": float(b.value)}
+
+    def set_timestamp_rules(self, tb: int, no_timestamps: int = -1, max_initial_index: int = 50):
+        """wh_ctx_set_timestamp_rules: Whisper's timestamp rules on every decode entry of this context (tb = id of <|0.00|>;
+        no_timestamps = <|notimestamps|>, suppressed at every step, -1: none; max_initial_index < 0: no bound on the first timestamp)."""
+        r = WhTimestampRules(C.sizeof(WhTimestampRules), tb, no_timestamps, max_initial_index)
+        self._check(self.lib.wh_ctx_set_timestamp_rules(self.h, C.byref(r)))
+
+    def clear_timestamp_rules(self):
+        self._check(self.lib.wh_ctx_set_timestamp_rules(self.h, None))
 
     # --- the reference's three functions -----------------------------------------------------
     def whisper_log_mel(self, audio_16k: np.ndarray) -> np.ndarray:
@@ -520,3 +535,70 @@ class HipRuntime:
 
     def sync(self):
         self.check(self.lib.hipDeviceSynchronize(), "hipDeviceSynchronize")
+
+
+# ---- timestamped segments (host library libwh_host.so: wh_host.h split_segments / merge_window_segments / SRT / VTT) -------------------
+HOST_LIB_PATH = os.path.join(HERE, "libwh_host.so")
+_host: Optional[C.CDLL] = None
+
+
+def load_host_library(path: str = HOST_LIB_PATH) -> C.CDLL:
+    global _host
+    if _host is None:
+        L = C.CDLL(path)
+        ll = C.POINTER(C.c_longlong)
+        L.whh_segments_json.argtypes = [ll, C.c_size_t, C.c_longlong, C.c_longlong, C.c_double, C.c_char_p, C.c_size_t]
+        L.whh_longform_segments_json.argtypes = [ll, C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
+                                                 C.c_longlong, C.c_longlong, C.c_char_p, C.c_size_t]
+        for f in (L.whh_srt, L.whh_vtt):
+            f.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
+        for f in (L.whh_segments_json, L.whh_longform_segments_json, L.whh_srt, L.whh_vtt):
+            f.restype = C.c_size_t
+        _host = L
+    return _host
+
+
+def _host_string(call) -> str:
+    n = call(None, 0)
+    buf = C.create_string_buffer(n + 1)
+    call(buf, n + 1)
+    return buf.value.decode()
+
+
+def split_segments(generated: Sequence[int], tb: int, eot: int, duration: float) -> List[dict]:
+    """One window's generated tokens -> [{start, end, tokens}] (openai-whisper's slicing rule; tokens = the segment's text ids)."""
+    import json
+    t = np.ascontiguousarray(list(generated), np.int64)
+    L = load_host_library()
+    return json.loads(_host_string(lambda o, c: L.whh_segments_json(t.ctypes.data_as(C.POINTER(C.c_longlong)), t.size, tb, eot, duration, o, c)))
+
+
+def longform_segments(windows: Sequence[Sequence[int]], starts: Sequence[float], durations: Sequence[float], overlap_s: float, tb: int,
+                      eot: int) -> List[dict]:
+    """Long-form: each window's segments shifted by its start; in the overlap of windows k and k+1 a segment belongs to k if it starts
+    before start(k+1) + overlap_s / 2."""
+    import json
+    t = np.ascontiguousarray([x for w in windows for x in w] or [0], np.int64)
+    lens = (C.c_size_t * max(1, len(windows)))(*[len(w) for w in windows])
+    st = (C.c_double * max(1, len(windows)))(*starts)
+    du = (C.c_double * max(1, len(windows)))(*durations)
+    L = load_host_library()
+    return json.loads(_host_string(lambda o, c: L.whh_longform_segments_json(t.ctypes.data_as(C.POINTER(C.c_longlong)), lens, len(windows), st, du,
+                                                                             overlap_s, tb, eot, o, c)))
+
+
+def _cue_call(fn, cues):
+    st = (C.c_double * max(1, len(cues)))(*[c[0] for c in cues])
+    en = (C.c_double * max(1, len(cues)))(*[c[1] for c in cues])
+    texts = b"".join(c[2].encode() + b"\0" for c in cues) + b"\0"
+    return _host_string(lambda o, cap: fn(st, en, texts, len(cues), o, cap))
+
+
+def srt(cues: Sequence[Tuple[float, float, str]]) -> str:
+    """SubRip text of (start, end, text) cues: 1-based numbers, HH:MM:SS,mmm."""
+    return _cue_call(load_host_library().whh_srt, cues)
+
+
+def vtt(cues: Sequence[Tuple[float, float, str]]) -> str:
+    """WebVTT text of (start, end, text) cues: WEBVTT header, 1-based numbers, HH:MM:SS.mmm."""
+    return _cue_call(load_host_library().whh_vtt, cues)

@@ -308,6 +308,12 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
         if (p->prompt[i] < 0 || p->prompt[i] >= D.vocab) return fail(c, WH_ERR_ARG, "decode: prompt id %lld outside the vocabulary", (long long)p->prompt[i]);
     for (size_t i = 0; i < p->n_forced; i++)
         if (p->forced[i] < 0 || p->forced[i] >= D.vocab) return fail(c, WH_ERR_ARG, "decode: forced id outside the vocabulary");
+    if (c->ts_on) {   // timestamp rules: <|0.00|> must lie above EOT (so EOT and the specials are text ids) and inside the vocabulary
+        if (c->ts_begin <= p->eot || c->ts_begin >= D.vocab)
+            return fail(c, WH_ERR_ARG, "decode: timestamp_begin %lld outside (eot %lld, vocab %d)", (long long)c->ts_begin, (long long)p->eot, D.vocab);
+        for (int i = 0; i < P; i++)
+            if (c->ts_no_ts >= 0 && p->prompt[i] == c->ts_no_ts) return fail(c, WH_ERR_ARG, "decode: the prompt holds <|notimestamps|> while timestamp rules are on");
+    }
 
     // the encoder states come from the encoder stream
     if (c->s_enc != s) CTX_HIP(c, hipStreamWaitEvent(s, c->ev_enc_done, 0));
@@ -330,6 +336,10 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
     std::vector<unsigned> mfirst, mbase;
     pack_mask(p->suppress, p->n_suppress, p->begin_suppress, p->n_begin_suppress, D.vocab, mfirst);  // :765-768
     pack_mask(p->suppress, p->n_suppress, nullptr, 0, D.vocab, mbase);
+    if (c->ts_on && c->ts_no_ts >= 0 && c->ts_no_ts < D.vocab) {   // timestamp rule 1: <|notimestamps|> at every step
+        mfirst[c->ts_no_ts >> 5] |= 1u << (c->ts_no_ts & 31);
+        mbase[c->ts_no_ts >> 5] |= 1u << (c->ts_no_ts & 31);
+    }
     CTX_HIP(c, hipMemcpyAsync(c->mask_first, mfirst.data(), mfirst.size() * 4, hipMemcpyHostToDevice, s));
     CTX_HIP(c, hipMemcpyAsync(c->mask_base, mbase.data(), mbase.size() * 4, hipMemcpyHostToDevice, s));
     CTX_HIP(c, hipStreamSynchronize(s));  // host vectors above go out of scope
@@ -534,6 +544,10 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
                 a.X = c->dxs; a.x_mpad = mpad;
                 a.pos_p = c->pos; a.n_prompt = P; a.mask_first = c->mask_first; a.mask_base = c->mask_base;
                 a.logits = d_logits; a.logits_rows = (int)logits_rows; a.logits_sel = d_sel; a.part_val = c->part_val; a.part_idx = c->part_idx;
+                if (c->ts_on) {
+                    a.ts_state = c->ts_state; a.ts_logits = c->ts_logits; a.ts_ld = c->ts_ld;
+                    a.ts_begin = (int)c->ts_begin; a.ts_max_init = c->ts_max_init;
+                }
                 wh_launch_lm_head(s, prec, a);
                 lm_parts = wh_lm_head_parts(prec, a);
             }
@@ -542,7 +556,12 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
                 NextEmbed ne;
                 ne.tok_emb = m->tok_emb; ne.pos_emb = m->dec_pos; ne.x = c->dx; ne.xslab = c->dxs; ne.stats = c->lnpart;
                 ne.xgamma = f8 ? m->dec[0].ln1_w : nullptr; ne.d = (int)d; ne.mpad = mpad; ne.shift = c->dshift;
-                wh_launch_argmax_finish(s, prec, c->part_val, c->part_idx, lm_parts, mpad, c->pos, c->step_ticket, st, nb, ne);
+                TsFinish tf;
+                if (c->ts_on) {
+                    tf.rules = true; tf.ts_logits = c->ts_logits; tf.ts_ld = c->ts_ld; tf.state = c->ts_state;
+                    tf.ts_begin = (int)c->ts_begin; tf.vocab = D.vocab;
+                }
+                wh_launch_argmax_finish(s, prec, c->part_val, c->part_idx, lm_parts, mpad, c->pos, c->step_ticket, st, nb, ne, tf);
             }
         }
     };
@@ -561,6 +580,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
         wh_ctx::StepKey key;
         key.nb = nb; key.n_prompt = P; key.eot = (int)p->eot; key.n_forced = (int)p->n_forced;
         key.logits_rows = (int)logits_rows; key.d_logits = d_logits; key.d_sel = d_sel;
+        if (c->ts_on) { key.ts_begin = (int)c->ts_begin; key.ts_max_init = c->ts_max_init; }
         if (!c->step_exec || !(c->step_key == key)) {
             drop_step_graph(c);   // nothing of it is in flight: every call ends with a stream synchronisation
             c->capturing = true;  // no event records inside the captured step
@@ -1055,6 +1075,44 @@ int wh_ctx_placement(const wh_ctx* c, float* first_us, float* kept_us) {
     return c->place_tries;
 }
 
+// Whisper's timestamp rules on every decode entry of the ctx.  The buffers — the rows' timestamp logits and a per-row state —
+// are allocated when rules are turned on (the logits again for another timestamp_begin); the captured decode step is recaptured when the
+// key changes (and before a buffer it holds is freed).
+int wh_ctx_set_timestamp_rules(wh_ctx* c, const wh_timestamp_rules* r) {
+    if (!c) return WH_ERR_ARG;
+    if (!r) {
+        c->ts_on = false;
+        return WH_OK;
+    }
+    if (r->struct_size != sizeof(wh_timestamp_rules)) return fail(c, WH_ERR_ARG, "wh_ctx_set_timestamp_rules: struct_size %zu, expected %zu", r->struct_size, sizeof(wh_timestamp_rules));
+    const int vocab = c->m->dims.vocab;
+    if (r->timestamp_begin <= 0 || r->timestamp_begin >= vocab)
+        return fail(c, WH_ERR_ARG, "wh_ctx_set_timestamp_rules: timestamp_begin %lld outside the vocabulary (%d)", (long long)r->timestamp_begin, vocab);
+    if (r->no_timestamps >= vocab || r->no_timestamps < -1)
+        return fail(c, WH_ERR_ARG, "wh_ctx_set_timestamp_rules: no_timestamps %lld outside the vocabulary", (long long)r->no_timestamps);
+    const int ld = vocab - (int)r->timestamp_begin;
+    if (!c->ts_logits || c->ts_ld != ld) {
+        hipSetDevice(c->m->device);
+        float* tl = nullptr; int* st = c->ts_state;
+        hipError_t e = hipMalloc((void**)&tl, (size_t)c->mpad * ld * 4);
+        if (e == hipSuccess && !st) e = hipMalloc((void**)&st, (size_t)c->mpad * 16);
+        if (e != hipSuccess) {
+            if (tl) hipFree(tl);
+            if (st && st != c->ts_state) hipFree(st);
+            return fail(c, WH_ERR_NOMEM, "wh_ctx_set_timestamp_rules: hipMalloc: %s", hipGetErrorString(e));
+        }
+        drop_step_graph(c);   // (a captured step may hold the old buffer's address)
+        if (c->ts_logits) hipFree(c->ts_logits);
+        c->ts_logits = tl; c->ts_ld = ld; c->ts_state = st;
+    }
+    c->ts_on = true;
+    c->ts_begin = r->timestamp_begin;
+    c->ts_no_ts = r->no_timestamps;
+    // (a bound past the vocabulary is no bound: clamped to the last timestamp, so tb + max_init never overflows in the kernels)
+    c->ts_max_init = r->max_initial_timestamp_index < 0 ? -1 : std::min<int>(r->max_initial_timestamp_index, vocab - 1 - (int)r->timestamp_begin);
+    return WH_OK;
+}
+
 void wh_ctx_free(wh_ctx* c) {
     if (!c) return;
     hipSetDevice(c->m->device);
@@ -1077,6 +1135,8 @@ void wh_ctx_free(wh_ctx* c) {
     if (c->raw_long) hipFree(c->raw_long);
     if (c->mel_out_long) hipFree(c->mel_out_long);
     if (c->logits) hipFree(c->logits);
+    if (c->ts_logits) hipFree(c->ts_logits);
+    if (c->ts_state) hipFree(c->ts_state);
     if (c->s_copy) { hipStreamSynchronize(c->s_copy); hipStreamDestroy(c->s_copy); }
     if (c->ev_h2d) hipEventDestroy(c->ev_h2d);
     if (c->pcm2) hipFree(c->pcm2);

@@ -339,6 +339,46 @@ __device__ __forceinline__ float wh_sub(float a, float b) {
     return a - b;
 }
 
+// ---- Whisper's timestamp rules in the LM head's epilogue (the RULES variants) --------------------------------------------
+// Row m of a position may emit text in [text_lo, tb) and timestamps in [ts_lo, ts_hi].  At the first generated position (gen == 0) the ranges
+// are rule 4's; later ones come from the row state k_argmax_finish<T, true> wrote ({text_lo, ts_lo, ts_hi, last timestamp} per row).
+__device__ __forceinline__ void ts_ranges(const int* state, int m, int gen, int tb, int max_init, int N, int& text_lo, int& ts_lo, int& ts_hi) {
+    if (gen == 0) {
+        text_lo = tb;
+        ts_lo = tb;
+        ts_hi = (max_init >= 0 && max_init < N - 1 - tb) ? tb + max_init : N - 1;   // (no tb + max_init overflow)
+    } else {
+        text_lo = state[4 * m];
+        ts_lo = state[4 * m + 1];
+        ts_hi = state[4 * m + 2];
+    }
+}
+// exp(x) for x <= 0 as one v_exp_f32 (2^(x log2 e)): relative error ~1e-6 over the range that matters to a log-sum-exp
+__device__ __forceinline__ float ts_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
+// online (max, sum of exp(v - max), index of the max) over the allowed timestamp logits, columns ascending: strict >, so the lowest index keeps
+// a tie; NaN is neither the max nor part of the sum
+__device__ __forceinline__ void ts_acc(float v, int n, float& tm, float& ts, int& ti) {
+    if (v > tm) { ts = ts * ts_exp(tm - v) + 1.0f; tm = v; ti = n; }
+    else if (v > -INFINITY) ts += ts_exp(v - tm);
+}
+__device__ __forceinline__ void ts_merge(float& tm, float& ts, int& ti, float m1, float s1, int i1) {
+    const float mx = fmaxf(tm, m1);
+    const float s = mx == -INFINITY ? 0.0f : ts * ts_exp(tm - mx) + s1 * ts_exp(m1 - mx);
+    if (m1 > tm || (m1 == tm && i1 < ti)) ti = i1;
+    tm = mx;
+    ts = s;
+}
+// one logit of the rules epilogue: the text argmax below tb inside [text_lo, tb); a timestamp goes to the row's timestamp logits, -inf where
+// suppressed or outside [ts_lo, ts_hi] (k_argmax_finish<T, true> reduces them: one predicated store here instead of an online sum of exp,
+// which spilled k_lm_head_tile's accumulators)
+__device__ __forceinline__ void ts_take(float v, int n, bool sup, int tb, int text_lo, int ts_lo, int ts_hi, float& bv, int& bi, float* ts_row) {
+    if (n < tb) {
+        if (!sup && n >= text_lo && v > bv) { bv = v; bi = n; }
+    } else {
+        ts_row[n - tb] = (!sup && n >= ts_lo && n <= ts_hi) ? v : -INFINITY;
+    }
+}
+
 #define WH_HIP_CHECK(expr)                                                                      \
     do {                                                                                        \
         hipError_t _e = (expr);                                                                 \

@@ -563,7 +563,9 @@ __global__ __launch_bounds__(NW * 64, 2) void k_dec_gemm_wide(SkinnyArgs a) {
 // partials per 16-column tile (reference argmax_last_dim_raw, src/main.rs:709-735).  The [M][K]
 // activation tile is staged in LDS once per workgroup; each wave then walks 16-row tiles of the
 // embedding matrix with all of a tile's weight fragments in flight before its first MFMA.
-template <typename T, int MT>
+// RULES: Whisper's timestamp rules (SkinnyArgs::ts_*): the masked argmax covers the allowed text ids only, the timestamp logits go to
+// SkinnyArgs::ts_logits for k_argmax_finish<T, true>; the logits are the same expression (the rules-off instantiations are unchanged).
+template <typename T, int MT, bool RULES = false>
 __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
     extern __shared__ __attribute__((aligned(128))) char smem_raw[];   // 128: h2 tiles find their 32-blocks from the address
     constexpr int EPC = 16 / (int)sizeof(T);
@@ -636,6 +638,16 @@ __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
     int biw[MT];
 #pragma unroll
     for (int t = 0; t < MT; t++) { bvw[t] = -INFINITY; biw[t] = 0x7fffffff; }
+    // RULES: the allowed ranges of each of this lane's rows
+    int tlo[MT], slo[MT], shi[MT];
+    if constexpr (RULES) {
+#pragma unroll
+        for (int t = 0; t < MT; t++) {
+            const int m = m0 + t * 16 + fl;
+            tlo[t] = a.ts_begin; slo[t] = a.N; shi[t] = 0;
+            if (m < a.M) ts_ranges(a.ts_state, m, gen, a.ts_begin, a.ts_max_init, a.N, tlo[t], slo[t], shi[t]);
+        }
+    }
     auto load_unit = [&](frag_t (&wq)[DEPTH], int u) {
         const int tile = first + (u / nchunk) * stride, c0 = (u % nchunk) * DEPTH;
         int nrow = tile * 16 + fl;
@@ -685,7 +697,10 @@ __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
                         if (slot >= 0) a.logits[((long)slot * a.logits_rows + gen) * a.N + nn] = v;
                     }
                     const bool sup = (mbits >> e) & 1u;
-                    if (!sup && v > bvw[t]) { bvw[t] = v; biw[t] = nn; }  // strict >, NaN never wins
+                    if constexpr (RULES) {
+                        if (tile * 16 + 16 <= a.ts_begin) { if (!sup && nn >= tlo[t] && v > bvw[t]) { bvw[t] = v; biw[t] = nn; } }   // text-only tile
+                        else ts_take(v, nn, sup, a.ts_begin, tlo[t], slo[t], shi[t], bvw[t], biw[t], a.ts_logits + (long)m * a.ts_ld);
+                    } else if (!sup && v > bvw[t]) { bvw[t] = v; biw[t] = nn; }  // strict >, NaN never wins
                 }
             }
         }
@@ -738,10 +753,13 @@ __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
 
 // Final reduce of the per-tile argmax partials + greedy bookkeeping for one clip per workgroup:
 // records the generated token, EOT stop (src/main.rs:781-783, 820-822) and the next input token.
-template <typename T>
+// RULES (ts.rules): the text partials of k_lm_head*<RULES> are merged as above; the row's allowed timestamp logits (ts.ts_logits) are reduced
+// to their (max, index, sum of exp); step 5 of the timestamp rules picks between the two (timestamps only when the log-sum-exp of the allowed
+// timestamps exceeds the best allowed text logit), and the next position's allowed ranges are written from the token fed next.
+template <typename T, bool RULES = false>
 __global__ __launch_bounds__(256) void k_argmax_finish(const float* __restrict__ part_val,
                                                        const int* __restrict__ part_idx, int n_tiles, int mpad, int* pos_p,
-                                                       int* ticket, DecodeState st, NextEmbed ne) {
+                                                       int* ticket, DecodeState st, NextEmbed ne, TsFinish ts) {
     __shared__ float sv[256];
     __shared__ int si[256];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -763,18 +781,49 @@ __global__ __launch_bounds__(256) void k_argmax_finish(const float* __restrict__
             if (v[u] > bv || (v[u] == bv && ix[u] < bi)) { bv = v[u]; bi = ix[u]; }
     }
     sv[tid] = bv; si[tid] = bi;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) {
-            float ov = sv[tid + s]; int oi = si[tid + s];
-            if (ov > sv[tid] || (ov == sv[tid] && oi < si[tid])) { sv[tid] = ov; si[tid] = oi; }
-        }
+    int rule_tok = 0;
+    if constexpr (RULES) {
+        __shared__ float stm[256], sts[256];
+        __shared__ int sti[256];
+        float tm = -INFINITY, tsum = 0.0f;
+        int ti = 0x7fffffff;
+        const float* tr = ts.ts_logits + (long)b * ts.ts_ld;
+        for (int i = tid; i < ts.ts_ld; i += 256) ts_acc(tr[i], ts.ts_begin + i, tm, tsum, ti);   // (each thread's columns ascend)
+        stm[tid] = tm; sts[tid] = tsum; sti[tid] = ti;
         __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (tid < s) {
+                float ov = sv[tid + s]; int oi = si[tid + s];
+                if (ov > sv[tid] || (ov == sv[tid] && oi < si[tid])) { sv[tid] = ov; si[tid] = oi; }
+                float m1 = stm[tid], s1 = sts[tid];
+                int i1 = sti[tid];
+                ts_merge(m1, s1, i1, stm[tid + s], sts[tid + s], sti[tid + s]);
+                stm[tid] = m1; sts[tid] = s1; sti[tid] = i1;
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            const float text_v = sv[0], ts_v = stm[0];
+            const float lse = ts_v == -INFINITY ? -INFINITY : ts_v + logf(sts[0]);
+            int w;
+            if (lse > text_v) w = sti[0];                                          // step 5: every id below tb is suppressed
+            else w = (ts_v > text_v || (ts_v == text_v && sti[0] < si[0])) ? sti[0] : si[0];   // step 6 over both
+            rule_tok = (w == 0x7fffffff) ? 0 : w;
+        }
+    } else {
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (tid < s) {
+                float ov = sv[tid + s]; int oi = si[tid + s];
+                if (ov > sv[tid] || (ov == sv[tid] && oi < si[tid])) { sv[tid] = ov; si[tid] = oi; }
+            }
+            __syncthreads();
+        }
     }
     if (tid == 0) {
         const int gen = pos - (st.n_prompt - 1);
         // nothing beat -inf (all suppressed / NaN / -inf): the reference's best_i stays 0
-        const int tok = (si[0] == 0x7fffffff) ? 0 : si[0];
+        const int tok = RULES ? rule_tok : (si[0] == 0x7fffffff) ? 0 : si[0];
         int next = tok;
         if (!st.done[b]) {
             st.out_tokens[b * st.tok_ld + st.n_prompt + gen] = tok;
@@ -784,6 +833,21 @@ __global__ __launch_bounds__(256) void k_argmax_finish(const float* __restrict__
             else if (tok == st.eot) st.done[b] = 1;
         }
         if (pos + 1 < st.tok_ld) st.feed[b * st.tok_ld + pos + 1] = next;
+        if constexpr (RULES) {
+            // the next position's ranges from the history it sees (seq = the fed tokens, `next` its last one): rules 2 and 3
+            const int tb = ts.ts_begin;
+            const bool last_ts = next >= tb;
+            const bool pen_ts = gen == 0 || st.feed[b * st.tok_ld + pos] >= tb;   // (the token fed at this position is seq[-2])
+            const int last_t = last_ts ? next : (gen == 0 ? -1 : ts.state[4 * b + 3]);
+            int text_lo = 0, ts_lo = tb;
+            if (last_ts && pen_ts) ts_lo = ts.vocab;          // after a pair: no timestamp
+            else if (last_ts) text_lo = st.eot;               // after a single one: no text id below EOT
+            if (last_t >= 0 && ts_lo < ts.vocab) ts_lo = max(ts_lo, (last_ts && !pen_ts) ? last_t : last_t + 1);
+            ts.state[4 * b] = text_lo;
+            ts.state[4 * b + 1] = ts_lo;
+            ts.state[4 * b + 2] = ts.vocab - 1;
+            ts.state[4 * b + 3] = last_t;
+        }
         si[0] = next;
     }
     if (ne.tok_emb) {
@@ -1365,7 +1429,7 @@ void wh_launch_dec_embed(hipStream_t s, int prec, const void* tok_emb, const flo
         hipLaunchKernelGGL(k_dec_embed<bf16>, grid, dim3(256), 0, s, (const bf16*)tok_emb, pos_emb, feed, feed_ld, pos_p, x, (bf16*)xslab, stats, rows, d, mpad, xgamma, shift);
 }
 
-template <typename T>
+template <typename T, bool RULES = false>
 void launch_lm_head_t(hipStream_t s, const SkinnyArgs& a, int* n_parts_out = nullptr) {
     const int n_tiles = (a.N + 15) / 16;
     int mt = std::min(wh_dbg_lm_mt, (a.M + 15) / 16);
@@ -1380,7 +1444,7 @@ void launch_lm_head_t(hipStream_t s, const SkinnyArgs& a, int* n_parts_out = nul
     if (n_parts_out) { *n_parts_out = (int)grid.x * 4; return; }  // query only: partials per row = waves per row group
 #define WH_LM(MT_)                                                \
     {                                                             \
-        auto kfn = k_lm_head<T, MT_>;                             \
+        auto kfn = k_lm_head<T, MT_, RULES>;                      \
         set_max_smem(kfn, sm);                                    \
         hipLaunchKernelGGL(kfn, grid, dim3(256), sm, s, a);       \
     }
@@ -1394,10 +1458,17 @@ void launch_lm_head_t(hipStream_t s, const SkinnyArgs& a, int* n_parts_out = nul
 }
 
 // a.X = final-LayerNorm'ed rows [M][K] in the compute dtype
+// a.ts_logits != nullptr: the timestamp-rules variants (same logits, same partial count)
 void wh_launch_lm_head(hipStream_t s, int prec, const SkinnyArgs& a) {
-    if (prec == WH_PREC_F32) launch_lm_head_t<float>(s, a);
-    else if (prec == WH_PREC_F16X3) { if (wh_lm_head_tile_x3_applicable(a)) wh_launch_lm_head_tile_x3(s, a); else launch_lm_head_t<h2>(s, a); }
+    const bool r = a.ts_logits != nullptr;
+    if (prec == WH_PREC_F32) { if (r) launch_lm_head_t<float, true>(s, a); else launch_lm_head_t<float>(s, a); }
+    else if (prec == WH_PREC_F16X3) {
+        if (wh_lm_head_tile_x3_applicable(a)) wh_launch_lm_head_tile_x3(s, a);
+        else if (r) launch_lm_head_t<h2, true>(s, a);
+        else launch_lm_head_t<h2>(s, a);
+    }
     else if (wh_lm_head_tile_applicable(a)) wh_launch_lm_head_tile(s, a);   // hundreds of rows: 256 x 256 tiles (wh_gemm8.hip), same logits
+    else if (r) launch_lm_head_t<bf16, true>(s, a);
     else launch_lm_head_t<bf16>(s, a);
 }
 
@@ -1411,11 +1482,18 @@ int wh_lm_head_parts(int prec, const SkinnyArgs& a) {
     return n;
 }
 
+template <bool RULES>
+void launch_argmax_finish_t(hipStream_t s, int prec, const float* part_val, const int* part_idx, int n_parts, int mpad, int* pos_p,
+                            int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts) {
+    if (prec == WH_PREC_F16X3) hipLaunchKernelGGL((k_argmax_finish<h2, RULES>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts);
+    else if (prec == WH_PREC_F32) hipLaunchKernelGGL((k_argmax_finish<float, RULES>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts);
+    else hipLaunchKernelGGL((k_argmax_finish<bf16, RULES>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts);
+}
+
 void wh_launch_argmax_finish(hipStream_t s, int prec, const float* part_val, const int* part_idx, int n_parts, int mpad, int* pos_p,
-                             int* ticket, const DecodeState& st, int B, const NextEmbed& ne) {
-    if (prec == WH_PREC_F16X3) hipLaunchKernelGGL(k_argmax_finish<h2>, dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne);
-    else if (prec == WH_PREC_F32) hipLaunchKernelGGL(k_argmax_finish<float>, dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne);
-    else hipLaunchKernelGGL(k_argmax_finish<bf16>, dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne);
+                             int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts) {
+    if (ts.rules) launch_argmax_finish_t<true>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts);
+    else launch_argmax_finish_t<false>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts);
 }
 
 void wh_launch_dec_self_attn(hipStream_t s, int prec, const void* qkv, void* kc, void* vc, void* out, const int* pos_p,

@@ -417,6 +417,8 @@ __global__ __launch_bounds__(512, Geo<BN>::WAVES_PER_SIMD) void k_gemm8(GemmArgs
 // Bit-identical logits: the same MFMA chain over k as k_lm_head (weights as the row operand, k ascending, one accumulator),
 // LayerNorm partial sums reduced in the same order, the same epilogue expression — so the launcher may pick by the call's
 // row count (tests/test_hip_parity.py::test_wide_batch_decode_gemm_is_bit_identical runs both).
+// RULES: Whisper's timestamp rules in the epilogue (k_lm_head<T, MT, true>'s contract: text partials, timestamp logits to SkinnyArgs::ts_logits).
+template <bool RULES = false>
 __global__ __launch_bounds__(512, 2) void k_lm_head_tile(SkinnyArgs a) {
     typedef Geo<256> G;
     constexpr int BN = 256, TM = G::TM, TN = G::TN, NSLOT = G::NSLOT, SLOT = G::SLOT, SLOT_A = G::SLOT_A;
@@ -439,6 +441,7 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile(SkinnyArgs a) {
     // before the ring, so they are the oldest vector-memory requests
     float* lnstat = reinterpret_cast<float*>(smem + (size_t)NSLOT * SLOT);   // [256][2] mean, rstd
     float* lnq = lnstat + 2 * BM;                                            // [4][256][2]
+    int* tsr = reinterpret_cast<int*>(lnq + 4 * BM * 2);                     // RULES: [256][4] the rows' allowed ranges (written after the main loop)
     if (a.ln_part) {
         const int r = tid & (BM - 1), h = tid >> 8, row = min(m0 + r, a.x_mpad - 1);
         float s1a, s2a, s1b, s2b;
@@ -448,6 +451,15 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile(SkinnyArgs a) {
         lnq[(h * BM + r) * 2 + 1] = s2a;
         lnq[((h + 2) * BM + r) * 2] = s1b;
         lnq[((h + 2) * BM + r) * 2 + 1] = s2b;
+    }
+    // RULES: the rows' state, requested behind the LayerNorm partials without waiting on the position (gen 0 ignores it); it turns into
+    // the allowed ranges in LDS after the main loop, so the epilogue reads them from LDS instead of eight dependent global loads
+    int ts_raw[3] = {0, 0, 0};
+    if constexpr (RULES) {
+        if (tid < BM) {
+            const int* r = a.ts_state + 4 * min(m0 + tid, a.M - 1);
+            ts_raw[0] = r[0]; ts_raw[1] = r[1]; ts_raw[2] = r[2];
+        }
     }
 
     const int rl = lane >> 2, ps = lane & 3;
@@ -530,6 +542,14 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile(SkinnyArgs a) {
             }
         }
     }
+    if constexpr (RULES) {
+        if (tid < BM) {
+            int lo = ts_raw[0], slo = ts_raw[1], shi = ts_raw[2];
+            const int gen0 = *a.pos_p - (a.n_prompt - 1);
+            if (gen0 == 0) ts_ranges(nullptr, 0, 0, a.ts_begin, a.ts_max_init, a.N, lo, slo, shi);   // rule 4
+            tsr[4 * tid] = lo; tsr[4 * tid + 1] = slo; tsr[4 * tid + 2] = shi;
+        }
+    }
     __syncthreads();   // lnstat written by the first 256 threads is visible to everyone (and every MFMA has its operands)
 
     // ---- epilogue: final LayerNorm fold + masked argmax, one partial per (wave, row) ------------------------------------
@@ -560,6 +580,10 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile(SkinnyArgs a) {
         const float mean = a.ln_part ? lnstat[2 * rloc] : 0.0f, rstd = a.ln_part ? lnstat[2 * rloc + 1] : 1.0f;
         float bv = -INFINITY;
         int bi = 0x7fffffff;
+        int tlo = a.ts_begin, slo = a.N, shi = 0;
+        if constexpr (RULES) {
+            if (m < a.M) { tlo = tsr[4 * rloc]; slo = tsr[4 * rloc + 1]; shi = tsr[4 * rloc + 2]; }
+        }
 #pragma unroll
         for (int j = 0; j < TN; j++) {
             const int n = nw0 + j * 16 + 4 * fg;
@@ -573,7 +597,10 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile(SkinnyArgs a) {
                         if (slot >= 0) a.logits[((long)slot * a.logits_rows + gen) * a.N + nn] = v;
                     }
                     const bool sup = (mbits[j] >> e) & 1u;
-                    if (!sup && v > bv) { bv = v; bi = nn; }  // strict >, columns ascending: lowest index on ties, NaN never wins
+                    if constexpr (RULES) {
+                        if (nw0 + j * 16 + 16 <= a.ts_begin) { if (!sup && nn >= tlo && v > bv) { bv = v; bi = nn; } }   // text-only column group
+                        else ts_take(v, nn, sup, a.ts_begin, tlo, slo, shi, bv, bi, a.ts_logits + (long)m * a.ts_ld);
+                    } else if (!sup && v > bv) { bv = v; bi = nn; }  // strict >, columns ascending: lowest index on ties, NaN never wins
                 }
             }
         }
@@ -664,10 +691,15 @@ bool wh_lm_head_tile_applicable(const SkinnyArgs& a) {
 int wh_lm_head_tile_parts(const SkinnyArgs& a) { return (a.N + 255) / 256; }
 void wh_launch_lm_head_tile(hipStream_t s, const SkinnyArgs& a) {
     typedef Geo<256> G;
-    const size_t sm = (size_t)G::NSLOT * G::SLOT + (size_t)BM * 2 * 4 * 5;   // ring + LayerNorm statistics ([256][2] + four quarter sums)
+    const size_t sm = (size_t)G::NSLOT * G::SLOT + (size_t)BM * 2 * 4 * 5 + (a.ts_logits ? (size_t)BM * 16 : 0);   // ring + LayerNorm statistics ([256][2] + four quarter sums) + RULES: the rows' ranges ([256][4])
     dim3 grid(((a.N + 255) / 256) * ((a.M + BM - 1) / BM));
-    wh_ensure_dyn_lds((const void*)k_lm_head_tile, sm);
-    hipLaunchKernelGGL(k_lm_head_tile, grid, dim3(512), sm, s, a);
+    if (a.ts_logits) {   // the timestamp-rules variant
+        wh_ensure_dyn_lds((const void*)k_lm_head_tile<true>, sm);
+        hipLaunchKernelGGL(k_lm_head_tile<true>, grid, dim3(512), sm, s, a);
+        return;
+    }
+    wh_ensure_dyn_lds((const void*)k_lm_head_tile<false>, sm);
+    hipLaunchKernelGGL(k_lm_head_tile<false>, grid, dim3(512), sm, s, a);
 }
 
 void wh_launch_ln_stats(hipStream_t s, const float* partials, int groups, long rows, int d, float* stat, float* shift, const float* shift_in) {

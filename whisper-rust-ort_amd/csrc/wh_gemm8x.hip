@@ -226,6 +226,8 @@ __global__ __launch_bounds__(512, 2) void k_gemm8x(GemmArgs g) {
 // consecutive 128-byte blocks), the tied embedding with the final LayerNorm's gamma folded in is the weight operand.  Same MFMA chain over k
 // as k_lm_head<h2> (three fp16 MFMAs per k-step in mma16's order, one accumulator), LayerNorm partial sums reduced in the same order, the
 // same epilogue expression: logits bit-identical, so the launcher may pick by the call's row count.
+// RULES: Whisper's timestamp rules in the epilogue (k_lm_head<T, MT, true>'s contract: text partials, timestamp logits to SkinnyArgs::ts_logits).
+template <bool RULES = false>
 __global__ __launch_bounds__(512, 2) void k_lm_head_tile_x3(SkinnyArgs a) {
     extern __shared__ __attribute__((aligned(128))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -245,6 +247,7 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile_x3(SkinnyArgs a) {
     // final LayerNorm: quarter sums of the producer's per-tile partials, two quarters per thread (row tid & 255)
     float* lnstat = reinterpret_cast<float*>(smem + (size_t)NSLOT * SLOT);   // [256][2] mean, rstd
     float* lnq = lnstat + 2 * BM;                                            // [4][256][2]
+    int* tsr = reinterpret_cast<int*>(lnq + 4 * BM * 2);                     // RULES: [256][4] the rows' allowed ranges (written after the main loop)
     if (a.ln_part) {
         const int r = tid & (BM - 1), h = tid >> 8, row = min(m0 + r, a.x_mpad - 1);
         float s1a, s2a, s1b, s2b;
@@ -254,6 +257,15 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile_x3(SkinnyArgs a) {
         lnq[(h * BM + r) * 2 + 1] = s2a;
         lnq[((h + 2) * BM + r) * 2] = s1b;
         lnq[((h + 2) * BM + r) * 2 + 1] = s2b;
+    }
+    // RULES: the rows' state, requested behind the LayerNorm partials without waiting on the position (gen 0 ignores it); it turns into
+    // the allowed ranges in LDS after the main loop, so the epilogue reads them from LDS instead of eight dependent global loads
+    int ts_raw[3] = {0, 0, 0};
+    if constexpr (RULES) {
+        if (tid < BM) {
+            const int* r = a.ts_state + 4 * min(m0 + tid, a.M - 1);
+            ts_raw[0] = r[0]; ts_raw[1] = r[1]; ts_raw[2] = r[2];
+        }
     }
 
     const int rl = lane >> 3, ps = lane & 7;
@@ -329,6 +341,14 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile_x3(SkinnyArgs a) {
             }
         }
     }
+    if constexpr (RULES) {
+        if (tid < BM) {
+            int lo = ts_raw[0], slo = ts_raw[1], shi = ts_raw[2];
+            const int gen0 = *a.pos_p - (a.n_prompt - 1);
+            if (gen0 == 0) ts_ranges(nullptr, 0, 0, a.ts_begin, a.ts_max_init, a.N, lo, slo, shi);   // rule 4
+            tsr[4 * tid] = lo; tsr[4 * tid + 1] = slo; tsr[4 * tid + 2] = shi;
+        }
+    }
     __syncthreads();   // lnstat visible to everyone; the ring is idle
 
     // ---- epilogue: final LayerNorm fold + masked argmax, one partial per (column tile, row) ----------------------------------------------
@@ -359,6 +379,10 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile_x3(SkinnyArgs a) {
         const float mean = a.ln_part ? lnstat[2 * rloc] : 0.0f, rstd = a.ln_part ? lnstat[2 * rloc + 1] : 1.0f;
         float bv = -INFINITY;
         int bi = 0x7fffffff;
+        int tlo = a.ts_begin, slo = a.N, shi = 0;
+        if constexpr (RULES) {
+            if (m < a.M) { tlo = tsr[4 * rloc]; slo = tsr[4 * rloc + 1]; shi = tsr[4 * rloc + 2]; }
+        }
 #pragma unroll
         for (int j = 0; j < TN; j++) {
             const int n = nw0 + j * 16 + 4 * fg;
@@ -372,7 +396,10 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile_x3(SkinnyArgs a) {
                         if (slot >= 0) a.logits[((long)slot * a.logits_rows + gen) * a.N + nn] = v;
                     }
                     const bool sup = (mbits[j] >> e) & 1u;
-                    if (!sup && v > bv) { bv = v; bi = nn; }  // strict >, columns ascending: lowest index on ties, NaN never wins
+                    if constexpr (RULES) {
+                        if (nw0 + j * 16 + 16 <= a.ts_begin) { if (!sup && nn >= tlo && v > bv) { bv = v; bi = nn; } }   // text-only column group
+                        else ts_take(v, nn, sup, a.ts_begin, tlo, slo, shi, bv, bi, a.ts_logits + (long)m * a.ts_ld);
+                    } else if (!sup && v > bv) { bv = v; bi = nn; }  // strict >, columns ascending: lowest index on ties, NaN never wins
                 }
             }
         }
@@ -450,8 +477,13 @@ bool wh_lm_head_tile_x3_applicable(const SkinnyArgs& a) {
 }
 int wh_lm_head_tile_x3_parts(const SkinnyArgs& a) { return (a.N + BN - 1) / BN; }
 void wh_launch_lm_head_tile_x3(hipStream_t s, const SkinnyArgs& a) {
-    const size_t sm = (size_t)NSLOT * SLOT + (size_t)BM * 2 * 4 * 5;   // ring + LayerNorm statistics ([256][2] + four quarter sums)
+    const size_t sm = (size_t)NSLOT * SLOT + (size_t)BM * 2 * 4 * 5 + (a.ts_logits ? (size_t)BM * 16 : 0);   // ring + LayerNorm statistics ([256][2] + four quarter sums) + RULES: the rows' ranges ([256][4])
     dim3 grid(((a.N + BN - 1) / BN) * ((a.M + BM - 1) / BM));
-    wh_ensure_dyn_lds((const void*)k_lm_head_tile_x3, sm);
-    hipLaunchKernelGGL(k_lm_head_tile_x3, grid, dim3(512), sm, s, a);
+    if (a.ts_logits) {   // the timestamp-rules variant
+        wh_ensure_dyn_lds((const void*)k_lm_head_tile_x3<true>, sm);
+        hipLaunchKernelGGL(k_lm_head_tile_x3<true>, grid, dim3(512), sm, s, a);
+        return;
+    }
+    wh_ensure_dyn_lds((const void*)k_lm_head_tile_x3<false>, sm);
+    hipLaunchKernelGGL(k_lm_head_tile_x3<false>, grid, dim3(512), sm, s, a);
 }

@@ -204,11 +204,20 @@ struct wh_ctx {
         int nb = 0, n_prompt = 0, eot = 0, n_forced = 0, logits_rows = 0;
         const float* d_logits = nullptr;
         const int* d_sel = nullptr;
+        int ts_begin = -1, ts_max_init = -1;   // timestamp rules: -1 = off (other kernels, other arguments)
         bool operator==(const StepKey& o) const {
             return nb == o.nb && n_prompt == o.n_prompt && eot == o.eot && n_forced == o.n_forced && logits_rows == o.logits_rows &&
-                   d_logits == o.d_logits && d_sel == o.d_sel;
+                   d_logits == o.d_logits && d_sel == o.d_sel && ts_begin == o.ts_begin && ts_max_init == o.ts_max_init;
         }
     } step_key;
+    // Whisper's timestamp rules (wh_ctx_set_timestamp_rules): off unless ts_on.  The timestamp logits and the per-row state
+    // are allocated when rules are set (not part of the workspace carve; the logits again when timestamp_begin changes) and freed in wh_ctx_free.
+    bool ts_on = false;
+    int64_t ts_begin = 0, ts_no_ts = -1;
+    int ts_max_init = 50;
+    float* ts_logits = nullptr; // [mpad][ts_ld] allowed timestamp logits of the current position (-inf: not allowed)
+    int ts_ld = 0;              // vocab - timestamp_begin
+    int* ts_state = nullptr;    // [mpad][4] {text_lo, ts_lo, ts_hi, last timestamp}
     hipGraph_t step_graph = nullptr;
     hipGraphExec_t step_exec = nullptr;
 };

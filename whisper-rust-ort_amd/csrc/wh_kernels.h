@@ -134,6 +134,23 @@ struct SkinnyArgs {
     const int* logits_sel = nullptr;   // [M]: slot of row m in `logits`, -1 = this row's logits are not kept
     float* part_val = nullptr;
     int* part_idx = nullptr;
+    // Whisper's timestamp rules (the RULES variants of the LM head): ids >= ts_begin are timestamps.  part_val / part_idx
+    // then hold the argmax of the allowed text ids; the timestamp logits go to ts_logits [x_mpad][ts_ld] (ts_ld = N - ts_begin), -inf where
+    // not allowed.  ts_state [x_mpad][4]: {text_lo, ts_lo, ts_hi, last timestamp} of each row's position from gen 1 on (k_argmax_finish
+    // writes it); gen 0 takes rule 4's ranges (ts_max_init < 0: no bound).
+    const int* ts_state = nullptr;
+    float* ts_logits = nullptr;
+    int ts_ld = 0;
+    int ts_begin = 0, ts_max_init = -1;
+};
+
+// the finish kernel's side of the timestamp rules (rules == false: not applied)
+struct TsFinish {
+    bool rules = false;
+    const float* ts_logits = nullptr;   // [mpad][ts_ld] allowed timestamp logits (-inf: not allowed), SkinnyArgs::ts_logits
+    int ts_ld = 0;
+    int* state = nullptr;               // [mpad][4], written for the next position
+    int ts_begin = 0, vocab = 0;
 };
 
 // embedding of the NEXT position fused into the argmax finish (tok_emb == nullptr: not fused)
@@ -220,7 +237,7 @@ int wh_lm_head_tile_x3_parts(const SkinnyArgs& a);
 void wh_launch_lm_head_tile_x3(hipStream_t s, const SkinnyArgs& a);
 int wh_lm_head_parts(int prec, const SkinnyArgs& a);  // argmax partials per row written by wh_launch_lm_head, layout [part][x_mpad]
 void wh_launch_argmax_finish(hipStream_t s, int prec, const float* part_val, const int* part_idx, int n_parts, int mpad, int* pos_p,
-                             int* ticket, const DecodeState& st, int B, const NextEmbed& ne);
+                             int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts = TsFinish());
 void wh_launch_dec_self_attn(hipStream_t s, int prec, const void* qkv, void* kc, void* vc, void* out, const int* pos_p,
                              int d, int n_heads, int tc, int B, int mpad);
 // stream_nt: non-temporal K/V loads (set when the cross K/V of all layers exceed what the Infinity Cache can keep)

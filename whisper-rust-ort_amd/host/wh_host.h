@@ -154,7 +154,10 @@ inline JVal stat_json(const StatBlock& s) {
 // ---------------------------------------------------------------------------------------------
 // rows + emitters — src/main.rs:1053-1060, 1193-1199, 1215-1232
 // ---------------------------------------------------------------------------------------------
-struct RowOut { std::string file; double duration_s, end_to_end_s, rtf; std::string text; };
+struct RowOut {
+    std::string file; double duration_s, end_to_end_s, rtf; std::string text;
+    std::string segments;   // JSON array of {start, end, text} (--timestamp-rules), empty: no key
+};
 
 inline double round_to(double v, double scale) { return std::round(v * scale) / scale; }  // f64::round: half away from zero
 
@@ -200,6 +203,7 @@ inline std::string per_file_json(const std::vector<RowOut>& rows) {  // :1232 to
         r.set("file", JVal::str(rows[i].file)).set("duration_s", JVal::num(rows[i].duration_s))
             .set("end_to_end_s", JVal::num(rows[i].end_to_end_s)).set("rtf", JVal::num(rows[i].rtf))
             .set("text", JVal::str(rows[i].text));
+        if (!rows[i].segments.empty()) { JVal sg; sg.raw = rows[i].segments; r.set("segments", sg); }
         o += "  ";
         r.write(o, 2);
         o += (i + 1 < rows.size()) ? ",\n" : "\n";
@@ -355,7 +359,7 @@ inline bool load_tokenizer(const std::string& path, Tokenizer& t) {
     return true;
 }
 
-struct WhisperSpecial { int64_t sot, eot, lang, task, no_timestamps; };
+struct WhisperSpecial { int64_t sot, eot, lang, task, no_timestamps, timestamp_begin; };
 
 inline WhisperSpecial special_tokens(const std::string& language, const std::string& task, const Tokenizer* tok) {
     if (tok && tok->loaded) {  // :529-541
@@ -364,15 +368,122 @@ inline WhisperSpecial special_tokens(const std::string& language, const std::str
             if (it == tok->special.end()) throw std::runtime_error("Tokenizer missing token: " + s);
             return it->second;
         };
-        return {get("<|startoftranscript|>"), get("<|endoftext|>"), get("<|" + language + "|>"), get("<|" + task + "|>"),
-                get("<|notimestamps|>")};
+        WhisperSpecial s{get("<|startoftranscript|>"), get("<|endoftext|>"), get("<|" + language + "|>"), get("<|" + task + "|>"),
+                         get("<|notimestamps|>"), 0};
+        auto ts = tok->special.find("<|0.00|>");   // <|0.00|> if the tokenizer lists it, else the id after <|notimestamps|>
+        s.timestamp_begin = ts != tok->special.end() ? ts->second : s.no_timestamps + 1;
+        return s;
     }
     WhisperSpecial s;  // :549-566 hard-coded multilingual ids
     s.sot = 50258; s.eot = 50257;
     s.lang = language == "en" ? 50259 : language == "hi" ? 50276 : 50259;
     s.task = task == "transcribe" ? 50359 : task == "translate" ? 50358 : 50359;
     s.no_timestamps = 50363;
+    s.timestamp_begin = 50364;
     return s;
+}
+
+// ---- timestamped segments (Whisper's timestamp tokens, openai-whisper's slicing rule) ---------------------------------------------------
+struct Segment { double start = 0, end = 0; std::vector<int64_t> tokens; };   // tokens: the text ids (no timestamp) of the segment
+constexpr double kTimePrecision = 0.02;   // seconds per timestamp step
+
+// Generated tokens of one 30 s window (the prompt left out; everything from the first EOT on is dropped) -> segments:
+//   - split at every pair of adjacent timestamps; a slice runs from its first token's time (0 if that is text) to its last token's;
+//   - tokens that end in a single timestamp: it closes the last slice;
+//   - text after the last pair with no closing timestamp: a final segment from the pair's second timestamp to `duration`;
+//   - no pair at all: one segment from 0 to the last timestamp (if one above <|0.00|> exists), else to `duration`.
+inline std::vector<Segment> split_segments(const std::vector<int64_t>& generated, int64_t tb, int64_t eot, double duration) {
+    std::vector<int64_t> t;
+    for (int64_t x : generated) {
+        if (x == eot) break;
+        t.push_back(x);
+    }
+    auto is_ts = [&](size_t i) { return t[i] >= tb; };
+    auto text_of = [&](size_t a, size_t b) {
+        std::vector<int64_t> o;
+        for (size_t i = a; i < b; i++)
+            if (!is_ts(i)) o.push_back(t[i]);
+        return o;
+    };
+    std::vector<size_t> cuts;
+    for (size_t i = 1; i < t.size(); i++)
+        if (is_ts(i - 1) && is_ts(i)) cuts.push_back(i);
+    std::vector<Segment> out;
+    if (cuts.empty()) {
+        Segment s;
+        s.end = duration;
+        for (size_t i = t.size(); i-- > 0;)
+            if (is_ts(i)) { if (t[i] > tb) s.end = (double)(t[i] - tb) * kTimePrecision; break; }
+        s.tokens = text_of(0, t.size());
+        out.push_back(s);
+        return out;
+    }
+    const bool single_end = t.size() >= 2 && is_ts(t.size() - 1) && !is_ts(t.size() - 2);
+    if (single_end) cuts.push_back(t.size());
+    size_t last = 0;
+    for (size_t c : cuts) {
+        Segment s;
+        s.start = is_ts(last) ? (double)(t[last] - tb) * kTimePrecision : 0.0;   // (only the first slice can open with text: from 0)
+        s.end = (double)(t[c - 1] - tb) * kTimePrecision;
+        s.tokens = text_of(last, c);
+        out.push_back(s);
+        last = c;
+    }
+    if (last < t.size()) {
+        std::vector<int64_t> rest = text_of(last, t.size());
+        if (!rest.empty()) {
+            Segment s;
+            s.start = is_ts(last) ? (double)(t[last] - tb) * kTimePrecision : out.back().end;
+            s.end = duration;
+            s.tokens = rest;
+            out.push_back(s);
+        }
+    }
+    return out;
+}
+
+// Long-form: window k's segments shifted by its start; where windows k and k+1 overlap, a segment belongs to k if it starts before
+// start(k+1) + overlap / 2, else to k + 1.
+inline std::vector<Segment> merge_window_segments(const std::vector<std::vector<Segment>>& windows, const std::vector<double>& starts, double overlap_s) {
+    std::vector<Segment> out;
+    for (size_t k = 0; k < windows.size(); k++) {
+        const double lo = k == 0 ? -1e300 : starts[k] + overlap_s / 2;
+        const double hi = k + 1 < windows.size() ? starts[k + 1] + overlap_s / 2 : 1e300;
+        for (Segment s : windows[k]) {
+            s.start += starts[k];
+            s.end += starts[k];
+            if (s.start >= lo && s.start < hi) out.push_back(s);
+        }
+    }
+    return out;
+}
+
+// "HH:MM:SS,mmm" (SRT) / "HH:MM:SS.mmm" (VTT), rounded to the millisecond
+inline std::string fmt_cue_time(double t, char sep) {
+    long long ms = std::llround(std::max(t, 0.0) * 1000.0);
+    char b[48];
+    snprintf(b, sizeof b, "%02lld:%02lld:%02lld%c%03lld", ms / 3600000, (ms / 60000) % 60, (ms / 1000) % 60, sep, ms % 1000);
+    return b;
+}
+struct Cue { double start, end; std::string text; };
+inline std::string srt_text(const std::vector<Cue>& cues) {
+    std::string o;
+    for (size_t i = 0; i < cues.size(); i++)
+        o += std::to_string(i + 1) + "\n" + fmt_cue_time(cues[i].start, ',') + " --> " + fmt_cue_time(cues[i].end, ',') + "\n" + cues[i].text + "\n\n";
+    return o;
+}
+inline std::string cues_json(const std::vector<Cue>& cues) {   // [{"start": s, "end": s, "text": "..."}] on one line
+    std::string o = "[";
+    for (size_t i = 0; i < cues.size(); i++)
+        o += (i ? ", " : "") + std::string("{\"start\": ") + fmt_f64(cues[i].start) + ", \"end\": " + fmt_f64(cues[i].end) + ", \"text\": " +
+             json_escape(cues[i].text) + "}";
+    return o + "]";
+}
+inline std::string vtt_text(const std::vector<Cue>& cues) {
+    std::string o = "WEBVTT\n\n";
+    for (size_t i = 0; i < cues.size(); i++)
+        o += std::to_string(i + 1) + "\n" + fmt_cue_time(cues[i].start, '.') + " --> " + fmt_cue_time(cues[i].end, '.') + "\n" + cues[i].text + "\n\n";
+    return o;
 }
 
 // GPT-2 byte-level alphabet: unicode code point → byte

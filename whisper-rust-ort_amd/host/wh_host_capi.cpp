@@ -76,6 +76,46 @@ size_t whh_decode_tokens(const long long* toks, size_t n, const char* tokenizer_
     if (tokenizer_json && *tokenizer_json) load_tokenizer(tokenizer_json, t);
     return put(decode_tokens(v, t.loaded ? &t : nullptr), out, cap);
 }
+// timestamped segments as JSON [{"start": s, "end": s, "tokens": [ids]}] (wh_host.h split_segments / merge_window_segments)
+static std::string segments_json(const std::vector<Segment>& segs) {
+    std::string o = "[";
+    char b[64];
+    for (size_t i = 0; i < segs.size(); i++) {
+        snprintf(b, sizeof b, "%s{\"start\": %.6f, \"end\": %.6f, \"tokens\": [", i ? ", " : "", segs[i].start, segs[i].end);
+        o += b;
+        for (size_t j = 0; j < segs[i].tokens.size(); j++) o += (j ? ", " : "") + std::to_string(segs[i].tokens[j]);
+        o += "]}";
+    }
+    return o + "]";
+}
+size_t whh_segments_json(const long long* toks, size_t n, long long tb, long long eot, double duration, char* out, size_t cap) {
+    return put(segments_json(split_segments(std::vector<int64_t>(toks, toks + n), tb, eot, duration)), out, cap);
+}
+// long-form: the windows' generated tokens back to back (lens[k] each), window starts and durations in seconds
+size_t whh_longform_segments_json(const long long* toks, const size_t* lens, size_t n_windows, const double* starts, const double* durations,
+                                  double overlap_s, long long tb, long long eot, char* out, size_t cap) {
+    std::vector<std::vector<Segment>> w;
+    for (size_t k = 0; k < n_windows; k++) {
+        w.push_back(split_segments(std::vector<int64_t>(toks, toks + lens[k]), tb, eot, durations[k]));
+        toks += lens[k];
+    }
+    return put(segments_json(merge_window_segments(w, std::vector<double>(starts, starts + n_windows), overlap_s)), out, cap);
+}
+static std::vector<Cue> cues_from(const double* starts, const double* ends, const char* texts, size_t n) {
+    std::vector<Cue> c;
+    for (size_t i = 0; i < n; i++) {
+        std::string t(texts);
+        texts += t.size() + 1;
+        c.push_back(Cue{starts[i], ends[i], t});
+    }
+    return c;
+}
+size_t whh_srt(const double* starts, const double* ends, const char* texts, size_t n, char* out, size_t cap) {
+    return put(srt_text(cues_from(starts, ends, texts, n)), out, cap);
+}
+size_t whh_vtt(const double* starts, const double* ends, const char* texts, size_t n, char* out, size_t cap) {
+    return put(vtt_text(cues_from(starts, ends, texts, n)), out, cap);
+}
 int whh_special_tokens(const char* language, const char* task, const char* tokenizer_json, long long* out5) {
     try {
         Tokenizer t;

@@ -31,6 +31,8 @@ struct Args {
                                      out_summary_json = "results/benchmarks/inference_summary.json";
     long long intra_op = 0, inter_op = 0;
     bool write_txt = false, timestamps = false;
+    // additive: Whisper's timestamp rules in the token loop, segments in the per-file JSON; SRT / VTT files (imply the rules)
+    bool timestamp_rules = false, write_srt = false, write_vtt = false;
     std::string tokenizer_json;
     size_t chunk_parallelism = 0;
     float chunk_length_s = 30.0f, overlap_s = 5.0f;
@@ -79,6 +81,9 @@ static bool parse_args(int argc, char** argv, Args& a) {
         std::string v;
         if (k == "--write-txt") a.write_txt = true;
         else if (k == "--timestamps") a.timestamps = true;
+        else if (k == "--timestamp-rules") a.timestamp_rules = true;
+        else if (k == "--write-srt") a.write_srt = a.timestamp_rules = true;
+        else if (k == "--write-vtt") a.write_vtt = a.timestamp_rules = true;
         else if (k == "--print-plan") a.print_plan = true;
         else if (k == "--help" || k == "-h") {
             printf("Usage: whisper_bench [--audio-dir DIR] [--model-id ID] [--onnx-dir DIR|synthetic:<preset>:<seed>] [--language en] "
@@ -86,7 +91,7 @@ static bool parse_args(int argc, char** argv, Args& a) {
                    "[--out-csv F] [--out-json F] [--out-summary-json F] [--intra-op N] [--inter-op N] [--write-txt] "
                    "[--tokenizer-json F] [--timestamps] [--chunk-parallelism N] [--chunk-length-s 30] [--overlap-s 5] "
                    "[--device 0] [--devices 0-7] [--streams-per-gpu 1] [--load-threads N] [--precision bf16|f32|fp8|f16x3] [--max-batch 16] "
-                   "[--synthetic-clips N] [--seed 1000] [--print-plan]\n");
+                   "[--synthetic-clips N] [--seed 1000] [--print-plan] [--timestamp-rules] [--write-srt] [--write-vtt]\n");
             exit(0);
         } else {
             if (!need(i, argv[i], v, inl)) return false;
@@ -266,12 +271,32 @@ static std::vector<int> parse_devices(const std::string& spec, int fallback) {  
 struct Timing { double preprocess_s = 0, model_only_s = 0, decode_s = 0, end_to_end_s = 0; };
 
 // transcribe_longform_chunked (src/main.rs:834-1008) over the C ABI
+// --timestamp-rules: the segments of one window's generated tokens (wh_host.h split_segments) and their cues
+static std::vector<Segment> window_segments(const std::vector<int64_t>& g, const WhisperSpecial& sp, double duration) {
+    return split_segments(g, sp.timestamp_begin, sp.eot, duration);
+}
+static std::vector<Cue> to_cues(const std::vector<Segment>& segs, const Tokenizer* tok) {
+    std::vector<Cue> c;
+    for (const Segment& s : segs) {
+        std::string text = trim(decode_tokens(s.tokens, tok));
+        if (!text.empty()) c.push_back(Cue{s.start, s.end, text});   // (a slice between two timestamp pairs may hold no text)
+    }
+    return c;
+}
+// the text ids of a generated sequence (timestamp tokens left out)
+static std::vector<int64_t> text_ids(const std::vector<int64_t>& g, int64_t tb) {
+    std::vector<int64_t> o;
+    for (int64_t x : g)
+        if (x < tb) o.push_back(x);
+    return o;
+}
+
 static std::string transcribe(wh_ctx* ctx, const std::vector<float>& audio, const Args& a, const Tokenizer* tok,
-                              const GenCfg& gen, Timing& t) {
+                              const GenCfg& gen, Timing& t, std::vector<Cue>* cues = nullptr) {
     const double t0 = now_s();
     WhisperSpecial sp = special_tokens(a.language, a.task, tok);
     std::vector<int64_t> prompt = {sp.sot, sp.lang, sp.task};
-    if (!a.timestamps) prompt.push_back(sp.no_timestamps);
+    if (!a.timestamps && !a.timestamp_rules) prompt.push_back(sp.no_timestamps);
     wh_decode_params p{};
     p.prompt = prompt.data(); p.n_prompt = prompt.size(); p.max_new_tokens = a.max_new_tokens; p.eot = sp.eot;
     p.suppress = gen.suppress.data(); p.n_suppress = gen.suppress.size();
@@ -291,14 +316,25 @@ static std::string transcribe(wh_ctx* ctx, const std::vector<float>& audio, cons
     t.model_only_s = wt.encode_s + wt.decode_s;
     const double td0 = now_s();
     std::vector<std::string> texts;
+    std::vector<size_t> offs(std::max<size_t>(1, got));
+    if (a.timestamp_rules) wh_longform_plan(audio.size(), a.chunk_length_s, a.overlap_s, offs.data(), offs.size(), &nch);
+    std::vector<std::vector<Segment>> wsegs;
+    std::vector<double> wstart;
     for (size_t c = 0; c < got; c++) {  // :926-943
         std::vector<int64_t> g;
         if (ntok[c] > prompt.size()) g.assign(toks.begin() + c * stride + prompt.size(), toks.begin() + c * stride + ntok[c]);
         if (!g.empty() && g.back() == sp.eot) g.pop_back();
+        if (a.timestamp_rules) {
+            const size_t len = std::min<size_t>(audio.size() - offs[c], (size_t)std::llround(a.chunk_length_s * 16000.0));
+            wsegs.push_back(window_segments(g, sp, (double)len / 16000.0));
+            wstart.push_back((double)offs[c] / 16000.0);
+            g = text_ids(g, sp.timestamp_begin);
+        }
         std::string text = decode_tokens(g, tok);
         if (text.empty()) text = "[EMPTY]";
         if (text != "[EMPTY]") texts.push_back(text);
     }
+    if (cues) *cues = to_cues(merge_window_segments(wsegs, wstart, a.overlap_s), tok);
     t.decode_s = now_s() - td0;
     std::string full = stitch_texts(texts);
     t.end_to_end_s = now_s() - t0;
@@ -364,6 +400,12 @@ int main(int argc, char** argv) {
                 wh_ctx* c = nullptr;
                 if (int rc = wh_ctx_create(m, a.max_batch, &c))
                     throw std::runtime_error(std::string("wh_ctx_create: ") + std::to_string(rc) + ": " + wh_last_error(nullptr));
+                if (a.timestamp_rules) {   // Whisper's timestamp rules on every context (no reference counterpart)
+                    WhisperSpecial sp = special_tokens(a.language, a.task, &tok);
+                    wh_timestamp_rules tr{sizeof(wh_timestamp_rules), sp.timestamp_begin, sp.no_timestamps, 50};
+                    if (int rc = wh_ctx_set_timestamp_rules(c, &tr))
+                        throw std::runtime_error(std::string("wh_ctx_set_timestamp_rules: ") + std::to_string(rc) + ": " + wh_last_error(c));
+                }
                 ctxs.push_back(c);
             }
         }
@@ -406,14 +448,14 @@ int main(int argc, char** argv) {
                             return hipHostMalloc((void**)&p, (size_t)WH_CLIP_SAMPLES * sizeof(float), hipHostMallocDefault) == hipSuccess ? p : nullptr;
                         },
                         [](float* p) { (void)hipHostFree(p); });
-        struct Result { std::string text; double dur = 0, load_s = 0; Timing t; bool ok = false; };
+        struct Result { std::string text; double dur = 0, load_s = 0; Timing t; bool ok = false; std::vector<Cue> cues; };
         const size_t nfiles = files.size();
         std::vector<Result> results(nfiles);
         const unsigned hc = std::thread::hardware_concurrency();
         const int n_loaders = a.load_threads > 0 ? a.load_threads : (int)std::min<unsigned>(8, std::max<unsigned>(1, hc / 2));
         WhisperSpecial sp = special_tokens(a.language, a.task, &tok);
         std::vector<int64_t> prompt = {sp.sot, sp.lang, sp.task};
-        if (!a.timestamps) prompt.push_back(sp.no_timestamps);
+        if (!a.timestamps && !a.timestamp_rules) prompt.push_back(sp.no_timestamps);
         std::vector<double> busy_s(ctxs.size(), 0.0);
         auto process = [&](size_t wi, std::vector<Item>& batch, std::vector<Item>* next) {
             wh_ctx* ctx = ctxs[wi];
@@ -422,7 +464,7 @@ int main(int argc, char** argv) {
             if (batch.size() == 1 && batch[0].n() > (size_t)WH_CLIP_SAMPLES) {
                 // a file longer than one window goes alone through the long-form entry (which batches its windows)
                 Result& r = results[batch[0].idx];
-                r.text = transcribe(ctx, batch[0].audio, a, &tok, gen, r.t);
+                r.text = transcribe(ctx, batch[0].audio, a, &tok, gen, r.t, &r.cues);
                 r.dur = batch[0].dur; r.load_s = batch[0].load_s; r.ok = true;
             } else {
                 // the per-window body of transcribe_longform_chunked (:870-915) for a batch of one-window files
@@ -448,6 +490,10 @@ int main(int argc, char** argv) {
                     std::vector<int64_t> g;
                     if (ntok[k] > prompt.size()) g.assign(toks.begin() + k * stride + prompt.size(), toks.begin() + k * stride + ntok[k]);
                     if (!g.empty() && g.back() == sp.eot) g.pop_back();
+                    if (a.timestamp_rules) {
+                        r.cues = to_cues(window_segments(g, sp, batch[k].dur), &tok);
+                        g = text_ids(g, sp.timestamp_begin);
+                    }
                     std::string text = decode_tokens(g, &tok);
                     if (text.empty()) text = "[EMPTY]";
                     std::vector<std::string> texts;
@@ -479,12 +525,19 @@ int main(int argc, char** argv) {
             if (!r.ok) throw std::runtime_error("file " + files[i] + " was not processed");
             const double end_to_end = r.load_s + r.t.end_to_end_s;   // :1190
             rows.push_back(make_row(files[i], r.dur, end_to_end, r.text));
+            if (a.timestamp_rules) rows.back().segments = cues_json(r.cues);
             loadl.push_back(r.load_s); pre.push_back(r.t.preprocess_s); model_only.push_back(r.t.model_only_s);
             dec.push_back(r.t.decode_s); e2e.push_back(end_to_end); rtfl.push_back(end_to_end / std::max(r.dur, 1e-9));
             audio_total += r.dur;
             if (a.write_txt) {
                 std::string base = files[i].substr(0, files[i].rfind('.'));
                 write_file((txt_dir.empty() ? "." : txt_dir) + "/" + base + ".transcript.txt", trim(r.text) + "\n");
+            }
+            if (a.write_srt || a.write_vtt) {   // subtitle files into the directory --write-txt uses
+                const std::string base = (txt_dir.empty() ? "." : txt_dir) + "/" + files[i].substr(0, files[i].rfind('.'));
+                if (!parent_dir(base).empty()) mkdir_p(parent_dir(base));
+                if (a.write_srt) write_file(base + ".srt", srt_text(r.cues));
+                if (a.write_vtt) write_file(base + ".vtt", vtt_text(r.cues));
             }
         }
         const double busy_max = *std::max_element(busy_s.begin(), busy_s.end());
@@ -507,6 +560,7 @@ int main(int argc, char** argv) {
                             // second the busiest context spent inside the library (what bench.py measures with PCM resident)
                             .set("wall_s", JVal::num(loop_s)).set("throughput_rtfx", JVal::num(audio_total / std::max(loop_s, 1e-12)))
                             .set("gpu_busy_s", JVal::num(busy_max)).set("gpu_throughput_rtfx", JVal::num(audio_total / std::max(busy_max, 1e-12))));
+        if (a.timestamp_rules) summary.set("timestamp_rules", JVal::boolean(true));
         write_file(a.out_summary_json, summary.pretty());
         printf("DONE\n");  // :1261-1268
         printf("Config used:\n%s\n", cfg.json(false).pretty().c_str());
