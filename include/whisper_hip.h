@@ -182,6 +182,27 @@ typedef struct {
     int32_t max_initial_timestamp_index; /* 50 = 1.0 s; < 0: unbounded */
 } wh_timestamp_rules;
 int wh_ctx_set_timestamp_rules(wh_ctx* c, const wh_timestamp_rules* r);
+/* Token log-probabilities and the no-speech probability of the greedy token loop (openai-whisper's GreedyDecoder.update and
+ * DecodingTask._main_loop; what faster-whisper and HF generate report as avg_logprob / no_speech_prob).  No reference entry corresponds.
+ * With this set, every decode entry of the ctx records, at every generated position, after the suppress masks and (when set) the timestamp
+ * rules including rule 5:  log p(token) = v[token] - log sum_{i allowed} exp(v[i])  of the recorded (argmax) token; NaN logits are left out
+ * of the sum as they are left out of the argmax; nothing allowed (the recorded token is then 0): -inf.  With wh_decode_params.forced the
+ * value belongs to the recorded token, not to the forced one.  no_speech >= 0 adds one LM-head launch per call at prompt position
+ * sot_index: no_speech_prob = softmax(v)[no_speech] over that position's unfiltered logits.  Tokens, logits and every other output are the
+ * same with this on or off.
+ * Refused with WH_ERR_ARG (the ctx unchanged): a wrong struct_size, a no_speech outside [0, vocab) other than -1, a negative sot_index; at
+ * decode time (before anything is launched) a probe whose sot_index is not below n_prompt - 1.  o == NULL turns it off (the default). */
+typedef struct {
+    size_t struct_size;   /* sizeof(wh_logprob_opts) */
+    int64_t no_speech;    /* id of <|nospeech|> (<|nocaptions|>); -1: no probe, no_speech_prob not computed */
+    int32_t sot_index;    /* prompt position whose logits the probe reads; must be < n_prompt - 1 (a non-emitting prompt position) at decode time */
+} wh_logprob_opts;
+int wh_ctx_set_logprobs(wh_ctx* c, const wh_logprob_opts* o);
+/* Of the last decode call on the ctx (any decode entry; every clip / window it returned tokens for, in that order):
+ * token_logprobs [n][cap_tokens]: entry i of clip b belongs to its generated token i (the prompt is not counted), 0 past the clip's end;
+ * cap_tokens must hold the longest clip's generated tokens.  no_speech_prob [n] (may be NULL; WH_ERR_STATE if asked for without a probe).
+ * token_logprobs == NULL: only *n_clips_out.  WH_ERR_STATE if the call ran with log-probabilities off; WH_ERR_ARG if cap_clips < n. */
+int wh_get_logprobs(const wh_ctx* c, float* token_logprobs, size_t cap_tokens, float* no_speech_prob, size_t cap_clips, size_t* n_clips_out);
 const char* wh_last_error(const wh_ctx* c); /* c == NULL: last load/create error of this thread */
 int wh_get_timings(const wh_ctx* c, wh_timing* out);
 

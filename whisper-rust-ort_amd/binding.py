@@ -34,7 +34,7 @@ EXPORTS = ("wh_model_load", "wh_model_create", "wh_model_free", "wh_model_get_di
            "wh_mel_frames", "wh_log_mel", "wh_encode", "wh_decode_greedy", "wh_decode_greedy_batch", "wh_decode_greedy_rows", "wh_transcribe_batch",
            "wh_transcribe_batch_next", "wh_transcribe_batch_device", "wh_transcribe_batch_device_next", "wh_longform_plan", "wh_transcribe_longform", "wh_profile_enable",
            "wh_profile_get", "wh_synthetic_weights", "wh_e4m3_quantize", "wh_e4m3_dequantize", "wh_abi_version",
-           "wh_device_count", "wh_ctx_set_timestamp_rules")
+           "wh_device_count", "wh_ctx_set_timestamp_rules", "wh_ctx_set_logprobs", "wh_get_logprobs")
 
 
 class WhisperHipError(RuntimeError):
@@ -72,6 +72,10 @@ class WhCtxOpts(C.Structure):
 class WhTimestampRules(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("timestamp_begin", C.c_int64), ("no_timestamps", C.c_int64),
                 ("max_initial_timestamp_index", C.c_int32)]
+
+
+class WhLogprobOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("no_speech", C.c_int64), ("sot_index", C.c_int32)]
 
 
 WH_CTX_TWO_STREAMS = 1
@@ -142,6 +146,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.wh_e4m3_dequantize.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, f32p]
     L.wh_e4m3_dequantize.restype = None
     L.wh_ctx_set_timestamp_rules.argtypes = [vp, C.POINTER(WhTimestampRules)]
+    L.wh_ctx_set_logprobs.argtypes = [vp, C.POINTER(WhLogprobOpts)]
+    L.wh_get_logprobs.argtypes = [vp, f32p, C.c_size_t, f32p, C.c_size_t, C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -238,6 +244,7 @@ class Context:
         cross_es: force the token loop's cross-attention onto the encoder states (True) or onto the projected K / V (False);
         None = the library's rule (bf16 whisper-base geometry, max_batch >= 256)."""
         self.model, self.lib, self.max_batch = model, model.lib, max_batch
+        self._gen_lens: List[int] = []
         h = C.c_void_p()
         flags = (WH_CTX_TWO_STREAMS if two_streams else 0) | (0 if cross_es is None else (WH_CTX_CROSS_ES_ON if cross_es else WH_CTX_CROSS_ES_OFF))
         if enc_cu_mask is None and dec_cu_mask is None and not flags:
@@ -279,6 +286,37 @@ class Context:
     def clear_timestamp_rules(self):
         self._check(self.lib.wh_ctx_set_timestamp_rules(self.h, None))
 
+    def set_logprobs(self, no_speech: int = -1, sot_index: int = 0):
+        """wh_ctx_set_logprobs: every decode entry of this context records the log-probability of each generated token; no_speech >= 0
+        also the no-speech probability (softmax of the unfiltered logits at prompt position sot_index, at that id)."""
+        o = WhLogprobOpts(C.sizeof(WhLogprobOpts), no_speech, sot_index)
+        self._check(self.lib.wh_ctx_set_logprobs(self.h, C.byref(o)))
+
+    def clear_logprobs(self):
+        self._check(self.lib.wh_ctx_set_logprobs(self.h, None))
+
+    def logprobs(self) -> Tuple[List[np.ndarray], Optional[np.ndarray]]:
+        """wh_get_logprobs of the last decode call: one float32 array per clip / window (one entry per generated token, EOT's included)
+        and the no-speech probabilities (None without a probe)."""
+        n = C.c_size_t(0)
+        self._check(self.lib.wh_get_logprobs(self.h, None, 0, None, 0, C.byref(n)))
+        k = int(n.value)
+        lens = list(self._gen_lens)
+        assert len(lens) == k, (len(lens), k)
+        cap = max(1, max(lens, default=0))
+        lp = np.zeros((max(1, k), cap), np.float32)
+        ns = np.zeros(max(1, k), np.float32)
+        rc = self.lib.wh_get_logprobs(self.h, _f32(lp), cap, _f32(ns), k, C.byref(n))
+        if rc == 3:   # WH_ERR_STATE: no probe
+            ns = None
+            rc = self.lib.wh_get_logprobs(self.h, _f32(lp), cap, None, k, C.byref(n))
+        self._check(rc)
+        return [lp[i, : lens[i]].copy() for i in range(k)], (ns[:k] if ns is not None else None)
+
+    def _took(self, toks: List[np.ndarray], params: "DecodeParams") -> List[np.ndarray]:
+        self._gen_lens = [len(t) - len(params.prompt) for t in toks]   # (what logprobs() cuts its rows to)
+        return toks
+
     # --- the reference's three functions -----------------------------------------------------
     def whisper_log_mel(self, audio_16k: np.ndarray) -> np.ndarray:
         """whisper_log_mel_80 (src/main.rs:407-509) → [n_mels, n_frames] f32."""
@@ -311,6 +349,7 @@ class Context:
         self._check(self.lib.wh_decode_greedy(self.h, C.byref(p), _i64(toks), cap, C.byref(n),
                                               _f32(logits) if want_logits else None, params.max_new_tokens))
         nt = int(n.value)
+        self._gen_lens = [nt - len(params.prompt)]
         return toks[:nt].copy(), (logits[: nt - len(params.prompt)].copy() if want_logits else None)
 
     def greedy_decode_resident_batch(self, params: DecodeParams, want_logits: bool = False
@@ -327,7 +366,7 @@ class Context:
         self._check(self.lib.wh_decode_greedy_batch(self.h, C.byref(p), _i64(toks), cap, n, nb, C.byref(got),
                                                     _f32(logits) if want_logits else None, params.max_new_tokens))
         k = int(got.value)
-        out = [toks[i, : n[i]].copy() for i in range(k)]
+        out = self._took([toks[i, : n[i]].copy() for i in range(k)], params)
         lg = [logits[i, : n[i] - len(params.prompt)] for i in range(k)] if want_logits else None
         return out, lg
 
@@ -345,7 +384,7 @@ class Context:
         self._check(self.lib.wh_decode_greedy_rows(self.h, C.byref(p), sel.ctypes.data_as(C.POINTER(C.c_int32)), len(sel), _i64(toks), cap, n, nb,
                                                    C.byref(got), _f32(logits), params.max_new_tokens))
         k = int(got.value)
-        out = [toks[i, : n[i]].copy() for i in range(k)]
+        out = self._took([toks[i, : n[i]].copy() for i in range(k)], params)
         return out, [logits[j, : n[int(r)] - len(params.prompt)] for j, r in enumerate(sel)]
 
     # --- fused batch entries ----------------------------------------------------------------------
@@ -363,7 +402,7 @@ class Context:
         n = (C.c_size_t * len(arrs))()
         self._check(self.lib.wh_transcribe_batch_next(self.h, cl, len(arrs), ncl, len(nxt) if nxt else 0, C.byref(p), _i64(toks), n))
         self._keep_next = nxt   # (contiguous copies, if any were made, must outlive the asynchronous copy)
-        return [toks[i, : n[i]].copy() for i in range(len(arrs))]
+        return self._took([toks[i, : n[i]].copy() for i in range(len(arrs))], params)
 
     def transcribe_batch(self, clips: Sequence[np.ndarray], params: DecodeParams) -> List[np.ndarray]:
         arrs = [np.ascontiguousarray(c, np.float32) for c in clips]
@@ -373,7 +412,7 @@ class Context:
         toks = np.zeros((len(arrs), stride), np.int64)
         n = (C.c_size_t * len(arrs))()
         self._check(self.lib.wh_transcribe_batch(self.h, cl, len(arrs), C.byref(p), _i64(toks), n))
-        return [toks[i, : n[i]].copy() for i in range(len(arrs))]
+        return self._took([toks[i, : n[i]].copy() for i in range(len(arrs))], params)
 
     def transcribe_batch_device(self, d_pcm_ptr: int, n_clips: int, params: DecodeParams, next_ptr: Optional[int] = None,
                                 next_n: int = 0) -> List[np.ndarray]:
@@ -388,7 +427,7 @@ class Context:
         else:
             self._check(self.lib.wh_transcribe_batch_device_next(self.h, C.c_void_p(d_pcm_ptr), n_clips, C.c_void_p(next_ptr), next_n,
                                                                  C.byref(p), _i64(toks), n))
-        return [toks[i, : n[i]].copy() for i in range(n_clips)]
+        return self._took([toks[i, : n[i]].copy() for i in range(n_clips)], params)
 
     def transcribe_longform(self, audio_16k: np.ndarray, params: DecodeParams, chunk_length_s: float = 30.0,
                             overlap_s: float = 5.0) -> List[np.ndarray]:
@@ -403,7 +442,7 @@ class Context:
         got = C.c_size_t(0)
         self._check(self.lib.wh_transcribe_longform(self.h, _f32(pcm), pcm.size, chunk_length_s, overlap_s, C.byref(p),
                                                     _i64(toks), n, k, C.byref(got)))
-        return [toks[i, : n[i]].copy() for i in range(int(got.value))]
+        return self._took([toks[i, : n[i]].copy() for i in range(int(got.value))], params)
 
     # --- measurement -------------------------------------------------------------------------------
     def timings(self) -> dict:
@@ -552,8 +591,16 @@ def load_host_library(path: str = HOST_LIB_PATH) -> C.CDLL:
                                                  C.c_longlong, C.c_longlong, C.c_char_p, C.c_size_t]
         for f in (L.whh_srt, L.whh_vtt):
             f.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
-        for f in (L.whh_segments_json, L.whh_longform_segments_json, L.whh_srt, L.whh_vtt):
+        L.whh_segments_conf_json.argtypes = [ll, C.c_size_t, C.c_longlong, C.c_longlong, C.c_double, C.c_double, C.c_double, C.c_char_p, C.c_size_t]
+        for f in (L.whh_segments_json, L.whh_segments_conf_json, L.whh_longform_segments_json, L.whh_srt, L.whh_vtt):
             f.restype = C.c_size_t
+        L.whh_synthetic_clip.argtypes = [C.c_ulonglong, C.POINTER(C.c_float), C.c_size_t]
+        L.whh_synthetic_clip.restype = C.c_size_t
+        L.whh_avg_logprob.argtypes = [C.POINTER(C.c_float), ll, C.c_size_t, C.c_longlong]
+        L.whh_avg_logprob.restype = C.c_double
+        L.whh_skip_window.argtypes = [C.c_double] * 4
+        L.whh_no_speech_token.argtypes = [C.c_char_p] * 3
+        L.whh_no_speech_token.restype = C.c_longlong
         _host = L
     return _host
 
@@ -565,11 +612,45 @@ def _host_string(call) -> str:
     return buf.value.decode()
 
 
-def split_segments(generated: Sequence[int], tb: int, eot: int, duration: float) -> List[dict]:
-    """One window's generated tokens -> [{start, end, tokens}] (openai-whisper's slicing rule; tokens = the segment's text ids)."""
+def cli_synthetic_clip(seed: int) -> np.ndarray:
+    """Clip `seed` of whisper_bench --synthetic-clips (file i of a run is clip --seed + i, --seed defaults to 1000)."""
+    x = np.zeros(WH_CLIP_SAMPLES, np.float32)
+    n = load_host_library().whh_synthetic_clip(seed, _f32(x), x.size)
+    assert n == x.size
+    return x
+
+
+def avg_logprob(logprobs: Sequence[float], tokens: Sequence[int], eot: int) -> float:
+    """openai-whisper's sum_logprobs / (len(tokens) + 1) of one window's generated tokens and their log-probabilities (EOT's included
+    in the sum when it was emitted, not in the length)."""
+    n = min(len(logprobs), len(tokens))
+    lp = np.ascontiguousarray(list(logprobs)[:n] or [0.0], np.float32)
+    t = np.ascontiguousarray(list(tokens)[:n] or [0], np.int64)
+    return float(load_host_library().whh_avg_logprob(lp.ctypes.data_as(C.POINTER(C.c_float)), t.ctypes.data_as(C.POINTER(C.c_longlong)), n, eot))
+
+
+def skip_window(no_speech_prob: float, avg_lp: float, no_speech_threshold: Optional[float] = None, logprob_threshold: Optional[float] = None) -> bool:
+    """The CLI's silence rule: no_speech_prob > no_speech_threshold and avg_logprob < logprob_threshold (None: that threshold is off)."""
+    nan = float("nan")
+    return bool(load_host_library().whh_skip_window(no_speech_prob, avg_lp, nan if no_speech_threshold is None else no_speech_threshold,
+                                                    nan if logprob_threshold is None else logprob_threshold))
+
+
+def no_speech_token(language: str = "en", task: str = "transcribe", tokenizer_json: str = "") -> int:
+    """WhisperSpecial::no_speech: the tokenizer's <|nospeech|> / <|nocaptions|>, else the id before <|notimestamps|> (50362)."""
+    return int(load_host_library().whh_no_speech_token(language.encode(), task.encode(), tokenizer_json.encode()))
+
+
+def split_segments(generated: Sequence[int], tb: int, eot: int, duration: float, avg_logprob: Optional[float] = None,
+                   no_speech_prob: Optional[float] = None) -> List[dict]:
+    """One window's generated tokens -> [{start, end, tokens}] (openai-whisper's slicing rule; tokens = the segment's text ids).  With
+    avg_logprob and no_speech_prob each segment also carries the window's two values."""
     import json
     t = np.ascontiguousarray(list(generated), np.int64)
     L = load_host_library()
+    if avg_logprob is not None and no_speech_prob is not None:
+        return json.loads(_host_string(lambda o, c: L.whh_segments_conf_json(t.ctypes.data_as(C.POINTER(C.c_longlong)), t.size, tb, eot, duration,
+                                                                              avg_logprob, no_speech_prob, o, c)))
     return json.loads(_host_string(lambda o, c: L.whh_segments_json(t.ctypes.data_as(C.POINTER(C.c_longlong)), t.size, tb, eot, duration, o, c)))
 
 

@@ -314,6 +314,9 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
         for (int i = 0; i < P; i++)
             if (c->ts_no_ts >= 0 && p->prompt[i] == c->ts_no_ts) return fail(c, WH_ERR_ARG, "decode: the prompt holds <|notimestamps|> while timestamp rules are on");
     }
+    const bool lp = c->lp_on, lp_probe = lp && c->lp_no_speech >= 0;
+    if (lp_probe && c->lp_sot_index >= P - 1)   // the probe reads a prompt position that emits nothing
+        return fail(c, WH_ERR_ARG, "decode: the no-speech probe's sot_index %d is not below n_prompt - 1 (%d)", c->lp_sot_index, P - 1);
 
     // the encoder states come from the encoder stream
     if (c->s_enc != s) CTX_HIP(c, hipStreamWaitEvent(s, c->ev_enc_done, 0));
@@ -414,6 +417,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
     DecodeState st;
     st.feed = c->feed; st.out_tokens = c->out_tokens; st.n_out = c->n_out; st.done = c->done;
     st.forced = c->forced; st.n_forced = (int)p->n_forced; st.n_prompt = P; st.eot = (int)p->eot; st.tok_ld = ld;
+    if (lp) st.logprob = c->lp_tok;
     const long cache_l = (long)nb * D.n_heads * D.n_text_ctx * WH_HEAD_DIM;  // elements per layer
     const int total_pos = P + NEW - 1;
     std::vector<int> done_h(nb);
@@ -431,7 +435,9 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
     };
     // `embed_first`: this step embeds its own input token; false when the previous step's argmax finish already did
     int lm_parts = 0;
-    auto launch_step = [&](bool emits, bool embed_first) {
+    // `probe`: a prompt position whose unfiltered logits the no-speech probe reads: the last fc2 leaves the position alone, the
+    // LM head's log-probability variant runs with an all-zero mask, and the probe's finish kernel advances the position
+    auto launch_step = [&](bool emits, bool embed_first, bool probe) {
         if (embed_first) {   // token + position embedding → x, raw slab, row sums (one "tile")
             Prof pr(c, WH_KG_DEC_OTHER);
             wh_launch_dec_embed(s, prec, m->tok_emb, m->dec_pos, c->feed, ld, c->pos, c->dx, c->dxs, c->lnpart, nb, (int)d, mpad,
@@ -531,7 +537,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
                 a.X = c->dh; a.x_mpad = mpad; a.W = L.fc2_w; a.bias = L.fc2_b; a.wscale = L.fc2_sc; a.R = c->dx; a.ldr = d; a.C = c->dx; a.ldc = d;
                 a.M = nb; a.N = (int)d; a.K = (int)F; a.xslab_out = c->dxs; a.stats_out = c->lnpart; a.row_shift = c->dshift;
                 if (f8) a.xgamma = (l + 1 < D.dec_layers) ? m->dec[l + 1].ln1_w : m->dec_ln_w;  // next consumer's LayerNorm
-                if (!emits && l == D.dec_layers - 1) { a.ticket = c->step_ticket; a.pos_w = c->pos; }  // prompt position: advance here
+                if (!emits && !probe && l == D.dec_layers - 1) { a.ticket = c->step_ticket; a.pos_w = c->pos; }  // prompt position: advance here
                 dec_gemm(true, a);
             }
         }
@@ -548,6 +554,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
                     a.ts_state = c->ts_state; a.ts_logits = c->ts_logits; a.ts_ld = c->ts_ld;
                     a.ts_begin = (int)c->ts_begin; a.ts_max_init = c->ts_max_init;
                 }
+                if (lp) a.part_sum = c->lp_part_sum;
                 wh_launch_lm_head(s, prec, a);
                 lm_parts = wh_lm_head_parts(prec, a);
             }
@@ -561,8 +568,25 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
                     tf.rules = true; tf.ts_logits = c->ts_logits; tf.ts_ld = c->ts_ld; tf.state = c->ts_state;
                     tf.ts_begin = (int)c->ts_begin; tf.vocab = D.vocab;
                 }
-                wh_launch_argmax_finish(s, prec, c->part_val, c->part_idx, lm_parts, mpad, c->pos, c->step_ticket, st, nb, ne, tf);
+                wh_launch_argmax_finish(s, prec, c->part_val, c->part_idx, lm_parts, mpad, c->pos, c->step_ticket, st, nb, ne, tf, lp ? c->lp_part_sum : nullptr);
             }
+        }
+        if (probe) {   // softmax(v)[no_speech] over this prompt position's unfiltered logits (no mask, no rules, nothing recorded)
+            int parts;
+            {
+                Prof pr(c, WH_KG_DEC_GEMM);
+                SkinnyArgs a;
+                a.W = m->lm_w; a.bias = m->lm_c; a.ln_s = m->lm_s; a.ln_part = c->lnpart; a.ln_tiles = ln_tiles_d;
+                a.M = nb; a.N = D.vocab; a.K = (int)d;
+                a.X = c->dxs; a.x_mpad = mpad;
+                a.pos_p = c->pos; a.n_prompt = P; a.mask_first = c->lp_mask_zero; a.mask_base = c->lp_mask_zero;
+                a.part_val = c->part_val; a.part_idx = c->part_idx; a.part_sum = c->lp_part_sum;
+                a.probe_id = (int)c->lp_no_speech; a.probe_out = c->lp_probe_v;
+                wh_launch_lm_head(s, prec, a);
+                parts = wh_lm_head_parts(prec, a);
+            }
+            Prof pr(c, WH_KG_DEC_OTHER);
+            wh_launch_nospeech_finish(s, c->part_val, c->lp_part_sum, parts, mpad, c->lp_probe_v, c->lp_ns, nb, c->pos);
         }
     };
     // Positions 0 .. P-1 (the prompt, the last of which emits the first token) are launched eagerly;
@@ -570,7 +594,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
     // reads the position from device memory, so the graph is position-independent.  The host then
     // pays one graph launch per token instead of ~50 kernel launches (src/main.rs:793-826 is one ORT
     // Run per token in the reference).
-    for (int step = 0; step < std::min(P, total_pos); step++) launch_step(step >= P - 1, true);
+    for (int step = 0; step < std::min(P, total_pos); step++) launch_step(step >= P - 1, true, lp_probe && step == c->lp_sot_index);
     const int remaining = total_pos - P;
     // with event timing on: every position is launched eagerly (stride 0/1), or only every stride-th one
     // (sampled live timing) while the others replay the graph
@@ -581,13 +605,14 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
         key.nb = nb; key.n_prompt = P; key.eot = (int)p->eot; key.n_forced = (int)p->n_forced;
         key.logits_rows = (int)logits_rows; key.d_logits = d_logits; key.d_sel = d_sel;
         if (c->ts_on) { key.ts_begin = (int)c->ts_begin; key.ts_max_init = c->ts_max_init; }
+        if (lp) key.lp_sum = c->lp_part_sum;
         if (!c->step_exec || !(c->step_key == key)) {
             drop_step_graph(c);   // nothing of it is in flight: every call ends with a stream synchronisation
             c->capturing = true;  // no event records inside the captured step
             hipGraph_t graph = nullptr;
             hipError_t ce = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
             if (ce == hipSuccess) {
-                launch_step(true, false);
+                launch_step(true, false, false);
                 ce = hipStreamEndCapture(s, &graph);
             }
             c->capturing = false;
@@ -616,7 +641,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
                 return fail(c, WH_ERR_HIP, "hipGraphLaunch failed: %s", hipGetErrorString(ge));
             }
         } else {
-            launch_step(true, false);
+            launch_step(true, false, false);
         }
         // diagnostic (profiles/README.md, rocprofv3 --pmc at whisper-large-v3 size): bound the number of dispatches in flight
         if (c->sync_every_pos) hipStreamSynchronize(s);
@@ -638,8 +663,23 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
     const double t0 = now_s();
     CTX_HIP(c, hipMemcpyAsync(toks.data(), c->out_tokens, toks.size() * 4, hipMemcpyDeviceToHost, s));
     CTX_HIP(c, hipMemcpyAsync(nout.data(), c->n_out, nb * 4, hipMemcpyDeviceToHost, s));
+    std::vector<float> lps, nsp;
+    if (lp) {
+        lps.resize((size_t)nb * ld);
+        CTX_HIP(c, hipMemcpyAsync(lps.data(), c->lp_tok, lps.size() * 4, hipMemcpyDeviceToHost, s));
+        if (lp_probe) {
+            nsp.resize(nb);
+            CTX_HIP(c, hipMemcpyAsync(nsp.data(), c->lp_ns, nb * 4, hipMemcpyDeviceToHost, s));
+        }
+    }
     CTX_HIP(c, hipStreamSynchronize(s));
     CTX_HIP(c, hipGetLastError());
+    if (lp) {   // kept for wh_get_logprobs: each clip's generated positions
+        for (int b = 0; b < nb; b++) c->lp_rows.emplace_back(lps.begin() + (size_t)b * ld + P, lps.begin() + (size_t)b * ld + nout[b]);
+        c->lp_ns_rows.insert(c->lp_ns_rows.end(), nsp.begin(), nsp.end());
+        c->lp_have = true;
+        c->lp_have_ns = lp_probe;
+    }
     for (int b = 0; b < nb; b++) {
         n_tokens_out[b] = (size_t)nout[b];
         for (int i = 0; i < nout[b]; i++) tokens_out[(size_t)b * tok_stride + i] = toks[(size_t)b * ld + i];
@@ -709,6 +749,10 @@ int finish_timing(wh_ctx* c, double t_start) {
 }
 
 int check_params(wh_ctx* c, const wh_decode_params* p) {
+    // (every decode entry passes here once, first: what wh_get_logprobs returns belongs to the call that starts now)
+    c->lp_have = c->lp_have_ns = false;
+    c->lp_rows.clear();
+    c->lp_ns_rows.clear();
     if (!p) return fail(c, WH_ERR_ARG, "decode params are NULL");
     if ((p->n_suppress && !p->suppress) || (p->n_begin_suppress && !p->begin_suppress) || (p->n_forced && !p->forced))
         return fail(c, WH_ERR_ARG, "decode params: NULL list with non-zero length");
@@ -1113,6 +1157,62 @@ int wh_ctx_set_timestamp_rules(wh_ctx* c, const wh_timestamp_rules* r) {
     return WH_OK;
 }
 
+// Token log-probabilities and the no-speech probe on every decode entry of the ctx.  The buffers are allocated the first
+// time it is turned on; the captured decode step is keyed on the setting (other kernels, one more argument).
+int wh_ctx_set_logprobs(wh_ctx* c, const wh_logprob_opts* o) {
+    if (!c) return WH_ERR_ARG;
+    if (!o) {
+        c->lp_on = false;
+        return WH_OK;
+    }
+    if (o->struct_size != sizeof(wh_logprob_opts)) return fail(c, WH_ERR_ARG, "wh_ctx_set_logprobs: struct_size %zu, expected %zu", o->struct_size, sizeof(wh_logprob_opts));
+    const int vocab = c->m->dims.vocab;
+    if (o->no_speech < -1 || o->no_speech >= vocab) return fail(c, WH_ERR_ARG, "wh_ctx_set_logprobs: no_speech %lld outside the vocabulary (%d)", (long long)o->no_speech, vocab);
+    if (o->sot_index < 0) return fail(c, WH_ERR_ARG, "wh_ctx_set_logprobs: negative sot_index");
+    if (!c->lp_buf) {
+        auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+        const size_t MP = (size_t)c->mpad, B = (size_t)c->max_batch, n_tiles = ((size_t)vocab + 15) / 16;
+        const size_t b_sum = up(MP * (n_tiles + 4) * 4), b_tok = up(B * c->tok_ld * 4), b_mask = up(((size_t)vocab / 32 + 1) * 4), b_pv = up(MP * 4), b_ns = up(B * 4);
+        hipSetDevice(c->m->device);
+        char* buf = nullptr;
+        hipError_t e = hipMalloc((void**)&buf, b_sum + b_tok + b_mask + b_pv + b_ns);
+        if (e == hipSuccess) e = hipMemset(buf, 0, b_sum + b_tok + b_mask + b_pv + b_ns);
+        if (e != hipSuccess) {
+            if (buf) hipFree(buf);
+            return fail(c, WH_ERR_NOMEM, "wh_ctx_set_logprobs: hipMalloc: %s", hipGetErrorString(e));
+        }
+        c->lp_buf = buf;
+        c->lp_part_sum = (float*)buf;
+        c->lp_tok = (float*)(buf + b_sum);
+        c->lp_mask_zero = (unsigned*)(buf + b_sum + b_tok);
+        c->lp_probe_v = (float*)(buf + b_sum + b_tok + b_mask);
+        c->lp_ns = (float*)(buf + b_sum + b_tok + b_mask + b_pv);
+    }
+    c->lp_on = true;
+    c->lp_no_speech = o->no_speech;
+    c->lp_sot_index = o->sot_index;
+    return WH_OK;
+}
+
+int wh_get_logprobs(const wh_ctx* c, float* token_logprobs, size_t cap_tokens, float* no_speech_prob, size_t cap_clips, size_t* n_clips_out) {
+    if (!c) return WH_ERR_ARG;
+    if (!c->lp_have) return WH_ERR_STATE;
+    const size_t n = c->lp_rows.size();
+    if (n_clips_out) *n_clips_out = n;
+    if (no_speech_prob && !c->lp_have_ns) return WH_ERR_STATE;
+    if ((token_logprobs || no_speech_prob) && cap_clips < n) return WH_ERR_ARG;
+    if (token_logprobs) {
+        for (size_t b = 0; b < n; b++)
+            if (c->lp_rows[b].size() > cap_tokens) return WH_ERR_ARG;
+        for (size_t b = 0; b < n; b++) {
+            std::fill(token_logprobs + b * cap_tokens, token_logprobs + (b + 1) * cap_tokens, 0.0f);
+            std::copy(c->lp_rows[b].begin(), c->lp_rows[b].end(), token_logprobs + b * cap_tokens);
+        }
+    }
+    if (no_speech_prob) std::copy(c->lp_ns_rows.begin(), c->lp_ns_rows.end(), no_speech_prob);
+    return WH_OK;
+}
+
 void wh_ctx_free(wh_ctx* c) {
     if (!c) return;
     hipSetDevice(c->m->device);
@@ -1137,6 +1237,7 @@ void wh_ctx_free(wh_ctx* c) {
     if (c->logits) hipFree(c->logits);
     if (c->ts_logits) hipFree(c->ts_logits);
     if (c->ts_state) hipFree(c->ts_state);
+    if (c->lp_buf) hipFree(c->lp_buf);
     if (c->s_copy) { hipStreamSynchronize(c->s_copy); hipStreamDestroy(c->s_copy); }
     if (c->ev_h2d) hipEventDestroy(c->ev_h2d);
     if (c->pcm2) hipFree(c->pcm2);

@@ -379,7 +379,60 @@ __device__ __forceinline__ void ts_take(float v, int n, bool sup, int tb, int te
     }
 }
 
-#define WH_HIP_CHECK(expr)                                                                      \
+// ---- token log-probabilities in the LM head's epilogue (the LP variants) --------------------------------------------------
+// The recorded token is the argmax of the allowed ids, so its log-probability is -log(sum of exp(v - max)) over them: the kernels carry a
+// (max, sum) pair wherever they carry a (max, index) pair.  NaN and -inf logits add nothing, as they never win the argmax.
+// online form, one logit: (m, s) is the running pair; m itself is moved by the caller's argmax (same condition: v > m)
+__device__ __forceinline__ void lp_acc(float v, float m, float& s) {
+    if (v > m) s = s * ts_exp(m - v) + 1.0f;
+    else if (v > -INFINITY) s += ts_exp(v - m);
+}
+// a sum relative to the maximum m moved to the maximum mx >= m
+__device__ __forceinline__ float lp_rescale(float s, float m, float mx) { return m == -INFINITY ? 0.0f : s * ts_exp(m - mx); }
+// (m, s) += (m1, s1); m is left to the caller's argmax merge
+__device__ __forceinline__ float lp_merge(float m, float s, float m1, float s1) {
+    const float mx = fmaxf(m, m1);
+    return lp_rescale(s, m, mx) + lp_rescale(s1, m1, mx);
+}
+// sum over the four lane groups that share a row in the 16 x 16 MFMA result layout (lanes l, l + 16, l + 32, l + 48): every one of them gets it
+__device__ __forceinline__ float lp_row_sum(float s) {
+    typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
+    u32x2_t t = __builtin_amdgcn_permlane16_swap(__float_as_uint(s), __float_as_uint(s), false, false);
+    s = __uint_as_float(t.x) + __uint_as_float(t.y);
+    t = __builtin_amdgcn_permlane32_swap(__float_as_uint(s), __float_as_uint(s), false, false);
+    return __uint_as_float(t.x) + __uint_as_float(t.y);
+}
+// second pass over one row of a tile kernel's accumulators (still live after the argmax): the sum of exp(v - bv) over this lane's columns
+// that are not suppressed and lie in [lo, hi), bv = the row's maximum over exactly those columns.  Branch-free: one v_exp_f32 and a select per
+// logit.  The column tests do not depend on the row; left to themselves they are hoisted out of the caller's unrolled row loop as sixteen
+// live lane masks (scalar-register spills), so the lane's first column and mask words pass through an empty asm per row and are tested again.
+// PROBE: the logit of column probe_id, if it is one of this lane's, goes to *probe.
+template <int TN, bool PROBE>
+__device__ __forceinline__ float lp_tile_row(const f32x4 (&acc)[TN], bool ln, float mean, float rstd, const float (&sv)[TN][4], const float (&cv)[TN][4],
+                                             const unsigned (&mbits)[TN], int n_first, int lo, int hi, float bv, int probe_id, float* probe) {
+    float s = 0.0f, pv = 0.0f;
+    asm volatile("" : "+v"(n_first));
+#pragma unroll
+    for (int j = 0; j < TN; j++) {
+        unsigned mb = mbits[j];
+        asm volatile("" : "+v"(mb));
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const int nn = n_first + j * 16 + e;
+            const float v = ln ? wh_ln_fold(acc[j][e], mean, rstd, sv[j][e], cv[j][e]) : acc[j][e];
+            if constexpr (PROBE) pv = (nn == probe_id) ? v : pv;
+            const bool ok = !((mb >> e) & 1u) && nn >= lo && nn < hi && v > -INFINITY;   // (NaN: not greater)
+            s += ok ? ts_exp(v - bv) : 0.0f;
+        }
+    }
+    if constexpr (PROBE) {
+        const int rel = probe_id - n_first;
+        if (rel >= 0 && rel < TN * 16 && (rel & 15) < 4) *probe = pv;
+    }
+    return s;
+}
+
+#define WH_HIP_CHECK(expr)                                                                     \
     do {                                                                                        \
         hipError_t _e = (expr);                                                                 \
         if (_e != hipSuccess) return wh_fail_hip(_e, #expr, __FILE__, __LINE__);                \

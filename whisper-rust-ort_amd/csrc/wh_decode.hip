@@ -565,7 +565,10 @@ __global__ __launch_bounds__(NW * 64, 2) void k_dec_gemm_wide(SkinnyArgs a) {
 // embedding matrix with all of a tile's weight fragments in flight before its first MFMA.
 // RULES: Whisper's timestamp rules (SkinnyArgs::ts_*): the masked argmax covers the allowed text ids only, the timestamp logits go to
 // SkinnyArgs::ts_logits for k_argmax_finish<T, true>; the logits are the same expression (the rules-off instantiations are unchanged).
-template <typename T, int MT, bool RULES = false>
+// LP: token log-probabilities (SkinnyArgs::part_sum): beside each (max, index) partial the sum of exp(v - max) over the ids the
+// partial ranged over, kept online per lane (a tile's accumulators are gone once the next tile starts) and merged over the row's four lane
+// groups; the logit of SkinnyArgs::probe_id goes to probe_out (the no-speech probe).  The LP = false instantiations are unchanged.
+template <typename T, int MT, bool RULES = false, bool LP = false>
 __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
     extern __shared__ __attribute__((aligned(128))) char smem_raw[];   // 128: h2 tiles find their 32-blocks from the address
     constexpr int EPC = 16 / (int)sizeof(T);
@@ -638,6 +641,11 @@ __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
     int biw[MT];
 #pragma unroll
     for (int t = 0; t < MT; t++) { bvw[t] = -INFINITY; biw[t] = 0x7fffffff; }
+    float lsw[LP ? MT : 1];   // LP: sum of exp(v - bvw[t]) over the ids bvw[t] ranged over
+    if constexpr (LP) {
+#pragma unroll
+        for (int t = 0; t < MT; t++) lsw[t] = 0.0f;
+    }
     // RULES: the allowed ranges of each of this lane's rows
     int tlo[MT], slo[MT], shi[MT];
     if constexpr (RULES) {
@@ -697,6 +705,11 @@ __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
                         if (slot >= 0) a.logits[((long)slot * a.logits_rows + gen) * a.N + nn] = v;
                     }
                     const bool sup = (mbits >> e) & 1u;
+                    if constexpr (LP) {
+                        if (nn == a.probe_id) a.probe_out[m] = v;
+                        const bool text_ok = RULES ? (!sup && nn >= tlo[t] && nn < a.ts_begin) : !sup;
+                        if (text_ok) lp_acc(v, bvw[t], lsw[t]);   // (before the argmax below moves bvw[t])
+                    }
                     if constexpr (RULES) {
                         if (tile * 16 + 16 <= a.ts_begin) { if (!sup && nn >= tlo[t] && v > bvw[t]) { bvw[t] = v; biw[t] = nn; } }   // text-only tile
                         else ts_take(v, nn, sup, a.ts_begin, tlo[t], slo[t], shi[t], bvw[t], biw[t], a.ts_logits + (long)m * a.ts_ld);
@@ -744,6 +757,10 @@ __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
         bv = take1 ? v1 : v0;
         bi = take1 ? i1 : i0;
         const int m = m0 + t * 16 + fl;
+        if constexpr (LP) {   // this lane's sum moved to the row's maximum, then the four lane groups' sums added
+            const float ls = lp_row_sum(lp_rescale(lsw[t], bvw[t], bv));
+            if (fg == 0 && m < a.M) a.part_sum[(long)part * a.x_mpad + m] = ls;
+        }
         if (fg == 0 && m < a.M) {
             a.part_val[(long)part * a.x_mpad + m] = bv;
             a.part_idx[(long)part * a.x_mpad + m] = bi;
@@ -756,16 +773,21 @@ __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
 // RULES (ts.rules): the text partials of k_lm_head*<RULES> are merged as above; the row's allowed timestamp logits (ts.ts_logits) are reduced
 // to their (max, index, sum of exp); step 5 of the timestamp rules picks between the two (timestamps only when the log-sum-exp of the allowed
 // timestamps exceeds the best allowed text logit), and the next position's allowed ranges are written from the token fed next.
-template <typename T, bool RULES = false>
+// LP (part_sum): the (max, sum of exp) pairs of the LM head's LP variants are merged beside the (max, index) pairs; the recorded token's
+// log-probability, -log(sum of exp(v - max) over the allowed ids), goes to st.logprob next to the token.  With RULES the text side and the
+// timestamp side are combined by what rule 5 decided: timestamps only -> the timestamp log-sum-exp alone.
+template <typename T, bool RULES = false, bool LP = false>
 __global__ __launch_bounds__(256) void k_argmax_finish(const float* __restrict__ part_val,
                                                        const int* __restrict__ part_idx, int n_tiles, int mpad, int* pos_p,
-                                                       int* ticket, DecodeState st, NextEmbed ne, TsFinish ts) {
+                                                       int* ticket, DecodeState st, NextEmbed ne, TsFinish ts, const float* __restrict__ part_sum) {
     __shared__ float sv[256];
     __shared__ int si[256];
+    __shared__ float ssum[LP ? 256 : 1];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int pos = *pos_p;
     float bv = -INFINITY;
     int bi = 0x7fffffff;
+    float bs = 0.0f;   // LP: sum of exp(v - bv)
     for (int i0 = tid; i0 < n_tiles; i0 += 256 * 8) {   // n_tiles = number of partials per row, layout [part][mpad]
         float v[8];
         int ix[8];
@@ -776,12 +798,26 @@ __global__ __launch_bounds__(256) void k_argmax_finish(const float* __restrict__
             ix[u] = 0x7fffffff;
             if (i < n_tiles) { v[u] = part_val[(long)i * mpad + b]; ix[u] = part_idx[(long)i * mpad + b]; }
         }
+        if constexpr (LP) {   // eight sums folded pairwise at their common maximum, then into the running pair
+            float sm[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) sm[u] = (i0 + u * 256 < n_tiles) ? part_sum[(long)(i0 + u * 256) * mpad + b] : 0.0f;
+            float mx = v[0];
+#pragma unroll
+            for (int u = 1; u < 8; u++) mx = fmaxf(mx, v[u]);
+            float r[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) r[u] = lp_rescale(sm[u], v[u], mx);
+            bs = lp_merge(bv, bs, mx, ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7])));
+        }
 #pragma unroll
         for (int u = 0; u < 8; u++)
             if (v[u] > bv || (v[u] == bv && ix[u] < bi)) { bv = v[u]; bi = ix[u]; }
     }
     sv[tid] = bv; si[tid] = bi;
+    if constexpr (LP) ssum[tid] = bs;
     int rule_tok = 0;
+    float lp = -INFINITY;   // LP: the recorded token's log-probability (nothing allowed: -inf)
     if constexpr (RULES) {
         __shared__ float stm[256], sts[256];
         __shared__ int sti[256];
@@ -794,6 +830,7 @@ __global__ __launch_bounds__(256) void k_argmax_finish(const float* __restrict__
         for (int s = 128; s > 0; s >>= 1) {
             if (tid < s) {
                 float ov = sv[tid + s]; int oi = si[tid + s];
+                if constexpr (LP) ssum[tid] = lp_merge(sv[tid], ssum[tid], ov, ssum[tid + s]);
                 if (ov > sv[tid] || (ov == sv[tid] && oi < si[tid])) { sv[tid] = ov; si[tid] = oi; }
                 float m1 = stm[tid], s1 = sts[tid];
                 int i1 = sti[tid];
@@ -809,15 +846,22 @@ __global__ __launch_bounds__(256) void k_argmax_finish(const float* __restrict__
             if (lse > text_v) w = sti[0];                                          // step 5: every id below tb is suppressed
             else w = (ts_v > text_v || (ts_v == text_v && sti[0] < si[0])) ? sti[0] : si[0];   // step 6 over both
             rule_tok = (w == 0x7fffffff) ? 0 : w;
+            if constexpr (LP) {
+                if (w != 0x7fffffff) lp = -logf(lse > text_v ? sts[0] : lp_merge(text_v, ssum[0], ts_v, sts[0]));
+            }
         }
     } else {
         __syncthreads();
         for (int s = 128; s > 0; s >>= 1) {
             if (tid < s) {
                 float ov = sv[tid + s]; int oi = si[tid + s];
+                if constexpr (LP) ssum[tid] = lp_merge(sv[tid], ssum[tid], ov, ssum[tid + s]);
                 if (ov > sv[tid] || (ov == sv[tid] && oi < si[tid])) { sv[tid] = ov; si[tid] = oi; }
             }
             __syncthreads();
+        }
+        if constexpr (LP) {
+            if (tid == 0 && si[0] != 0x7fffffff) lp = -logf(ssum[0]);
         }
     }
     if (tid == 0) {
@@ -828,6 +872,7 @@ __global__ __launch_bounds__(256) void k_argmax_finish(const float* __restrict__
         if (!st.done[b]) {
             st.out_tokens[b * st.tok_ld + st.n_prompt + gen] = tok;
             st.n_out[b] = st.n_prompt + gen + 1;
+            if constexpr (LP) st.logprob[b * st.tok_ld + st.n_prompt + gen] = lp;
             const bool forced = gen < st.n_forced;
             if (forced) next = st.forced[gen];
             else if (tok == st.eot) st.done[b] = 1;
@@ -894,6 +939,35 @@ __global__ __launch_bounds__(256) void k_argmax_finish(const float* __restrict__
         }
     }
     advance_if_last(ticket, pos_p, gridDim.x);
+}
+
+// The no-speech probe's finish: row b's (max, sum of exp) partials of an LP launch of the LM head over the unfiltered logits of
+// a prompt position -> softmax(v)[no_speech] = exp(probe_v[b] - max - log(sum)).  One wave per row.  The probe's prompt step does not advance the
+// position through its last GEMM's ticket (the LM head above still reads it): block 0 does it here, nothing in this kernel reads it.
+__global__ __launch_bounds__(64) void k_nospeech_finish(const float* __restrict__ part_val, const float* __restrict__ part_sum, int n_parts, int mpad,
+                                                        const float* __restrict__ probe_v, float* __restrict__ prob, int* pos_p) {
+    __shared__ float sm[64], ss[64];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    float m = -INFINITY, s = 0.0f;
+    for (int i = tid; i < n_parts; i += 64) {
+        const float m1 = part_val[(long)i * mpad + b], s1 = part_sum[(long)i * mpad + b];
+        s = lp_merge(m, s, m1, s1);
+        m = fmaxf(m, m1);
+    }
+    sm[tid] = m; ss[tid] = s;
+    __syncthreads();
+    for (int h = 32; h > 0; h >>= 1) {
+        if (tid < h) {
+            const float m1 = sm[tid + h];
+            ss[tid] = lp_merge(sm[tid], ss[tid], m1, ss[tid + h]);
+            sm[tid] = fmaxf(sm[tid], m1);
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        prob[b] = sm[0] == -INFINITY ? 0.0f : expf(probe_v[b] - sm[0] - logf(ss[0]));
+        if (b == 0) *pos_p += 1;
+    }
 }
 
 // ---- decoder self-attention, one position ([3P] :417-425, 468-475): one wave per (head, clip) ---
@@ -1429,7 +1503,7 @@ void wh_launch_dec_embed(hipStream_t s, int prec, const void* tok_emb, const flo
         hipLaunchKernelGGL(k_dec_embed<bf16>, grid, dim3(256), 0, s, (const bf16*)tok_emb, pos_emb, feed, feed_ld, pos_p, x, (bf16*)xslab, stats, rows, d, mpad, xgamma, shift);
 }
 
-template <typename T, bool RULES = false>
+template <typename T, bool RULES = false, bool LP = false>
 void launch_lm_head_t(hipStream_t s, const SkinnyArgs& a, int* n_parts_out = nullptr) {
     const int n_tiles = (a.N + 15) / 16;
     int mt = std::min(wh_dbg_lm_mt, (a.M + 15) / 16);
@@ -1444,7 +1518,7 @@ void launch_lm_head_t(hipStream_t s, const SkinnyArgs& a, int* n_parts_out = nul
     if (n_parts_out) { *n_parts_out = (int)grid.x * 4; return; }  // query only: partials per row = waves per row group
 #define WH_LM(MT_)                                                \
     {                                                             \
-        auto kfn = k_lm_head<T, MT_, RULES>;                      \
+        auto kfn = k_lm_head<T, MT_, RULES, LP>;                  \
         set_max_smem(kfn, sm);                                    \
         hipLaunchKernelGGL(kfn, grid, dim3(256), sm, s, a);       \
     }
@@ -1459,17 +1533,23 @@ void launch_lm_head_t(hipStream_t s, const SkinnyArgs& a, int* n_parts_out = nul
 
 // a.X = final-LayerNorm'ed rows [M][K] in the compute dtype
 // a.ts_logits != nullptr: the timestamp-rules variants (same logits, same partial count)
+// a.part_sum != nullptr: the log-probability variants (same logits, same (max, index) partials)
+template <typename T>
+static void launch_lm_head_v(hipStream_t s, const SkinnyArgs& a) {
+    const bool r = a.ts_logits != nullptr, l = a.part_sum != nullptr;
+    if (r && l) launch_lm_head_t<T, true, true>(s, a);
+    else if (r) launch_lm_head_t<T, true>(s, a);
+    else if (l) launch_lm_head_t<T, false, true>(s, a);
+    else launch_lm_head_t<T>(s, a);
+}
 void wh_launch_lm_head(hipStream_t s, int prec, const SkinnyArgs& a) {
-    const bool r = a.ts_logits != nullptr;
-    if (prec == WH_PREC_F32) { if (r) launch_lm_head_t<float, true>(s, a); else launch_lm_head_t<float>(s, a); }
+    if (prec == WH_PREC_F32) launch_lm_head_v<float>(s, a);
     else if (prec == WH_PREC_F16X3) {
         if (wh_lm_head_tile_x3_applicable(a)) wh_launch_lm_head_tile_x3(s, a);
-        else if (r) launch_lm_head_t<h2, true>(s, a);
-        else launch_lm_head_t<h2>(s, a);
+        else launch_lm_head_v<h2>(s, a);
     }
     else if (wh_lm_head_tile_applicable(a)) wh_launch_lm_head_tile(s, a);   // hundreds of rows: 256 x 256 tiles (wh_gemm8.hip), same logits
-    else if (r) launch_lm_head_t<bf16, true>(s, a);
-    else launch_lm_head_t<bf16>(s, a);
+    else launch_lm_head_v<bf16>(s, a);
 }
 
 // number of argmax partials per row the LM head writes for this shape (its layout is [part][x_mpad])
@@ -1482,18 +1562,25 @@ int wh_lm_head_parts(int prec, const SkinnyArgs& a) {
     return n;
 }
 
-template <bool RULES>
+template <bool RULES, bool LP>
 void launch_argmax_finish_t(hipStream_t s, int prec, const float* part_val, const int* part_idx, int n_parts, int mpad, int* pos_p,
-                            int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts) {
-    if (prec == WH_PREC_F16X3) hipLaunchKernelGGL((k_argmax_finish<h2, RULES>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts);
-    else if (prec == WH_PREC_F32) hipLaunchKernelGGL((k_argmax_finish<float, RULES>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts);
-    else hipLaunchKernelGGL((k_argmax_finish<bf16, RULES>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts);
+                            int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts, const float* part_sum) {
+    if (prec == WH_PREC_F16X3) hipLaunchKernelGGL((k_argmax_finish<h2, RULES, LP>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum);
+    else if (prec == WH_PREC_F32) hipLaunchKernelGGL((k_argmax_finish<float, RULES, LP>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum);
+    else hipLaunchKernelGGL((k_argmax_finish<bf16, RULES, LP>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum);
 }
 
 void wh_launch_argmax_finish(hipStream_t s, int prec, const float* part_val, const int* part_idx, int n_parts, int mpad, int* pos_p,
-                             int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts) {
-    if (ts.rules) launch_argmax_finish_t<true>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts);
-    else launch_argmax_finish_t<false>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts);
+                             int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts, const float* part_sum) {
+    if (ts.rules && part_sum) launch_argmax_finish_t<true, true>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum);
+    else if (ts.rules) launch_argmax_finish_t<true, false>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum);
+    else if (part_sum) launch_argmax_finish_t<false, true>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum);
+    else launch_argmax_finish_t<false, false>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum);
+}
+
+void wh_launch_nospeech_finish(hipStream_t s, const float* part_val, const float* part_sum, int n_parts, int mpad, const float* probe_v,
+                               float* prob, int B, int* pos_p) {
+    hipLaunchKernelGGL(k_nospeech_finish, dim3(B), dim3(64), 0, s, part_val, part_sum, n_parts, mpad, probe_v, prob, pos_p);
 }
 
 void wh_launch_dec_self_attn(hipStream_t s, int prec, const void* qkv, void* kc, void* vc, void* out, const int* pos_p,

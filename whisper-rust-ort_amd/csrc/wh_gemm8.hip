@@ -418,7 +418,9 @@ __global__ __launch_bounds__(512, Geo<BN>::WAVES_PER_SIMD) void k_gemm8(GemmArgs
 // LayerNorm partial sums reduced in the same order, the same epilogue expression — so the launcher may pick by the call's
 // row count (tests/test_hip_parity.py::test_wide_batch_decode_gemm_is_bit_identical runs both).
 // RULES: Whisper's timestamp rules in the epilogue (k_lm_head<T, MT, true>'s contract: text partials, timestamp logits to SkinnyArgs::ts_logits).
-template <bool RULES = false>
+// LP: token log-probabilities (k_lm_head<T, MT, RULES, true>'s contract: SkinnyArgs::part_sum, probe_id / probe_out).  No running maximum in the
+// column loop: once a row's maximum is known, a second pass over the row's accumulators adds exp(v - max).
+template <bool RULES = false, bool LP = false>
 __global__ __launch_bounds__(512, 2) void k_lm_head_tile(SkinnyArgs a) {
     typedef Geo<256> G;
     constexpr int BN = 256, TM = G::TM, TN = G::TN, NSLOT = G::NSLOT, SLOT = G::SLOT, SLOT_A = G::SLOT_A;
@@ -574,6 +576,7 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile(SkinnyArgs a) {
     }
     float* red_v = reinterpret_cast<float*>(smem);            // [4][256] — every wave is past the last barrier of the main loop
     int* red_i = reinterpret_cast<int*>(smem) + G::WN * BM;
+    float* red_s = reinterpret_cast<float*>(smem) + 2 * G::WN * BM;   // LP: [4][256] sum of exp(v - red_v)
 #pragma unroll
     for (int i = 0; i < TM; i++) {
         const int rloc = wm * (TM * 16) + i * 16 + fl, m = m0 + rloc;
@@ -624,21 +627,43 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile(SkinnyArgs a) {
             red_i[wn * BM + rloc] = bi;
         }
     }
+    if constexpr (LP) {
+        // The rows' maxima are known: a second pass over the accumulators adds exp(v - max) over the same ids.  A loop of its own (inside the
+        // loop above the two passes of neighbouring rows overlap and the rules variant spills); each row's maximum comes back from LDS, where
+        // this wave's own lanes put it (the rules variant has no probe: the probe runs rules-off).
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < TM; i++) {
+            const int rloc = wm * (TM * 16) + i * 16 + fl, m = m0 + rloc;
+            const float mean = a.ln_part ? lnstat[2 * rloc] : 0.0f, rstd = a.ln_part ? lnstat[2 * rloc + 1] : 1.0f;
+            const float bv = red_v[wn * BM + rloc];
+            int tlo = 0;
+            if constexpr (RULES) tlo = tsr[4 * rloc];
+            const float ls = lp_row_sum(lp_tile_row<TN, !RULES>(acc[i], a.ln_part != nullptr, mean, rstd, sv, cv, mbits, nw0 + 4 * fg, tlo,
+                                                                RULES ? min(a.ts_begin, a.N) : a.N, bv, m < a.M ? a.probe_id : -1, a.probe_out + m));
+            if (fg == 0) red_s[wn * BM + rloc] = ls;
+        }
+    }
     __syncthreads();
     // one partial per (column tile, row): 203 instead of 812 partials per row for k_argmax_finish to read (strided by the row pitch)
     if (tid < BM && m0 + tid < a.M) {
         float bv = red_v[tid];
         int bi = red_i[tid];
+        float ls = LP ? red_s[tid] : 0.0f;
 #pragma unroll
         for (int w = 1; w < G::WN; w++) {
             const float v1 = red_v[w * BM + tid];
             const int i1 = red_i[w * BM + tid];
+            if constexpr (LP) ls = lp_merge(bv, ls, v1, red_s[w * BM + tid]);
             const bool take1 = v1 > bv || (v1 == bv && i1 < bi);
             bv = take1 ? v1 : bv;
             bi = take1 ? i1 : bi;
         }
         a.part_val[(long)ct * a.x_mpad + m0 + tid] = bv;
         a.part_idx[(long)ct * a.x_mpad + m0 + tid] = bi;
+        if constexpr (LP) a.part_sum[(long)ct * a.x_mpad + m0 + tid] = ls;
     }
 }
 
@@ -693,13 +718,17 @@ void wh_launch_lm_head_tile(hipStream_t s, const SkinnyArgs& a) {
     typedef Geo<256> G;
     const size_t sm = (size_t)G::NSLOT * G::SLOT + (size_t)BM * 2 * 4 * 5 + (a.ts_logits ? (size_t)BM * 16 : 0);   // ring + LayerNorm statistics ([256][2] + four quarter sums) + RULES: the rows' ranges ([256][4])
     dim3 grid(((a.N + 255) / 256) * ((a.M + BM - 1) / BM));
-    if (a.ts_logits) {   // the timestamp-rules variant
-        wh_ensure_dyn_lds((const void*)k_lm_head_tile<true>, sm);
-        hipLaunchKernelGGL(k_lm_head_tile<true>, grid, dim3(512), sm, s, a);
-        return;
+#define WH_LM_TILE(R_, L_)                                                         \
+    {                                                                              \
+        wh_ensure_dyn_lds((const void*)k_lm_head_tile<R_, L_>, sm);               \
+        hipLaunchKernelGGL((k_lm_head_tile<R_, L_>), grid, dim3(512), sm, s, a);  \
     }
-    wh_ensure_dyn_lds((const void*)k_lm_head_tile<false>, sm);
-    hipLaunchKernelGGL(k_lm_head_tile<false>, grid, dim3(512), sm, s, a);
+    // a.ts_logits: the timestamp-rules variants; a.part_sum: the log-probability variants
+    if (a.ts_logits && a.part_sum) WH_LM_TILE(true, true)
+    else if (a.ts_logits) WH_LM_TILE(true, false)
+    else if (a.part_sum) WH_LM_TILE(false, true)
+    else WH_LM_TILE(false, false)
+#undef WH_LM_TILE
 }
 
 void wh_launch_ln_stats(hipStream_t s, const float* partials, int groups, long rows, int d, float* stat, float* shift, const float* shift_in) {

@@ -205,9 +205,10 @@ struct wh_ctx {
         const float* d_logits = nullptr;
         const int* d_sel = nullptr;
         int ts_begin = -1, ts_max_init = -1;   // timestamp rules: -1 = off (other kernels, other arguments)
+        const float* lp_sum = nullptr;         // token log-probabilities: nullptr = off (other kernels, other arguments)
         bool operator==(const StepKey& o) const {
             return nb == o.nb && n_prompt == o.n_prompt && eot == o.eot && n_forced == o.n_forced && logits_rows == o.logits_rows &&
-                   d_logits == o.d_logits && d_sel == o.d_sel && ts_begin == o.ts_begin && ts_max_init == o.ts_max_init;
+                   d_logits == o.d_logits && d_sel == o.d_sel && ts_begin == o.ts_begin && ts_max_init == o.ts_max_init && lp_sum == o.lp_sum;
         }
     } step_key;
     // Whisper's timestamp rules (wh_ctx_set_timestamp_rules): off unless ts_on.  The timestamp logits and the per-row state
@@ -218,6 +219,22 @@ struct wh_ctx {
     float* ts_logits = nullptr; // [mpad][ts_ld] allowed timestamp logits of the current position (-inf: not allowed)
     int ts_ld = 0;              // vocab - timestamp_begin
     int* ts_state = nullptr;    // [mpad][4] {text_lo, ts_lo, ts_hi, last timestamp}
+    // Token log-probabilities and the no-speech probe (wh_ctx_set_logprobs): off unless lp_on.  One allocation made by the setter
+    // (not part of the workspace carve), freed in wh_ctx_free: the (max, sum) partials' sums, the tokens' log-probabilities, an all-zero
+    // suppress mask, the probe's logit and its result.
+    bool lp_on = false;
+    int64_t lp_no_speech = -1;
+    int lp_sot_index = 0;
+    char* lp_buf = nullptr;
+    float* lp_part_sum = nullptr;   // [part][mpad], beside part_val / part_idx
+    float* lp_tok = nullptr;        // [max_batch][tok_ld], DecodeState::logprob
+    unsigned* lp_mask_zero = nullptr;
+    float* lp_probe_v = nullptr;    // [mpad] logit of no_speech at the probed position
+    float* lp_ns = nullptr;         // [max_batch] no-speech probability
+    // what wh_get_logprobs returns: the last decode call's clips in the order their tokens were returned (a long-form call: every device batch)
+    bool lp_have = false, lp_have_ns = false;
+    std::vector<std::vector<float>> lp_rows;
+    std::vector<float> lp_ns_rows;
     hipGraph_t step_graph = nullptr;
     hipGraphExec_t step_exec = nullptr;
 };

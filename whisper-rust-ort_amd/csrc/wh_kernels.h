@@ -142,6 +142,12 @@ struct SkinnyArgs {
     float* ts_logits = nullptr;
     int ts_ld = 0;
     int ts_begin = 0, ts_max_init = -1;
+    // Token log-probabilities (the LP variants of the LM head): part_sum [part][x_mpad], beside part_val / part_idx, holds the sum of
+    // exp(v - part_val) over the ids the partial ranged over (rules off: the unsuppressed ids; rules on: the allowed text ids).  probe_id >= 0:
+    // the logit of that id of every row goes to probe_out [M] whatever the masks say (the no-speech probe).
+    float* part_sum = nullptr;
+    int probe_id = -1;
+    float* probe_out = nullptr;
 };
 
 // the finish kernel's side of the timestamp rules (rules == false: not applied)
@@ -175,6 +181,7 @@ struct DecodeState {
     int n_prompt = 0;
     int eot = 0;
     int tok_ld = 0;
+    float* logprob = nullptr;   // [B][tok_ld], indexed like out_tokens: the log-probability of each recorded token (k_argmax_finish<T, RULES, true>)
 };
 
 void wh_build_mel_tables(int n_mels, std::vector<double>& tw, std::vector<float>& win, std::vector<float>& fbT);
@@ -237,7 +244,12 @@ int wh_lm_head_tile_x3_parts(const SkinnyArgs& a);
 void wh_launch_lm_head_tile_x3(hipStream_t s, const SkinnyArgs& a);
 int wh_lm_head_parts(int prec, const SkinnyArgs& a);  // argmax partials per row written by wh_launch_lm_head, layout [part][x_mpad]
 void wh_launch_argmax_finish(hipStream_t s, int prec, const float* part_val, const int* part_idx, int n_parts, int mpad, int* pos_p,
-                             int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts = TsFinish());
+                             int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts = TsFinish(),
+                             const float* part_sum = nullptr);   // part_sum: the log-probability variant (writes st.logprob)
+// the no-speech probe's finish: prob[b] = exp(probe_v[b] - log-sum-exp of row b's (part_val, part_sum) partials); advances the position
+// (the probe's prompt step leaves that to this kernel)
+void wh_launch_nospeech_finish(hipStream_t s, const float* part_val, const float* part_sum, int n_parts, int mpad, const float* probe_v,
+                               float* prob, int B, int* pos_p);
 void wh_launch_dec_self_attn(hipStream_t s, int prec, const void* qkv, void* kc, void* vc, void* out, const int* pos_p,
                              int d, int n_heads, int tc, int B, int mpad);
 // stream_nt: non-temporal K/V loads (set when the cross K/V of all layers exceed what the Infinity Cache can keep)

@@ -157,7 +157,18 @@ inline JVal stat_json(const StatBlock& s) {
 struct RowOut {
     std::string file; double duration_s, end_to_end_s, rtf; std::string text;
     std::string segments;   // JSON array of {start, end, text} (--timestamp-rules), empty: no key
+    bool has_conf = false;  // --logprobs: avg_logprob and no_speech_prob keys
+    double avg_logprob = 0, no_speech_prob = 0;
 };
+
+// avg_logprob / no_speech_prob in JSON: shortest text that reads back as the same float (the library's values are floats); a window in which
+// nothing was allowed has avg_logprob -inf, which JSON cannot hold: null
+inline std::string fmt_conf(double v) {
+    if (!std::isfinite(v)) return "null";
+    char b[48];
+    snprintf(b, sizeof b, "%.9g", v);
+    return b;
+}
 
 inline double round_to(double v, double scale) { return std::round(v * scale) / scale; }  // f64::round: half away from zero
 
@@ -203,6 +214,7 @@ inline std::string per_file_json(const std::vector<RowOut>& rows) {  // :1232 to
         r.set("file", JVal::str(rows[i].file)).set("duration_s", JVal::num(rows[i].duration_s))
             .set("end_to_end_s", JVal::num(rows[i].end_to_end_s)).set("rtf", JVal::num(rows[i].rtf))
             .set("text", JVal::str(rows[i].text));
+        if (rows[i].has_conf) { JVal v; v.raw = fmt_conf(rows[i].avg_logprob); r.set("avg_logprob", v); v.raw = fmt_conf(rows[i].no_speech_prob); r.set("no_speech_prob", v); }
         if (!rows[i].segments.empty()) { JVal sg; sg.raw = rows[i].segments; r.set("segments", sg); }
         o += "  ";
         r.write(o, 2);
@@ -359,7 +371,7 @@ inline bool load_tokenizer(const std::string& path, Tokenizer& t) {
     return true;
 }
 
-struct WhisperSpecial { int64_t sot, eot, lang, task, no_timestamps, timestamp_begin; };
+struct WhisperSpecial { int64_t sot, eot, lang, task, no_timestamps, timestamp_begin, no_speech; };
 
 inline WhisperSpecial special_tokens(const std::string& language, const std::string& task, const Tokenizer* tok) {
     if (tok && tok->loaded) {  // :529-541
@@ -369,9 +381,14 @@ inline WhisperSpecial special_tokens(const std::string& language, const std::str
             return it->second;
         };
         WhisperSpecial s{get("<|startoftranscript|>"), get("<|endoftext|>"), get("<|" + language + "|>"), get("<|" + task + "|>"),
-                         get("<|notimestamps|>"), 0};
+                         get("<|notimestamps|>"), 0, 0};
         auto ts = tok->special.find("<|0.00|>");   // <|0.00|> if the tokenizer lists it, else the id after <|notimestamps|>
         s.timestamp_begin = ts != tok->special.end() ? ts->second : s.no_timestamps + 1;
+        s.no_speech = s.no_timestamps - 1;   // <|nospeech|> (<|nocaptions|> in the older vocabularies) if the tokenizer lists it, else the id before <|notimestamps|>
+        for (const char* name : {"<|nospeech|>", "<|nocaptions|>"}) {
+            auto ns = tok->special.find(name);
+            if (ns != tok->special.end()) { s.no_speech = ns->second; break; }
+        }
         return s;
     }
     WhisperSpecial s;  // :549-566 hard-coded multilingual ids
@@ -380,11 +397,69 @@ inline WhisperSpecial special_tokens(const std::string& language, const std::str
     s.task = task == "transcribe" ? 50359 : task == "translate" ? 50358 : 50359;
     s.no_timestamps = 50363;
     s.timestamp_begin = 50364;
+    s.no_speech = s.no_timestamps - 1;   // 50362
     return s;
 }
 
+// ---- the CLI's --synthetic-clips input ------------------------------------------------------------------------------------------------
+// deterministic in-memory clip (SURVEY §8d config 3 shape): three enveloped sinusoids (80-4000 Hz) + noise of standard
+// deviation 0.02, clipped to [-1, 1].  Built for speed, because the loader threads have to keep a GPU fed that transcribes
+// ~900 clips per second: oscillators and the 4 Hz raised-cosine envelope advance by complex rotation in float (re-seeded
+// from sin/cos every 1024 samples so the recurrence cannot drift), the noise is a 4-term Irwin-Hall sum (four 16-bit
+// uniforms from one splitmix64 draw, variance-matched to N(0,1)): ~3 ms per 30 s clip on one host core.
+inline std::vector<float> synthetic_clip(uint64_t seed) {
+    uint64_t st = seed * 0x9E3779B97F4A7C15ull + 1;
+    auto next64 = [&]() { st += 0x9E3779B97F4A7C15ull; uint64_t z = st; z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 27; z *= 0x94D049BB133111EBull; z ^= z >> 31; return z; };
+    auto u01 = [&]() { return (double)(next64() >> 11) / 9007199254740992.0; };
+    double fr[4], ph[4];
+    for (int j = 0; j < 3; j++) { fr[j] = 80.0 + 3920.0 * u01(); ph[j] = 2 * M_PI * u01(); }
+    fr[3] = 4.0; ph[3] = 0.0;   // envelope 0.5 - 0.5 cos(2 pi 4 t)
+    std::vector<float> x(480000);   // one 30 s window
+    float re[4], im[4], cr[4], ci[4];
+    for (int j = 0; j < 4; j++) { const double w = 2 * M_PI * fr[j] / 16000.0; cr[j] = (float)cos(w); ci[j] = (float)sin(w); }
+    const float nscale = 0.02f * 1.7320508f / 32768.0f;   // sum of 4 U(-1/2,1/2) has variance 1/3
+    for (size_t i = 0; i < x.size(); i++) {
+        if ((i & 1023) == 0)
+            for (int j = 0; j < 4; j++) { const double a = 2 * M_PI * fr[j] * ((double)i / 16000.0) + ph[j]; re[j] = (float)cos(a); im[j] = (float)sin(a); }
+        const float s = im[0] + im[1] + im[2], env = 0.5f - 0.5f * re[3];
+        const uint64_t r = next64();
+        const int sum4 = (int)(r & 0xFFFF) + (int)((r >> 16) & 0xFFFF) + (int)((r >> 32) & 0xFFFF) + (int)(r >> 48) - 2 * 65535;
+        const float v = 0.25f * s * env + nscale * (float)sum4 * 0.5f;
+        x[i] = std::max(-1.0f, std::min(1.0f, v));
+        for (int j = 0; j < 4; j++) { const float nr = re[j] * cr[j] - im[j] * ci[j]; im[j] = re[j] * ci[j] + im[j] * cr[j]; re[j] = nr; }
+    }
+    return x;
+}
+
 // ---- timestamped segments (Whisper's timestamp tokens, openai-whisper's slicing rule) ---------------------------------------------------
-struct Segment { double start = 0, end = 0; std::vector<int64_t> tokens; };   // tokens: the text ids (no timestamp) of the segment
+struct Segment {
+    double start = 0, end = 0;
+    std::vector<int64_t> tokens;   // the text ids (no timestamp) of the segment
+    bool has_conf = false;         // avg_logprob / no_speech_prob supplied: its window's values (openai-whisper puts them on every segment of a window)
+    double avg_logprob = 0, no_speech_prob = 0;
+};
+// openai-whisper's sum_logprobs / (len(tokens) + 1) of one window: the sum runs over the generated tokens' log-probabilities up to and
+// including the first EOT, the length counts the tokens before it (a window cut at max_new_tokens has no EOT: every token counts)
+inline double avg_logprob(const std::vector<float>& logprobs, const std::vector<int64_t>& tokens, int64_t eot) {
+    double s = 0;
+    size_t n = 0;
+    for (size_t i = 0; i < logprobs.size() && i < tokens.size(); i++) {
+        s += (double)logprobs[i];
+        if (tokens[i] == eot) break;
+        n++;
+    }
+    return s / (double)(n + 1);
+}
+// openai-whisper's silence rule for one window: skipped (empty text, no segments) when no_speech_prob > no_speech_threshold and avg_logprob <
+// logprob_threshold.  A NaN threshold is off: without a no-speech threshold nothing is skipped, without a log-probability threshold the
+// no-speech test decides alone.  openai's defaults are 0.6 and -1.0.
+inline bool skip_window(double no_speech_prob, double avg_lp, double no_speech_threshold, double logprob_threshold) {
+    if (std::isnan(no_speech_threshold) || !(no_speech_prob > no_speech_threshold)) return false;
+    return std::isnan(logprob_threshold) || avg_lp < logprob_threshold;
+}
+inline void set_conf(std::vector<Segment>& segs, double avg_lp, double no_speech_prob) {
+    for (Segment& s : segs) { s.has_conf = true; s.avg_logprob = avg_lp; s.no_speech_prob = no_speech_prob; }
+}
 constexpr double kTimePrecision = 0.02;   // seconds per timestamp step
 
 // Generated tokens of one 30 s window (the prompt left out; everything from the first EOT on is dropped) -> segments:
@@ -465,7 +540,10 @@ inline std::string fmt_cue_time(double t, char sep) {
     snprintf(b, sizeof b, "%02lld:%02lld:%02lld%c%03lld", ms / 3600000, (ms / 60000) % 60, (ms / 1000) % 60, sep, ms % 1000);
     return b;
 }
-struct Cue { double start, end; std::string text; };
+struct Cue {
+    double start, end; std::string text;
+    bool has_conf = false; double avg_logprob = 0, no_speech_prob = 0;   // its segment's (--logprobs)
+};
 inline std::string srt_text(const std::vector<Cue>& cues) {
     std::string o;
     for (size_t i = 0; i < cues.size(); i++)
@@ -476,7 +554,8 @@ inline std::string cues_json(const std::vector<Cue>& cues) {   // [{"start": s, 
     std::string o = "[";
     for (size_t i = 0; i < cues.size(); i++)
         o += (i ? ", " : "") + std::string("{\"start\": ") + fmt_f64(cues[i].start) + ", \"end\": " + fmt_f64(cues[i].end) + ", \"text\": " +
-             json_escape(cues[i].text) + "}";
+             json_escape(cues[i].text) +
+             (cues[i].has_conf ? ", \"avg_logprob\": " + fmt_conf(cues[i].avg_logprob) + ", \"no_speech_prob\": " + fmt_conf(cues[i].no_speech_prob) : std::string()) + "}";
     return o + "]";
 }
 inline std::string vtt_text(const std::vector<Cue>& cues) {

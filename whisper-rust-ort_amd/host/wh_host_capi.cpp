@@ -84,12 +84,35 @@ static std::string segments_json(const std::vector<Segment>& segs) {
         snprintf(b, sizeof b, "%s{\"start\": %.6f, \"end\": %.6f, \"tokens\": [", i ? ", " : "", segs[i].start, segs[i].end);
         o += b;
         for (size_t j = 0; j < segs[i].tokens.size(); j++) o += (j ? ", " : "") + std::to_string(segs[i].tokens[j]);
-        o += "]}";
+        o += "]";
+        if (segs[i].has_conf) o += ", \"avg_logprob\": " + fmt_conf(segs[i].avg_logprob) + ", \"no_speech_prob\": " + fmt_conf(segs[i].no_speech_prob);   // only when supplied
+        o += "}";
     }
     return o + "]";
 }
 size_t whh_segments_json(const long long* toks, size_t n, long long tb, long long eot, double duration, char* out, size_t cap) {
     return put(segments_json(split_segments(std::vector<int64_t>(toks, toks + n), tb, eot, duration)), out, cap);
+}
+// the same with the window's avg_logprob / no_speech_prob on each of its segments
+size_t whh_segments_conf_json(const long long* toks, size_t n, long long tb, long long eot, double duration, double avg_lp, double no_speech_prob,
+                              char* out, size_t cap) {
+    std::vector<Segment> segs = split_segments(std::vector<int64_t>(toks, toks + n), tb, eot, duration);
+    set_conf(segs, avg_lp, no_speech_prob);
+    return put(segments_json(segs), out, cap);
+}
+double whh_avg_logprob(const float* logprobs, const long long* toks, size_t n, long long eot) {
+    return avg_logprob(std::vector<float>(logprobs, logprobs + n), std::vector<int64_t>(toks, toks + n), eot);
+}
+// the silence rule the CLI applies (wh_host.h skip_window; a NaN threshold is off)
+int whh_skip_window(double no_speech_prob, double avg_lp, double no_speech_threshold, double logprob_threshold) {
+    return skip_window(no_speech_prob, avg_lp, no_speech_threshold, logprob_threshold) ? 1 : 0;
+}
+long long whh_no_speech_token(const char* language, const char* task, const char* tokenizer_json) {
+    try {
+        Tokenizer t;
+        if (tokenizer_json && *tokenizer_json) load_tokenizer(tokenizer_json, t);
+        return special_tokens(language, task, t.loaded ? &t : nullptr).no_speech;
+    } catch (...) { return -1; }
 }
 // long-form: the windows' generated tokens back to back (lens[k] each), window starts and durations in seconds
 size_t whh_longform_segments_json(const long long* toks, const size_t* lens, size_t n_windows, const double* starts, const double* durations,
@@ -124,6 +147,12 @@ int whh_special_tokens(const char* language, const char* task, const char* token
         out5[0] = s.sot; out5[1] = s.eot; out5[2] = s.lang; out5[3] = s.task; out5[4] = s.no_timestamps;
         return 0;
     } catch (...) { return 1; }
+}
+// clip `seed` of the CLI's --synthetic-clips input (file i of a run is clip --seed + i): 480000 samples
+size_t whh_synthetic_clip(unsigned long long seed, float* out, size_t cap) {
+    std::vector<float> x = synthetic_clip(seed);
+    if (out) memcpy(out, x.data(), std::min(cap, x.size()) * sizeof(float));
+    return x.size();
 }
 int whh_load_wav(const char* path, float* out, size_t cap, size_t* n, double* dur) {
     try {

@@ -33,6 +33,9 @@ struct Args {
     bool write_txt = false, timestamps = false;
     // additive: Whisper's timestamp rules in the token loop, segments in the per-file JSON; SRT / VTT files (imply the rules)
     bool timestamp_rules = false, write_srt = false, write_vtt = false;
+    // additive: avg_logprob / no_speech_prob in the per-file JSON (wh_ctx_set_logprobs); the thresholds of openai-whisper's silence rule (NaN: off)
+    bool logprobs = false;
+    double no_speech_threshold = std::nan(""), logprob_threshold = std::nan("");
     std::string tokenizer_json;
     size_t chunk_parallelism = 0;
     float chunk_length_s = 30.0f, overlap_s = 5.0f;
@@ -84,6 +87,7 @@ static bool parse_args(int argc, char** argv, Args& a) {
         else if (k == "--timestamp-rules") a.timestamp_rules = true;
         else if (k == "--write-srt") a.write_srt = a.timestamp_rules = true;
         else if (k == "--write-vtt") a.write_vtt = a.timestamp_rules = true;
+        else if (k == "--logprobs") a.logprobs = true;
         else if (k == "--print-plan") a.print_plan = true;
         else if (k == "--help" || k == "-h") {
             printf("Usage: whisper_bench [--audio-dir DIR] [--model-id ID] [--onnx-dir DIR|synthetic:<preset>:<seed>] [--language en] "
@@ -91,7 +95,11 @@ static bool parse_args(int argc, char** argv, Args& a) {
                    "[--out-csv F] [--out-json F] [--out-summary-json F] [--intra-op N] [--inter-op N] [--write-txt] "
                    "[--tokenizer-json F] [--timestamps] [--chunk-parallelism N] [--chunk-length-s 30] [--overlap-s 5] "
                    "[--device 0] [--devices 0-7] [--streams-per-gpu 1] [--load-threads N] [--precision bf16|f32|fp8|f16x3] [--max-batch 16] "
-                   "[--synthetic-clips N] [--seed 1000] [--print-plan] [--timestamp-rules] [--write-srt] [--write-vtt]\n");
+                   "[--synthetic-clips N] [--seed 1000] [--print-plan] [--timestamp-rules] [--write-srt] [--write-vtt] "
+                   "[--logprobs] [--no-speech-threshold X] [--logprob-threshold Y]\n"
+                   "  --logprobs               avg_logprob and no_speech_prob in every row of the per-file JSON (and in its segments)\n"
+                   "  --no-speech-threshold X  with --logprob-threshold Y: a window with no_speech_prob > X and avg_logprob < Y becomes empty text and\n"
+                   "  --logprob-threshold Y    no segments (both off unless given, each implies --logprobs; openai-whisper's defaults are 0.6 and -1.0)\n");
             exit(0);
         } else {
             if (!need(i, argv[i], v, inl)) return false;
@@ -120,6 +128,8 @@ static bool parse_args(int argc, char** argv, Args& a) {
             else if (k == "--precision") a.precision = v;
             else if (k == "--max-batch") a.max_batch = atoi(v.c_str());
             else if (k == "--synthetic-clips") a.synthetic_clips = strtoull(v.c_str(), nullptr, 10);
+            else if (k == "--no-speech-threshold") { a.no_speech_threshold = strtod(v.c_str(), nullptr); a.logprobs = true; }
+            else if (k == "--logprob-threshold") { a.logprob_threshold = strtod(v.c_str(), nullptr); a.logprobs = true; }
             else if (k == "--seed") a.seed = strtoull(v.c_str(), nullptr, 10);
             else { fprintf(stderr, "error: unexpected argument '%s'\n", k.c_str()); return false; }
         }
@@ -190,35 +200,6 @@ static GenCfg load_generation_cfg(const std::string& path) {  // src/main.rs:650
     return g;
 }
 
-// deterministic in-memory clip (SURVEY §8d config 3 shape): three enveloped sinusoids (80-4000 Hz) + noise of standard
-// deviation 0.02, clipped to [-1, 1].  Built for speed, because the loader threads have to keep a GPU fed that transcribes
-// ~900 clips per second: oscillators and the 4 Hz raised-cosine envelope advance by complex rotation in float (re-seeded
-// from sin/cos every 1024 samples so the recurrence cannot drift), the noise is a 4-term Irwin-Hall sum (four 16-bit
-// uniforms from one splitmix64 draw, variance-matched to N(0,1)): ~3 ms per 30 s clip on one host core.
-static std::vector<float> synthetic_clip(uint64_t seed) {
-    uint64_t st = seed * 0x9E3779B97F4A7C15ull + 1;
-    auto next64 = [&]() { st += 0x9E3779B97F4A7C15ull; uint64_t z = st; z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 27; z *= 0x94D049BB133111EBull; z ^= z >> 31; return z; };
-    auto u01 = [&]() { return (double)(next64() >> 11) / 9007199254740992.0; };
-    double fr[4], ph[4];
-    for (int j = 0; j < 3; j++) { fr[j] = 80.0 + 3920.0 * u01(); ph[j] = 2 * M_PI * u01(); }
-    fr[3] = 4.0; ph[3] = 0.0;   // envelope 0.5 - 0.5 cos(2 pi 4 t)
-    std::vector<float> x(WH_CLIP_SAMPLES);
-    float re[4], im[4], cr[4], ci[4];
-    for (int j = 0; j < 4; j++) { const double w = 2 * M_PI * fr[j] / 16000.0; cr[j] = (float)cos(w); ci[j] = (float)sin(w); }
-    const float nscale = 0.02f * 1.7320508f / 32768.0f;   // sum of 4 U(-1/2,1/2) has variance 1/3
-    for (size_t i = 0; i < x.size(); i++) {
-        if ((i & 1023) == 0)
-            for (int j = 0; j < 4; j++) { const double a = 2 * M_PI * fr[j] * ((double)i / 16000.0) + ph[j]; re[j] = (float)cos(a); im[j] = (float)sin(a); }
-        const float s = im[0] + im[1] + im[2], env = 0.5f - 0.5f * re[3];
-        const uint64_t r = next64();
-        const int sum4 = (int)(r & 0xFFFF) + (int)((r >> 16) & 0xFFFF) + (int)((r >> 32) & 0xFFFF) + (int)(r >> 48) - 2 * 65535;
-        const float v = 0.25f * s * env + nscale * (float)sum4 * 0.5f;
-        x[i] = std::max(-1.0f, std::min(1.0f, v));
-        for (int j = 0; j < 4; j++) { const float nr = re[j] * cr[j] - im[j] * ci[j]; im[j] = re[j] * ci[j] + im[j] * cr[j]; re[j] = nr; }
-    }
-    return x;
-}
-
 // A model id of the form org/name that was downloaded earlier has its files under
 // $HF_HOME/hub/models--org--name/snapshots/<revision>/ ($HF_HOME defaults to $HOME/.cache/huggingface): the tokenizer.json of
 // the most recently modified snapshot directory that holds one (reference src/main.rs:597-633).  "" when there is none.
@@ -279,7 +260,7 @@ static std::vector<Cue> to_cues(const std::vector<Segment>& segs, const Tokenize
     std::vector<Cue> c;
     for (const Segment& s : segs) {
         std::string text = trim(decode_tokens(s.tokens, tok));
-        if (!text.empty()) c.push_back(Cue{s.start, s.end, text});   // (a slice between two timestamp pairs may hold no text)
+        if (!text.empty()) c.push_back(Cue{s.start, s.end, text, s.has_conf, s.avg_logprob, s.no_speech_prob});   // (a slice between two timestamp pairs may hold no text)
     }
     return c;
 }
@@ -291,8 +272,40 @@ static std::vector<int64_t> text_ids(const std::vector<int64_t>& g, int64_t tb) 
     return o;
 }
 
+// --logprobs: what a file's row carries.  One window: its avg_logprob and no_speech_prob.  Several windows (long-form): the windows' summed
+// log-probabilities over their summed lengths + 1 each, and the mean of their no-speech probabilities.
+struct Conf {
+    bool has = false;
+    double sum_lp = 0, len = 0, sum_ns = 0;
+    size_t windows = 0;
+    void add(double avg_lp, size_t n_tokens, double ns) { has = true; sum_lp += avg_lp * (double)(n_tokens + 1); len += (double)(n_tokens + 1); sum_ns += ns; windows++; }
+    double avg_logprob() const { return len > 0 ? sum_lp / len : 0.0; }
+    double no_speech_prob() const { return windows ? sum_ns / (double)windows : 0.0; }
+};
+// the last decode call's log-probabilities ([n][max_new_tokens], 0 past a window's end) and no-speech probabilities
+static void fetch_logprobs(wh_ctx* ctx, size_t n, size_t max_new, std::vector<float>& lp, std::vector<float>& ns) {
+    lp.assign(std::max<size_t>(1, n) * max_new, 0.0f);
+    ns.assign(std::max<size_t>(1, n), 0.0f);
+    size_t got = 0;
+    if (int rc = wh_get_logprobs(ctx, lp.data(), max_new, ns.data(), n, &got))
+        throw std::runtime_error(std::string("wh_get_logprobs: ") + std::to_string(rc));
+    if (got != n) throw std::runtime_error("wh_get_logprobs: " + std::to_string(got) + " windows, expected " + std::to_string(n));
+}
+// one window under --logprobs: its avg_logprob (over the generated tokens `g`, EOT still on them), the silence rule; returns true if the window is
+// to be skipped
+static bool window_conf(const Args& a, const std::vector<int64_t>& g, const float* lp, double ns, int64_t eot, Conf& conf, double& avg_lp) {
+    avg_lp = avg_logprob(std::vector<float>(lp, lp + g.size()), g, eot);
+    size_t n = 0;
+    while (n < g.size() && g[n] != eot) n++;
+    conf.add(avg_lp, n, ns);
+    return skip_window(ns, avg_lp, a.no_speech_threshold, a.logprob_threshold);
+}
+static void cues_conf(std::vector<Cue>& cues, double avg_lp, double ns) {
+    for (Cue& c : cues) { c.has_conf = true; c.avg_logprob = avg_lp; c.no_speech_prob = ns; }
+}
+
 static std::string transcribe(wh_ctx* ctx, const std::vector<float>& audio, const Args& a, const Tokenizer* tok,
-                              const GenCfg& gen, Timing& t, std::vector<Cue>* cues = nullptr) {
+                              const GenCfg& gen, Timing& t, std::vector<Cue>* cues = nullptr, Conf* conf = nullptr) {
     const double t0 = now_s();
     WhisperSpecial sp = special_tokens(a.language, a.task, tok);
     std::vector<int64_t> prompt = {sp.sot, sp.lang, sp.task};
@@ -314,6 +327,8 @@ static std::string transcribe(wh_ctx* ctx, const std::vector<float>& audio, cons
     wh_get_timings(ctx, &wt);
     t.preprocess_s = wt.preprocess_s;
     t.model_only_s = wt.encode_s + wt.decode_s;
+    std::vector<float> lps, nss;
+    if (a.logprobs) fetch_logprobs(ctx, got, a.max_new_tokens, lps, nss);
     const double td0 = now_s();
     std::vector<std::string> texts;
     std::vector<size_t> offs(std::max<size_t>(1, got));
@@ -323,14 +338,19 @@ static std::string transcribe(wh_ctx* ctx, const std::vector<float>& audio, cons
     for (size_t c = 0; c < got; c++) {  // :926-943
         std::vector<int64_t> g;
         if (ntok[c] > prompt.size()) g.assign(toks.begin() + c * stride + prompt.size(), toks.begin() + c * stride + ntok[c]);
+        double avg_lp = 0;
+        Conf unused;
+        const bool skip = a.logprobs && window_conf(a, g, lps.data() + c * a.max_new_tokens, nss[c], sp.eot, conf ? *conf : unused, avg_lp);
+        if (skip) g.clear();   // the silence rule: empty text, no segments
         if (!g.empty() && g.back() == sp.eot) g.pop_back();
         if (a.timestamp_rules) {
             const size_t len = std::min<size_t>(audio.size() - offs[c], (size_t)std::llround(a.chunk_length_s * 16000.0));
-            wsegs.push_back(window_segments(g, sp, (double)len / 16000.0));
+            wsegs.push_back(skip ? std::vector<Segment>() : window_segments(g, sp, (double)len / 16000.0));
+            if (a.logprobs) set_conf(wsegs.back(), avg_lp, nss[c]);
             wstart.push_back((double)offs[c] / 16000.0);
             g = text_ids(g, sp.timestamp_begin);
         }
-        std::string text = decode_tokens(g, tok);
+        std::string text = skip ? std::string() : decode_tokens(g, tok);
         if (text.empty()) text = "[EMPTY]";
         if (text != "[EMPTY]") texts.push_back(text);
     }
@@ -406,6 +426,12 @@ int main(int argc, char** argv) {
                     if (int rc = wh_ctx_set_timestamp_rules(c, &tr))
                         throw std::runtime_error(std::string("wh_ctx_set_timestamp_rules: ") + std::to_string(rc) + ": " + wh_last_error(c));
                 }
+                if (a.logprobs) {   // token log-probabilities and the no-speech probe at <|startoftranscript|> (prompt position 0)
+                    WhisperSpecial sp = special_tokens(a.language, a.task, &tok);
+                    wh_logprob_opts lo{sizeof(wh_logprob_opts), sp.no_speech, 0};
+                    if (int rc = wh_ctx_set_logprobs(c, &lo))
+                        throw std::runtime_error(std::string("wh_ctx_set_logprobs: ") + std::to_string(rc) + ": " + wh_last_error(c));
+                }
                 ctxs.push_back(c);
             }
         }
@@ -448,7 +474,7 @@ int main(int argc, char** argv) {
                             return hipHostMalloc((void**)&p, (size_t)WH_CLIP_SAMPLES * sizeof(float), hipHostMallocDefault) == hipSuccess ? p : nullptr;
                         },
                         [](float* p) { (void)hipHostFree(p); });
-        struct Result { std::string text; double dur = 0, load_s = 0; Timing t; bool ok = false; std::vector<Cue> cues; };
+        struct Result { std::string text; double dur = 0, load_s = 0; Timing t; bool ok = false; std::vector<Cue> cues; Conf conf; };
         const size_t nfiles = files.size();
         std::vector<Result> results(nfiles);
         const unsigned hc = std::thread::hardware_concurrency();
@@ -464,7 +490,7 @@ int main(int argc, char** argv) {
             if (batch.size() == 1 && batch[0].n() > (size_t)WH_CLIP_SAMPLES) {
                 // a file longer than one window goes alone through the long-form entry (which batches its windows)
                 Result& r = results[batch[0].idx];
-                r.text = transcribe(ctx, batch[0].audio, a, &tok, gen, r.t, &r.cues);
+                r.text = transcribe(ctx, batch[0].audio, a, &tok, gen, r.t, &r.cues, &r.conf);
                 r.dur = batch[0].dur; r.load_s = batch[0].load_s; r.ok = true;
             } else {
                 // the per-window body of transcribe_longform_chunked (:870-915) for a batch of one-window files
@@ -484,17 +510,23 @@ int main(int argc, char** argv) {
                 const double batch_s = now_s() - t0;
                 wh_timing wt{};
                 wh_get_timings(ctx, &wt);
+                std::vector<float> lps, nss;
+                if (a.logprobs) fetch_logprobs(ctx, batch.size(), a.max_new_tokens, lps, nss);
                 for (size_t k = 0; k < batch.size(); k++) {   // :926-943
                     Result& r = results[batch[k].idx];
                     const double td0 = now_s();
                     std::vector<int64_t> g;
                     if (ntok[k] > prompt.size()) g.assign(toks.begin() + k * stride + prompt.size(), toks.begin() + k * stride + ntok[k]);
+                    double avg_lp = 0;
+                    const bool skip = a.logprobs && window_conf(a, g, lps.data() + k * a.max_new_tokens, nss[k], sp.eot, r.conf, avg_lp);
+                    if (skip) g.clear();   // the silence rule: empty text, no segments
                     if (!g.empty() && g.back() == sp.eot) g.pop_back();
                     if (a.timestamp_rules) {
-                        r.cues = to_cues(window_segments(g, sp, batch[k].dur), &tok);
+                        if (!skip) r.cues = to_cues(window_segments(g, sp, batch[k].dur), &tok);
+                        if (a.logprobs) cues_conf(r.cues, avg_lp, nss[k]);
                         g = text_ids(g, sp.timestamp_begin);
                     }
-                    std::string text = decode_tokens(g, &tok);
+                    std::string text = skip ? std::string() : decode_tokens(g, &tok);
                     if (text.empty()) text = "[EMPTY]";
                     std::vector<std::string> texts;
                     if (text != "[EMPTY]") texts.push_back(text);
@@ -526,6 +558,7 @@ int main(int argc, char** argv) {
             const double end_to_end = r.load_s + r.t.end_to_end_s;   // :1190
             rows.push_back(make_row(files[i], r.dur, end_to_end, r.text));
             if (a.timestamp_rules) rows.back().segments = cues_json(r.cues);
+            if (r.conf.has) { rows.back().has_conf = true; rows.back().avg_logprob = r.conf.avg_logprob(); rows.back().no_speech_prob = r.conf.no_speech_prob(); }
             loadl.push_back(r.load_s); pre.push_back(r.t.preprocess_s); model_only.push_back(r.t.model_only_s);
             dec.push_back(r.t.decode_s); e2e.push_back(end_to_end); rtfl.push_back(end_to_end / std::max(r.dur, 1e-9));
             audio_total += r.dur;
@@ -561,6 +594,7 @@ int main(int argc, char** argv) {
                             .set("wall_s", JVal::num(loop_s)).set("throughput_rtfx", JVal::num(audio_total / std::max(loop_s, 1e-12)))
                             .set("gpu_busy_s", JVal::num(busy_max)).set("gpu_throughput_rtfx", JVal::num(audio_total / std::max(busy_max, 1e-12))));
         if (a.timestamp_rules) summary.set("timestamp_rules", JVal::boolean(true));
+        if (a.logprobs) summary.set("logprobs", JVal::boolean(true));
         write_file(a.out_summary_json, summary.pretty());
         printf("DONE\n");  // :1261-1268
         printf("Config used:\n%s\n", cfg.json(false).pretty().c_str());
