@@ -203,6 +203,37 @@ int wh_ctx_set_logprobs(wh_ctx* c, const wh_logprob_opts* o);
  * cap_tokens must hold the longest clip's generated tokens.  no_speech_prob [n] (may be NULL; WH_ERR_STATE if asked for without a probe).
  * token_logprobs == NULL: only *n_clips_out.  WH_ERR_STATE if the call ran with log-probabilities off; WH_ERR_ARG if cap_clips < n. */
 int wh_get_logprobs(const wh_ctx* c, float* token_logprobs, size_t cap_tokens, float* no_speech_prob, size_t cap_clips, size_t* n_clips_out);
+/* Language detection in the greedy token loop, one language per clip (openai-whisper's detect_language; faster-whisper's language /
+ * language_probability / all_language_probs; HF generate without language=).  No reference entry corresponds: the reference takes --language
+ * from the command line (src/main.rs:851).  Detection in openai-whisper is a decoder pass over [sot] alone; the decoder is causal, so the logits
+ * at the sot position of the ordinary prompt pass are the same numbers and detection costs no extra decoder pass.  With this set, every decode
+ * entry of the ctx (wh_decode_greedy*, wh_transcribe_batch*, the device / pipelined entries, wh_transcribe_longform) computes, per clip:
+ *   - v = the unfiltered logits of prompt position sot_index (no suppress masks, no timestamp rules apply to it);
+ *   - probs[j] = exp(v[id_j] - m) / sum_k exp(v[id_k] - m) over the listed ids, m their maximum, in the order the caller listed them;
+ *     NaN logits are left out, as everywhere else in the loop: a NaN logit gets probability 0;
+ *   - the chosen language = the listed id with the largest logit; ties go to the lowest id (not the lowest list position); NaN never wins;
+ *   - nothing finite (every listed logit NaN or -inf): the lowest listed id is chosen and all probabilities are 0;
+ *   - the chosen id becomes the row's token at prompt position sot_index + 1: it is fed to the decoder there and appears there in tokens_out.
+ *     The caller's prompt[sot_index + 1] is a placeholder and is ignored (any value);
+ *   - everything after that position runs exactly as if the caller had passed that prompt for that clip.
+ * wh_transcribe_longform follows openai-whisper's transcribe(): the language of the file is the language of its first window, decoded into
+ * every window; wh_get_languages then reports that id and window 0's probabilities for every window.
+ * forced, the timestamp rules and the log-probabilities concern generated positions only and are untouched; the no-speech probe may sit at
+ * the same sot_index.  With detection off, tokens, logits and every other output are what they were without this entry.
+ * Refused with WH_ERR_ARG (the ctx unchanged): a wrong struct_size, n_lang outside 1 .. WH_MAX_LANGUAGES, an id outside [0, vocab), an id
+ * listed twice, a negative sot_index; at decode time (before anything is launched) sot_index + 1 >= n_prompt.  o == NULL turns it off (the default). */
+#define WH_MAX_LANGUAGES 128
+typedef struct {
+    size_t struct_size;       /* sizeof(wh_language_opts) */
+    const int64_t* lang_ids;  /* [n_lang] distinct ids in [0, vocab), any order; copied by the setter */
+    size_t n_lang;            /* 1 .. WH_MAX_LANGUAGES */
+    int32_t sot_index;        /* prompt position whose logits are read; the chosen id replaces prompt[sot_index + 1] of every clip */
+} wh_language_opts;
+int wh_ctx_set_language_detection(wh_ctx* c, const wh_language_opts* o);
+/* Of the last decode call on the ctx (any decode entry; every clip / window it returned tokens for, in that order): lang_out [n] the chosen
+ * ids, probs [n][n_lang] (may be NULL) the probabilities in list order.  lang_out == NULL: only *n_clips_out.  WH_ERR_STATE if the call ran
+ * with detection off; WH_ERR_ARG if cap_clips < n. */
+int wh_get_languages(const wh_ctx* c, int64_t* lang_out, float* probs, size_t cap_clips, size_t* n_clips_out);
 const char* wh_last_error(const wh_ctx* c); /* c == NULL: last load/create error of this thread */
 int wh_get_timings(const wh_ctx* c, wh_timing* out);
 

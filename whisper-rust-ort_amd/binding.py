@@ -34,7 +34,8 @@ EXPORTS = ("wh_model_load", "wh_model_create", "wh_model_free", "wh_model_get_di
            "wh_mel_frames", "wh_log_mel", "wh_encode", "wh_decode_greedy", "wh_decode_greedy_batch", "wh_decode_greedy_rows", "wh_transcribe_batch",
            "wh_transcribe_batch_next", "wh_transcribe_batch_device", "wh_transcribe_batch_device_next", "wh_longform_plan", "wh_transcribe_longform", "wh_profile_enable",
            "wh_profile_get", "wh_synthetic_weights", "wh_e4m3_quantize", "wh_e4m3_dequantize", "wh_abi_version",
-           "wh_device_count", "wh_ctx_set_timestamp_rules", "wh_ctx_set_logprobs", "wh_get_logprobs")
+           "wh_device_count", "wh_ctx_set_timestamp_rules", "wh_ctx_set_logprobs", "wh_get_logprobs",
+           "wh_ctx_set_language_detection", "wh_get_languages")
 
 
 class WhisperHipError(RuntimeError):
@@ -78,6 +79,11 @@ class WhLogprobOpts(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("no_speech", C.c_int64), ("sot_index", C.c_int32)]
 
 
+class WhLanguageOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("lang_ids", C.POINTER(C.c_int64)), ("n_lang", C.c_size_t), ("sot_index", C.c_int32)]
+
+
+WH_MAX_LANGUAGES = 128
 WH_CTX_TWO_STREAMS = 1
 WH_CTX_CROSS_ES_ON = 2
 WH_CTX_CROSS_ES_OFF = 4
@@ -148,6 +154,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.wh_ctx_set_timestamp_rules.argtypes = [vp, C.POINTER(WhTimestampRules)]
     L.wh_ctx_set_logprobs.argtypes = [vp, C.POINTER(WhLogprobOpts)]
     L.wh_get_logprobs.argtypes = [vp, f32p, C.c_size_t, f32p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.wh_ctx_set_language_detection.argtypes = [vp, C.POINTER(WhLanguageOpts)]
+    L.wh_get_languages.argtypes = [vp, i64p, f32p, C.c_size_t, C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -312,6 +320,29 @@ class Context:
             rc = self.lib.wh_get_logprobs(self.h, _f32(lp), cap, None, k, C.byref(n))
         self._check(rc)
         return [lp[i, : lens[i]].copy() for i in range(k)], (ns[:k] if ns is not None else None)
+
+    def set_language_detection(self, ids: Sequence[int], sot_index: int = 0):
+        """wh_ctx_set_language_detection: every decode entry of this context picks each clip's language among `ids` (distinct token ids, any
+        order) from the unfiltered logits of prompt position sot_index and decodes with it at prompt position sot_index + 1 (the prompt's
+        own token there is a placeholder)."""
+        a = np.ascontiguousarray(list(ids), np.int64)
+        o = WhLanguageOpts(C.sizeof(WhLanguageOpts), _i64(a) if a.size else None, a.size, sot_index)
+        self._check(self.lib.wh_ctx_set_language_detection(self.h, C.byref(o)))
+        self._n_lang = int(a.size)
+
+    def clear_language_detection(self):
+        self._check(self.lib.wh_ctx_set_language_detection(self.h, None))
+
+    def languages(self) -> Tuple[np.ndarray, np.ndarray]:
+        """wh_get_languages of the last decode call: (ids int64 [n], probs float32 [n, n_lang]) — one row per clip / window, the
+        probabilities in the order the ids were listed."""
+        n = C.c_size_t(0)
+        self._check(self.lib.wh_get_languages(self.h, None, None, 0, C.byref(n)))
+        k = int(n.value)
+        ids = np.zeros(max(1, k), np.int64)
+        probs = np.zeros((max(1, k), getattr(self, "_n_lang", WH_MAX_LANGUAGES)), np.float32)
+        self._check(self.lib.wh_get_languages(self.h, _i64(ids), _f32(probs), k, C.byref(n)))
+        return ids[:k], probs[:k]
 
     def _took(self, toks: List[np.ndarray], params: "DecodeParams") -> List[np.ndarray]:
         self._gen_lens = [len(t) - len(params.prompt) for t in toks]   # (what logprobs() cuts its rows to)
@@ -601,6 +632,8 @@ def load_host_library(path: str = HOST_LIB_PATH) -> C.CDLL:
         L.whh_skip_window.argtypes = [C.c_double] * 4
         L.whh_no_speech_token.argtypes = [C.c_char_p] * 3
         L.whh_no_speech_token.restype = C.c_longlong
+        L.whh_language_table.argtypes = [C.c_char_p, C.c_longlong, ll, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
+        L.whh_language_table.restype = C.c_longlong
         _host = L
     return _host
 
@@ -639,6 +672,17 @@ def skip_window(no_speech_prob: float, avg_lp: float, no_speech_threshold: Optio
 def no_speech_token(language: str = "en", task: str = "transcribe", tokenizer_json: str = "") -> int:
     """WhisperSpecial::no_speech: the tokenizer's <|nospeech|> / <|nocaptions|>, else the id before <|notimestamps|> (50362)."""
     return int(load_host_library().whh_no_speech_token(language.encode(), task.encode(), tokenizer_json.encode()))
+
+
+def language_table(vocab: int, tokenizer_json: str = "") -> Tuple[List[str], List[int]]:
+    """The CLI's --language auto table: (codes, token ids) — the tokenizer's <|xx|> tokens when one is given, else the multilingual block
+    from 50259 on (99 codes, 100 when the vocabulary has 51866 ids).  ValueError with the CLI's message when the vocabulary cannot hold it."""
+    ids = (C.c_longlong * WH_MAX_LANGUAGES)()
+    codes, err = C.create_string_buffer(1024), C.create_string_buffer(1024)
+    n = load_host_library().whh_language_table(tokenizer_json.encode(), vocab, ids, len(ids), codes, len(codes), err, len(err))
+    if n < 0:
+        raise ValueError(err.value.decode())
+    return codes.value.decode().split(","), [int(ids[i]) for i in range(n)]
 
 
 def split_segments(generated: Sequence[int], tb: int, eot: int, duration: float, avg_logprob: Optional[float] = None,

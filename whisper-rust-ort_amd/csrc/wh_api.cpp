@@ -304,15 +304,21 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
     if (P <= 0 || NEW <= 0 || !p->prompt) return fail(c, WH_ERR_ARG, "decode: empty prompt or max_new_tokens == 0");
     if (P + NEW > D.n_text_ctx) return fail(c, WH_ERR_ARG, "decode: prompt (%d) + max_new_tokens (%d) exceeds %d positions", P, NEW, D.n_text_ctx);
     if (p->n_forced > (size_t)NEW) return fail(c, WH_ERR_ARG, "decode: more forced tokens than max_new_tokens");
+    // language detection: per-row detection at prompt position lang_sot_index (lang_det), or — later batches of a long-form call — the
+    // language of the file's first window as an ordinary prompt token (lang_fix).  Either way the caller's prompt[lang_sot_index + 1] is a placeholder.
+    const bool lang_any = c->lang_on, lang_fix = lang_any && c->lang_fixed >= 0, lang_det = lang_any && !lang_fix;
+    const int lang_slot = lang_any ? c->lang_sot_index + 1 : -1;
+    if (lang_any && lang_slot >= P)
+        return fail(c, WH_ERR_ARG, "decode: language detection's sot_index %d + 1 is not below n_prompt (%d)", c->lang_sot_index, P);
     for (int i = 0; i < P; i++)
-        if (p->prompt[i] < 0 || p->prompt[i] >= D.vocab) return fail(c, WH_ERR_ARG, "decode: prompt id %lld outside the vocabulary", (long long)p->prompt[i]);
+        if (i != lang_slot && (p->prompt[i] < 0 || p->prompt[i] >= D.vocab)) return fail(c, WH_ERR_ARG, "decode: prompt id %lld outside the vocabulary", (long long)p->prompt[i]);
     for (size_t i = 0; i < p->n_forced; i++)
         if (p->forced[i] < 0 || p->forced[i] >= D.vocab) return fail(c, WH_ERR_ARG, "decode: forced id outside the vocabulary");
     if (c->ts_on) {   // timestamp rules: <|0.00|> must lie above EOT (so EOT and the specials are text ids) and inside the vocabulary
         if (c->ts_begin <= p->eot || c->ts_begin >= D.vocab)
             return fail(c, WH_ERR_ARG, "decode: timestamp_begin %lld outside (eot %lld, vocab %d)", (long long)c->ts_begin, (long long)p->eot, D.vocab);
         for (int i = 0; i < P; i++)
-            if (c->ts_no_ts >= 0 && p->prompt[i] == c->ts_no_ts) return fail(c, WH_ERR_ARG, "decode: the prompt holds <|notimestamps|> while timestamp rules are on");
+            if (i != lang_slot && c->ts_no_ts >= 0 && p->prompt[i] == c->ts_no_ts) return fail(c, WH_ERR_ARG, "decode: the prompt holds <|notimestamps|> while timestamp rules are on");
     }
     const bool lp = c->lp_on, lp_probe = lp && c->lp_no_speech >= 0;
     if (lp_probe && c->lp_sot_index >= P - 1)   // the probe reads a prompt position that emits nothing
@@ -325,7 +331,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
     const int ld = c->tok_ld;
     std::vector<int> feed((size_t)nb * ld, 0);
     for (int b = 0; b < nb; b++)
-        for (int i = 0; i < P; i++) feed[(size_t)b * ld + i] = (int)p->prompt[i];
+        for (int i = 0; i < P; i++) feed[(size_t)b * ld + i] = i == lang_slot ? (lang_fix ? (int)c->lang_fixed : 0) : (int)p->prompt[i];
     CTX_HIP(c, hipMemcpyAsync(c->feed, feed.data(), feed.size() * 4, hipMemcpyHostToDevice, s));
     CTX_HIP(c, hipMemcpyAsync(c->out_tokens, feed.data(), feed.size() * 4, hipMemcpyHostToDevice, s));
     std::vector<int> nout(nb, P);
@@ -437,7 +443,9 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
     int lm_parts = 0;
     // `probe`: a prompt position whose unfiltered logits the no-speech probe reads: the last fc2 leaves the position alone, the
     // LM head's log-probability variant runs with an all-zero mask, and the probe's finish kernel advances the position
-    auto launch_step = [&](bool emits, bool embed_first, bool probe) {
+    // `lang`: the prompt position whose logits language detection reads: the language head and its finish run before the probe (if
+    // the probe sits at the same position); the finish advances the position unless the probe's finish will
+    auto launch_step = [&](bool emits, bool embed_first, bool probe, bool lang = false) {
         if (embed_first) {   // token + position embedding → x, raw slab, row sums (one "tile")
             Prof pr(c, WH_KG_DEC_OTHER);
             wh_launch_dec_embed(s, prec, m->tok_emb, m->dec_pos, c->feed, ld, c->pos, c->dx, c->dxs, c->lnpart, nb, (int)d, mpad,
@@ -537,7 +545,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
                 a.X = c->dh; a.x_mpad = mpad; a.W = L.fc2_w; a.bias = L.fc2_b; a.wscale = L.fc2_sc; a.R = c->dx; a.ldr = d; a.C = c->dx; a.ldc = d;
                 a.M = nb; a.N = (int)d; a.K = (int)F; a.xslab_out = c->dxs; a.stats_out = c->lnpart; a.row_shift = c->dshift;
                 if (f8) a.xgamma = (l + 1 < D.dec_layers) ? m->dec[l + 1].ln1_w : m->dec_ln_w;  // next consumer's LayerNorm
-                if (!emits && !probe && l == D.dec_layers - 1) { a.ticket = c->step_ticket; a.pos_w = c->pos; }  // prompt position: advance here
+                if (!emits && !probe && !lang && l == D.dec_layers - 1) { a.ticket = c->step_ticket; a.pos_w = c->pos; }  // prompt position: advance here
                 dec_gemm(true, a);
             }
         }
@@ -571,6 +579,18 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
                 wh_launch_argmax_finish(s, prec, c->part_val, c->part_idx, lm_parts, mpad, c->pos, c->step_ticket, st, nb, ne, tf, lp ? c->lp_part_sum : nullptr);
             }
         }
+        if (lang) {   // the listed ids' unfiltered logits of this prompt position -> each row's language token at the next one
+            {
+                Prof pr(c, WH_KG_DEC_GEMM);
+                LangHeadArgs a;
+                a.X = c->dxs; a.x_mpad = mpad; a.W = m->lm_w; a.bias = m->lm_c; a.ln_s = m->lm_s; a.ln_part = c->lnpart; a.ln_tiles = ln_tiles_d;
+                a.ids = c->lang_d_ids; a.n_lang = (int)c->lang_ids.size(); a.M = nb; a.K = (int)d; a.out = c->lang_logits;
+                wh_launch_lang_head(s, prec, a);
+            }
+            Prof pr(c, WH_KG_DEC_OTHER);
+            wh_launch_lang_finish(s, c->lang_logits, c->lang_d_ids, (int)c->lang_ids.size(), c->lang_bcast ? 0 : -1, c->lang_probs, c->lang_chosen,
+                                  c->feed, c->out_tokens, ld, lang_slot, nb, probe ? nullptr : c->pos);
+        }
         if (probe) {   // softmax(v)[no_speech] over this prompt position's unfiltered logits (no mask, no rules, nothing recorded)
             int parts;
             {
@@ -594,7 +614,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
     // reads the position from device memory, so the graph is position-independent.  The host then
     // pays one graph launch per token instead of ~50 kernel launches (src/main.rs:793-826 is one ORT
     // Run per token in the reference).
-    for (int step = 0; step < std::min(P, total_pos); step++) launch_step(step >= P - 1, true, lp_probe && step == c->lp_sot_index);
+    for (int step = 0; step < std::min(P, total_pos); step++) launch_step(step >= P - 1, true, lp_probe && step == c->lp_sot_index, lang_det && step == c->lang_sot_index);
     const int remaining = total_pos - P;
     // with event timing on: every position is launched eagerly (stride 0/1), or only every stride-th one
     // (sampled live timing) while the others replay the graph
@@ -672,8 +692,28 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
             CTX_HIP(c, hipMemcpyAsync(nsp.data(), c->lp_ns, nb * 4, hipMemcpyDeviceToHost, s));
         }
     }
+    const size_t n_lang = c->lang_ids.size();
+    std::vector<int> lch;
+    std::vector<float> lpr;
+    if (lang_det) {
+        lch.resize(nb);
+        lpr.resize((size_t)nb * n_lang);
+        CTX_HIP(c, hipMemcpyAsync(lch.data(), c->lang_chosen, nb * 4, hipMemcpyDeviceToHost, s));
+        CTX_HIP(c, hipMemcpyAsync(lpr.data(), c->lang_probs, lpr.size() * 4, hipMemcpyDeviceToHost, s));
+    }
     CTX_HIP(c, hipStreamSynchronize(s));
     CTX_HIP(c, hipGetLastError());
+    if (lang_fix) {   // the file's language and window 0's probabilities (the first rows kept), once per window of this batch
+        for (int b = 0; b < nb; b++) {
+            c->lang_rows.push_back(c->lang_fixed);
+            for (size_t j = 0; j < n_lang; j++) { const float pj = c->lang_prob_rows[j]; c->lang_prob_rows.push_back(pj); }
+        }
+    } else if (lang_det) {
+        for (int b = 0; b < nb; b++) c->lang_rows.push_back(lch[b]);
+        c->lang_prob_rows.insert(c->lang_prob_rows.end(), lpr.begin(), lpr.end());
+        c->lang_have = true;
+        c->lang_have_n = n_lang;
+    }
     if (lp) {   // kept for wh_get_logprobs: each clip's generated positions
         for (int b = 0; b < nb; b++) c->lp_rows.emplace_back(lps.begin() + (size_t)b * ld + P, lps.begin() + (size_t)b * ld + nout[b]);
         c->lp_ns_rows.insert(c->lp_ns_rows.end(), nsp.begin(), nsp.end());
@@ -753,6 +793,9 @@ int check_params(wh_ctx* c, const wh_decode_params* p) {
     c->lp_have = c->lp_have_ns = false;
     c->lp_rows.clear();
     c->lp_ns_rows.clear();
+    c->lang_have = false;
+    c->lang_rows.clear();
+    c->lang_prob_rows.clear();
     if (!p) return fail(c, WH_ERR_ARG, "decode params are NULL");
     if ((p->n_suppress && !p->suppress) || (p->n_begin_suppress && !p->begin_suppress) || (p->n_forced && !p->forced))
         return fail(c, WH_ERR_ARG, "decode params: NULL list with non-zero length");
@@ -1194,6 +1237,70 @@ int wh_ctx_set_logprobs(wh_ctx* c, const wh_logprob_opts* o) {
     return WH_OK;
 }
 
+// Language detection on every decode entry of the ctx.  The buffers are allocated the first time it is turned on; nothing of
+// it enters the captured decode step.
+int wh_ctx_set_language_detection(wh_ctx* c, const wh_language_opts* o) {
+    if (!c) return WH_ERR_ARG;
+    if (!o) {
+        c->lang_on = false;
+        return WH_OK;
+    }
+    if (o->struct_size != sizeof(wh_language_opts)) return fail(c, WH_ERR_ARG, "wh_ctx_set_language_detection: struct_size %zu, expected %zu", o->struct_size, sizeof(wh_language_opts));
+    const int vocab = c->m->dims.vocab;
+    if (o->n_lang < 1 || o->n_lang > WH_MAX_LANGUAGES || !o->lang_ids) return fail(c, WH_ERR_ARG, "wh_ctx_set_language_detection: n_lang %zu outside 1..%d (or a NULL list)", o->n_lang, WH_MAX_LANGUAGES);
+    if (o->sot_index < 0) return fail(c, WH_ERR_ARG, "wh_ctx_set_language_detection: negative sot_index");
+    for (size_t i = 0; i < o->n_lang; i++) {
+        if (o->lang_ids[i] < 0 || o->lang_ids[i] >= vocab) return fail(c, WH_ERR_ARG, "wh_ctx_set_language_detection: id %lld outside the vocabulary (%d)", (long long)o->lang_ids[i], vocab);
+        for (size_t j = 0; j < i; j++)
+            if (o->lang_ids[j] == o->lang_ids[i]) return fail(c, WH_ERR_ARG, "wh_ctx_set_language_detection: id %lld listed twice", (long long)o->lang_ids[i]);
+    }
+    hipSetDevice(c->m->device);
+    char* buf = c->lang_buf;
+    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t MP = (size_t)c->mpad, B = (size_t)c->max_batch;
+    const size_t b_ids = up(WH_LANG_LD * 4), b_log = up(MP * WH_LANG_LD * 4), b_pr = up(B * WH_LANG_LD * 4), b_ch = up(B * 4);
+    if (!buf) {
+        hipError_t e = hipMalloc((void**)&buf, b_ids + b_log + b_pr + b_ch);
+        if (e == hipSuccess) e = hipMemset(buf, 0, b_ids + b_log + b_pr + b_ch);
+        if (e != hipSuccess) {
+            if (buf) hipFree(buf);
+            return fail(c, WH_ERR_NOMEM, "wh_ctx_set_language_detection: hipMalloc: %s", hipGetErrorString(e));
+        }
+    }
+    int ids[WH_LANG_LD];
+    for (int i = 0; i < WH_LANG_LD; i++) ids[i] = (int)o->lang_ids[(size_t)i < o->n_lang ? i : 0];
+    hipError_t e = hipMemcpy(buf, ids, sizeof ids, hipMemcpyHostToDevice);   // (nothing of the ctx is in flight: every call ends with a stream synchronisation)
+    if (e != hipSuccess) {
+        if (!c->lang_buf) hipFree(buf);
+        else if (c->lang_on) {   // put the list in force back
+            for (int i = 0; i < WH_LANG_LD; i++) ids[i] = (int)c->lang_ids[(size_t)i < c->lang_ids.size() ? i : 0];
+            hipMemcpy(buf, ids, sizeof ids, hipMemcpyHostToDevice);
+        }
+        return fail(c, WH_ERR_HIP, "wh_ctx_set_language_detection: hipMemcpy: %s", hipGetErrorString(e));
+    }
+    c->lang_buf = buf;
+    c->lang_d_ids = (int*)buf;
+    c->lang_logits = (float*)(buf + b_ids);
+    c->lang_probs = (float*)(buf + b_ids + b_log);
+    c->lang_chosen = (int*)(buf + b_ids + b_log + b_pr);
+    c->lang_ids.assign(o->lang_ids, o->lang_ids + o->n_lang);
+    c->lang_sot_index = o->sot_index;
+    c->lang_on = true;
+    return WH_OK;
+}
+
+int wh_get_languages(const wh_ctx* c, int64_t* lang_out, float* probs, size_t cap_clips, size_t* n_clips_out) {
+    if (!c) return WH_ERR_ARG;
+    if (!c->lang_have) return WH_ERR_STATE;
+    const size_t n = c->lang_rows.size();
+    if (n_clips_out) *n_clips_out = n;
+    if (!lang_out) return WH_OK;
+    if (cap_clips < n) return WH_ERR_ARG;
+    std::copy(c->lang_rows.begin(), c->lang_rows.end(), lang_out);
+    if (probs) std::copy(c->lang_prob_rows.begin(), c->lang_prob_rows.end(), probs);
+    return WH_OK;
+}
+
 int wh_get_logprobs(const wh_ctx* c, float* token_logprobs, size_t cap_tokens, float* no_speech_prob, size_t cap_clips, size_t* n_clips_out) {
     if (!c) return WH_ERR_ARG;
     if (!c->lp_have) return WH_ERR_STATE;
@@ -1238,6 +1345,7 @@ void wh_ctx_free(wh_ctx* c) {
     if (c->ts_logits) hipFree(c->ts_logits);
     if (c->ts_state) hipFree(c->ts_state);
     if (c->lp_buf) hipFree(c->lp_buf);
+    if (c->lang_buf) hipFree(c->lang_buf);
     if (c->s_copy) { hipStreamSynchronize(c->s_copy); hipStreamDestroy(c->s_copy); }
     if (c->ev_h2d) hipEventDestroy(c->ev_h2d);
     if (c->pcm2) hipFree(c->pcm2);
@@ -1683,6 +1791,13 @@ int wh_transcribe_longform(wh_ctx* c, const float* pcm, size_t n_samples, double
     const size_t stride = p->n_prompt + p->max_new_tokens;
     const wh_dims& D = c->m->dims;
     double enc_s = 0, dec_s = 0;
+    // language detection: the language of the file is the language of its first window (openai-whisper's transcribe()) — the first device
+    // batch broadcasts its row 0's choice, later batches take that id as an ordinary prompt token
+    struct LangScope {
+        wh_ctx* c;
+        ~LangScope() { c->lang_bcast = false; c->lang_fixed = -1; }
+    } lang_scope{c};
+    c->lang_bcast = true;
     for (size_t base = 0; base < nch; base += c->max_batch) {
         const int nb = (int)std::min<size_t>(c->max_batch, nch - base);
         std::vector<int> src(nb, 0), fs(nb), nfs(1, (int)nf);
@@ -1705,6 +1820,7 @@ int wh_transcribe_longform(wh_ctx* c, const float* pcm, size_t n_samples, double
         CTX_HIP(c, hipEventRecord(c->ev[2], s));
         rc = run_decode(c, nb, p, tokens_out + base * stride, stride, n_tokens_out + base, nullptr, 0);
         if (rc) return rc;
+        if (c->lang_on && base == 0) c->lang_fixed = c->lang_rows[0];
         float a = 0, b = 0;
         hipEventElapsedTime(&a, c->ev[4], c->ev[2]);
         hipEventElapsedTime(&b, c->ev[5], c->ev[3]);

@@ -970,6 +970,177 @@ __global__ __launch_bounds__(64) void k_nospeech_finish(const float* __restrict_
     }
 }
 
+// ---- language detection ---------------------------------------------------------
+// The language head: the logits of the n_lang listed ids of every row at a prompt position, out [x_mpad][WH_LANG_LD] f32 (column j = the id
+// listed j-th).  k_lm_head's K walk with the weight rows gathered by id: the same activation tile in LDS, the same LayerNorm statistics
+// (quarter sums in the same order), per (id, row) the same MFMA sequence over ascending k-slabs into one accumulator and the same epilogue
+// (wh_ln_fold) — so a listed id's logit is bit for bit what k_lm_head / k_lm_head_tile / the split-fp16 forms give that id at that position.
+// One wave per 16 listed ids (at most 8 waves over two workgroups per row group); no masks, no argmax partials, no position.
+template <typename T, int MT>
+__global__ __launch_bounds__(256) void k_lang_head(LangHeadArgs a) {
+    extern __shared__ __attribute__((aligned(128))) char smem_raw[];   // 128: h2 tiles find their 32-blocks from the address
+    constexpr int EPC = 16 / (int)sizeof(T);
+    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int fl = lane & 15, fg = lane >> 4;
+    const int n_tiles = (a.n_lang + 15) >> 4;
+    const int m0 = blockIdx.y * MT * 16;
+    T* Xs = reinterpret_cast<T*>(smem_raw);
+    constexpr int ROWS = MT * 16;
+    const int nslab = a.K >> 5, cps = ROWS * 32 / EPC;  // 16-B chunks per slab of this row group
+    u32x4 xr[16];
+    int xo[16];
+    auto stage_load = [&](int c0) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const int c = min(c0 + i * 256, nslab * cps - 1), sl = c / cps, o = (c - sl * cps) * EPC;
+            xo[i] = sl * ROWS * 32 + o;
+            xr[i] = *reinterpret_cast<const u32x4*>((const T*)a.X + ((long)sl * a.x_mpad + m0) * 32 + o);
+        }
+    };
+    auto stage_store = [&](int c0) {
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+            if (c0 + i * 256 < nslab * cps) *reinterpret_cast<u32x4*>(Xs + xo[i]) = xr[i];
+    };
+    stage_load(tid);
+    float* lnstat = reinterpret_cast<float*>(smem_raw + (size_t)nslab * ROWS * 32 * sizeof(T));  // [ROWS][2]
+    {   // mean / rstd of this row group: k_lm_head's reduction, term for term
+        float* lnq = lnstat + 2 * ROWS;  // [4][ROWS][2]
+        if (tid < 4 * ROWS) {
+            const int r = tid % ROWS, q = tid / ROWS;
+            float s1, s2;
+            ln_partial_sum(a.ln_part, a.ln_tiles, a.x_mpad, m0 + r, q, 4, s1, s2);
+            lnq[(q * ROWS + r) * 2] = s1;
+            lnq[(q * ROWS + r) * 2 + 1] = s2;
+        }
+        __syncthreads();
+        if (tid < ROWS) {
+            const float s1 = (lnq[tid * 2] + lnq[(ROWS + tid) * 2]) + (lnq[(2 * ROWS + tid) * 2] + lnq[(3 * ROWS + tid) * 2]);
+            const float s2 = (lnq[tid * 2 + 1] + lnq[(ROWS + tid) * 2 + 1]) + (lnq[(2 * ROWS + tid) * 2 + 1] + lnq[(3 * ROWS + tid) * 2 + 1]);
+            float mean, rstd;
+            wh_ln_mean_rstd(s1, s2, (float)a.K, false, mean, rstd);
+            lnstat[2 * tid] = mean;
+            lnstat[2 * tid + 1] = rstd;
+        }
+    }
+    const int iters = a.K >> 5;
+    constexpr int DEPTH = sizeof(typename FragT<T>::type) <= 16 ? 16 : 8;   // two register sets of DEPTH weight fragments
+    const int nchunk = (iters + DEPTH - 1) / DEPTH;
+    const int tile = blockIdx.x * 4 + wave;
+    const int units = tile < n_tiles ? nchunk : 0;
+    typedef typename FragT<T>::type frag_t;
+    frag_t wA[DEPTH], wB[DEPTH];
+    f32x4 acc[MT];
+#pragma unroll
+    for (int t = 0; t < MT; t++) acc[t] = f32x4{0, 0, 0, 0};
+    // this lane's weight row: the id listed at tile * 16 + fl (the list is padded to WH_LANG_LD entries with valid ids)
+    const T* wp = (const T*)a.W + (long)a.ids[min(tile, WH_LANG_LD / 16 - 1) * 16 + fl] * a.K + fg * 8;
+    auto load_unit = [&](frag_t (&wq)[DEPTH], int u) {
+#pragma unroll
+        for (int i = 0; i < DEPTH; i++)
+            if (u * DEPTH + i < iters) wq[i] = load_frag<T>(wp + (u * DEPTH + i) * 32);
+    };
+    auto compute_unit = [&](const frag_t (&wq)[DEPTH], int u) {
+#pragma unroll
+        for (int i = 0; i < DEPTH; i++) {
+            if (u * DEPTH + i < iters) {
+#pragma unroll
+                for (int t = 0; t < MT; t++) {
+                    frag_t xf = load_frag<T>(Xs + ((long)(u * DEPTH + i) * ROWS + t * 16 + fl) * 32 + fg * 8);
+                    mma16(acc[t], wq[i], xf);
+                }
+            }
+        }
+    };
+    if (units > 0) load_unit(wA, 0);   // in flight while the activation tile is staged
+    stage_store(tid);
+    for (int c0 = tid + 256 * 16; c0 < nslab * cps; c0 += 256 * 16) {  // K > 512
+        stage_load(c0);
+        stage_store(c0);
+    }
+    __syncthreads();
+    for (int u = 0; u < units; u += 2) {
+        const bool hasB = u + 1 < units;
+        if (hasB) load_unit(wB, u + 1);
+        compute_unit(wA, u);
+        if (hasB) {
+            if (u + 2 < units) load_unit(wA, u + 2);
+            compute_unit(wB, u + 1);
+        }
+    }
+    if (units == 0) return;
+    const int j0 = tile * 16 + 4 * fg;   // list positions of this lane's 4 accumulator elements
+    float sv[4] = {0, 0, 0, 0}, cv[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        const int id = a.ids[j0 + e];
+        sv[e] = a.ln_s[id];
+        cv[e] = a.bias[id];
+    }
+#pragma unroll
+    for (int t = 0; t < MT; t++) {
+        const int m = m0 + t * 16 + fl;
+        const float mean = lnstat[2 * (t * 16 + fl)], rstd = lnstat[2 * (t * 16 + fl) + 1];
+        f32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; e++) v[e] = wh_ln_fold(acc[t][e], mean, rstd, sv[e], cv[e]);
+        if (m < a.M) *reinterpret_cast<f32x4*>(a.out + (long)m * WH_LANG_LD + j0) = v;   // (columns past n_lang hold padding ids' logits, never read)
+    }
+}
+
+// The language finish: one wave per row.  Over the row's n_lang logits (NaN left out): the maximum and its id (ties to the lowest id, not to
+// the lowest list position), the probabilities exp(v - m) / sum in list order, and the chosen id as the row's token at prompt position
+// tok_pos (fed there, recorded there).  Nothing finite: the lowest listed id, all probabilities 0.  src_row >= 0 (long-form): every row takes
+// that row's result.  pos_p != nullptr: block 0 advances the position (when no other finish kernel of this prompt step does).
+__global__ __launch_bounds__(64) void k_lang_finish(const float* __restrict__ logits, const int* __restrict__ ids, int n_lang, int src_row,
+                                                    float* __restrict__ probs, int* __restrict__ chosen, int* __restrict__ feed,
+                                                    int* __restrict__ out_tokens, int tok_ld, int tok_pos, int* pos_p) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const float* row = logits + (long)(src_row >= 0 ? src_row : b) * WH_LANG_LD;
+    float v[2];
+    int id[2];
+    float bv = -INFINITY;
+    int bi = 0x7fffffff, lo = 0x7fffffff;   // best finite-or-infinite logit's id; lowest listed id
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        const int j = lane + 64 * k;
+        const bool in = j < n_lang;
+        v[k] = in ? row[j] : NAN;
+        id[k] = in ? ids[j] : 0x7fffffff;
+        lo = min(lo, id[k]);
+        if (v[k] > bv || (v[k] == bv && id[k] < bi)) { bv = v[k]; bi = id[k]; }   // NaN never wins; -inf only over nothing
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(bv, off);
+        const int oi = __shfl_xor(bi, off), ol = __shfl_xor(lo, off);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        lo = min(lo, ol);
+    }
+    const bool none = bv == -INFINITY;   // every logit NaN or -inf
+    float e[2], s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        // (a +inf maximum: the limit — 1 for the +inf entries, 0 for the others)
+        e[k] = (none || !(v[k] == v[k])) ? 0.0f : (bv == INFINITY ? (v[k] == INFINITY ? 1.0f : 0.0f) : ts_exp(v[k] - bv));
+        s += e[k];
+    }
+    s = wave_sum(s);
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        const int j = lane + 64 * k;
+        if (j < n_lang) probs[(long)b * n_lang + j] = none ? 0.0f : e[k] / s;
+    }
+    if (lane == 0) {
+        const int tok = none ? lo : bi;
+        chosen[b] = tok;
+        feed[(long)b * tok_ld + tok_pos] = tok;
+        out_tokens[(long)b * tok_ld + tok_pos] = tok;
+        if (pos_p && b == 0) *pos_p += 1;
+    }
+}
+
 // ---- decoder self-attention, one position ([3P] :417-425, 468-475): one wave per (head, clip) ---
 // qkv: [B][3d] (q pre-scaled | k | v) of the current position.
 // K cache [B][H][TC][64]  (lane j scores key j: its row is 8 x 16-byte loads, issued before anything else)
@@ -1581,6 +1752,41 @@ void wh_launch_argmax_finish(hipStream_t s, int prec, const float* part_val, con
 void wh_launch_nospeech_finish(hipStream_t s, const float* part_val, const float* part_sum, int n_parts, int mpad, const float* probe_v,
                                float* prob, int B, int* pos_p) {
     hipLaunchKernelGGL(k_nospeech_finish, dim3(B), dim3(64), 0, s, part_val, part_sum, n_parts, mpad, probe_v, prob, pos_p);
+}
+
+template <typename T>
+static void launch_lang_head_t(hipStream_t s, const LangHeadArgs& a) {
+    // row groups as launch_lm_head_t forms them (the pitch of the slab covers whole groups)
+    int mt = std::min(wh_dbg_lm_mt, (a.M + 15) / 16);
+    auto lds = [&](int t) { return (size_t)t * 16 * a.K * sizeof(T) + (size_t)t * 16 * 2 * 4 * 5; };
+    while (mt > 1 && lds(mt) > 150 * 1024) mt--;
+    if (mt > 4) mt = 4;
+    const size_t sm = lds(mt);
+    dim3 grid(((a.n_lang + 15) / 16 + 3) / 4, (a.M + 16 * mt - 1) / (16 * mt));
+#define WH_LH(MT_)                                          \
+    {                                                       \
+        auto kfn = k_lang_head<T, MT_>;                     \
+        set_max_smem(kfn, sm);                              \
+        hipLaunchKernelGGL(kfn, grid, dim3(256), sm, s, a); \
+    }
+    switch (mt) {
+        case 1: WH_LH(1) break;
+        case 2: WH_LH(2) break;
+        case 3: WH_LH(3) break;
+        default: WH_LH(4) break;
+    }
+#undef WH_LH
+}
+
+void wh_launch_lang_head(hipStream_t s, int prec, const LangHeadArgs& a) {
+    if (prec == WH_PREC_F32) launch_lang_head_t<float>(s, a);
+    else if (prec == WH_PREC_F16X3) launch_lang_head_t<h2>(s, a);
+    else launch_lang_head_t<bf16>(s, a);   // (fp8 mode: the embedding is bf16)
+}
+
+void wh_launch_lang_finish(hipStream_t s, const float* logits, const int* ids, int n_lang, int src_row, float* probs, int* chosen, int* feed,
+                           int* out_tokens, int tok_ld, int tok_pos, int B, int* pos_p) {
+    hipLaunchKernelGGL(k_lang_finish, dim3(B), dim3(64), 0, s, logits, ids, n_lang, src_row, probs, chosen, feed, out_tokens, tok_ld, tok_pos, pos_p);
 }
 
 void wh_launch_dec_self_attn(hipStream_t s, int prec, const void* qkv, void* kc, void* vc, void* out, const int* pos_p,

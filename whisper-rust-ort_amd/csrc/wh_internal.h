@@ -235,6 +235,26 @@ struct wh_ctx {
     bool lp_have = false, lp_have_ns = false;
     std::vector<std::vector<float>> lp_rows;
     std::vector<float> lp_ns_rows;
+    // Language detection (wh_ctx_set_language_detection): off unless lang_on.  One allocation made by the setter (not part of the
+    // workspace carve), freed in wh_ctx_free: the id list, the listed ids' logits, the probabilities and the chosen ids.  Lives in the eagerly
+    // launched prompt positions only: the captured step and its key know nothing of it.
+    bool lang_on = false;
+    int lang_sot_index = 0;
+    std::vector<int64_t> lang_ids;  // the caller's list, in the caller's order
+    char* lang_buf = nullptr;
+    int* lang_d_ids = nullptr;      // [WH_LANG_LD], padded with the first listed id
+    float* lang_logits = nullptr;   // [mpad][WH_LANG_LD]
+    float* lang_probs = nullptr;    // [max_batch][n_lang]
+    int* lang_chosen = nullptr;     // [max_batch]
+    // long-form: the first device batch detects on its row 0 for every row (lang_bcast); later batches of the same call decode with that id
+    // in the prompt (lang_fixed >= 0) and report window 0's probabilities
+    bool lang_bcast = false;
+    int64_t lang_fixed = -1;
+    // what wh_get_languages returns: the last decode call's clips in the order their tokens were returned
+    bool lang_have = false;
+    size_t lang_have_n = 0;         // n_lang of that call
+    std::vector<int64_t> lang_rows;
+    std::vector<float> lang_prob_rows;   // [clips][lang_have_n]
     hipGraph_t step_graph = nullptr;
     hipGraphExec_t step_exec = nullptr;
 };

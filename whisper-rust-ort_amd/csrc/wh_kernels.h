@@ -250,6 +250,28 @@ void wh_launch_argmax_finish(hipStream_t s, int prec, const float* part_val, con
 // (the probe's prompt step leaves that to this kernel)
 void wh_launch_nospeech_finish(hipStream_t s, const float* part_val, const float* part_sum, int n_parts, int mpad, const float* probe_v,
                                float* prob, int B, int* pos_p);
+// Language detection (wh_ctx_set_language_detection).  The language head: the LM head's logits of the n_lang listed ids only,
+// at the position whose rows are in X — the LM head's operands (raw slab, LayerNorm partials, folded embedding / s / c) with the weight rows
+// gathered by id; bit-identical to what wh_launch_lm_head computes for those ids.  out [x_mpad][WH_LANG_LD] f32, column j = ids[j].
+constexpr int WH_LANG_LD = 128;   // == WH_MAX_LANGUAGES
+struct LangHeadArgs {
+    const void* X = nullptr;   // k-slab-major [K/32][x_mpad][32], compute dtype
+    int x_mpad = 64;
+    const void* W = nullptr;   // [vocab][K] (wh_model::lm_w)
+    const float* bias = nullptr;   // lm_c
+    const float* ln_s = nullptr;   // lm_s
+    const float* ln_part = nullptr;
+    int ln_tiles = 0;
+    const int* ids = nullptr;  // [WH_LANG_LD] device: the listed ids, padded with a listed id
+    int n_lang = 0;
+    int M = 0, K = 0;
+    float* out = nullptr;
+};
+void wh_launch_lang_head(hipStream_t s, int prec, const LangHeadArgs& a);
+// The language finish, one wave per row: probs [B][n_lang] (list order), chosen [B], and the chosen id written to feed / out_tokens
+// [B][tok_ld] at column tok_pos.  src_row >= 0: every row takes that row's result (long-form).  pos_p != nullptr: advances the position.
+void wh_launch_lang_finish(hipStream_t s, const float* logits, const int* ids, int n_lang, int src_row, float* probs, int* chosen, int* feed,
+                           int* out_tokens, int tok_ld, int tok_pos, int B, int* pos_p);
 void wh_launch_dec_self_attn(hipStream_t s, int prec, const void* qkv, void* kc, void* vc, void* out, const int* pos_p,
                              int d, int n_heads, int tc, int B, int mpad);
 // stream_nt: non-temporal K/V loads (set when the cross K/V of all layers exceed what the Infinity Cache can keep)

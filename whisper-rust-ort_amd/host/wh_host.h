@@ -159,6 +159,9 @@ struct RowOut {
     std::string segments;   // JSON array of {start, end, text} (--timestamp-rules), empty: no key
     bool has_conf = false;  // --logprobs: avg_logprob and no_speech_prob keys
     double avg_logprob = 0, no_speech_prob = 0;
+    bool has_lang = false;  // --language auto: the detected language code and its probability
+    std::string language;
+    double language_probability = 0;
 };
 
 // avg_logprob / no_speech_prob in JSON: shortest text that reads back as the same float (the library's values are floats); a window in which
@@ -194,14 +197,18 @@ inline std::string csv_field(const std::string& f) {  // csv crate, QuoteStyle::
 }
 
 inline std::string csv_text(const std::vector<RowOut>& rows) {  // :1215-1229
-    std::string o = "file,duration_s,end_to_end_s,rtf,text\n";
+    bool lang = false;   // --language auto: two more columns (any other run: the reference's five)
+    for (auto& r : rows) lang = lang || r.has_lang;
+    std::string o = lang ? "file,duration_s,end_to_end_s,rtf,text,language,language_probability\n" : "file,duration_s,end_to_end_s,rtf,text\n";
     char b[64];
     for (auto& r : rows) {
         o += csv_field(r.file) + ",";
         snprintf(b, sizeof b, "%.3f", r.duration_s); o += b; o += ",";
         snprintf(b, sizeof b, "%.4f", r.end_to_end_s); o += b; o += ",";
         snprintf(b, sizeof b, "%.6f", r.rtf); o += b; o += ",";
-        o += csv_field(r.text) + "\n";
+        o += csv_field(r.text);
+        if (lang) { o += "," + csv_field(r.language) + "," + fmt_conf(r.language_probability); }
+        o += "\n";
     }
     return o;
 }
@@ -214,6 +221,7 @@ inline std::string per_file_json(const std::vector<RowOut>& rows) {  // :1232 to
         r.set("file", JVal::str(rows[i].file)).set("duration_s", JVal::num(rows[i].duration_s))
             .set("end_to_end_s", JVal::num(rows[i].end_to_end_s)).set("rtf", JVal::num(rows[i].rtf))
             .set("text", JVal::str(rows[i].text));
+        if (rows[i].has_lang) { JVal v; v.raw = fmt_conf(rows[i].language_probability); r.set("language", JVal::str(rows[i].language)).set("language_probability", v); }
         if (rows[i].has_conf) { JVal v; v.raw = fmt_conf(rows[i].avg_logprob); r.set("avg_logprob", v); v.raw = fmt_conf(rows[i].no_speech_prob); r.set("no_speech_prob", v); }
         if (!rows[i].segments.empty()) { JVal sg; sg.raw = rows[i].segments; r.set("segments", sg); }
         o += "  ";
@@ -380,7 +388,8 @@ inline WhisperSpecial special_tokens(const std::string& language, const std::str
             if (it == tok->special.end()) throw std::runtime_error("Tokenizer missing token: " + s);
             return it->second;
         };
-        WhisperSpecial s{get("<|startoftranscript|>"), get("<|endoftext|>"), get("<|" + language + "|>"), get("<|" + task + "|>"),
+        // (--language auto: the language slot of the prompt is a placeholder the library overwrites per clip)
+        WhisperSpecial s{get("<|startoftranscript|>"), get("<|endoftext|>"), get("<|" + (language == "auto" ? std::string("en") : language) + "|>"), get("<|" + task + "|>"),
                          get("<|notimestamps|>"), 0, 0};
         auto ts = tok->special.find("<|0.00|>");   // <|0.00|> if the tokenizer lists it, else the id after <|notimestamps|>
         s.timestamp_begin = ts != tok->special.end() ? ts->second : s.no_timestamps + 1;
@@ -399,6 +408,43 @@ inline WhisperSpecial special_tokens(const std::string& language, const std::str
     s.timestamp_begin = 50364;
     s.no_speech = s.no_timestamps - 1;   // 50362
     return s;
+}
+
+// ---- --language auto: the ids language detection chooses among (wh_ctx_set_language_detection) ----------------------------------------
+// Whisper's language codes in the order of their tokens (openai-whisper tokenizer.py LANGUAGES): <|en|> is the id after
+// <|startoftranscript|>, the others follow; the 100th (yue) exists in the 51866-id vocabulary of large-v3 only.
+inline const std::vector<std::string>& whisper_language_codes() {
+    static const std::vector<std::string> codes = {
+        "en", "zh", "de", "es", "ru", "ko", "fr", "ja", "pt", "tr", "pl", "ca", "nl", "ar", "sv", "it", "id", "hi", "fi", "vi",
+        "he", "uk", "el", "ms", "cs", "ro", "da", "hu", "ta", "no", "th", "ur", "hr", "bg", "lt", "la", "mi", "ml", "cy", "sk",
+        "te", "fa", "lv", "bn", "sr", "az", "sl", "kn", "et", "mk", "br", "eu", "is", "hy", "ne", "mn", "bs", "kk", "sq", "sw",
+        "gl", "mr", "pa", "si", "km", "sn", "yo", "so", "af", "oc", "ka", "be", "tg", "sd", "gu", "am", "yi", "lo", "uz", "fo",
+        "ht", "ps", "tk", "nn", "mt", "sa", "lb", "my", "bo", "tl", "mg", "as", "tt", "haw", "ln", "ha", "ba", "jw", "su", "yue"};
+    return codes;
+}
+struct LanguageTable {
+    std::vector<std::string> codes;
+    std::vector<int64_t> ids;
+};
+// With a tokenizer: its <|xx|> tokens of the codes above, in that order.  Without: the multilingual block starting at 50259 — 99 codes, 100
+// when the vocabulary has 51866 ids; a vocabulary too small to hold that block is refused.
+inline LanguageTable language_table(const Tokenizer* tok, long long vocab) {
+    LanguageTable t;
+    const std::vector<std::string>& all = whisper_language_codes();
+    if (tok && tok->loaded) {
+        for (const std::string& c : all) {
+            auto it = tok->special.find("<|" + c + "|>");
+            if (it != tok->special.end() && it->second < vocab) { t.codes.push_back(c); t.ids.push_back(it->second); }
+        }
+        if (t.ids.empty()) throw std::runtime_error("--language auto: the tokenizer lists no <|xx|> language token");
+        return t;
+    }
+    const size_t n = vocab == 51866 ? 100 : 99;
+    if (vocab < 50259 + (long long)n)
+        throw std::runtime_error("--language auto needs a tokenizer.json or a multilingual vocabulary: the language tokens are ids 50259.." + std::to_string(50259 + n - 1) +
+                                 ", this model's vocabulary has " + std::to_string(vocab) + " ids");
+    for (size_t i = 0; i < n; i++) { t.codes.push_back(all[i]); t.ids.push_back(50259 + (int64_t)i); }
+    return t;
 }
 
 // ---- the CLI's --synthetic-clips input ------------------------------------------------------------------------------------------------

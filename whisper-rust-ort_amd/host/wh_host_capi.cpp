@@ -139,6 +139,25 @@ size_t whh_srt(const double* starts, const double* ends, const char* texts, size
 size_t whh_vtt(const double* starts, const double* ends, const char* texts, size_t n, char* out, size_t cap) {
     return put(vtt_text(cues_from(starts, ends, texts, n)), out, cap);
 }
+// --language auto: the language table (wh_host.h language_table) as comma-joined codes and their ids; returns the count, or -1 with the
+// refusal's text in err
+long long whh_language_table(const char* tokenizer_json, long long vocab, long long* ids, size_t cap_ids, char* codes, size_t cap_codes, char* err, size_t cap_err) {
+    try {
+        Tokenizer t;
+        if (tokenizer_json && *tokenizer_json) load_tokenizer(tokenizer_json, t);
+        LanguageTable lt = language_table(t.loaded ? &t : nullptr, vocab);
+        std::string joined;
+        for (size_t i = 0; i < lt.codes.size(); i++) {
+            joined += (i ? "," : "") + lt.codes[i];
+            if (ids && i < cap_ids) ids[i] = lt.ids[i];
+        }
+        put(joined, codes, cap_codes);
+        return (long long)lt.ids.size();
+    } catch (const std::exception& e) {
+        put(e.what(), err, cap_err);
+        return -1;
+    }
+}
 int whh_special_tokens(const char* language, const char* task, const char* tokenizer_json, long long* out5) {
     try {
         Tokenizer t;

@@ -90,13 +90,16 @@ static bool parse_args(int argc, char** argv, Args& a) {
         else if (k == "--logprobs") a.logprobs = true;
         else if (k == "--print-plan") a.print_plan = true;
         else if (k == "--help" || k == "-h") {
-            printf("Usage: whisper_bench [--audio-dir DIR] [--model-id ID] [--onnx-dir DIR|synthetic:<preset>:<seed>] [--language en] "
+            printf("Usage: whisper_bench [--audio-dir DIR] [--model-id ID] [--onnx-dir DIR|synthetic:<preset>:<seed>] [--language en|auto] "
                    "[--task transcribe] [--max-new-tokens 128] [--warmup 0] [--limit-files 0] [--discovery-best-json F] "
                    "[--out-csv F] [--out-json F] [--out-summary-json F] [--intra-op N] [--inter-op N] [--write-txt] "
                    "[--tokenizer-json F] [--timestamps] [--chunk-parallelism N] [--chunk-length-s 30] [--overlap-s 5] "
                    "[--device 0] [--devices 0-7] [--streams-per-gpu 1] [--load-threads N] [--precision bf16|f32|fp8|f16x3] [--max-batch 16] "
                    "[--synthetic-clips N] [--seed 1000] [--print-plan] [--timestamp-rules] [--write-srt] [--write-vtt] "
                    "[--logprobs] [--no-speech-threshold X] [--logprob-threshold Y]\n"
+                   "  --language auto          the language of every file is detected from its audio (its first window's, for a file of several) among\n"
+                   "                           the tokenizer's <|xx|> tokens, else the multilingual ids from 50259 on; the per-file JSON and CSV gain\n"
+                   "                           language and language_probability\n"
                    "  --logprobs               avg_logprob and no_speech_prob in every row of the per-file JSON (and in its segments)\n"
                    "  --no-speech-threshold X  with --logprob-threshold Y: a window with no_speech_prob > X and avg_logprob < Y becomes empty text and\n"
                    "  --logprob-threshold Y    no segments (both off unless given, each implies --logprobs; openai-whisper's defaults are 0.6 and -1.0)\n");
@@ -291,6 +294,23 @@ static void fetch_logprobs(wh_ctx* ctx, size_t n, size_t max_new, std::vector<fl
         throw std::runtime_error(std::string("wh_get_logprobs: ") + std::to_string(rc));
     if (got != n) throw std::runtime_error("wh_get_logprobs: " + std::to_string(got) + " windows, expected " + std::to_string(n));
 }
+// --language auto: the last decode call's languages as (code, probability of the chosen language) per window
+struct Lang { bool has = false; std::string code; double prob = 0; };
+static std::vector<Lang> fetch_languages(wh_ctx* ctx, size_t n, const LanguageTable& lt) {
+    std::vector<int64_t> ids(std::max<size_t>(1, n));
+    std::vector<float> probs(std::max<size_t>(1, n) * lt.ids.size());
+    size_t got = 0;
+    if (int rc = wh_get_languages(ctx, ids.data(), probs.data(), n, &got))
+        throw std::runtime_error(std::string("wh_get_languages: ") + std::to_string(rc));
+    if (got != n) throw std::runtime_error("wh_get_languages: " + std::to_string(got) + " windows, expected " + std::to_string(n));
+    std::vector<Lang> out(n);
+    for (size_t k = 0; k < n; k++) {
+        const size_t j = (size_t)(std::find(lt.ids.begin(), lt.ids.end(), ids[k]) - lt.ids.begin());
+        if (j >= lt.ids.size()) throw std::runtime_error("wh_get_languages: id " + std::to_string(ids[k]) + " is not in the language table");
+        out[k] = Lang{true, lt.codes[j], (double)probs[k * lt.ids.size() + j]};
+    }
+    return out;
+}
 // one window under --logprobs: its avg_logprob (over the generated tokens `g`, EOT still on them), the silence rule; returns true if the window is
 // to be skipped
 static bool window_conf(const Args& a, const std::vector<int64_t>& g, const float* lp, double ns, int64_t eot, Conf& conf, double& avg_lp) {
@@ -305,7 +325,8 @@ static void cues_conf(std::vector<Cue>& cues, double avg_lp, double ns) {
 }
 
 static std::string transcribe(wh_ctx* ctx, const std::vector<float>& audio, const Args& a, const Tokenizer* tok,
-                              const GenCfg& gen, Timing& t, std::vector<Cue>* cues = nullptr, Conf* conf = nullptr) {
+                              const GenCfg& gen, Timing& t, std::vector<Cue>* cues = nullptr, Conf* conf = nullptr,
+                              const LanguageTable* lt = nullptr, Lang* lang = nullptr) {
     const double t0 = now_s();
     WhisperSpecial sp = special_tokens(a.language, a.task, tok);
     std::vector<int64_t> prompt = {sp.sot, sp.lang, sp.task};
@@ -329,6 +350,7 @@ static std::string transcribe(wh_ctx* ctx, const std::vector<float>& audio, cons
     t.model_only_s = wt.encode_s + wt.decode_s;
     std::vector<float> lps, nss;
     if (a.logprobs) fetch_logprobs(ctx, got, a.max_new_tokens, lps, nss);
+    if (lt && lang && got) *lang = fetch_languages(ctx, got, *lt)[0];   // the file's language: its first window's
     const double td0 = now_s();
     std::vector<std::string> texts;
     std::vector<size_t> offs(std::max<size_t>(1, got));
@@ -410,12 +432,19 @@ int main(int argc, char** argv) {
         }
         std::vector<wh_model*> models;
         std::vector<wh_ctx*> ctxs;
+        const bool lang_auto = a.language == "auto";
+        LanguageTable lang_table;
         for (int dev : devices) {
             wh_model* m = nullptr;
             if (int rc = wh_model_load(a.onnx_dir.c_str(), dev, prec, &m))
                 throw std::runtime_error("Failed to load " + a.onnx_dir + " on device " + std::to_string(dev) + ": libwhisper_hip error " +
                                          std::to_string(rc) + ": " + wh_last_error(nullptr));
             models.push_back(m);
+            if (lang_auto && lang_table.ids.empty()) {
+                wh_dims dims{};
+                wh_model_get_dims(m, &dims);
+                lang_table = language_table(tok.loaded ? &tok : nullptr, dims.vocab);
+            }
             for (int st = 0; st < a.streams_per_gpu; st++) {
                 wh_ctx* c = nullptr;
                 if (int rc = wh_ctx_create(m, a.max_batch, &c))
@@ -431,6 +460,11 @@ int main(int argc, char** argv) {
                     wh_logprob_opts lo{sizeof(wh_logprob_opts), sp.no_speech, 0};
                     if (int rc = wh_ctx_set_logprobs(c, &lo))
                         throw std::runtime_error(std::string("wh_ctx_set_logprobs: ") + std::to_string(rc) + ": " + wh_last_error(c));
+                }
+                if (lang_auto) {   // each clip's language from the logits at <|startoftranscript|> (prompt position 0), decoded into position 1
+                    wh_language_opts lo{sizeof(wh_language_opts), lang_table.ids.data(), lang_table.ids.size(), 0};
+                    if (int rc = wh_ctx_set_language_detection(c, &lo))
+                        throw std::runtime_error(std::string("wh_ctx_set_language_detection: ") + std::to_string(rc) + ": " + wh_last_error(c));
                 }
                 ctxs.push_back(c);
             }
@@ -474,7 +508,7 @@ int main(int argc, char** argv) {
                             return hipHostMalloc((void**)&p, (size_t)WH_CLIP_SAMPLES * sizeof(float), hipHostMallocDefault) == hipSuccess ? p : nullptr;
                         },
                         [](float* p) { (void)hipHostFree(p); });
-        struct Result { std::string text; double dur = 0, load_s = 0; Timing t; bool ok = false; std::vector<Cue> cues; Conf conf; };
+        struct Result { std::string text; double dur = 0, load_s = 0; Timing t; bool ok = false; std::vector<Cue> cues; Conf conf; Lang lang; };
         const size_t nfiles = files.size();
         std::vector<Result> results(nfiles);
         const unsigned hc = std::thread::hardware_concurrency();
@@ -490,7 +524,7 @@ int main(int argc, char** argv) {
             if (batch.size() == 1 && batch[0].n() > (size_t)WH_CLIP_SAMPLES) {
                 // a file longer than one window goes alone through the long-form entry (which batches its windows)
                 Result& r = results[batch[0].idx];
-                r.text = transcribe(ctx, batch[0].audio, a, &tok, gen, r.t, &r.cues, &r.conf);
+                r.text = transcribe(ctx, batch[0].audio, a, &tok, gen, r.t, &r.cues, &r.conf, lang_auto ? &lang_table : nullptr, &r.lang);
                 r.dur = batch[0].dur; r.load_s = batch[0].load_s; r.ok = true;
             } else {
                 // the per-window body of transcribe_longform_chunked (:870-915) for a batch of one-window files
@@ -512,8 +546,11 @@ int main(int argc, char** argv) {
                 wh_get_timings(ctx, &wt);
                 std::vector<float> lps, nss;
                 if (a.logprobs) fetch_logprobs(ctx, batch.size(), a.max_new_tokens, lps, nss);
+                std::vector<Lang> langs;
+                if (lang_auto) langs = fetch_languages(ctx, batch.size(), lang_table);
                 for (size_t k = 0; k < batch.size(); k++) {   // :926-943
                     Result& r = results[batch[k].idx];
+                    if (lang_auto) r.lang = langs[k];
                     const double td0 = now_s();
                     std::vector<int64_t> g;
                     if (ntok[k] > prompt.size()) g.assign(toks.begin() + k * stride + prompt.size(), toks.begin() + k * stride + ntok[k]);
@@ -558,6 +595,7 @@ int main(int argc, char** argv) {
             const double end_to_end = r.load_s + r.t.end_to_end_s;   // :1190
             rows.push_back(make_row(files[i], r.dur, end_to_end, r.text));
             if (a.timestamp_rules) rows.back().segments = cues_json(r.cues);
+            if (r.lang.has) { rows.back().has_lang = true; rows.back().language = r.lang.code; rows.back().language_probability = r.lang.prob; }
             if (r.conf.has) { rows.back().has_conf = true; rows.back().avg_logprob = r.conf.avg_logprob(); rows.back().no_speech_prob = r.conf.no_speech_prob(); }
             loadl.push_back(r.load_s); pre.push_back(r.t.preprocess_s); model_only.push_back(r.t.model_only_s);
             dec.push_back(r.t.decode_s); e2e.push_back(end_to_end); rtfl.push_back(end_to_end / std::max(r.dur, 1e-9));
