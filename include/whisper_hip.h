@@ -234,6 +234,34 @@ int wh_ctx_set_language_detection(wh_ctx* c, const wh_language_opts* o);
  * ids, probs [n][n_lang] (may be NULL) the probabilities in list order.  lang_out == NULL: only *n_clips_out.  WH_ERR_STATE if the call ran
  * with detection off; WH_ERR_ARG if cap_clips < n. */
 int wh_get_languages(const wh_ctx* c, int64_t* lang_out, float* probs, size_t cap_clips, size_t* n_clips_out);
+/* Per-clip text context: a variable-length prompt prefix for every clip of a batch (openai-whisper's initial_prompt /
+ * condition_on_previous_text, faster-whisper's initial_prompt / hotwords, HF prompt_ids: <|startofprev|> previous text ... before
+ * <|startoftranscript|>).  No reference entry corresponds: the reference's prompt is [sot, lang, task, notimestamps] (src/main.rs:739-749).
+ * With this set, clip b of every decode entry of the ctx (wh_decode_greedy*, wh_transcribe_batch*, the device / pipelined entries — for the
+ * _next forms the batch being decoded —, wh_transcribe_longform) decodes exactly as if its prompt were prefix_b ++ p->prompt: model positions
+ * 0 .. n_b + n_prompt - 1 hold that sequence and the generated tokens follow.  The rows of a batch are aligned at the end of their prefixes
+ * (a row with a shorter prefix waits), so a call runs max_b n_b + n_prompt + max_new_tokens - 1 decoder positions for the whole batch.
+ * Outputs keep their layout: tokens_out is [n][n_prompt + max_new_tokens] = p->prompt ++ generated (the prefix is not echoed), n_tokens_out,
+ * wh_get_logprobs and the logits rows count generated tokens as before; forced, the suppress lists, the timestamp rules (whose
+ * <|notimestamps|> check concerns p->prompt only) and the sot_index of the no-speech probe (a position of p->prompt; the probe reads the
+ * prefixed row, as openai-whisper's main loop does) keep their meaning.  wh_transcribe_longform takes ONE prefix (n_clips == 1) for the file:
+ * for window 0 only (WH_PREFIX_FIRST_WINDOW, openai-whisper with condition_on_previous_text=False) or for every window.  With prefixes off,
+ * or all empty, tokens, logits and every other output are what they were without this entry.
+ * Refused with WH_ERR_ARG (the ctx unchanged): a wrong struct_size, n_clips outside 1 .. max_batch, offsets[0] != 0 or decreasing offsets,
+ * an id outside [0, vocab), an unknown scope.  At decode time, before anything is launched: n_clips differs from the call's clip count
+ * (long-form: from 1), or longest prefix + n_prompt + max_new_tokens > n_text_ctx -> WH_ERR_ARG; language detection on together with a
+ * non-empty prefix -> WH_ERR_UNSUPPORTED (the logits at <|startoftranscript|> then depend on the prefix; detect with an un-prefixed call
+ * first).  o == NULL turns it off (the default). */
+#define WH_PREFIX_FIRST_WINDOW 0   /* wh_transcribe_longform: the prefix conditions window 0 only */
+#define WH_PREFIX_ALL_WINDOWS  1   /* ... every window */
+typedef struct {
+    size_t struct_size;      /* sizeof(wh_prefix_opts) */
+    const int64_t* ids;      /* the clips' prefixes back to back; copied by the setter */
+    const size_t* offsets;   /* [n_clips + 1], offsets[0] == 0, non-decreasing; clip b's prefix is ids[offsets[b] .. offsets[b+1]) */
+    size_t n_clips;          /* 1 .. max_batch */
+    int32_t longform_scope;  /* WH_PREFIX_* */
+} wh_prefix_opts;
+int wh_ctx_set_prefixes(wh_ctx* c, const wh_prefix_opts* o);
 const char* wh_last_error(const wh_ctx* c); /* c == NULL: last load/create error of this thread */
 int wh_get_timings(const wh_ctx* c, wh_timing* out);
 

@@ -35,7 +35,7 @@ EXPORTS = ("wh_model_load", "wh_model_create", "wh_model_free", "wh_model_get_di
            "wh_transcribe_batch_next", "wh_transcribe_batch_device", "wh_transcribe_batch_device_next", "wh_longform_plan", "wh_transcribe_longform", "wh_profile_enable",
            "wh_profile_get", "wh_synthetic_weights", "wh_e4m3_quantize", "wh_e4m3_dequantize", "wh_abi_version",
            "wh_device_count", "wh_ctx_set_timestamp_rules", "wh_ctx_set_logprobs", "wh_get_logprobs",
-           "wh_ctx_set_language_detection", "wh_get_languages")
+           "wh_ctx_set_language_detection", "wh_get_languages", "wh_ctx_set_prefixes")
 
 
 class WhisperHipError(RuntimeError):
@@ -83,7 +83,22 @@ class WhLanguageOpts(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("lang_ids", C.POINTER(C.c_int64)), ("n_lang", C.c_size_t), ("sot_index", C.c_int32)]
 
 
+class WhPrefixOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("ids", C.POINTER(C.c_int64)), ("offsets", C.POINTER(C.c_size_t)), ("n_clips", C.c_size_t),
+                ("longform_scope", C.c_int32)]
+
+
+def pack_prefixes(prefixes: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.ndarray]:
+    """wh_prefix_opts' two arrays for a list of per-clip prefixes: (ids int64 back to back, offsets uint64 [n + 1])."""
+    offsets = np.zeros(len(prefixes) + 1, np.uint64)
+    for i, pre in enumerate(prefixes):
+        offsets[i + 1] = offsets[i] + np.uint64(len(pre))
+    ids = np.ascontiguousarray([t for pre in prefixes for t in pre], np.int64)
+    return ids, offsets
+
+
 WH_MAX_LANGUAGES = 128
+WH_PREFIX_FIRST_WINDOW, WH_PREFIX_ALL_WINDOWS = 0, 1
 WH_CTX_TWO_STREAMS = 1
 WH_CTX_CROSS_ES_ON = 2
 WH_CTX_CROSS_ES_OFF = 4
@@ -156,6 +171,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.wh_get_logprobs.argtypes = [vp, f32p, C.c_size_t, f32p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.wh_ctx_set_language_detection.argtypes = [vp, C.POINTER(WhLanguageOpts)]
     L.wh_get_languages.argtypes = [vp, i64p, f32p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.wh_ctx_set_prefixes.argtypes = [vp, C.POINTER(WhPrefixOpts)]
     _lib = L
     return L
 
@@ -343,6 +359,18 @@ class Context:
         probs = np.zeros((max(1, k), getattr(self, "_n_lang", WH_MAX_LANGUAGES)), np.float32)
         self._check(self.lib.wh_get_languages(self.h, _i64(ids), _f32(probs), k, C.byref(n)))
         return ids[:k], probs[:k]
+
+    def set_prefixes(self, prefixes: Sequence[Sequence[int]], all_windows: bool = False):
+        """wh_ctx_set_prefixes: clip b of every decode entry of this context decodes as if its prompt were prefixes[b] ++ params.prompt (text
+        context: <|startofprev|> previous text ...); the outputs keep their layout, the prefix is not echoed.  transcribe_longform takes one
+        prefix, for window 0 only or (all_windows) for every window."""
+        ids, offsets = pack_prefixes(prefixes)
+        o = WhPrefixOpts(C.sizeof(WhPrefixOpts), _i64(ids) if ids.size else None, offsets.ctypes.data_as(C.POINTER(C.c_size_t)), len(prefixes),
+                         WH_PREFIX_ALL_WINDOWS if all_windows else WH_PREFIX_FIRST_WINDOW)
+        self._check(self.lib.wh_ctx_set_prefixes(self.h, C.byref(o)))
+
+    def clear_prefixes(self):
+        self._check(self.lib.wh_ctx_set_prefixes(self.h, None))
 
     def _took(self, toks: List[np.ndarray], params: "DecodeParams") -> List[np.ndarray]:
         self._gen_lens = [len(t) - len(params.prompt) for t in toks]   # (what logprobs() cuts its rows to)

@@ -285,6 +285,35 @@ void pack_mask(const int64_t* a, size_t na, const int64_t* b, size_t nb, int voc
         if (b[i] >= 0 && b[i] < vocab) out[b[i] >> 5] |= 1u << (b[i] & 31);
 }
 
+// Per-clip prefixes: the prefix lengths of the nb rows of a device batch and what a decode entry refuses because of them,
+// checked by every entry before it launches anything and again by run_decode.  first_row = index of the batch's first window in a long-form
+// call (-1: the rows are the call's clips).  len_out (optional) [nb]; the return value of prefix_max is the longest one.
+const int64_t* prefix_of(const wh_ctx* c, long first_row, int b, int* len) {
+    size_t clip = (size_t)b;
+    if (first_row >= 0) {   // long-form: one prefix for the file, for window 0 or for every window
+        if (c->pfx_scope == WH_PREFIX_FIRST_WINDOW && first_row + b != 0) { *len = 0; return c->pfx_ids.data(); }
+        clip = 0;
+    }
+    *len = (int)(c->pfx_offsets[clip + 1] - c->pfx_offsets[clip]);
+    return c->pfx_ids.data() + c->pfx_offsets[clip];
+}
+int prefix_check(wh_ctx* c, const wh_decode_params* p, int nb, bool longform) {
+    if (!c->pfx_on) return WH_OK;
+    const size_t n_clips = c->pfx_offsets.size() - 1;
+    if (longform ? n_clips != 1 : n_clips != (size_t)nb)
+        return fail(c, WH_ERR_ARG, "decode: wh_ctx_set_prefixes was given %zu clips, this call has %d", n_clips, longform ? 1 : nb);
+    int nmax = 0;
+    for (size_t b = 0; b < n_clips; b++) nmax = std::max(nmax, (int)(c->pfx_offsets[b + 1] - c->pfx_offsets[b]));
+    if (nmax == 0) return WH_OK;
+    if ((size_t)nmax + p->n_prompt + p->max_new_tokens > (size_t)c->m->dims.n_text_ctx)
+        return fail(c, WH_ERR_ARG, "decode: longest prefix (%d) + prompt (%zu) + max_new_tokens (%zu) exceeds %d positions", nmax, p->n_prompt, p->max_new_tokens,
+                    c->m->dims.n_text_ctx);
+    if (c->lang_on)
+        return fail(c, WH_ERR_UNSUPPORTED, "decode: language detection with a non-empty prefix is not supported (the logits at <|startoftranscript|> depend on the "
+                                           "prefix): detect the language with an un-prefixed call first, then decode with that language in the prompt");
+    return WH_OK;
+}
+
 // ---- cross-KV + greedy loop for the nb clips whose encoder states are resident ------------------
 // `after_kv` (optional) runs on the host right after the cross-K/V projection has been enqueued and its completion event
 // recorded: the place where the NEXT batch's encoder pass is put on the encoder stream, before the host is tied up in the
@@ -323,6 +352,23 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
     const bool lp = c->lp_on, lp_probe = lp && c->lp_no_speech >= 0;
     if (lp_probe && c->lp_sot_index >= P - 1)   // the probe reads a prompt position that emits nothing
         return fail(c, WH_ERR_ARG, "decode: the no-speech probe's sot_index %d is not below n_prompt - 1 (%d)", c->lp_sot_index, P - 1);
+    // per-clip prefixes: row b is idle for off[b] = Nmax - n_b global positions, then runs prefix_b ++ prompt; every row reaches prompt[0] at
+    // global position Nmax, so on the device the prompt is simply PP = Nmax + P positions long
+    {
+        int rc = prefix_check(c, p, nb, c->pfx_win_base >= 0);
+        if (rc) return rc;
+    }
+    std::vector<int> plen(nb, 0);
+    std::vector<const int64_t*> pids(nb, nullptr);
+    int Nmax = 0;
+    if (c->pfx_on)
+        for (int b = 0; b < nb; b++) {
+            pids[b] = prefix_of(c, c->pfx_win_base, b, &plen[b]);
+            Nmax = std::max(Nmax, plen[b]);
+        }
+    const bool pfx = Nmax > 0;   // (all prefixes empty: exactly the launches of a context without prefixes)
+    const int PP = Nmax + P;
+    const int* d_off = pfx ? c->pfx_off : nullptr;
 
     // the encoder states come from the encoder stream
     if (c->s_enc != s) CTX_HIP(c, hipStreamWaitEvent(s, c->ev_enc_done, 0));
@@ -330,11 +376,19 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
     // token state
     const int ld = c->tok_ld;
     std::vector<int> feed((size_t)nb * ld, 0);
-    for (int b = 0; b < nb; b++)
-        for (int i = 0; i < P; i++) feed[(size_t)b * ld + i] = i == lang_slot ? (lang_fix ? (int)c->lang_fixed : 0) : (int)p->prompt[i];
+    for (int b = 0; b < nb; b++) {
+        for (int i = 0; i < plen[b]; i++) feed[(size_t)b * ld + Nmax - plen[b] + i] = (int)pids[b][i];   // (columns below Nmax - n_b: filler id 0 of an idle row)
+        for (int i = 0; i < P; i++) feed[(size_t)b * ld + Nmax + i] = i == lang_slot ? (lang_fix ? (int)c->lang_fixed : 0) : (int)p->prompt[i];
+    }
+    if (pfx) {
+        std::vector<int> off(nb);
+        for (int b = 0; b < nb; b++) off[b] = Nmax - plen[b];
+        CTX_HIP(c, hipMemcpyAsync(c->pfx_off, off.data(), nb * 4, hipMemcpyHostToDevice, s));
+        CTX_HIP(c, hipStreamSynchronize(s));
+    }
     CTX_HIP(c, hipMemcpyAsync(c->feed, feed.data(), feed.size() * 4, hipMemcpyHostToDevice, s));
     CTX_HIP(c, hipMemcpyAsync(c->out_tokens, feed.data(), feed.size() * 4, hipMemcpyHostToDevice, s));
-    std::vector<int> nout(nb, P);
+    std::vector<int> nout(nb, PP);
     CTX_HIP(c, hipMemcpyAsync(c->n_out, nout.data(), nb * 4, hipMemcpyHostToDevice, s));
     CTX_HIP(c, hipMemsetAsync(c->done, 0, nb * 4, s));
     CTX_HIP(c, hipMemsetAsync(c->pos, 0, 4, s));
@@ -422,10 +476,10 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
 
     DecodeState st;
     st.feed = c->feed; st.out_tokens = c->out_tokens; st.n_out = c->n_out; st.done = c->done;
-    st.forced = c->forced; st.n_forced = (int)p->n_forced; st.n_prompt = P; st.eot = (int)p->eot; st.tok_ld = ld;
+    st.forced = c->forced; st.n_forced = (int)p->n_forced; st.n_prompt = PP; st.eot = (int)p->eot; st.tok_ld = ld;
     if (lp) st.logprob = c->lp_tok;
     const long cache_l = (long)nb * D.n_heads * D.n_text_ctx * WH_HEAD_DIM;  // elements per layer
-    const int total_pos = P + NEW - 1;
+    const int total_pos = PP + NEW - 1;
     std::vector<int> done_h(nb);
     // one decoder position = ~50 kernel launches; `emits` adds final LN + LM head + argmax
     const int mpad = c->mpad;  // row pitch of the k-slab-major decode activations
@@ -449,7 +503,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
         if (embed_first) {   // token + position embedding → x, raw slab, row sums (one "tile")
             Prof pr(c, WH_KG_DEC_OTHER);
             wh_launch_dec_embed(s, prec, m->tok_emb, m->dec_pos, c->feed, ld, c->pos, c->dx, c->dxs, c->lnpart, nb, (int)d, mpad,
-                                f8 ? m->dec[0].ln1_w : nullptr, c->dshift);
+                                f8 ? m->dec[0].ln1_w : nullptr, c->dshift, d_off);
         }
         for (int l = 0; l < D.dec_layers; l++) {
             const DecLayerDev& L = m->dec[l];
@@ -466,7 +520,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
                 Prof pr(c, WH_KG_DEC_OTHER);
                 wh_launch_dec_self_attn(s, prec, c->dqkv, (char*)c->self_k + l * cache_l * esz,
                                         (char*)c->self_v + l * cache_l * esz, c->datt, c->pos, (int)d, D.n_heads,
-                                        D.n_text_ctx, nb, mpad);
+                                        D.n_text_ctx, nb, mpad, d_off);
             }
             {   // self-attention out-proj + residual → x, raw slab, LN2 partials
                 Prof pr(c, WH_KG_DEC_GEMM);
@@ -556,7 +610,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
                 a.W = m->lm_w; a.bias = m->lm_c; a.ln_s = m->lm_s; a.ln_part = c->lnpart; a.ln_tiles = ln_tiles_d;
                 a.M = nb; a.N = D.vocab; a.K = (int)d;
                 a.X = c->dxs; a.x_mpad = mpad;
-                a.pos_p = c->pos; a.n_prompt = P; a.mask_first = c->mask_first; a.mask_base = c->mask_base;
+                a.pos_p = c->pos; a.n_prompt = PP; a.mask_first = c->mask_first; a.mask_base = c->mask_base;
                 a.logits = d_logits; a.logits_rows = (int)logits_rows; a.logits_sel = d_sel; a.part_val = c->part_val; a.part_idx = c->part_idx;
                 if (c->ts_on) {
                     a.ts_state = c->ts_state; a.ts_logits = c->ts_logits; a.ts_ld = c->ts_ld;
@@ -570,7 +624,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
                 Prof pr(c, WH_KG_DEC_OTHER);
                 NextEmbed ne;
                 ne.tok_emb = m->tok_emb; ne.pos_emb = m->dec_pos; ne.x = c->dx; ne.xslab = c->dxs; ne.stats = c->lnpart;
-                ne.xgamma = f8 ? m->dec[0].ln1_w : nullptr; ne.d = (int)d; ne.mpad = mpad; ne.shift = c->dshift;
+                ne.xgamma = f8 ? m->dec[0].ln1_w : nullptr; ne.d = (int)d; ne.mpad = mpad; ne.shift = c->dshift; ne.off = d_off;
                 TsFinish tf;
                 if (c->ts_on) {
                     tf.rules = true; tf.ts_logits = c->ts_logits; tf.ts_ld = c->ts_ld; tf.state = c->ts_state;
@@ -589,7 +643,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
             }
             Prof pr(c, WH_KG_DEC_OTHER);
             wh_launch_lang_finish(s, c->lang_logits, c->lang_d_ids, (int)c->lang_ids.size(), c->lang_bcast ? 0 : -1, c->lang_probs, c->lang_chosen,
-                                  c->feed, c->out_tokens, ld, lang_slot, nb, probe ? nullptr : c->pos);
+                                  c->feed, c->out_tokens, ld, Nmax + lang_slot, nb, probe ? nullptr : c->pos);
         }
         if (probe) {   // softmax(v)[no_speech] over this prompt position's unfiltered logits (no mask, no rules, nothing recorded)
             int parts;
@@ -599,7 +653,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
                 a.W = m->lm_w; a.bias = m->lm_c; a.ln_s = m->lm_s; a.ln_part = c->lnpart; a.ln_tiles = ln_tiles_d;
                 a.M = nb; a.N = D.vocab; a.K = (int)d;
                 a.X = c->dxs; a.x_mpad = mpad;
-                a.pos_p = c->pos; a.n_prompt = P; a.mask_first = c->lp_mask_zero; a.mask_base = c->lp_mask_zero;
+                a.pos_p = c->pos; a.n_prompt = PP; a.mask_first = c->lp_mask_zero; a.mask_base = c->lp_mask_zero;
                 a.part_val = c->part_val; a.part_idx = c->part_idx; a.part_sum = c->lp_part_sum;
                 a.probe_id = (int)c->lp_no_speech; a.probe_out = c->lp_probe_v;
                 wh_launch_lm_head(s, prec, a);
@@ -614,15 +668,16 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
     // reads the position from device memory, so the graph is position-independent.  The host then
     // pays one graph launch per token instead of ~50 kernel launches (src/main.rs:793-826 is one ORT
     // Run per token in the reference).
-    for (int step = 0; step < std::min(P, total_pos); step++) launch_step(step >= P - 1, true, lp_probe && step == c->lp_sot_index, lang_det && step == c->lang_sot_index);
-    const int remaining = total_pos - P;
+    for (int step = 0; step < std::min(PP, total_pos); step++)
+        launch_step(step >= PP - 1, true, lp_probe && step == Nmax + c->lp_sot_index, lang_det && step == Nmax + c->lang_sot_index);
+    const int remaining = total_pos - PP;
     // with event timing on: every position is launched eagerly (stride 0/1), or only every stride-th one
     // (sampled live timing) while the others replay the graph
     const int stride = c->prof ? c->prof_stride : 0;
     const bool use_graph = remaining > 1 && !c->no_graph && (!c->prof || stride > 1);
     if (use_graph) {
         wh_ctx::StepKey key;
-        key.nb = nb; key.n_prompt = P; key.eot = (int)p->eot; key.n_forced = (int)p->n_forced;
+        key.nb = nb; key.n_prompt = PP; key.pfx = pfx; key.eot = (int)p->eot; key.n_forced = (int)p->n_forced;
         key.logits_rows = (int)logits_rows; key.d_logits = d_logits; key.d_sel = d_sel;
         if (c->ts_on) { key.ts_begin = (int)c->ts_begin; key.ts_max_init = c->ts_max_init; }
         if (lp) key.lp_sum = c->lp_part_sum;
@@ -715,19 +770,19 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
         c->lang_have_n = n_lang;
     }
     if (lp) {   // kept for wh_get_logprobs: each clip's generated positions
-        for (int b = 0; b < nb; b++) c->lp_rows.emplace_back(lps.begin() + (size_t)b * ld + P, lps.begin() + (size_t)b * ld + nout[b]);
+        for (int b = 0; b < nb; b++) c->lp_rows.emplace_back(lps.begin() + (size_t)b * ld + PP, lps.begin() + (size_t)b * ld + nout[b]);
         c->lp_ns_rows.insert(c->lp_ns_rows.end(), nsp.begin(), nsp.end());
         c->lp_have = true;
         c->lp_have_ns = lp_probe;
     }
     for (int b = 0; b < nb; b++) {
-        n_tokens_out[b] = (size_t)nout[b];
-        for (int i = 0; i < nout[b]; i++) tokens_out[(size_t)b * tok_stride + i] = toks[(size_t)b * ld + i];
+        n_tokens_out[b] = (size_t)(nout[b] - Nmax);   // the prefix columns are not echoed: shared prompt ++ generated, as without prefixes
+        for (int i = Nmax; i < nout[b]; i++) tokens_out[(size_t)b * tok_stride + i - Nmax] = toks[(size_t)b * ld + i];
     }
     if (logits_out) {
         for (size_t i = 0; i < n_lrows; i++) {
             const int b = sel ? sel[i] : (int)i;
-            const size_t rows = (size_t)nout[b] - P;
+            const size_t rows = (size_t)nout[b] - PP;
             CTX_HIP(c, hipMemcpy(logits_out + i * logits_rows * D.vocab, d_logits + i * logits_rows * D.vocab,
                                  std::min(rows, logits_rows) * D.vocab * 4, hipMemcpyDeviceToHost));
         }
@@ -1289,6 +1344,43 @@ int wh_ctx_set_language_detection(wh_ctx* c, const wh_language_opts* o) {
     return WH_OK;
 }
 
+// Per-clip prompt prefixes on every decode entry of the ctx.  The setter copies the ids; the per-row offsets are computed and
+// uploaded by each call (run_decode).
+int wh_ctx_set_prefixes(wh_ctx* c, const wh_prefix_opts* o) {
+    if (!c) return WH_ERR_ARG;
+    if (!o) {
+        c->pfx_on = false;
+        return WH_OK;
+    }
+    if (o->struct_size != sizeof(wh_prefix_opts)) return fail(c, WH_ERR_ARG, "wh_ctx_set_prefixes: struct_size %zu, expected %zu", o->struct_size, sizeof(wh_prefix_opts));
+    if (o->n_clips < 1 || o->n_clips > (size_t)c->max_batch || !o->offsets) return fail(c, WH_ERR_ARG, "wh_ctx_set_prefixes: n_clips %zu outside 1..max_batch (%d) (or NULL offsets)", o->n_clips, c->max_batch);
+    if (o->longform_scope != WH_PREFIX_FIRST_WINDOW && o->longform_scope != WH_PREFIX_ALL_WINDOWS) return fail(c, WH_ERR_ARG, "wh_ctx_set_prefixes: unknown longform_scope %d", (int)o->longform_scope);
+    if (o->offsets[0] != 0) return fail(c, WH_ERR_ARG, "wh_ctx_set_prefixes: offsets[0] must be 0");
+    for (size_t b = 0; b < o->n_clips; b++)
+        if (o->offsets[b + 1] < o->offsets[b]) return fail(c, WH_ERR_ARG, "wh_ctx_set_prefixes: offsets decrease at clip %zu", b);
+    const size_t n_ids = o->offsets[o->n_clips];
+    if (n_ids && !o->ids) return fail(c, WH_ERR_ARG, "wh_ctx_set_prefixes: ids is NULL");
+    const int vocab = c->m->dims.vocab;
+    for (size_t i = 0; i < n_ids; i++)
+        if (o->ids[i] < 0 || o->ids[i] >= vocab) return fail(c, WH_ERR_ARG, "wh_ctx_set_prefixes: id %lld outside the vocabulary (%d)", (long long)o->ids[i], vocab);
+    if (!c->pfx_off) {
+        hipSetDevice(c->m->device);
+        int* buf = nullptr;
+        hipError_t e = hipMalloc((void**)&buf, (size_t)c->max_batch * 4);
+        if (e == hipSuccess) e = hipMemset(buf, 0, (size_t)c->max_batch * 4);
+        if (e != hipSuccess) {
+            if (buf) hipFree(buf);
+            return fail(c, WH_ERR_NOMEM, "wh_ctx_set_prefixes: hipMalloc: %s", hipGetErrorString(e));
+        }
+        c->pfx_off = buf;
+    }
+    c->pfx_ids.assign(o->ids, o->ids + n_ids);
+    c->pfx_offsets.assign(o->offsets, o->offsets + o->n_clips + 1);
+    c->pfx_scope = o->longform_scope;
+    c->pfx_on = true;
+    return WH_OK;
+}
+
 int wh_get_languages(const wh_ctx* c, int64_t* lang_out, float* probs, size_t cap_clips, size_t* n_clips_out) {
     if (!c) return WH_ERR_ARG;
     if (!c->lang_have) return WH_ERR_STATE;
@@ -1346,6 +1438,7 @@ void wh_ctx_free(wh_ctx* c) {
     if (c->ts_state) hipFree(c->ts_state);
     if (c->lp_buf) hipFree(c->lp_buf);
     if (c->lang_buf) hipFree(c->lang_buf);
+    if (c->pfx_off) hipFree(c->pfx_off);
     if (c->s_copy) { hipStreamSynchronize(c->s_copy); hipStreamDestroy(c->s_copy); }
     if (c->ev_h2d) hipEventDestroy(c->ev_h2d);
     if (c->pcm2) hipFree(c->pcm2);
@@ -1513,6 +1606,8 @@ int wh_decode_greedy(wh_ctx* c, const wh_decode_params* p, int64_t* tokens_out, 
     if (!tokens_out || !n_tokens_out || cap_tokens < p->n_prompt + p->max_new_tokens)
         return fail(c, WH_ERR_ARG, "tokens_out needs capacity n_prompt + max_new_tokens");
     if (logits_out && cap_logits_rows < p->max_new_tokens) return fail(c, WH_ERR_ARG, "logits_out needs max_new_tokens rows");
+    rc = prefix_check(c, p, 1, false);
+    if (rc) return rc;
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -1534,6 +1629,8 @@ int wh_decode_greedy_batch(wh_ctx* c, const wh_decode_params* p, int64_t* tokens
     if (!tokens_out || !n_tokens_out || cap_clips < (size_t)nb || cap_tokens < p->n_prompt + p->max_new_tokens)
         return fail(c, WH_ERR_ARG, "tokens_out needs %d rows of capacity n_prompt + max_new_tokens", nb);
     if (logits_out && cap_logits_rows < p->max_new_tokens) return fail(c, WH_ERR_ARG, "logits_out needs max_new_tokens rows per clip");
+    rc = prefix_check(c, p, nb, false);
+    if (rc) return rc;
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -1556,6 +1653,8 @@ int wh_decode_greedy_rows(wh_ctx* c, const wh_decode_params* p, const int32_t* r
     if (!tokens_out || !n_tokens_out || cap_clips < (size_t)nb || cap_tokens < p->n_prompt + p->max_new_tokens)
         return fail(c, WH_ERR_ARG, "tokens_out needs %d rows of capacity n_prompt + max_new_tokens", nb);
     if (cap_logits_rows < p->max_new_tokens) return fail(c, WH_ERR_ARG, "logits_out needs max_new_tokens rows per selected clip");
+    rc = prefix_check(c, p, nb, false);
+    if (rc) return rc;
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -1615,6 +1714,8 @@ int wh_transcribe_batch(wh_ctx* c, const wh_clip* clips, size_t n_clips, const w
     if (rc) return rc;
     if (!clips || !tokens_out || !n_tokens_out) return fail(c, WH_ERR_ARG, "NULL argument");
     if (n_clips == 0 || n_clips > (size_t)c->max_batch) return fail(c, WH_ERR_ARG, "n_clips must be 1..max_batch (%d)", c->max_batch);
+    rc = prefix_check(c, p, (int)n_clips, false);
+    if (rc) return rc;
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -1659,6 +1760,8 @@ int wh_transcribe_batch_next(wh_ctx* c, const wh_clip* clips, size_t n_clips, co
     if (rc) return rc;
     if (!clips || !tokens_out || !n_tokens_out) return fail(c, WH_ERR_ARG, "NULL argument");
     if (n_clips == 0 || n_clips > (size_t)c->max_batch) return fail(c, WH_ERR_ARG, "n_clips must be 1..max_batch (%d)", c->max_batch);
+    rc = prefix_check(c, p, (int)n_clips, false);
+    if (rc) return rc;
     if (next_clips && (n_next == 0 || n_next > (size_t)c->max_batch)) return fail(c, WH_ERR_ARG, "n_next must be 1..max_batch (%d)", c->max_batch);
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
@@ -1720,6 +1823,8 @@ int wh_transcribe_batch_device_next(wh_ctx* c, const float* d_pcm, size_t n_clip
     if (rc) return rc;
     if (!d_pcm || !tokens_out || !n_tokens_out) return fail(c, WH_ERR_ARG, "NULL argument");
     if (n_clips == 0 || n_clips > (size_t)c->max_batch) return fail(c, WH_ERR_ARG, "n_clips must be 1..max_batch (%d)", c->max_batch);
+    rc = prefix_check(c, p, (int)n_clips, false);
+    if (rc) return rc;
     if (d_pcm_next && (n_clips_next == 0 || n_clips_next > (size_t)c->max_batch))
         return fail(c, WH_ERR_ARG, "n_clips_next must be 1..max_batch (%d)", c->max_batch);
     CTX_HIP(c, hipSetDevice(c->m->device));
@@ -1770,6 +1875,8 @@ int wh_transcribe_longform(wh_ctx* c, const float* pcm, size_t n_samples, double
     int rc = check_params(c, p);
     if (rc) return rc;
     if (!tokens_out || !n_tokens_out || !n_chunks_out) return fail(c, WH_ERR_ARG, "NULL argument");
+    rc = prefix_check(c, p, 1, true);
+    if (rc) return rc;
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -1795,7 +1902,7 @@ int wh_transcribe_longform(wh_ctx* c, const float* pcm, size_t n_samples, double
     // batch broadcasts its row 0's choice, later batches take that id as an ordinary prompt token
     struct LangScope {
         wh_ctx* c;
-        ~LangScope() { c->lang_bcast = false; c->lang_fixed = -1; }
+        ~LangScope() { c->lang_bcast = false; c->lang_fixed = -1; c->pfx_win_base = -1; }   // (and the prefix's window scope)
     } lang_scope{c};
     c->lang_bcast = true;
     for (size_t base = 0; base < nch; base += c->max_batch) {
@@ -1818,6 +1925,7 @@ int wh_transcribe_longform(wh_ctx* c, const float* pcm, size_t n_samples, double
         rc = run_encoder(c, nb, false);
         if (rc) return rc;
         CTX_HIP(c, hipEventRecord(c->ev[2], s));
+        c->pfx_win_base = (long)base;   // per-clip prefixes: which rows of this batch are window 0
         rc = run_decode(c, nb, p, tokens_out + base * stride, stride, n_tokens_out + base, nullptr, 0);
         if (rc) return rc;
         if (c->lang_on && base == 0) c->lang_fixed = c->lang_rows[0];

@@ -65,17 +65,23 @@ __device__ __forceinline__ long slab_idx(int m, int k, int mpad) { return ((long
 // Token embedding + learned position ([3P] :737, :757-766) for the rows of this position: writes the f32
 // residual stream, its raw copy in the compute dtype (slab layout) and each row's {sum x, sum x^2}
 // (one "tile" of LayerNorm partials).  One wave per row.
-template <typename T>
+// PFX (per-clip prefixes): row b sits at model position max(g - off[b], 0) of the global position g = *pos_p — the token
+// is still feed[b][g] (the host laid the rows out right-aligned), only the position row differs.  0 <= off[b] <= g + 1 keeps the position
+// row inside [0, g] ⊂ [0, n_text_ctx); an idle row (g < off[b]) embeds its filler token at position 0 and nothing reads the result.
+template <typename T, bool PFX = false>
 __global__ __launch_bounds__(256) void k_dec_embed(const T* __restrict__ tok_emb, const float* __restrict__ pos_emb,
                                                    const int* __restrict__ feed, int feed_ld,
                                                    const int* __restrict__ pos_p, float* __restrict__ x,
                                                    T* __restrict__ xslab, float* __restrict__ stats, int rows, int d,
-                                                   int mpad, const float* __restrict__ xgamma, float* __restrict__ shift) {
+                                                   int mpad, const float* __restrict__ xgamma, float* __restrict__ shift,
+                                                   const int* __restrict__ off) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int lane = threadIdx.x & 63, pos = *pos_p;
     const T* er = tok_emb + (long)feed[row * feed_ld + pos] * d;
-    const float* pr = pos_emb + (long)pos * d;
+    int mpos = pos;   // the row's model position
+    if constexpr (PFX) mpos = max(pos - max(off[row], 0), 0);
+    const float* pr = pos_emb + (long)mpos * d;
     // pass 1: the residual row and its mean; pass 2: the slab copy and the sums of the CENTRED row (SkinnyArgs::row_shift)
     float s0 = 0.0f;
     for (int c = lane * 4; c < d; c += 256) {
@@ -776,7 +782,10 @@ __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
 // LP (part_sum): the (max, sum of exp) pairs of the LM head's LP variants are merged beside the (max, index) pairs; the recorded token's
 // log-probability, -log(sum of exp(v - max) over the allowed ids), goes to st.logprob next to the token.  With RULES the text side and the
 // timestamp side are combined by what rule 5 decided: timestamps only -> the timestamp log-sum-exp alone.
-template <typename T, bool RULES = false, bool LP = false>
+// PFX (per-clip prefixes): the next position's embedding takes position row max(pos + 1 - ne.off[b], 0) — inside
+// [0, pos + 1] ⊂ [0, n_text_ctx) for any ne.off[b] >= 0; tokens, `gen`, the rules and the log-probabilities are in global positions and
+// do not change (every row reaches <|startoftranscript|> at the same global position).
+template <typename T, bool RULES = false, bool LP = false, bool PFX = false>
 __global__ __launch_bounds__(256) void k_argmax_finish(const float* __restrict__ part_val,
                                                        const int* __restrict__ part_idx, int n_tiles, int mpad, int* pos_p,
                                                        int* ticket, DecodeState st, NextEmbed ne, TsFinish ts, const float* __restrict__ part_sum) {
@@ -902,7 +911,9 @@ __global__ __launch_bounds__(256) void k_argmax_finish(const float* __restrict__
         const int next = si[0];
         __syncthreads();
         const T* er = (const T*)ne.tok_emb + (long)next * ne.d;
-        const float* pr = ne.pos_emb + (long)(pos + 1) * ne.d;
+        int mpos = pos + 1;   // the row's next model position
+        if constexpr (PFX) mpos = max(pos + 1 - max(ne.off[b], 0), 0);
+        const float* pr = ne.pos_emb + (long)mpos * ne.d;
         // the row's mean first (k_dec_embed's two passes): the slab copy and the sums are of the centred row
         float mean = 0.0f;
         if (ne.shift) {
@@ -1146,19 +1157,32 @@ __global__ __launch_bounds__(64) void k_lang_finish(const float* __restrict__ lo
 // K cache [B][H][TC][64]  (lane j scores key j: its row is 8 x 16-byte loads, issued before anything else)
 // V cache [B][H][TC][64]  (lane e reads column e of every cached row: one 128-byte line per wave load)
 // The new k / v are appended (present.{i}.decoder.{key,value}) and used straight from registers.
-template <typename T, typename TO = T>   // TO: the attention output as the out-projection's operand (slab layout)
+// PFX (per-clip prefixes): row b's history starts at cache row off[b] of its (clip, head) plane, not at row 0.  With
+// adv = min(off[b], g) at the global position g = *pos_p the kernel advances both plane pointers by adv rows and runs on the local
+// position g - adv with a local plane length tc - adv — so which lane scores which key, the prefetch groups and every summation order are
+// those of an un-prefixed row at that model position (bit-identical results).  An idle row (g < off[b]) has adv = g: local position 0,
+// it attends to its current key only and appends its k / v at cache row g < off[b], which no later position of the row reads.
+// Invariants, for any row and any off[b] (clamped to >= 0 here; the host guarantees off[b] <= Nmax and g < tc):
+//   * 0 <= adv <= g, so the row appended is cache row adv + (g - adv) = g < tc of the row's own plane — nothing outside it is written;
+//   * every cached row read is adv + r with r < g - adv (live keys) or r <= (tc - adv) - 1 (the masked V prefetch is clamped with the
+//     LOCAL plane length tc - adv, i.e. to cache row tc - 1 of the same plane) — nothing outside the plane is read;
+//   * sc[] is indexed by local positions < tc <= 512.
+template <typename T, typename TO = T, bool PFX = false>   // TO: the attention output as the out-projection's operand (slab layout)
 __global__ __launch_bounds__(64) void k_dec_self_attn(const T* __restrict__ qkv, T* __restrict__ kc,
                                                       T* __restrict__ vc, TO* __restrict__ out,
-                                                      const int* __restrict__ pos_p, int d, int n_heads, int tc,
-                                                      int mpad) {
+                                                      const int* __restrict__ pos_p, int d, int n_heads, int tc_plane,
+                                                      int mpad, const int* __restrict__ off) {
     constexpr int HD = WH_HEAD_DIM;
     typedef typename FragT<T>::type frag_t;
     __shared__ __attribute__((aligned(16))) float qs[HD];
     __shared__ __attribute__((aligned(16))) float sc[512];
-    const int h = blockIdx.x, b = blockIdx.y, lane = threadIdx.x, pos = *pos_p;
+    const int h = blockIdx.x, b = blockIdx.y, lane = threadIdx.x, gpos = *pos_p;
+    int adv = 0;   // cache rows of the plane below the row's first key
+    if constexpr (PFX) adv = min(max(off[b], 0), gpos);
+    const int pos = gpos - adv, tc = tc_plane - adv;   // local position, local plane length
     const T* row = qkv + (long)b * 3 * d;
-    T* kcb = kc + ((long)b * n_heads + h) * tc * HD;
-    T* vcb = vc + ((long)b * n_heads + h) * tc * HD;
+    T* kcb = kc + (((long)b * n_heads + h) * tc_plane + adv) * HD;
+    T* vcb = vc + (((long)b * n_heads + h) * tc_plane + adv) * HD;
     // 1. the cached K rows of this lane's first two keys go in flight before anything else
     frag_t kr[2][HD / 8];
 #pragma unroll
@@ -1663,15 +1687,23 @@ void wh_launch_dec_gemm(hipStream_t s, int prec, bool out_f32, const SkinnyArgs&
     else launch_dec_gemm_split<bf16, bf16, bf16>(s, a);
 }
 
-void wh_launch_dec_embed(hipStream_t s, int prec, const void* tok_emb, const float* pos_emb, const int* feed, int feed_ld,
-                         const int* pos_p, float* x, void* xslab, float* stats, int rows, int d, int mpad, const float* xgamma, float* shift) {
+template <bool PFX>
+void launch_dec_embed_t(hipStream_t s, int prec, const void* tok_emb, const float* pos_emb, const int* feed, int feed_ld,
+                        const int* pos_p, float* x, void* xslab, float* stats, int rows, int d, int mpad, const float* xgamma, float* shift, const int* off) {
     dim3 grid((rows + 3) / 4);
     if (prec == WH_PREC_F16X3)
-        hipLaunchKernelGGL(k_dec_embed<h2>, grid, dim3(256), 0, s, (const h2*)tok_emb, pos_emb, feed, feed_ld, pos_p, x, (h2*)xslab, stats, rows, d, mpad, xgamma, shift);
+        hipLaunchKernelGGL((k_dec_embed<h2, PFX>), grid, dim3(256), 0, s, (const h2*)tok_emb, pos_emb, feed, feed_ld, pos_p, x, (h2*)xslab, stats, rows, d, mpad, xgamma, shift, off);
     else if (prec == WH_PREC_F32)
-        hipLaunchKernelGGL(k_dec_embed<float>, grid, dim3(256), 0, s, (const float*)tok_emb, pos_emb, feed, feed_ld, pos_p, x, (float*)xslab, stats, rows, d, mpad, xgamma, shift);
+        hipLaunchKernelGGL((k_dec_embed<float, PFX>), grid, dim3(256), 0, s, (const float*)tok_emb, pos_emb, feed, feed_ld, pos_p, x, (float*)xslab, stats, rows, d, mpad, xgamma, shift, off);
     else
-        hipLaunchKernelGGL(k_dec_embed<bf16>, grid, dim3(256), 0, s, (const bf16*)tok_emb, pos_emb, feed, feed_ld, pos_p, x, (bf16*)xslab, stats, rows, d, mpad, xgamma, shift);
+        hipLaunchKernelGGL((k_dec_embed<bf16, PFX>), grid, dim3(256), 0, s, (const bf16*)tok_emb, pos_emb, feed, feed_ld, pos_p, x, (bf16*)xslab, stats, rows, d, mpad, xgamma, shift, off);
+}
+
+// off != nullptr (here and in wh_launch_argmax_finish / wh_launch_dec_self_attn): the prefix-aware instantiations
+void wh_launch_dec_embed(hipStream_t s, int prec, const void* tok_emb, const float* pos_emb, const int* feed, int feed_ld,
+                         const int* pos_p, float* x, void* xslab, float* stats, int rows, int d, int mpad, const float* xgamma, float* shift, const int* off) {
+    if (off) launch_dec_embed_t<true>(s, prec, tok_emb, pos_emb, feed, feed_ld, pos_p, x, xslab, stats, rows, d, mpad, xgamma, shift, off);
+    else launch_dec_embed_t<false>(s, prec, tok_emb, pos_emb, feed, feed_ld, pos_p, x, xslab, stats, rows, d, mpad, xgamma, shift, off);
 }
 
 template <typename T, bool RULES = false, bool LP = false>
@@ -1733,12 +1765,19 @@ int wh_lm_head_parts(int prec, const SkinnyArgs& a) {
     return n;
 }
 
+template <bool RULES, bool LP, bool PFX>
+void launch_argmax_finish_p(hipStream_t s, int prec, const float* part_val, const int* part_idx, int n_parts, int mpad, int* pos_p,
+                            int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts, const float* part_sum) {
+    if (prec == WH_PREC_F16X3) hipLaunchKernelGGL((k_argmax_finish<h2, RULES, LP, PFX>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum);
+    else if (prec == WH_PREC_F32) hipLaunchKernelGGL((k_argmax_finish<float, RULES, LP, PFX>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum);
+    else hipLaunchKernelGGL((k_argmax_finish<bf16, RULES, LP, PFX>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum);
+}
+
 template <bool RULES, bool LP>
 void launch_argmax_finish_t(hipStream_t s, int prec, const float* part_val, const int* part_idx, int n_parts, int mpad, int* pos_p,
                             int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts, const float* part_sum) {
-    if (prec == WH_PREC_F16X3) hipLaunchKernelGGL((k_argmax_finish<h2, RULES, LP>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum);
-    else if (prec == WH_PREC_F32) hipLaunchKernelGGL((k_argmax_finish<float, RULES, LP>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum);
-    else hipLaunchKernelGGL((k_argmax_finish<bf16, RULES, LP>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum);
+    if (ne.tok_emb && ne.off) launch_argmax_finish_p<RULES, LP, true>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum);
+    else launch_argmax_finish_p<RULES, LP, false>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum);
 }
 
 void wh_launch_argmax_finish(hipStream_t s, int prec, const float* part_val, const int* part_idx, int n_parts, int mpad, int* pos_p,
@@ -1789,15 +1828,22 @@ void wh_launch_lang_finish(hipStream_t s, const float* logits, const int* ids, i
     hipLaunchKernelGGL(k_lang_finish, dim3(B), dim3(64), 0, s, logits, ids, n_lang, src_row, probs, chosen, feed, out_tokens, tok_ld, tok_pos, pos_p);
 }
 
-void wh_launch_dec_self_attn(hipStream_t s, int prec, const void* qkv, void* kc, void* vc, void* out, const int* pos_p,
-                             int d, int n_heads, int tc, int B, int mpad) {
+template <bool PFX>
+void launch_dec_self_attn_t(hipStream_t s, int prec, const void* qkv, void* kc, void* vc, void* out, const int* pos_p,
+                            int d, int n_heads, int tc, int B, int mpad, const int* off) {
     dim3 grid(n_heads, B);
     if (prec == WH_PREC_F16X3)   // f32 q/k/v and caches (no matrix-core work here), the output as the out-projection's fp16-limb operand
-        hipLaunchKernelGGL((k_dec_self_attn<float, h2>), grid, dim3(64), 0, s, (const float*)qkv, (float*)kc, (float*)vc, (h2*)out, pos_p, d, n_heads, tc, mpad);
+        hipLaunchKernelGGL((k_dec_self_attn<float, h2, PFX>), grid, dim3(64), 0, s, (const float*)qkv, (float*)kc, (float*)vc, (h2*)out, pos_p, d, n_heads, tc, mpad, off);
     else if (prec == WH_PREC_F32)
-        hipLaunchKernelGGL(k_dec_self_attn<float>, grid, dim3(64), 0, s, (const float*)qkv, (float*)kc, (float*)vc, (float*)out, pos_p, d, n_heads, tc, mpad);
+        hipLaunchKernelGGL((k_dec_self_attn<float, float, PFX>), grid, dim3(64), 0, s, (const float*)qkv, (float*)kc, (float*)vc, (float*)out, pos_p, d, n_heads, tc, mpad, off);
     else
-        hipLaunchKernelGGL(k_dec_self_attn<bf16>, grid, dim3(64), 0, s, (const bf16*)qkv, (bf16*)kc, (bf16*)vc, (bf16*)out, pos_p, d, n_heads, tc, mpad);
+        hipLaunchKernelGGL((k_dec_self_attn<bf16, bf16, PFX>), grid, dim3(64), 0, s, (const bf16*)qkv, (bf16*)kc, (bf16*)vc, (bf16*)out, pos_p, d, n_heads, tc, mpad, off);
+}
+
+void wh_launch_dec_self_attn(hipStream_t s, int prec, const void* qkv, void* kc, void* vc, void* out, const int* pos_p,
+                             int d, int n_heads, int tc, int B, int mpad, const int* off) {
+    if (off) launch_dec_self_attn_t<true>(s, prec, qkv, kc, vc, out, pos_p, d, n_heads, tc, B, mpad, off);
+    else launch_dec_self_attn_t<false>(s, prec, qkv, kc, vc, out, pos_p, d, n_heads, tc, B, mpad, off);
 }
 
 // Occupancy cap of the cross-attention stream.  With more than two workgroups resident per CU (1024 clips = 4 per CU) every one

@@ -206,9 +206,10 @@ struct wh_ctx {
         const int* d_sel = nullptr;
         int ts_begin = -1, ts_max_init = -1;   // timestamp rules: -1 = off (other kernels, other arguments)
         const float* lp_sum = nullptr;         // token log-probabilities: nullptr = off (other kernels, other arguments)
+        bool pfx = false;                      // per-clip prefixes with a non-empty one in the batch: the prefix-aware kernels
         bool operator==(const StepKey& o) const {
             return nb == o.nb && n_prompt == o.n_prompt && eot == o.eot && n_forced == o.n_forced && logits_rows == o.logits_rows &&
-                   d_logits == o.d_logits && d_sel == o.d_sel && ts_begin == o.ts_begin && ts_max_init == o.ts_max_init && lp_sum == o.lp_sum;
+                   d_logits == o.d_logits && d_sel == o.d_sel && ts_begin == o.ts_begin && ts_max_init == o.ts_max_init && lp_sum == o.lp_sum && pfx == o.pfx;
         }
     } step_key;
     // Whisper's timestamp rules (wh_ctx_set_timestamp_rules): off unless ts_on.  The timestamp logits and the per-row state
@@ -255,6 +256,15 @@ struct wh_ctx {
     size_t lang_have_n = 0;         // n_lang of that call
     std::vector<int64_t> lang_rows;
     std::vector<float> lang_prob_rows;   // [clips][lang_have_n]
+    // Per-clip prompt prefixes (wh_ctx_set_prefixes): off unless pfx_on.  pfx_off is allocated by the first setter call (not part
+    // of the workspace carve) and freed in wh_ctx_free; run_decode fills it per call.  A call whose rows all have empty prefixes passes no
+    // offsets to the kernels and launches what a context without prefixes launches.
+    bool pfx_on = false;
+    std::vector<int64_t> pfx_ids;      // the clips' prefixes back to back (the setter's copy)
+    std::vector<size_t> pfx_offsets;   // [n_clips + 1]
+    int pfx_scope = 0;                 // WH_PREFIX_*
+    int* pfx_off = nullptr;            // [max_batch] device: first live global position of each row (Nmax - n_b)
+    long pfx_win_base = -1;            // long-form: index of the device batch's first window (row b is window pfx_win_base + b); -1: rows are clips
     hipGraph_t step_graph = nullptr;
     hipGraphExec_t step_exec = nullptr;
 };

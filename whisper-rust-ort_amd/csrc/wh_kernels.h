@@ -169,6 +169,7 @@ struct NextEmbed {
     float* shift = nullptr;          // [mpad]: the row's mean, subtracted from the slab copy and the sums (SkinnyArgs::row_shift)
     const float* xgamma = nullptr;
     int d = 0, mpad = 0;
+    const int* off = nullptr;        // per-clip prefixes: [B] first live position of each row (nullptr: every row starts at 0)
 };
 
 struct DecodeState {
@@ -232,7 +233,8 @@ void wh_launch_dec_gemm(hipStream_t s, int prec, bool out_f32, const SkinnyArgs&
 bool wh_dec_tile_applicable(int prec, const SkinnyArgs& a);
 void wh_launch_dec_tile(hipStream_t s, int prec, bool out_f32, const SkinnyArgs& a);
 void wh_launch_dec_embed(hipStream_t s, int prec, const void* tok_emb, const float* pos_emb, const int* feed, int feed_ld,
-                         const int* pos_p, float* x, void* xslab, float* stats, int rows, int d, int mpad, const float* xgamma, float* shift);
+                         const int* pos_p, float* x, void* xslab, float* stats, int rows, int d, int mpad, const float* xgamma, float* shift,
+                         const int* off = nullptr);   // off [rows]: per-clip prefixes, each row's first live position
 void wh_launch_lm_head(hipStream_t s, int prec, const SkinnyArgs& a);
 // wh_gemm8.hip: the same contract on 256 x 256 LDS-DMA tiles for hundreds of rows (bit-identical logits; bf16 operands)
 bool wh_lm_head_tile_applicable(const SkinnyArgs& a);
@@ -273,7 +275,7 @@ void wh_launch_lang_head(hipStream_t s, int prec, const LangHeadArgs& a);
 void wh_launch_lang_finish(hipStream_t s, const float* logits, const int* ids, int n_lang, int src_row, float* probs, int* chosen, int* feed,
                            int* out_tokens, int tok_ld, int tok_pos, int B, int* pos_p);
 void wh_launch_dec_self_attn(hipStream_t s, int prec, const void* qkv, void* kc, void* vc, void* out, const int* pos_p,
-                             int d, int n_heads, int tc, int B, int mpad);
+                             int d, int n_heads, int tc, int B, int mpad, const int* off = nullptr);   // off [B]: as in wh_launch_dec_embed
 // stream_nt: non-temporal K/V loads (set when the cross K/V of all layers exceed what the Infinity Cache can keep)
 // splits == 1: the normalised output goes straight to `out` (slab layout, row pitch mpad); else partials for the consumer's merge
 void wh_launch_dec_cross_attn(hipStream_t s, int prec, const void* q, const void* ck, const void* cv, float* part,

@@ -162,6 +162,8 @@ struct RowOut {
     bool has_lang = false;  // --language auto: the detected language code and its probability
     std::string language;
     double language_probability = 0;
+    bool has_prompt = false;  // --prompt-ids / --prompt-ids-dir: the length of the file's text context (<|startofprev|> included; 0: none)
+    long long prompt_tokens = 0;
 };
 
 // avg_logprob / no_speech_prob in JSON: shortest text that reads back as the same float (the library's values are floats); a window in which
@@ -222,6 +224,7 @@ inline std::string per_file_json(const std::vector<RowOut>& rows) {  // :1232 to
             .set("end_to_end_s", JVal::num(rows[i].end_to_end_s)).set("rtf", JVal::num(rows[i].rtf))
             .set("text", JVal::str(rows[i].text));
         if (rows[i].has_lang) { JVal v; v.raw = fmt_conf(rows[i].language_probability); r.set("language", JVal::str(rows[i].language)).set("language_probability", v); }
+        if (rows[i].has_prompt) r.set("prompt_tokens", JVal::integer(rows[i].prompt_tokens));
         if (rows[i].has_conf) { JVal v; v.raw = fmt_conf(rows[i].avg_logprob); r.set("avg_logprob", v); v.raw = fmt_conf(rows[i].no_speech_prob); r.set("no_speech_prob", v); }
         if (!rows[i].segments.empty()) { JVal sg; sg.raw = rows[i].segments; r.set("segments", sg); }
         o += "  ";
@@ -379,7 +382,7 @@ inline bool load_tokenizer(const std::string& path, Tokenizer& t) {
     return true;
 }
 
-struct WhisperSpecial { int64_t sot, eot, lang, task, no_timestamps, timestamp_begin, no_speech; };
+struct WhisperSpecial { int64_t sot, eot, lang, task, no_timestamps, timestamp_begin, no_speech, sot_prev; };
 
 inline WhisperSpecial special_tokens(const std::string& language, const std::string& task, const Tokenizer* tok) {
     if (tok && tok->loaded) {  // :529-541
@@ -398,6 +401,8 @@ inline WhisperSpecial special_tokens(const std::string& language, const std::str
             auto ns = tok->special.find(name);
             if (ns != tok->special.end()) { s.no_speech = ns->second; break; }
         }
+        auto sp = tok->special.find("<|startofprev|>");   // text context (--prompt-ids): <|startofprev|> if the tokenizer lists it, else the multilingual id
+        s.sot_prev = sp != tok->special.end() ? sp->second : 50361;
         return s;
     }
     WhisperSpecial s;  // :549-566 hard-coded multilingual ids
@@ -407,7 +412,20 @@ inline WhisperSpecial special_tokens(const std::string& language, const std::str
     s.no_timestamps = 50363;
     s.timestamp_begin = 50364;
     s.no_speech = s.no_timestamps - 1;   // 50362
+    s.sot_prev = 50361;
     return s;
+}
+
+// ---- text context (--prompt-ids; wh_ctx_set_prefixes) ----------------------------------------------------------------------------------
+// openai-whisper's rule (decoding.py _get_initial_tokens): [<|startofprev|>] ++ the last n_text_ctx / 2 - 1 ids of the history; no history,
+// no prefix.
+inline std::vector<int64_t> build_prev_prefix(const std::vector<int64_t>& history, int64_t sot_prev, int n_text_ctx) {
+    std::vector<int64_t> out;
+    if (history.empty()) return out;
+    const size_t keep = std::min(history.size(), (size_t)std::max(n_text_ctx / 2 - 1, 0));
+    out.push_back(sot_prev);
+    out.insert(out.end(), history.end() - (long)keep, history.end());
+    return out;
 }
 
 // ---- --language auto: the ids language detection chooses among (wh_ctx_set_language_detection) ----------------------------------------

@@ -158,6 +158,12 @@ long long whh_language_table(const char* tokenizer_json, long long vocab, long l
         return -1;
     }
 }
+// text context: build_prev_prefix's ids into out (cap entries at most); returns the prefix length
+size_t whh_build_prefix(const long long* history, size_t n, long long sot_prev, int n_text_ctx, long long* out, size_t cap) {
+    std::vector<int64_t> pre = build_prev_prefix(std::vector<int64_t>(history, history + n), sot_prev, n_text_ctx);
+    for (size_t i = 0; i < pre.size() && out && i < cap; i++) out[i] = pre[i];
+    return pre.size();
+}
 int whh_special_tokens(const char* language, const char* task, const char* tokenizer_json, long long* out5) {
     try {
         Tokenizer t;

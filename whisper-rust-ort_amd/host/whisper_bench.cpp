@@ -48,7 +48,29 @@ struct Args {
     bool print_plan = false;   // --print-plan: print the device -> context plan of this command line and exit before any device is touched
     size_t synthetic_clips = 0;
     uint64_t seed = 1000;
+    // additive: text context (wh_ctx_set_prefixes): ids for every file, or DIR/<audio stem>.txt per file; the prefix on every window of a long file
+    std::string prompt_ids, prompt_ids_dir;
+    bool prompt_all_windows = false;
+    bool prompts() const { return !prompt_ids.empty() || !prompt_ids_dir.empty(); }
 };
+
+// ids separated by commas or whitespace
+static std::vector<int64_t> parse_ids(const std::string& txt, const std::string& what) {
+    std::vector<int64_t> out;
+    size_t i = 0;
+    while (i < txt.size()) {
+        if (txt[i] == ',' || isspace((unsigned char)txt[i])) { i++; continue; }
+        size_t j = i;
+        while (j < txt.size() && txt[j] != ',' && !isspace((unsigned char)txt[j])) j++;
+        const std::string w = txt.substr(i, j - i);
+        char* e = nullptr;
+        const long long v = strtoll(w.c_str(), &e, 10);
+        if (*e || v < 0) throw std::runtime_error(what + ": '" + w + "' is not a token id");
+        out.push_back(v);
+        i = j;
+    }
+    return out;
+}
 
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -89,6 +111,7 @@ static bool parse_args(int argc, char** argv, Args& a) {
         else if (k == "--write-vtt") a.write_vtt = a.timestamp_rules = true;
         else if (k == "--logprobs") a.logprobs = true;
         else if (k == "--print-plan") a.print_plan = true;
+        else if (k == "--prompt-all-windows") a.prompt_all_windows = true;
         else if (k == "--help" || k == "-h") {
             printf("Usage: whisper_bench [--audio-dir DIR] [--model-id ID] [--onnx-dir DIR|synthetic:<preset>:<seed>] [--language en|auto] "
                    "[--task transcribe] [--max-new-tokens 128] [--warmup 0] [--limit-files 0] [--discovery-best-json F] "
@@ -96,10 +119,15 @@ static bool parse_args(int argc, char** argv, Args& a) {
                    "[--tokenizer-json F] [--timestamps] [--chunk-parallelism N] [--chunk-length-s 30] [--overlap-s 5] "
                    "[--device 0] [--devices 0-7] [--streams-per-gpu 1] [--load-threads N] [--precision bf16|f32|fp8|f16x3] [--max-batch 16] "
                    "[--synthetic-clips N] [--seed 1000] [--print-plan] [--timestamp-rules] [--write-srt] [--write-vtt] "
-                   "[--logprobs] [--no-speech-threshold X] [--logprob-threshold Y]\n"
+                   "[--logprobs] [--no-speech-threshold X] [--logprob-threshold Y] [--prompt-ids a,b,c] [--prompt-ids-dir DIR] [--prompt-all-windows]\n"
                    "  --language auto          the language of every file is detected from its audio (its first window's, for a file of several) among\n"
                    "                           the tokenizer's <|xx|> tokens, else the multilingual ids from 50259 on; the per-file JSON and CSV gain\n"
                    "                           language and language_probability\n"
+                   "  --prompt-ids a,b,c       text context for every file: token ids of the previous text / vocabulary hints; <|startofprev|> is put in\n"
+                   "                           front and only the last n_text_ctx/2 - 1 ids are kept (openai-whisper's initial_prompt rule)\n"
+                   "  --prompt-ids-dir DIR     the same per file: DIR/<audio stem>.txt holds the ids, separated by commas or whitespace (no file: the\n"
+                   "                           --prompt-ids list, else no context); the per-file JSON gains prompt_tokens\n"
+                   "  --prompt-all-windows     a file of several windows: the context conditions every window (default: the first one only)\n"
                    "  --logprobs               avg_logprob and no_speech_prob in every row of the per-file JSON (and in its segments)\n"
                    "  --no-speech-threshold X  with --logprob-threshold Y: a window with no_speech_prob > X and avg_logprob < Y becomes empty text and\n"
                    "  --logprob-threshold Y    no segments (both off unless given, each implies --logprobs; openai-whisper's defaults are 0.6 and -1.0)\n");
@@ -134,6 +162,8 @@ static bool parse_args(int argc, char** argv, Args& a) {
             else if (k == "--no-speech-threshold") { a.no_speech_threshold = strtod(v.c_str(), nullptr); a.logprobs = true; }
             else if (k == "--logprob-threshold") { a.logprob_threshold = strtod(v.c_str(), nullptr); a.logprobs = true; }
             else if (k == "--seed") a.seed = strtoull(v.c_str(), nullptr, 10);
+            else if (k == "--prompt-ids") a.prompt_ids = v;
+            else if (k == "--prompt-ids-dir") a.prompt_ids_dir = v;
             else { fprintf(stderr, "error: unexpected argument '%s'\n", k.c_str()); return false; }
         }
     }
@@ -326,8 +356,13 @@ static void cues_conf(std::vector<Cue>& cues, double avg_lp, double ns) {
 
 static std::string transcribe(wh_ctx* ctx, const std::vector<float>& audio, const Args& a, const Tokenizer* tok,
                               const GenCfg& gen, Timing& t, std::vector<Cue>* cues = nullptr, Conf* conf = nullptr,
-                              const LanguageTable* lt = nullptr, Lang* lang = nullptr) {
+                              const LanguageTable* lt = nullptr, Lang* lang = nullptr, const std::vector<int64_t>* prefix = nullptr) {
     const double t0 = now_s();
+    if (a.prompts()) {   // the file's text context, on its first window or on every one (no context: an empty prefix)
+        const size_t offs[2] = {0, prefix ? prefix->size() : 0};
+        wh_prefix_opts po{sizeof(wh_prefix_opts), prefix ? prefix->data() : nullptr, offs, 1, a.prompt_all_windows ? WH_PREFIX_ALL_WINDOWS : WH_PREFIX_FIRST_WINDOW};
+        if (int rc = wh_ctx_set_prefixes(ctx, &po)) throw std::runtime_error(std::string("wh_ctx_set_prefixes: ") + std::to_string(rc) + ": " + wh_last_error(ctx));
+    }
     WhisperSpecial sp = special_tokens(a.language, a.task, tok);
     std::vector<int64_t> prompt = {sp.sot, sp.lang, sp.task};
     if (!a.timestamps && !a.timestamp_rules) prompt.push_back(sp.no_timestamps);
@@ -386,6 +421,11 @@ static std::string transcribe(wh_ctx* ctx, const std::vector<float>& audio, cons
 int main(int argc, char** argv) {
     Args a;
     if (!parse_args(argc, argv, a)) return 2;
+    if (a.language == "auto" && a.prompts()) {   // (the library would refuse each call: reported here, before any device is touched)
+        fprintf(stderr, "Error: --language auto cannot be combined with --prompt-ids / --prompt-ids-dir: the language is detected from the logits at "
+                        "<|startoftranscript|>, which a text context changes; detect the language with a run without the prompt flags first\n");
+        return 2;
+    }
     try {
         for (auto* p : {&a.out_csv, &a.out_json, &a.out_summary_json})
             if (!parent_dir(*p).empty()) mkdir_p(parent_dir(*p));
@@ -489,6 +529,30 @@ int main(int argc, char** argv) {
         if (a.limit_files > 0 && files.size() > a.limit_files) files.resize(a.limit_files);
         if (files.empty()) throw std::runtime_error("No audio files found in " + a.audio_dir);
 
+        // text context: each file's prefix = <|startofprev|> ++ the tail of its ids (wh_host.h build_prev_prefix)
+        std::vector<std::vector<int64_t>> file_prefix(files.size());
+        if (a.prompts()) {
+            wh_dims dims{};
+            wh_model_get_dims(models[0], &dims);
+            const WhisperSpecial spp = special_tokens(a.language, a.task, &tok);
+            const std::vector<int64_t> every = parse_ids(a.prompt_ids, "--prompt-ids");
+            for (size_t i = 0; i < files.size(); i++) {
+                std::vector<int64_t> hist = every;
+                const std::string path = a.prompt_ids_dir + "/" + files[i].substr(0, files[i].rfind('.')) + ".txt";
+                if (!a.prompt_ids_dir.empty() && is_file(path)) {
+                    FILE* f = fopen(path.c_str(), "rb");
+                    if (!f) throw std::runtime_error("cannot read " + path);
+                    std::string txt; char b[4096]; size_t n;
+                    while ((n = fread(b, 1, sizeof b, f)) > 0) txt.append(b, n);
+                    fclose(f);
+                    hist = parse_ids(txt, path);
+                }
+                for (int64_t t : hist)
+                    if (t >= dims.vocab) throw std::runtime_error("prompt id " + std::to_string(t) + " of " + files[i] + " is outside the vocabulary (" + std::to_string(dims.vocab) + ")");
+                file_prefix[i] = build_prev_prefix(hist, spp.sot_prev, dims.n_text_ctx);
+            }
+        }
+
         auto load = [&](size_t idx, std::vector<float>& audio, double& dur) {
             if (a.synthetic_clips) { audio = synthetic_clip(a.seed + idx); dur = (double)audio.size() / 16000.0; }
             else load_audio_16k_mono(a.audio_dir + "/" + files[idx], audio, &dur);
@@ -524,7 +588,7 @@ int main(int argc, char** argv) {
             if (batch.size() == 1 && batch[0].n() > (size_t)WH_CLIP_SAMPLES) {
                 // a file longer than one window goes alone through the long-form entry (which batches its windows)
                 Result& r = results[batch[0].idx];
-                r.text = transcribe(ctx, batch[0].audio, a, &tok, gen, r.t, &r.cues, &r.conf, lang_auto ? &lang_table : nullptr, &r.lang);
+                r.text = transcribe(ctx, batch[0].audio, a, &tok, gen, r.t, &r.cues, &r.conf, lang_auto ? &lang_table : nullptr, &r.lang, &file_prefix[batch[0].idx]);
                 r.dur = batch[0].dur; r.load_s = batch[0].load_s; r.ok = true;
             } else {
                 // the per-window body of transcribe_longform_chunked (:870-915) for a batch of one-window files
@@ -537,6 +601,16 @@ int main(int argc, char** argv) {
                 std::vector<wh_clip> clips(batch.size()), nclips(next ? next->size() : 0);
                 for (size_t k = 0; k < batch.size(); k++) { clips[k].pcm = batch[k].data(); clips[k].n_samples = batch[k].n(); }
                 for (size_t k = 0; k < nclips.size(); k++) { nclips[k].pcm = (*next)[k].data(); nclips[k].n_samples = (*next)[k].n(); }
+                if (a.prompts()) {   // every file of the batch with its own text context
+                    std::vector<int64_t> ids;
+                    std::vector<size_t> offs(1, 0);
+                    for (size_t k = 0; k < batch.size(); k++) {
+                        ids.insert(ids.end(), file_prefix[batch[k].idx].begin(), file_prefix[batch[k].idx].end());
+                        offs.push_back(ids.size());
+                    }
+                    wh_prefix_opts po{sizeof(wh_prefix_opts), ids.data(), offs.data(), batch.size(), WH_PREFIX_FIRST_WINDOW};
+                    if (int rc = wh_ctx_set_prefixes(ctx, &po)) throw std::runtime_error(std::string("wh_ctx_set_prefixes: ") + std::to_string(rc) + ": " + wh_last_error(ctx));
+                }
                 const double t0 = now_s();
                 // the next batch of this worker, if it is loaded already, is copied to the device beside this batch's work
                 int rc = wh_transcribe_batch_next(ctx, clips.data(), clips.size(), nclips.empty() ? nullptr : nclips.data(), nclips.size(), &p, toks.data(), ntok.data());
@@ -595,6 +669,7 @@ int main(int argc, char** argv) {
             const double end_to_end = r.load_s + r.t.end_to_end_s;   // :1190
             rows.push_back(make_row(files[i], r.dur, end_to_end, r.text));
             if (a.timestamp_rules) rows.back().segments = cues_json(r.cues);
+            if (a.prompts()) { rows.back().has_prompt = true; rows.back().prompt_tokens = (long long)file_prefix[i].size(); }
             if (r.lang.has) { rows.back().has_lang = true; rows.back().language = r.lang.code; rows.back().language_probability = r.lang.prob; }
             if (r.conf.has) { rows.back().has_conf = true; rows.back().avg_logprob = r.conf.avg_logprob(); rows.back().no_speech_prob = r.conf.no_speech_prob(); }
             loadl.push_back(r.load_s); pre.push_back(r.t.preprocess_s); model_only.push_back(r.t.model_only_s);
