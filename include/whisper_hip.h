@@ -262,6 +262,35 @@ typedef struct {
     int32_t longform_scope;  /* WH_PREFIX_* */
 } wh_prefix_opts;
 int wh_ctx_set_prefixes(wh_ctx* c, const wh_prefix_opts* o);
+/* Repetition penalty and no-repeat n-grams in the greedy token loop (HF generate's RepetitionPenaltyLogitsProcessor and
+ * NoRepeatNGramLogitsProcessor; faster-whisper / CTranslate2's repetition_penalty and no_repeat_ngram_size).  No reference entry corresponds:
+ * the reference keeps plain argmax (src/main.rs:709-735).  With this set, every decode entry of the ctx (wh_decode_greedy*,
+ * wh_transcribe_batch*, the device / pipelined entries, wh_transcribe_longform) adjusts each row's logits at every generated position, before
+ * the suppress masks and the timestamp rules (HF's processor order):
+ *   - history h = the row's fed tokens at generated positions so far (with wh_decode_params.forced: the forced ones).  The prompt, a per-clip
+ *     prefix and the language token are not part of it;
+ *   - exempt(id) = the timestamp rules are set and id >= timestamp_begin: never penalised, never banned (with the rules off no id is exempt);
+ *   - penalty: for every distinct non-exempt id in h, v' = v > 0 ? v * inv : v * p with p the f32 penalty and inv = 1.0f / p computed once in
+ *     f32 (one f32 multiplication; at most one ulp from HF's division).  NaN stays NaN and never wins, +-inf stays;
+ *   - ban, n = no_repeat_ngram_size: if len(h) + 1 >= n, let s = the last n - 1 ids of h (empty for n = 1); for every i with
+ *     h[i : i+n-1] == s and i + n - 1 < len(h) the id h[i+n-1] is set to -inf unless exempt.  Timestamps are ordinary members of the
+ *     n-grams.  A banned id that is also penalised is banned;
+ *   - the recorded token is the argmax of the adjusted logits after the masks and rules (ties to the lowest id, NaN never wins, nothing left:
+ *     0); rule 5 compares against the largest adjusted allowed text logit; wh_get_logprobs reports the log-softmax of the adjusted, allowed
+ *     logits; logits_out of the parity entries stays the raw logits, bit for bit; the no-speech probe and language detection read prompt
+ *     positions and are untouched.
+ * The setter allocates a per-row bitmap [max_batch][ceil(vocab / 32)] and a per-row side buffer float [max_batch][vocab] (425 MB reserved at 2048
+ * whisper-base rows; at most 448 entries written per row and step) and frees both when the option is cleared.  {1.0f, 0} is the same as
+ * NULL: the plain kernels are launched, and tokens, logits and every other output are what they were without this entry.
+ * Refused with WH_ERR_ARG (the ctx unchanged): a wrong struct_size, a penalty that is not finite or <= 0, no_repeat_ngram_size outside
+ * 0 .. WH_MAX_NGRAM.  o == NULL turns it off (the default). */
+#define WH_MAX_NGRAM 32
+typedef struct {
+    size_t struct_size;           /* sizeof(wh_repetition_opts) */
+    float repetition_penalty;     /* > 0, finite; 1.0f = off */
+    int32_t no_repeat_ngram_size; /* 0 = off; 1 .. WH_MAX_NGRAM */
+} wh_repetition_opts;
+int wh_ctx_set_repetition(wh_ctx* c, const wh_repetition_opts* o);
 const char* wh_last_error(const wh_ctx* c); /* c == NULL: last load/create error of this thread */
 int wh_get_timings(const wh_ctx* c, wh_timing* out);
 

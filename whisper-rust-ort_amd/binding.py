@@ -35,7 +35,7 @@ EXPORTS = ("wh_model_load", "wh_model_create", "wh_model_free", "wh_model_get_di
            "wh_transcribe_batch_next", "wh_transcribe_batch_device", "wh_transcribe_batch_device_next", "wh_longform_plan", "wh_transcribe_longform", "wh_profile_enable",
            "wh_profile_get", "wh_synthetic_weights", "wh_e4m3_quantize", "wh_e4m3_dequantize", "wh_abi_version",
            "wh_device_count", "wh_ctx_set_timestamp_rules", "wh_ctx_set_logprobs", "wh_get_logprobs",
-           "wh_ctx_set_language_detection", "wh_get_languages", "wh_ctx_set_prefixes")
+           "wh_ctx_set_language_detection", "wh_get_languages", "wh_ctx_set_prefixes", "wh_ctx_set_repetition")
 
 
 class WhisperHipError(RuntimeError):
@@ -86,6 +86,13 @@ class WhLanguageOpts(C.Structure):
 class WhPrefixOpts(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("ids", C.POINTER(C.c_int64)), ("offsets", C.POINTER(C.c_size_t)), ("n_clips", C.c_size_t),
                 ("longform_scope", C.c_int32)]
+
+
+WH_MAX_NGRAM = 32
+
+
+class WhRepetitionOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32)]
 
 
 def pack_prefixes(prefixes: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.ndarray]:
@@ -172,6 +179,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.wh_ctx_set_language_detection.argtypes = [vp, C.POINTER(WhLanguageOpts)]
     L.wh_get_languages.argtypes = [vp, i64p, f32p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.wh_ctx_set_prefixes.argtypes = [vp, C.POINTER(WhPrefixOpts)]
+    L.wh_ctx_set_repetition.argtypes = [vp, C.POINTER(WhRepetitionOpts)]
     _lib = L
     return L
 
@@ -371,6 +379,16 @@ class Context:
 
     def clear_prefixes(self):
         self._check(self.lib.wh_ctx_set_prefixes(self.h, None))
+
+    def set_repetition(self, penalty: float = 1.0, ngram: int = 0):
+        """wh_ctx_set_repetition: every decode entry of this context applies HF's repetition penalty (v > 0 ? v / penalty : v * penalty on the
+        ids of the row's generated history) and bans the ids that would repeat an n-gram of `ngram` ids, before the suppress masks and the
+        timestamp rules (timestamps are exempt while the rules are on).  (1.0, 0) turns it off."""
+        o = WhRepetitionOpts(C.sizeof(WhRepetitionOpts), penalty, ngram)
+        self._check(self.lib.wh_ctx_set_repetition(self.h, C.byref(o)))
+
+    def clear_repetition(self):
+        self._check(self.lib.wh_ctx_set_repetition(self.h, None))
 
     def _took(self, toks: List[np.ndarray], params: "DecodeParams") -> List[np.ndarray]:
         self._gen_lens = [len(t) - len(params.prompt) for t in toks]   # (what logprobs() cuts its rows to)

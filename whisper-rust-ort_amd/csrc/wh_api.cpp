@@ -6,6 +6,7 @@
 // transcribe_longform_chunked (:870-915, 946-967).
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <cmath>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -393,6 +394,8 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
     CTX_HIP(c, hipMemsetAsync(c->done, 0, nb * 4, s));
     CTX_HIP(c, hipMemsetAsync(c->pos, 0, 4, s));
     CTX_HIP(c, hipMemsetAsync(c->step_ticket, 0, 4, s));
+    const bool rep_on = c->rep_on;
+    if (rep_on) CTX_HIP(c, hipMemsetAsync(c->rep_bits, 0, (size_t)nb * c->rep_words * 4, s));   // no history yet: nothing is touched
     std::vector<int> forced(p->n_forced);
     for (size_t i = 0; i < p->n_forced; i++) forced[i] = (int)p->forced[i];
     if (!forced.empty()) CTX_HIP(c, hipMemcpyAsync(c->forced, forced.data(), forced.size() * 4, hipMemcpyHostToDevice, s));
@@ -617,6 +620,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
                     a.ts_begin = (int)c->ts_begin; a.ts_max_init = c->ts_max_init;
                 }
                 if (lp) a.part_sum = c->lp_part_sum;
+                if (rep_on) { a.rep_bits = c->rep_bits; a.rep_side = c->rep_side; a.rep_words = c->rep_words; }
                 wh_launch_lm_head(s, prec, a);
                 lm_parts = wh_lm_head_parts(prec, a);
             }
@@ -630,7 +634,14 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
                     tf.rules = true; tf.ts_logits = c->ts_logits; tf.ts_ld = c->ts_ld; tf.state = c->ts_state;
                     tf.ts_begin = (int)c->ts_begin; tf.vocab = D.vocab;
                 }
-                wh_launch_argmax_finish(s, prec, c->part_val, c->part_idx, lm_parts, mpad, c->pos, c->step_ticket, st, nb, ne, tf, lp ? c->lp_part_sum : nullptr);
+                RepFinish rf;
+                if (rep_on) {
+                    rf.on = true; rf.bits = c->rep_bits; rf.side = c->rep_side; rf.words = c->rep_words; rf.vocab = D.vocab;
+                    rf.p = c->rep_p; rf.inv = c->rep_inv; rf.ngram = c->rep_n;
+                    if (c->ts_on) rf.exempt_from = (int)c->ts_begin;   // timestamps repeat in pairs and the rules own them
+                    rf.mask_first = c->mask_first; rf.mask_base = c->mask_base;
+                }
+                wh_launch_argmax_finish(s, prec, c->part_val, c->part_idx, lm_parts, mpad, c->pos, c->step_ticket, st, nb, ne, tf, lp ? c->lp_part_sum : nullptr, rf);
             }
         }
         if (lang) {   // the listed ids' unfiltered logits of this prompt position -> each row's language token at the next one
@@ -681,6 +692,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
         key.logits_rows = (int)logits_rows; key.d_logits = d_logits; key.d_sel = d_sel;
         if (c->ts_on) { key.ts_begin = (int)c->ts_begin; key.ts_max_init = c->ts_max_init; }
         if (lp) key.lp_sum = c->lp_part_sum;
+        if (rep_on) { key.rep = true; key.rep_p = c->rep_p; key.rep_n = c->rep_n; }
         if (!c->step_exec || !(c->step_key == key)) {
             drop_step_graph(c);   // nothing of it is in flight: every call ends with a stream synchronisation
             c->capturing = true;  // no event records inside the captured step
@@ -1292,6 +1304,51 @@ int wh_ctx_set_logprobs(wh_ctx* c, const wh_logprob_opts* o) {
     return WH_OK;
 }
 
+// Repetition penalty and no-repeat n-grams on every decode entry of the ctx.  The bitmap and the side buffer are allocated when
+// the option is turned on and freed when it is cleared ({1.0f, 0} clears it); the captured decode step is keyed on the setting and dropped
+// before a buffer it holds is freed.
+static void rep_release(wh_ctx* c) {
+    if (c->rep_bits || c->rep_side) drop_step_graph(c);   // (a captured step may hold the buffers' addresses)
+    if (c->rep_bits) hipFree(c->rep_bits);
+    if (c->rep_side) hipFree(c->rep_side);
+    c->rep_bits = nullptr; c->rep_side = nullptr;
+    c->rep_on = false; c->rep_p = c->rep_inv = 1.0f; c->rep_n = 0;
+}
+int wh_ctx_set_repetition(wh_ctx* c, const wh_repetition_opts* o) {
+    if (!c) return WH_ERR_ARG;
+    if (o) {
+        if (o->struct_size != sizeof(wh_repetition_opts)) return fail(c, WH_ERR_ARG, "wh_ctx_set_repetition: struct_size %zu, expected %zu", o->struct_size, sizeof(wh_repetition_opts));
+        if (!std::isfinite(o->repetition_penalty) || !(o->repetition_penalty > 0.0f))
+            return fail(c, WH_ERR_ARG, "wh_ctx_set_repetition: repetition_penalty %g is not a finite value above 0", (double)o->repetition_penalty);
+        if (o->no_repeat_ngram_size < 0 || o->no_repeat_ngram_size > WH_MAX_NGRAM)
+            return fail(c, WH_ERR_ARG, "wh_ctx_set_repetition: no_repeat_ngram_size %d outside 0 .. %d", (int)o->no_repeat_ngram_size, WH_MAX_NGRAM);
+    }
+    if (!o || (o->repetition_penalty == 1.0f && o->no_repeat_ngram_size == 0)) {
+        hipSetDevice(c->m->device);
+        rep_release(c);
+        return WH_OK;
+    }
+    if (!c->rep_bits) {
+        hipSetDevice(c->m->device);
+        const size_t vocab = (size_t)c->m->dims.vocab, words = (vocab + 31) / 32, B = (size_t)c->max_batch;
+        unsigned* bits = nullptr; float* side = nullptr;
+        hipError_t e = hipMalloc((void**)&bits, B * words * 4);
+        if (e == hipSuccess) e = hipMalloc((void**)&side, B * vocab * 4);
+        if (e == hipSuccess) e = hipMemset(bits, 0, B * words * 4);
+        if (e != hipSuccess) {
+            if (bits) hipFree(bits);
+            if (side) hipFree(side);
+            return fail(c, WH_ERR_NOMEM, "wh_ctx_set_repetition: hipMalloc: %s", hipGetErrorString(e));
+        }
+        c->rep_bits = bits; c->rep_side = side; c->rep_words = (int)words;
+    }
+    c->rep_on = true;
+    c->rep_p = o->repetition_penalty;
+    c->rep_inv = 1.0f / o->repetition_penalty;
+    c->rep_n = o->no_repeat_ngram_size;
+    return WH_OK;
+}
+
 // Language detection on every decode entry of the ctx.  The buffers are allocated the first time it is turned on; nothing of
 // it enters the captured decode step.
 int wh_ctx_set_language_detection(wh_ctx* c, const wh_language_opts* o) {
@@ -1439,6 +1496,8 @@ void wh_ctx_free(wh_ctx* c) {
     if (c->lp_buf) hipFree(c->lp_buf);
     if (c->lang_buf) hipFree(c->lang_buf);
     if (c->pfx_off) hipFree(c->pfx_off);
+    if (c->rep_bits) hipFree(c->rep_bits);
+    if (c->rep_side) hipFree(c->rep_side);
     if (c->s_copy) { hipStreamSynchronize(c->s_copy); hipStreamDestroy(c->s_copy); }
     if (c->ev_h2d) hipEventDestroy(c->ev_h2d);
     if (c->pcm2) hipFree(c->pcm2);

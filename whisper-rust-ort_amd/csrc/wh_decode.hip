@@ -574,7 +574,11 @@ __global__ __launch_bounds__(NW * 64, 2) void k_dec_gemm_wide(SkinnyArgs a) {
 // LP: token log-probabilities (SkinnyArgs::part_sum): beside each (max, index) partial the sum of exp(v - max) over the ids the
 // partial ranged over, kept online per lane (a tile's accumulators are gone once the next tile starts) and merged over the row's four lane
 // groups; the logit of SkinnyArgs::probe_id goes to probe_out (the no-speech probe).  The LP = false instantiations are unchanged.
-template <typename T, int MT, bool RULES = false, bool LP = false>
+// REP: repetition penalty / no-repeat n-grams (SkinnyArgs::rep_*): the row's touched-id bits are OR-ed into the suppress bits, so a
+// touched id enters no partial, no sum and no timestamp logit; its raw logit (the same expression) leaves by one predicated store to the row's
+// side buffer for k_argmax_finish<..., REP>.  Bitmap and side-buffer indices stay inside row m's slice (m < M, nn < N).  The REP = false
+// instantiations are unchanged.
+template <typename T, int MT, bool RULES = false, bool LP = false, bool REP = false>
 __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
     extern __shared__ __attribute__((aligned(128))) char smem_raw[];   // 128: h2 tiles find their 32-blocks from the address
     constexpr int EPC = 16 / (int)sizeof(T);
@@ -701,6 +705,10 @@ __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
         for (int t = 0; t < MT; t++) {
             const int m = m0 + t * 16 + fl;
             const float mean = a.ln_part ? lnstat[2 * (t * 16 + fl)] : 0.0f, rstd = a.ln_part ? lnstat[2 * (t * 16 + fl) + 1] : 1.0f;
+            unsigned rbits = 0;   // REP: touched bits of this lane's 4 columns of row m
+            if constexpr (REP) {
+                if (n < a.N && m < a.M) rbits = a.rep_bits[(long)m * a.rep_words + (n >> 5)] >> (n & 31);
+            }
 #pragma unroll
             for (int e = 0; e < 4; e++) {
                 const int nn = n + e;
@@ -710,7 +718,10 @@ __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
                         const int slot = a.logits_sel ? a.logits_sel[m] : m;
                         if (slot >= 0) a.logits[((long)slot * a.logits_rows + gen) * a.N + nn] = v;
                     }
-                    const bool sup = (mbits >> e) & 1u;
+                    if constexpr (REP) {
+                        if ((rbits >> e) & 1u) a.rep_side[(long)m * a.N + nn] = v;
+                    }
+                    const bool sup = ((mbits | rbits) >> e) & 1u;
                     if constexpr (LP) {
                         if (nn == a.probe_id) a.probe_out[m] = v;
                         const bool text_ok = RULES ? (!sup && nn >= tlo[t] && nn < a.ts_begin) : !sup;
@@ -785,13 +796,32 @@ __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
 // PFX (per-clip prefixes): the next position's embedding takes position row max(pos + 1 - ne.off[b], 0) — inside
 // [0, pos + 1] ⊂ [0, n_text_ctx) for any ne.off[b] >= 0; tokens, `gen`, the rules and the log-probabilities are in global positions and
 // do not change (every row reaches <|startoftranscript|> at the same global position).
-template <typename T, bool RULES = false, bool LP = false, bool PFX = false>
+// REP (rp.on; repetition penalty / no-repeat n-grams): the LM head's REP variants kept the row's touched ids out of the partials
+// and left their raw logits in rp.side.  The workgroup walks the row's generated history h = st.feed[b][n_prompt .. pos] (reads stay in those
+// columns; at most WH_REP_MAX_HIST entries, in LDS), and for each distinct touched id reads the stored logit, drops it if it is banned,
+// suppressed by the masks or below the rules' text_lo, else applies the penalty (one f32 multiplication by p or 1 / p) and merges
+// (value, id[, 1]) into its reduction — before rule 5 and the log-probability are formed.  After `next` is chosen it rewrites the row's bits
+// for the next position (history h ++ [next]): clears this position's bans, sets `next` when the penalty is on, sets the new bans.  Row b's
+// bits are written by workgroup b only, and the LM head of position pos + 1 runs after this kernel in stream / graph order.
+// entry i of the history hs[0 .. L) is banned when it closes an n-gram whose first n - 1 ids equal the history's last n - 1
+__device__ __forceinline__ void rep_bans(const int* hs, unsigned char* ban, int L, int n, int exempt_from, int tid) {
+    for (int i = tid; i < L; i += 256) {
+        bool b = n > 0 && L >= n - 1 && i >= n - 1 && hs[i] < exempt_from;
+        for (int k = 0; b && k < n - 1; k++) b = hs[i - (n - 1) + k] == hs[L - (n - 1) + k];
+        ban[i] = b ? 1 : 0;
+    }
+}
+
+template <typename T, bool RULES = false, bool LP = false, bool PFX = false, bool REP = false>
 __global__ __launch_bounds__(256) void k_argmax_finish(const float* __restrict__ part_val,
                                                        const int* __restrict__ part_idx, int n_tiles, int mpad, int* pos_p,
-                                                       int* ticket, DecodeState st, NextEmbed ne, TsFinish ts, const float* __restrict__ part_sum) {
+                                                       int* ticket, DecodeState st, NextEmbed ne, TsFinish ts, const float* __restrict__ part_sum,
+                                                       RepFinish rp) {
     __shared__ float sv[256];
     __shared__ int si[256];
     __shared__ float ssum[LP ? 256 : 1];
+    __shared__ int rh[REP ? WH_REP_MAX_HIST + 1 : 1];              // REP: the row's generated history, then `next`
+    __shared__ unsigned char rban[REP ? WH_REP_MAX_HIST + 1 : 1];  // REP: entry i's id is banned
     const int b = blockIdx.x, tid = threadIdx.x;
     const int pos = *pos_p;
     float bv = -INFINITY;
@@ -822,6 +852,34 @@ __global__ __launch_bounds__(256) void k_argmax_finish(const float* __restrict__
 #pragma unroll
         for (int u = 0; u < 8; u++)
             if (v[u] > bv || (v[u] == bv && ix[u] < bi)) { bv = v[u]; bi = ix[u]; }
+    }
+    int rep_L = 0;
+    if constexpr (REP) {
+        const int gen = pos - (st.n_prompt - 1);
+        rep_L = min(max(gen, 0), WH_REP_MAX_HIST);
+        const int* hrow = st.feed + (long)b * st.tok_ld + st.n_prompt;   // columns [n_prompt, pos]
+        for (int i = tid; i < rep_L; i += 256) rh[i] = hrow[i];
+        __syncthreads();
+        rep_bans(rh, rban, rep_L, rp.ngram, rp.exempt_from, tid);
+        __syncthreads();
+        const unsigned* mask = (gen == 0) ? rp.mask_first : rp.mask_base;
+        int text_lo = 0;
+        if constexpr (RULES) text_lo = gen > 0 ? ts.state[4 * b] : ts.ts_begin;   // (read before thread 0 writes the next position's state)
+        const unsigned* brow = rp.bits + (long)b * rp.words;
+        for (int i = tid; i < rep_L; i += 256) {
+            const int id = rh[i];
+            bool first = true, banned = false;
+            for (int j = 0; j < rep_L; j++)
+                if (rh[j] == id) { first = first && j >= i; banned = banned || rban[j]; }
+            if (!first || id < 0 || id >= rp.vocab) continue;                   // each distinct id once
+            if (!((brow[id >> 5] >> (id & 31)) & 1u)) continue;                 // not touched: the LM head's partials hold it
+            if (banned || ((mask[id >> 5] >> (id & 31)) & 1u) || id < text_lo) continue;
+            float v = rp.side[(long)b * rp.vocab + id];
+            v = v > 0.0f ? v * rp.inv : v * rp.p;
+            if (!(v > -INFINITY)) continue;                                     // NaN and -inf: never win, add nothing
+            if constexpr (LP) bs = lp_merge(bv, bs, v, 1.0f);
+            if (v > bv || (v == bv && id < bi)) { bv = v; bi = id; }
+        }
     }
     sv[tid] = bv; si[tid] = bi;
     if constexpr (LP) ssum[tid] = bs;
@@ -903,6 +961,28 @@ __global__ __launch_bounds__(256) void k_argmax_finish(const float* __restrict__
             ts.state[4 * b + 3] = last_t;
         }
         si[0] = next;
+    }
+    if constexpr (REP) {
+        // the row's bits for the next position, whose history is h ++ [next]
+        __syncthreads();
+        const int next = si[0];
+        unsigned* brow = rp.bits + (long)b * rp.words;
+        const bool pen = rp.p != 1.0f;
+        if (!pen) {   // this position's bans leave (with the penalty on they stay set: every banned id is in the history)
+            for (int i = tid; i < rep_L; i += 256)
+                if (rban[i] && rh[i] >= 0 && rh[i] < rp.vocab) {
+                    const unsigned old = atomicAnd(&brow[rh[i] >> 5], ~(1u << (rh[i] & 31)));   // (returning form: done before the barrier below)
+                    asm volatile("" ::"v"(old));
+                }
+        }
+        __syncthreads();
+        if (tid == 0) rh[rep_L] = next;
+        __syncthreads();
+        rep_bans(rh, rban, rep_L + 1, rp.ngram, rp.exempt_from, tid);
+        __syncthreads();
+        if (tid == 0 && pen && next >= 0 && next < min(rp.exempt_from, rp.vocab)) atomicOr(&brow[next >> 5], 1u << (next & 31));
+        for (int i = tid; i < rep_L + 1; i += 256)
+            if (rban[i] && rh[i] >= 0 && rh[i] < rp.vocab) atomicOr(&brow[rh[i] >> 5], 1u << (rh[i] & 31));
     }
     if (ne.tok_emb) {
         // token + position embedding of the next position for this clip's row (k_dec_embed's work, one launch
@@ -1706,7 +1786,7 @@ void wh_launch_dec_embed(hipStream_t s, int prec, const void* tok_emb, const flo
     else launch_dec_embed_t<false>(s, prec, tok_emb, pos_emb, feed, feed_ld, pos_p, x, xslab, stats, rows, d, mpad, xgamma, shift, off);
 }
 
-template <typename T, bool RULES = false, bool LP = false>
+template <typename T, bool RULES = false, bool LP = false, bool REP = false>
 void launch_lm_head_t(hipStream_t s, const SkinnyArgs& a, int* n_parts_out = nullptr) {
     const int n_tiles = (a.N + 15) / 16;
     int mt = std::min(wh_dbg_lm_mt, (a.M + 15) / 16);
@@ -1721,7 +1801,7 @@ void launch_lm_head_t(hipStream_t s, const SkinnyArgs& a, int* n_parts_out = nul
     if (n_parts_out) { *n_parts_out = (int)grid.x * 4; return; }  // query only: partials per row = waves per row group
 #define WH_LM(MT_)                                                \
     {                                                             \
-        auto kfn = k_lm_head<T, MT_, RULES, LP>;                  \
+        auto kfn = k_lm_head<T, MT_, RULES, LP, REP>;             \
         set_max_smem(kfn, sm);                                    \
         hipLaunchKernelGGL(kfn, grid, dim3(256), sm, s, a);       \
     }
@@ -1737,9 +1817,17 @@ void launch_lm_head_t(hipStream_t s, const SkinnyArgs& a, int* n_parts_out = nul
 // a.X = final-LayerNorm'ed rows [M][K] in the compute dtype
 // a.ts_logits != nullptr: the timestamp-rules variants (same logits, same partial count)
 // a.part_sum != nullptr: the log-probability variants (same logits, same (max, index) partials)
+// a.rep_bits != nullptr: the repetition variants (same logits, same partial count)
 template <typename T>
 static void launch_lm_head_v(hipStream_t s, const SkinnyArgs& a) {
     const bool r = a.ts_logits != nullptr, l = a.part_sum != nullptr;
+    if (a.rep_bits) {
+        if (r && l) launch_lm_head_t<T, true, true, true>(s, a);
+        else if (r) launch_lm_head_t<T, true, false, true>(s, a);
+        else if (l) launch_lm_head_t<T, false, true, true>(s, a);
+        else launch_lm_head_t<T, false, false, true>(s, a);
+        return;
+    }
     if (r && l) launch_lm_head_t<T, true, true>(s, a);
     else if (r) launch_lm_head_t<T, true>(s, a);
     else if (l) launch_lm_head_t<T, false, true>(s, a);
@@ -1765,27 +1853,32 @@ int wh_lm_head_parts(int prec, const SkinnyArgs& a) {
     return n;
 }
 
-template <bool RULES, bool LP, bool PFX>
+template <bool RULES, bool LP, bool PFX, bool REP>
 void launch_argmax_finish_p(hipStream_t s, int prec, const float* part_val, const int* part_idx, int n_parts, int mpad, int* pos_p,
-                            int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts, const float* part_sum) {
-    if (prec == WH_PREC_F16X3) hipLaunchKernelGGL((k_argmax_finish<h2, RULES, LP, PFX>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum);
-    else if (prec == WH_PREC_F32) hipLaunchKernelGGL((k_argmax_finish<float, RULES, LP, PFX>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum);
-    else hipLaunchKernelGGL((k_argmax_finish<bf16, RULES, LP, PFX>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum);
+                            int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts, const float* part_sum, const RepFinish& rp) {
+    if (prec == WH_PREC_F16X3) hipLaunchKernelGGL((k_argmax_finish<h2, RULES, LP, PFX, REP>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum, rp);
+    else if (prec == WH_PREC_F32) hipLaunchKernelGGL((k_argmax_finish<float, RULES, LP, PFX, REP>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum, rp);
+    else hipLaunchKernelGGL((k_argmax_finish<bf16, RULES, LP, PFX, REP>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum, rp);
 }
 
 template <bool RULES, bool LP>
 void launch_argmax_finish_t(hipStream_t s, int prec, const float* part_val, const int* part_idx, int n_parts, int mpad, int* pos_p,
-                            int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts, const float* part_sum) {
-    if (ne.tok_emb && ne.off) launch_argmax_finish_p<RULES, LP, true>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum);
-    else launch_argmax_finish_p<RULES, LP, false>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum);
+                            int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts, const float* part_sum, const RepFinish& rp) {
+    const bool pfx = ne.tok_emb && ne.off;
+    if (rp.on) {   // the repetition variants
+        if (pfx) launch_argmax_finish_p<RULES, LP, true, true>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum, rp);
+        else launch_argmax_finish_p<RULES, LP, false, true>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum, rp);
+    }
+    else if (pfx) launch_argmax_finish_p<RULES, LP, true, false>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum, rp);
+    else launch_argmax_finish_p<RULES, LP, false, false>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum, rp);
 }
 
 void wh_launch_argmax_finish(hipStream_t s, int prec, const float* part_val, const int* part_idx, int n_parts, int mpad, int* pos_p,
-                             int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts, const float* part_sum) {
-    if (ts.rules && part_sum) launch_argmax_finish_t<true, true>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum);
-    else if (ts.rules) launch_argmax_finish_t<true, false>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum);
-    else if (part_sum) launch_argmax_finish_t<false, true>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum);
-    else launch_argmax_finish_t<false, false>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum);
+                             int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts, const float* part_sum, const RepFinish& rp) {
+    if (ts.rules && part_sum) launch_argmax_finish_t<true, true>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum, rp);
+    else if (ts.rules) launch_argmax_finish_t<true, false>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum, rp);
+    else if (part_sum) launch_argmax_finish_t<false, true>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum, rp);
+    else launch_argmax_finish_t<false, false>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum, rp);
 }
 
 void wh_launch_nospeech_finish(hipStream_t s, const float* part_val, const float* part_sum, int n_parts, int mpad, const float* probe_v,

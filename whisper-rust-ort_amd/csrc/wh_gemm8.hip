@@ -420,7 +420,11 @@ __global__ __launch_bounds__(512, Geo<BN>::WAVES_PER_SIMD) void k_gemm8(GemmArgs
 // RULES: Whisper's timestamp rules in the epilogue (k_lm_head<T, MT, true>'s contract: text partials, timestamp logits to SkinnyArgs::ts_logits).
 // LP: token log-probabilities (k_lm_head<T, MT, RULES, true>'s contract: SkinnyArgs::part_sum, probe_id / probe_out).  No running maximum in the
 // column loop: once a row's maximum is known, a second pass over the row's accumulators adds exp(v - max).
-template <bool RULES = false, bool LP = false>
+// REP: repetition penalty / no-repeat n-grams (k_lm_head<T, MT, RULES, LP, true>'s contract: an id whose bit is set in the row's slice of
+// SkinnyArgs::rep_bits enters no partial and no sum, its raw logit goes to SkinnyArgs::rep_side; m < M, nn < N keep both inside row m's slice).
+// The tile's 256 rows x 8 bitmap words are staged in LDS after the main loop (one global load round per workgroup), so a row costs one 8-byte
+// LDS read.
+template <bool RULES = false, bool LP = false, bool REP = false>
 __global__ __launch_bounds__(512, 2) void k_lm_head_tile(SkinnyArgs a) {
     typedef Geo<256> G;
     constexpr int BN = 256, TM = G::TM, TN = G::TN, NSLOT = G::NSLOT, SLOT = G::SLOT, SLOT_A = G::SLOT_A;
@@ -444,6 +448,7 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile(SkinnyArgs a) {
     float* lnstat = reinterpret_cast<float*>(smem + (size_t)NSLOT * SLOT);   // [256][2] mean, rstd
     float* lnq = lnstat + 2 * BM;                                            // [4][256][2]
     int* tsr = reinterpret_cast<int*>(lnq + 4 * BM * 2);                     // RULES: [256][4] the rows' allowed ranges (written after the main loop)
+    unsigned* rbw = reinterpret_cast<unsigned*>(tsr + 4 * BM);               // REP: [256][8] the rows' touched bits of this tile's 256 columns (written after the main loop)
     if (a.ln_part) {
         const int r = tid & (BM - 1), h = tid >> 8, row = min(m0 + r, a.x_mpad - 1);
         float s1a, s2a, s1b, s2b;
@@ -552,6 +557,16 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile(SkinnyArgs a) {
             tsr[4 * tid] = lo; tsr[4 * tid + 1] = slo; tsr[4 * tid + 2] = shi;
         }
     }
+    if constexpr (REP) {
+        if (tid < BM) {   // row m0 + tid's words n0 / 32 .. + 7 (n0 is a multiple of 256: word-aligned); past the row's last word: 0
+            const unsigned* src = a.rep_bits + (long)min(m0 + tid, a.M - 1) * a.rep_words;
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const int w = (n0 >> 5) + k;
+                rbw[tid * 8 + k] = w < a.rep_words ? src[w] : 0u;
+            }
+        }
+    }
     __syncthreads();   // lnstat written by the first 256 threads is visible to everyone (and every MFMA has its operands)
 
     // ---- epilogue: final LayerNorm fold + masked argmax, one partial per (wave, row) ------------------------------------
@@ -577,6 +592,34 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile(SkinnyArgs a) {
     float* red_v = reinterpret_cast<float*>(smem);            // [4][256] — every wave is past the last barrier of the main loop
     int* red_i = reinterpret_cast<int*>(smem) + G::WN * BM;
     float* red_s = reinterpret_cast<float*>(smem) + 2 * G::WN * BM;   // LP: [4][256] sum of exp(v - red_v)
+    if constexpr (REP) {
+        // A lane with a touched id among its 16 columns of a row (rare: a row has at most one per history token) sends the raw logits of those
+        // ids (the same expression) to the row's side buffer and replaces their accumulators by NaN, which enters no argmax, no sum of exp and
+        // no log-probability pass: the loops below are the REP = false ones.  (With the touched bits as a second, row-dependent suppress mask
+        // inside them the rules variants spilled; inside their row loop this pass took the loop past the unroller's size limit and the
+        // accumulators went to scratch.)  With the rules on a touched id is never a timestamp, so the timestamp logits are not concerned.
+#pragma unroll
+        for (int i = 0; i < TM; i++) {
+            const int rloc = wm * (TM * 16) + i * 16 + fl, m = m0 + rloc;
+            const wh_u32x2 rw = *reinterpret_cast<const wh_u32x2*>(rbw + rloc * 8 + wn * 2);   // the two bitmap words of this wave's 64 columns of row m
+            if ((((rw.x | rw.y) >> (4 * fg)) & 0x000f000fu) != 0u && m < a.M) {
+                const float mean = a.ln_part ? lnstat[2 * rloc] : 0.0f, rstd = a.ln_part ? lnstat[2 * rloc + 1] : 1.0f;
+                int nf = nw0 + 4 * fg;   // (through an empty asm per row: the column tests are not hoisted out of the row loop as live lane masks, cf. lp_tile_row)
+                asm volatile("" : "+v"(nf));
+#pragma unroll
+                for (int j = 0; j < TN; j++) {
+                    const unsigned rb = ((j < 2) ? rw.x : rw.y) >> ((j & 1) * 16 + 4 * fg);
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        const int nn = nf + j * 16 + e;
+                        const bool t = ((rb >> e) & 1u) && nn < a.N;
+                        if (t) a.rep_side[(long)m * a.N + nn] = a.ln_part ? wh_ln_fold(acc[i][j][e], mean, rstd, sv[j][e], cv[j][e]) : acc[i][j][e];
+                        acc[i][j][e] = t ? __builtin_nanf("") : acc[i][j][e];
+                    }
+                }
+            }
+        }
+    }
 #pragma unroll
     for (int i = 0; i < TM; i++) {
         const int rloc = wm * (TM * 16) + i * 16 + fl, m = m0 + rloc;
@@ -625,6 +668,25 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile(SkinnyArgs a) {
         if (fg == 0) {   // this wave's (max, index) of row rloc: the four waves that share the row meet in LDS (the ring is idle now)
             red_v[wn * BM + rloc] = bv;
             red_i[wn * BM + rloc] = bi;
+        }
+    }
+    if constexpr (REP) {
+        // parity path: the logits rows keep the raw values (the loop above stored NaN for the touched ids); no accumulator is read, so the
+        // row loop stays rolled
+        if (a.logits && gen >= 0 && gen < a.logits_rows) {
+#pragma unroll 1
+            for (int i = 0; i < TM; i++) {
+                const int rloc = wm * (TM * 16) + i * 16 + fl, m = m0 + rloc;
+                const wh_u32x2 rw = *reinterpret_cast<const wh_u32x2*>(rbw + rloc * 8 + wn * 2);
+                if ((((rw.x | rw.y) >> (4 * fg)) & 0x000f000fu) == 0u || m >= a.M) continue;
+                const int slot = a.logits_sel ? a.logits_sel[m] : m;
+                if (slot < 0) continue;
+                for (int c = 0; c < 16; c++) {
+                    const int j = c >> 2, e = c & 3, nn = nw0 + j * 16 + 4 * fg + e;
+                    const unsigned rb = ((j < 2) ? rw.x : rw.y) >> ((j & 1) * 16 + 4 * fg);
+                    if (((rb >> e) & 1u) && nn < a.N) a.logits[((long)slot * a.logits_rows + gen) * a.N + nn] = a.rep_side[(long)m * a.N + nn];
+                }
+            }
         }
     }
     if constexpr (LP) {
@@ -716,18 +778,25 @@ bool wh_lm_head_tile_applicable(const SkinnyArgs& a) {
 int wh_lm_head_tile_parts(const SkinnyArgs& a) { return (a.N + 255) / 256; }
 void wh_launch_lm_head_tile(hipStream_t s, const SkinnyArgs& a) {
     typedef Geo<256> G;
-    const size_t sm = (size_t)G::NSLOT * G::SLOT + (size_t)BM * 2 * 4 * 5 + (a.ts_logits ? (size_t)BM * 16 : 0);   // ring + LayerNorm statistics ([256][2] + four quarter sums) + RULES: the rows' ranges ([256][4])
+    const size_t sm = (size_t)G::NSLOT * G::SLOT + (size_t)BM * 2 * 4 * 5 + ((a.ts_logits || a.rep_bits) ? (size_t)BM * 16 : 0) +
+                      (a.rep_bits ? (size_t)BM * 32 : 0);   // ring + LayerNorm statistics ([256][2] + four quarter sums) + RULES: the rows' ranges ([256][4]) + REP: the rows' touched bits ([256][8], behind the ranges' place)
     dim3 grid(((a.N + 255) / 256) * ((a.M + BM - 1) / BM));
-#define WH_LM_TILE(R_, L_)                                                         \
-    {                                                                              \
-        wh_ensure_dyn_lds((const void*)k_lm_head_tile<R_, L_>, sm);               \
-        hipLaunchKernelGGL((k_lm_head_tile<R_, L_>), grid, dim3(512), sm, s, a);  \
+#define WH_LM_TILE(R_, L_, P_)                                                         \
+    {                                                                                  \
+        wh_ensure_dyn_lds((const void*)k_lm_head_tile<R_, L_, P_>, sm);               \
+        hipLaunchKernelGGL((k_lm_head_tile<R_, L_, P_>), grid, dim3(512), sm, s, a);  \
     }
-    // a.ts_logits: the timestamp-rules variants; a.part_sum: the log-probability variants
-    if (a.ts_logits && a.part_sum) WH_LM_TILE(true, true)
-    else if (a.ts_logits) WH_LM_TILE(true, false)
-    else if (a.part_sum) WH_LM_TILE(false, true)
-    else WH_LM_TILE(false, false)
+    // a.ts_logits: the timestamp-rules variants; a.part_sum: the log-probability variants; a.rep_bits: the repetition variants
+    if (a.rep_bits) {
+        if (a.ts_logits && a.part_sum) WH_LM_TILE(true, true, true)
+        else if (a.ts_logits) WH_LM_TILE(true, false, true)
+        else if (a.part_sum) WH_LM_TILE(false, true, true)
+        else WH_LM_TILE(false, false, true)
+    }
+    else if (a.ts_logits && a.part_sum) WH_LM_TILE(true, true, false)
+    else if (a.ts_logits) WH_LM_TILE(true, false, false)
+    else if (a.part_sum) WH_LM_TILE(false, true, false)
+    else WH_LM_TILE(false, false, false)
 #undef WH_LM_TILE
 }
 

@@ -207,9 +207,13 @@ struct wh_ctx {
         int ts_begin = -1, ts_max_init = -1;   // timestamp rules: -1 = off (other kernels, other arguments)
         const float* lp_sum = nullptr;         // token log-probabilities: nullptr = off (other kernels, other arguments)
         bool pfx = false;                      // per-clip prefixes with a non-empty one in the batch: the prefix-aware kernels
+        bool rep = false;                      // repetition penalty / no-repeat n-grams: other kernels, other arguments
+        float rep_p = 1.0f;
+        int rep_n = 0;
         bool operator==(const StepKey& o) const {
             return nb == o.nb && n_prompt == o.n_prompt && eot == o.eot && n_forced == o.n_forced && logits_rows == o.logits_rows &&
-                   d_logits == o.d_logits && d_sel == o.d_sel && ts_begin == o.ts_begin && ts_max_init == o.ts_max_init && lp_sum == o.lp_sum && pfx == o.pfx;
+                   d_logits == o.d_logits && d_sel == o.d_sel && ts_begin == o.ts_begin && ts_max_init == o.ts_max_init && lp_sum == o.lp_sum && pfx == o.pfx &&
+                   rep == o.rep && rep_p == o.rep_p && rep_n == o.rep_n;
         }
     } step_key;
     // Whisper's timestamp rules (wh_ctx_set_timestamp_rules): off unless ts_on.  The timestamp logits and the per-row state
@@ -265,6 +269,15 @@ struct wh_ctx {
     int pfx_scope = 0;                 // WH_PREFIX_*
     int* pfx_off = nullptr;            // [max_batch] device: first live global position of each row (Nmax - n_b)
     long pfx_win_base = -1;            // long-form: index of the device batch's first window (row b is window pfx_win_base + b); -1: rows are clips
+    // Repetition penalty / no-repeat n-grams (wh_ctx_set_repetition): off unless rep_on.  The bitmap and the side buffer are
+    // allocated by the setter (not part of the workspace carve) and freed when the option is cleared and in wh_ctx_free; run_decode clears the
+    // bitmap at the start of a call.
+    bool rep_on = false;
+    float rep_p = 1.0f, rep_inv = 1.0f;
+    int rep_n = 0;
+    int rep_words = 0;                 // ceil(vocab / 32)
+    unsigned* rep_bits = nullptr;      // [max_batch][rep_words] touched ids of each row's current position
+    float* rep_side = nullptr;         // [max_batch][vocab] raw logits of the touched ids (only those entries are written)
     hipGraph_t step_graph = nullptr;
     hipGraphExec_t step_exec = nullptr;
 };

@@ -148,6 +148,27 @@ struct SkinnyArgs {
     float* part_sum = nullptr;
     int probe_id = -1;
     float* probe_out = nullptr;
+    // Repetition penalty / no-repeat n-grams (the REP variants of the LM head): rep_bits [M][rep_words], bit n of row m set =
+    // id n is touched (penalised or banned) at row m's position; rep_words = ceil(N / 32).  A touched id is treated as suppressed (it enters no
+    // argmax partial, no sum of exp and no timestamp logit) and its raw logit goes to rep_side [M][N] for k_argmax_finish<..., REP>.  Only the
+    // touched entries of a row are written (at most one per history token: 448 per row and step).  Indices stay inside row m's own slice: m < M, n < N.
+    const unsigned* rep_bits = nullptr;
+    float* rep_side = nullptr;
+    int rep_words = 0;
+};
+
+// the finish kernel's side of the repetition controls (on == false: not applied)
+constexpr int WH_REP_MAX_HIST = 512;   // generated history the finish kernel keeps in LDS (wh_model_build refuses n_text_ctx > 512)
+struct RepFinish {
+    bool on = false;
+    unsigned* bits = nullptr;           // [B][words], SkinnyArgs::rep_bits: read for this position, rewritten for the next one (row b: by workgroup b only)
+    const float* side = nullptr;        // [B][vocab], SkinnyArgs::rep_side
+    int words = 0, vocab = 0;
+    float p = 1.0f, inv = 1.0f;         // penalty and 1.0f / penalty (computed once on the host)
+    int ngram = 0;                      // 0: no ban
+    int exempt_from = 0x7fffffff;       // ids >= this are never touched (timestamp_begin with the rules on)
+    const unsigned* mask_first = nullptr;   // the suppress masks the LM head applied (a touched id they suppress is dropped)
+    const unsigned* mask_base = nullptr;
 };
 
 // the finish kernel's side of the timestamp rules (rules == false: not applied)
@@ -247,7 +268,8 @@ void wh_launch_lm_head_tile_x3(hipStream_t s, const SkinnyArgs& a);
 int wh_lm_head_parts(int prec, const SkinnyArgs& a);  // argmax partials per row written by wh_launch_lm_head, layout [part][x_mpad]
 void wh_launch_argmax_finish(hipStream_t s, int prec, const float* part_val, const int* part_idx, int n_parts, int mpad, int* pos_p,
                              int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts = TsFinish(),
-                             const float* part_sum = nullptr);   // part_sum: the log-probability variant (writes st.logprob)
+                             const float* part_sum = nullptr,    // part_sum: the log-probability variant (writes st.logprob)
+                             const RepFinish& rep = RepFinish());   // rep.on: the repetition variant
 // the no-speech probe's finish: prob[b] = exp(probe_v[b] - log-sum-exp of row b's (part_val, part_sum) partials); advances the position
 // (the probe's prompt step leaves that to this kernel)
 void wh_launch_nospeech_finish(hipStream_t s, const float* part_val, const float* part_sum, int n_parts, int mpad, const float* probe_v,

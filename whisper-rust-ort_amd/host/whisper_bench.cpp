@@ -51,6 +51,10 @@ struct Args {
     // additive: text context (wh_ctx_set_prefixes): ids for every file, or DIR/<audio stem>.txt per file; the prefix on every window of a long file
     std::string prompt_ids, prompt_ids_dir;
     bool prompt_all_windows = false;
+    // additive: HF's repetition penalty and no-repeat n-grams in the token loop (wh_ctx_set_repetition); each is echoed in the summary when given
+    bool have_rep_penalty = false, have_rep_ngram = false;
+    float rep_penalty = 1.0f;
+    int rep_ngram = 0;
     bool prompts() const { return !prompt_ids.empty() || !prompt_ids_dir.empty(); }
 };
 
@@ -119,7 +123,10 @@ static bool parse_args(int argc, char** argv, Args& a) {
                    "[--tokenizer-json F] [--timestamps] [--chunk-parallelism N] [--chunk-length-s 30] [--overlap-s 5] "
                    "[--device 0] [--devices 0-7] [--streams-per-gpu 1] [--load-threads N] [--precision bf16|f32|fp8|f16x3] [--max-batch 16] "
                    "[--synthetic-clips N] [--seed 1000] [--print-plan] [--timestamp-rules] [--write-srt] [--write-vtt] "
-                   "[--logprobs] [--no-speech-threshold X] [--logprob-threshold Y] [--prompt-ids a,b,c] [--prompt-ids-dir DIR] [--prompt-all-windows]\n"
+                   "[--logprobs] [--no-speech-threshold X] [--logprob-threshold Y] [--prompt-ids a,b,c] [--prompt-ids-dir DIR] [--prompt-all-windows] "
+                   "[--repetition-penalty F] [--no-repeat-ngram-size N]\n"
+                   "  --repetition-penalty F   HF generate's repetition_penalty on each row's generated history (F > 0; 1 = off)\n"
+                   "  --no-repeat-ngram-size N no n-gram of N ids is generated twice (0 = off, at most 32); timestamps are exempt from both\n"
                    "  --language auto          the language of every file is detected from its audio (its first window's, for a file of several) among\n"
                    "                           the tokenizer's <|xx|> tokens, else the multilingual ids from 50259 on; the per-file JSON and CSV gain\n"
                    "                           language and language_probability\n"
@@ -164,6 +171,24 @@ static bool parse_args(int argc, char** argv, Args& a) {
             else if (k == "--seed") a.seed = strtoull(v.c_str(), nullptr, 10);
             else if (k == "--prompt-ids") a.prompt_ids = v;
             else if (k == "--prompt-ids-dir") a.prompt_ids_dir = v;
+            else if (k == "--repetition-penalty") {   // what wh_ctx_set_repetition refuses is refused here, before any device is touched
+                char* end = nullptr;
+                a.rep_penalty = strtof(v.c_str(), &end);
+                if (v.empty() || *end || !std::isfinite(a.rep_penalty) || !(a.rep_penalty > 0.0f)) {
+                    fprintf(stderr, "error: --repetition-penalty '%s' is not a finite value above 0\n", v.c_str());
+                    return false;
+                }
+                a.have_rep_penalty = true;
+            } else if (k == "--no-repeat-ngram-size") {
+                char* end = nullptr;
+                const long n = strtol(v.c_str(), &end, 10);
+                if (v.empty() || *end || n < 0 || n > WH_MAX_NGRAM) {
+                    fprintf(stderr, "error: --no-repeat-ngram-size '%s' is outside 0 .. %d\n", v.c_str(), WH_MAX_NGRAM);
+                    return false;
+                }
+                a.rep_ngram = (int)n;
+                a.have_rep_ngram = true;
+            }
             else { fprintf(stderr, "error: unexpected argument '%s'\n", k.c_str()); return false; }
         }
     }
@@ -501,6 +526,11 @@ int main(int argc, char** argv) {
                     if (int rc = wh_ctx_set_logprobs(c, &lo))
                         throw std::runtime_error(std::string("wh_ctx_set_logprobs: ") + std::to_string(rc) + ": " + wh_last_error(c));
                 }
+                if (a.have_rep_penalty || a.have_rep_ngram) {   // repetition penalty / no-repeat n-grams on every context (no reference counterpart)
+                    wh_repetition_opts ro{sizeof(wh_repetition_opts), a.rep_penalty, a.rep_ngram};
+                    if (int rc = wh_ctx_set_repetition(c, &ro))
+                        throw std::runtime_error(std::string("wh_ctx_set_repetition: ") + std::to_string(rc) + ": " + wh_last_error(c));
+                }
                 if (lang_auto) {   // each clip's language from the logits at <|startoftranscript|> (prompt position 0), decoded into position 1
                     wh_language_opts lo{sizeof(wh_language_opts), lang_table.ids.data(), lang_table.ids.size(), 0};
                     if (int rc = wh_ctx_set_language_detection(c, &lo))
@@ -708,6 +738,8 @@ int main(int argc, char** argv) {
                             .set("gpu_busy_s", JVal::num(busy_max)).set("gpu_throughput_rtfx", JVal::num(audio_total / std::max(busy_max, 1e-12))));
         if (a.timestamp_rules) summary.set("timestamp_rules", JVal::boolean(true));
         if (a.logprobs) summary.set("logprobs", JVal::boolean(true));
+        if (a.have_rep_penalty) summary.set("repetition_penalty", JVal::num(a.rep_penalty));
+        if (a.have_rep_ngram) summary.set("no_repeat_ngram_size", JVal::integer(a.rep_ngram));
         write_file(a.out_summary_json, summary.pretty());
         printf("DONE\n");  // :1261-1268
         printf("Config used:\n%s\n", cfg.json(false).pretty().c_str());
