@@ -316,29 +316,41 @@ int prefix_check(wh_ctx* c, const wh_decode_params* p, int nb, bool longform) {
 }
 
 // ---- cross-KV + greedy loop for the nb clips whose encoder states are resident ------------------
-// `after_kv` (optional) runs on the host right after the cross-K/V projection has been enqueued and its completion event
-// recorded: the place where the NEXT batch's encoder pass is put on the encoder stream, before the host is tied up in the
-// token loop.
-// `sel` (optional, with logits_out): the n_sel batch rows whose logits are read back — logits_out is then [n_sel][logits_rows][vocab]
-int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out, size_t tok_stride,
-               size_t* n_tokens_out, float* logits_out, size_t logits_rows, const std::function<int()>& after_kv = nullptr,
-               const int32_t* sel = nullptr, size_t n_sel = 0) {
-    wh_model* m = c->m;
-    const wh_dims& D = m->dims;
-    hipStream_t s = c->stream;
-    c->cur = s;
-    const int prec = m->prec;
-    const long d = D.d_model, S = D.n_audio_ctx, F = D.ffn;
-    const size_t esz = m->esz;
-    const int P = (int)p->n_prompt, NEW = (int)p->max_new_tokens;
+// run_decode (below) is a sequence of stages: plan_decode -> upload_token_state -> prepare_logits -> project_cross_kv -> the prompt
+// positions (launch_step, eagerly) -> run_token_loop (the captured step) -> read_back.
+
+// Everything a decode call decides before it touches the device: the step's key (but for the logits addresses) and what only the host needs.
+struct DecodePlan {
+    wh_ctx::StepKey key;   // key.n_prompt = PP, key.pfx: see below
+    int P = 0, NEW = 0;
+    // per-clip prefixes: row b is idle for Nmax - plen[b] global positions, then runs prefix_b ++ prompt; every row reaches prompt[0] at
+    // global position Nmax, so on the device the prompt is simply PP = Nmax + P positions long.  key.pfx = Nmax > 0
+    // (all prefixes empty: exactly the launches of a context without prefixes)
+    int Nmax = 0;
+    std::vector<int> plen;
+    std::vector<const int64_t*> pids;
+    // language detection: per-row detection at prompt position lang_sot_index (lang_det), or — later batches of a long-form call — the
+    // language of the file's first window as an ordinary prompt token (lang_fix).  Either way the caller's prompt[lang_slot] is a placeholder.
+    bool lang_det = false, lang_fix = false, lp_probe = false;
+    int lang_slot = -1;
+    int lang_pos = -1, probe_pos = -1;   // global positions whose logits language detection / the no-speech probe read (-1: none)
+    // logits kept for the parity harness: n_lrows rows of the batch (sel_map[b] = slot of row b, when the caller selects rows)
+    bool want_logits = false;
+    size_t n_lrows = 0;
+    std::vector<int> sel_map;
+};
+
+// all validation; no HIP call
+int plan_decode(wh_ctx* c, int nb, const wh_decode_params* p, bool want_logits, size_t logits_rows, const int32_t* sel, size_t n_sel, DecodePlan& pl) {
+    const wh_dims& D = c->m->dims;
+    const int P = pl.P = (int)p->n_prompt, NEW = pl.NEW = (int)p->max_new_tokens;
     if (P <= 0 || NEW <= 0 || !p->prompt) return fail(c, WH_ERR_ARG, "decode: empty prompt or max_new_tokens == 0");
     if (P + NEW > D.n_text_ctx) return fail(c, WH_ERR_ARG, "decode: prompt (%d) + max_new_tokens (%d) exceeds %d positions", P, NEW, D.n_text_ctx);
     if (p->n_forced > (size_t)NEW) return fail(c, WH_ERR_ARG, "decode: more forced tokens than max_new_tokens");
-    // language detection: per-row detection at prompt position lang_sot_index (lang_det), or — later batches of a long-form call — the
-    // language of the file's first window as an ordinary prompt token (lang_fix).  Either way the caller's prompt[lang_sot_index + 1] is a placeholder.
-    const bool lang_any = c->lang_on, lang_fix = lang_any && c->lang_fixed >= 0, lang_det = lang_any && !lang_fix;
-    const int lang_slot = lang_any ? c->lang_sot_index + 1 : -1;
-    if (lang_any && lang_slot >= P)
+    pl.lang_fix = c->lang_on && c->lang_fixed >= 0;
+    pl.lang_det = c->lang_on && !pl.lang_fix;
+    const int lang_slot = pl.lang_slot = c->lang_on ? c->lang_sot_index + 1 : -1;
+    if (c->lang_on && lang_slot >= P)
         return fail(c, WH_ERR_ARG, "decode: language detection's sot_index %d + 1 is not below n_prompt (%d)", c->lang_sot_index, P);
     for (int i = 0; i < P; i++)
         if (i != lang_slot && (p->prompt[i] < 0 || p->prompt[i] >= D.vocab)) return fail(c, WH_ERR_ARG, "decode: prompt id %lld outside the vocabulary", (long long)p->prompt[i]);
@@ -350,112 +362,119 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
         for (int i = 0; i < P; i++)
             if (i != lang_slot && c->ts_no_ts >= 0 && p->prompt[i] == c->ts_no_ts) return fail(c, WH_ERR_ARG, "decode: the prompt holds <|notimestamps|> while timestamp rules are on");
     }
-    const bool lp = c->lp_on, lp_probe = lp && c->lp_no_speech >= 0;
-    if (lp_probe && c->lp_sot_index >= P - 1)   // the probe reads a prompt position that emits nothing
+    pl.lp_probe = c->lp_on && c->lp_no_speech >= 0;
+    if (pl.lp_probe && c->lp_sot_index >= P - 1)   // the probe reads a prompt position that emits nothing
         return fail(c, WH_ERR_ARG, "decode: the no-speech probe's sot_index %d is not below n_prompt - 1 (%d)", c->lp_sot_index, P - 1);
-    // per-clip prefixes: row b is idle for off[b] = Nmax - n_b global positions, then runs prefix_b ++ prompt; every row reaches prompt[0] at
-    // global position Nmax, so on the device the prompt is simply PP = Nmax + P positions long
-    {
-        int rc = prefix_check(c, p, nb, c->pfx_win_base >= 0);
-        if (rc) return rc;
-    }
-    std::vector<int> plen(nb, 0);
-    std::vector<const int64_t*> pids(nb, nullptr);
-    int Nmax = 0;
+    if (int rc = prefix_check(c, p, nb, c->pfx_win_base >= 0)) return rc;
+    pl.plen.assign(nb, 0);
+    pl.pids.assign(nb, nullptr);
     if (c->pfx_on)
         for (int b = 0; b < nb; b++) {
-            pids[b] = prefix_of(c, c->pfx_win_base, b, &plen[b]);
-            Nmax = std::max(Nmax, plen[b]);
+            pl.pids[b] = prefix_of(c, c->pfx_win_base, b, &pl.plen[b]);
+            pl.Nmax = std::max(pl.Nmax, pl.plen[b]);
         }
-    const bool pfx = Nmax > 0;   // (all prefixes empty: exactly the launches of a context without prefixes)
-    const int PP = Nmax + P;
-    const int* d_off = pfx ? c->pfx_off : nullptr;
+    if (pl.lang_det) pl.lang_pos = pl.Nmax + c->lang_sot_index;
+    if (pl.lp_probe) pl.probe_pos = pl.Nmax + c->lp_sot_index;
+    pl.want_logits = want_logits;
+    pl.n_lrows = sel ? n_sel : (size_t)nb;
+    if (want_logits && sel) {
+        pl.sel_map.assign(nb, -1);
+        for (size_t i = 0; i < n_sel; i++) {
+            if (sel[i] < 0 || sel[i] >= nb || pl.sel_map[sel[i]] >= 0) return fail(c, WH_ERR_ARG, "decode: logits row %d outside the batch or listed twice", (int)sel[i]);
+            pl.sel_map[sel[i]] = (int)i;
+        }
+    }
+    wh_ctx::StepKey& key = pl.key;
+    key.nb = nb; key.n_prompt = pl.Nmax + P; key.pfx = pl.Nmax > 0; key.eot = (int)p->eot; key.n_forced = (int)p->n_forced;
+    key.logits_rows = (int)logits_rows;
+    if (c->ts_on) { key.ts_begin = (int)c->ts_begin; key.ts_max_init = c->ts_max_init; }
+    if (c->lp_on) key.lp_sum = c->lp_part_sum;
+    if (c->rep_on) { key.rep = true; key.rep_p = c->rep_p; key.rep_n = c->rep_n; }
+    return WH_OK;
+}
 
-    // the encoder states come from the encoder stream
-    if (c->s_enc != s) CTX_HIP(c, hipStreamWaitEvent(s, c->ev_enc_done, 0));
-    CTX_HIP(c, hipEventRecord(c->ev[5], s));   // decode start (stage timing)
-    // token state
-    const int ld = c->tok_ld;
+// feed, out_tokens, n_out, done, pos, ticket, repetition bits, forced ids, the two suppress masks, the prefix offsets
+int upload_token_state(wh_ctx* c, const wh_decode_params* p, const DecodePlan& pl) {
+    hipStream_t s = c->stream;
+    const int nb = pl.key.nb, ld = c->tok_ld, Nmax = pl.Nmax, vocab = c->m->dims.vocab;
     std::vector<int> feed((size_t)nb * ld, 0);
     for (int b = 0; b < nb; b++) {
-        for (int i = 0; i < plen[b]; i++) feed[(size_t)b * ld + Nmax - plen[b] + i] = (int)pids[b][i];   // (columns below Nmax - n_b: filler id 0 of an idle row)
-        for (int i = 0; i < P; i++) feed[(size_t)b * ld + Nmax + i] = i == lang_slot ? (lang_fix ? (int)c->lang_fixed : 0) : (int)p->prompt[i];
+        for (int i = 0; i < pl.plen[b]; i++) feed[(size_t)b * ld + Nmax - pl.plen[b] + i] = (int)pl.pids[b][i];   // (columns below Nmax - n_b: filler id 0 of an idle row)
+        for (int i = 0; i < pl.P; i++) feed[(size_t)b * ld + Nmax + i] = i == pl.lang_slot ? (pl.lang_fix ? (int)c->lang_fixed : 0) : (int)p->prompt[i];
     }
-    if (pfx) {
+    if (pl.key.pfx) {
         std::vector<int> off(nb);
-        for (int b = 0; b < nb; b++) off[b] = Nmax - plen[b];
+        for (int b = 0; b < nb; b++) off[b] = Nmax - pl.plen[b];
         CTX_HIP(c, hipMemcpyAsync(c->pfx_off, off.data(), nb * 4, hipMemcpyHostToDevice, s));
         CTX_HIP(c, hipStreamSynchronize(s));
     }
     CTX_HIP(c, hipMemcpyAsync(c->feed, feed.data(), feed.size() * 4, hipMemcpyHostToDevice, s));
     CTX_HIP(c, hipMemcpyAsync(c->out_tokens, feed.data(), feed.size() * 4, hipMemcpyHostToDevice, s));
-    std::vector<int> nout(nb, PP);
+    std::vector<int> nout(nb, pl.key.n_prompt);
     CTX_HIP(c, hipMemcpyAsync(c->n_out, nout.data(), nb * 4, hipMemcpyHostToDevice, s));
     CTX_HIP(c, hipMemsetAsync(c->done, 0, nb * 4, s));
     CTX_HIP(c, hipMemsetAsync(c->pos, 0, 4, s));
     CTX_HIP(c, hipMemsetAsync(c->step_ticket, 0, 4, s));
-    const bool rep_on = c->rep_on;
-    if (rep_on) CTX_HIP(c, hipMemsetAsync(c->rep_bits, 0, (size_t)nb * c->rep_words * 4, s));   // no history yet: nothing is touched
+    if (c->rep_on) CTX_HIP(c, hipMemsetAsync(c->rep_bits, 0, (size_t)nb * c->rep_words * 4, s));   // no history yet: nothing is touched
     std::vector<int> forced(p->n_forced);
     for (size_t i = 0; i < p->n_forced; i++) forced[i] = (int)p->forced[i];
     if (!forced.empty()) CTX_HIP(c, hipMemcpyAsync(c->forced, forced.data(), forced.size() * 4, hipMemcpyHostToDevice, s));
     std::vector<unsigned> mfirst, mbase;
-    pack_mask(p->suppress, p->n_suppress, p->begin_suppress, p->n_begin_suppress, D.vocab, mfirst);  // :765-768
-    pack_mask(p->suppress, p->n_suppress, nullptr, 0, D.vocab, mbase);
-    if (c->ts_on && c->ts_no_ts >= 0 && c->ts_no_ts < D.vocab) {   // timestamp rule 1: <|notimestamps|> at every step
+    pack_mask(p->suppress, p->n_suppress, p->begin_suppress, p->n_begin_suppress, vocab, mfirst);  // :765-768
+    pack_mask(p->suppress, p->n_suppress, nullptr, 0, vocab, mbase);
+    if (c->ts_on && c->ts_no_ts >= 0 && c->ts_no_ts < vocab) {   // timestamp rule 1: <|notimestamps|> at every step
         mfirst[c->ts_no_ts >> 5] |= 1u << (c->ts_no_ts & 31);
         mbase[c->ts_no_ts >> 5] |= 1u << (c->ts_no_ts & 31);
     }
     CTX_HIP(c, hipMemcpyAsync(c->mask_first, mfirst.data(), mfirst.size() * 4, hipMemcpyHostToDevice, s));
     CTX_HIP(c, hipMemcpyAsync(c->mask_base, mbase.data(), mbase.size() * 4, hipMemcpyHostToDevice, s));
     CTX_HIP(c, hipStreamSynchronize(s));  // host vectors above go out of scope
+    return WH_OK;
+}
 
-    float* d_logits = nullptr;
-    const int* d_sel = nullptr;
-    const size_t n_lrows = sel ? n_sel : (size_t)nb;   // batch rows whose logits are kept
-    if (logits_out && sel) {
-        std::vector<int> map(nb, -1);
-        for (size_t i = 0; i < n_sel; i++) {
-            if (sel[i] < 0 || sel[i] >= nb || map[sel[i]] >= 0) return fail(c, WH_ERR_ARG, "decode: logits row %d outside the batch or listed twice", (int)sel[i]);
-            map[sel[i]] = (int)i;
-        }
-        CTX_HIP(c, hipMemcpy(c->logits_sel, map.data(), nb * 4, hipMemcpyHostToDevice));
-        d_sel = c->logits_sel;
+// the parity buffer of a call that keeps logits: the row selection goes to the device, the buffer grows on demand; completes the key
+int prepare_logits(wh_ctx* c, DecodePlan& pl) {
+    if (!pl.want_logits) return WH_OK;
+    if (!pl.sel_map.empty()) {
+        CTX_HIP(c, hipMemcpy(c->logits_sel, pl.sel_map.data(), pl.key.nb * 4, hipMemcpyHostToDevice));
+        pl.key.d_sel = c->logits_sel;
     }
-    if (logits_out) {
-        const size_t need = n_lrows * logits_rows * D.vocab;
-        if (need > c->logits_cap) {
-            drop_step_graph(c);  // the captured step holds the old buffer's address
-            if (c->logits) CTX_HIP(c, hipFree(c->logits));
-            c->logits = nullptr;
-            c->logits_cap = 0;
-            CTX_HIP(c, hipMalloc((void**)&c->logits, need * 4));
-            c->logits_cap = need;
-        }
-        d_logits = c->logits;
+    const size_t need = pl.n_lrows * pl.key.logits_rows * c->m->dims.vocab;
+    if (need > c->logits_cap) {
+        drop_step_graph(c);  // the captured step holds the old buffer's address
+        if (c->logits) CTX_HIP(c, hipFree(c->logits));
+        c->logits = nullptr;
+        c->logits_cap = 0;
+        CTX_HIP(c, hipMalloc((void**)&c->logits, need * 4));
+        c->logits_cap = need;
     }
+    pl.key.d_logits = c->logits;
+    return WH_OK;
+}
 
-    const bool f8 = prec == WH_PREC_FP8;
-    // the cross K/V of all layers are re-read at every position: below ~half the 256 MiB Infinity Cache they are served
-    // from it; above, their stream only evicts the decode weights and activations — then they are loaded non-temporally
-    const bool kv_nt = (c->cross_es ? 1.0 : (double)D.dec_layers * 2.0) * nb * S * d * (f8 ? 1 : (double)esz) > 128.0 * 1024 * 1024;
-    // cross-attention K/V of every decoder layer, once per clip: present.{i}.encoder.{key,value}
-    // of the step-0 decoder run (src/main.rs:771-787)
-    const long kv_stride = (long)nb * S * d;  // elements between consecutive [nb][S][d] planes
+// cross-attention K/V of every decoder layer, once per clip: present.{i}.encoder.{key,value} of the step-0 decoder run (src/main.rs:771-787).
+// `after_kv` (optional) runs on the host right after the projection has been enqueued and its completion event recorded: the place where
+// the NEXT batch's encoder pass is put on the encoder stream, before the host is tied up in the token loop.
+int project_cross_kv(wh_ctx* c, int nb, const std::function<int()>& after_kv) {
+    wh_model* m = c->m;
+    const wh_dims& D = m->dims;
+    hipStream_t s = c->stream;
+    const int prec = m->prec;
+    const long d = D.d_model, S = D.n_audio_ctx;
     if (c->cross_es) {
         // no projection: the token loop attends over the encoder states themselves (wh_cross_es.hip).  Their final LayerNorm runs
         // here, on the decode stream, into decode-side storage — the encoder-side workspace is free for the next pass afterwards
         Prof pr(c, WH_KG_DEC_GEMM);
         if (prec == WH_PREC_F16X3 && wh_es3_enabled()) wh_launch_layernorm_es3(s, c->x, m->enc_ln_w, m->enc_ln_b, c->es_E, (long)nb * S, (int)S, c->es_rows);   // fp16 + e4m3 remainder rows
         else if (prec == WH_PREC_F16X3) wh_launch_layernorm_es2(s, c->x, m->enc_ln_w, m->enc_ln_b, c->es_E, (long)nb * S, (int)S, c->es_rows);   // fp16 limb planes
-        else if (f8) wh_launch_layernorm_es8(s, c->x, m->enc_ln_w, m->enc_ln_b, c->es_E, (long)nb * S, (int)S, c->es_rows);                 // e4m3 rows
+        else if (prec == WH_PREC_FP8) wh_launch_layernorm_es8(s, c->x, m->enc_ln_w, m->enc_ln_b, c->es_E, (long)nb * S, (int)S, c->es_rows);                 // e4m3 rows
         else wh_launch_layernorm_blocks(s, prec, c->x, m->enc_ln_w, m->enc_ln_b, c->es_E, (long)nb * S, (int)d, c->es_rows == (int)S ? 0 : (int)S, c->es_rows);
     } else {
         Prof pr(c, WH_KG_DEC_GEMM);
         GemmArgs g;
         g.small_ctx = c->max_batch <= WH_SMALL_CTX_CLIPS;
         g.A = c->enc_out; g.lda = d; g.W = m->cross_kv_w; g.ldw = d;
-        g.C = c->cross_kv; g.ldc = d; g.n_per = (int)d; g.c_ns = kv_stride;
+        g.C = c->cross_kv; g.ldc = d; g.n_per = (int)d; g.c_ns = (long)nb * S * d;   // elements between consecutive [nb][S][d] planes
         g.bias = m->cross_kv_b; g.bias_mode = 1; g.wscale = m->cross_kv_sc;
         g.M = nb * (int)S; g.N = (int)(D.dec_layers * 2 * d); g.K = (int)d;
         if (c->enc_fold) {   // encoder's final LayerNorm folded in: raw bf16 rows, statistics from the last fc2's epilogue
@@ -463,7 +482,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
         }
         if (c->mx_ok) { g.A = c->xn8; g.a_sc = c->xn8_sc; g.W = m->cross_kv_w8; CTX_LAUNCH(c, wh_launch_gemm8_mx(s, 0, g)); }   // xn8 = MX(final LN), run_encoder
         else CTX_LAUNCH(c, wh_launch_gemm(s, prec, prec == WH_PREC_F16X3, g));   // (split-fp16 mode: K and V as f32 rows — their consumer is the f32 attention kernel, no matrix-core operand)
-        if (f8) {  // bf16 projection → e4m3 codes, one scale per (layer, K|V, clip, head)
+        if (prec == WH_PREC_FP8) {  // bf16 projection → e4m3 codes, one scale per (layer, K|V, clip, head)
             const long planes = (long)D.dec_layers * 2 * nb;
             CTX_HIP(c, hipMemsetAsync(c->kv_amax, 0, planes * D.n_heads * 4, s));
             wh_launch_kv_quant(s, c->cross_kv, (unsigned*)c->kv_amax, c->cross_kv8, planes, (int)S, (int)d, D.n_heads);
@@ -476,248 +495,279 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
         if (rc) return rc;
         c->cur = s;
     }
+    return WH_OK;
+}
 
-    DecodeState st;
-    st.feed = c->feed; st.out_tokens = c->out_tokens; st.n_out = c->n_out; st.done = c->done;
-    st.forced = c->forced; st.n_forced = (int)p->n_forced; st.n_prompt = PP; st.eot = (int)p->eot; st.tok_ld = ld;
-    if (lp) st.logprob = c->lp_tok;
-    const long cache_l = (long)nb * D.n_heads * D.n_text_ctx * WH_HEAD_DIM;  // elements per layer
-    const int total_pos = PP + NEW - 1;
-    std::vector<int> done_h(nb);
-    // one decoder position = ~50 kernel launches; `emits` adds final LN + LM head + argmax
-    const int mpad = c->mpad;  // row pitch of the k-slab-major decode activations
-    // LayerNorm never runs as a kernel in the decoder: the kernel that produces a residual-stream row also
-    // emits its raw copy in the compute dtype (c->dxs, slab layout) and per-column-tile partial sums
-    // (c->lnpart); the GEMM that consumes LN(x) has γ folded into its weights and applies mean / rstd in
-    // its epilogue (wh_model.cpp fold_ln).
-    const int ln_tiles_d = (int)(d / 16);
+// ---- one decoder position (~50 kernel launches) ---------------------------------------------------
+// LayerNorm never runs as a kernel in the decoder: the kernel that produces a residual-stream row also emits its raw copy in the
+// compute dtype (c->dxs, slab layout) and per-column-tile partial sums (c->lnpart); the GEMM that consumes LN(x) has γ folded into
+// its weights and applies mean / rstd in its epilogue (wh_model.cpp fold_ln).
+// What a prompt position does besides the layers.  It embeds its own input token (a generated position's input was embedded by the
+// previous position's argmax finish); only the last prompt position emits.
+struct PromptStep {
+    bool emits = false;
+    bool lang = false;    // language detection reads this position's logits; the chosen id goes to column lang_col
+    int lang_col = 0;
+    bool probe = false;   // the no-speech probe reads this position's logits
+};
+
+// The launches of a position see the context (model, fixed workspace addresses, option buffers) and the step's key, nothing else.
+struct Step {
+    wh_ctx* c;
+    const wh_ctx::StepKey& k;
+    wh_model* m = c->m;
+    const wh_dims& D = m->dims;
+    hipStream_t s = c->stream;
+    const int prec = m->prec, nb = k.nb, mpad = c->mpad, ln_tiles_d = D.d_model / 16;
+    const long d = D.d_model, S = D.n_audio_ctx;
+    const bool f8 = prec == WH_PREC_FP8, rules = k.ts_begin >= 0;
+    // the cross K/V of all layers are re-read at every position: below ~half the 256 MiB Infinity Cache they are served
+    // from it; above, their stream only evicts the decode weights and activations — then they are loaded non-temporally
+    const bool kv_nt = (c->cross_es ? 1.0 : (double)D.dec_layers * 2.0) * nb * S * d * (f8 ? 1 : (double)m->esz) > 128.0 * 1024 * 1024;
+    const int* d_off = k.pfx ? c->pfx_off : nullptr;
+
     // the decode GEMMs: tile GEMMs on contexts of a thousand clips and more (a property of the context, never of the call)
-    auto dec_gemm = [&](bool out_f32, const SkinnyArgs& ga) {
-        if (c->dec_tile && wh_dec_tile_applicable(prec, ga)) wh_launch_dec_tile(s, prec, out_f32, ga);
-        else wh_launch_dec_gemm(s, prec, out_f32, ga);
-    };
-    // `embed_first`: this step embeds its own input token; false when the previous step's argmax finish already did
-    int lm_parts = 0;
-    // `probe`: a prompt position whose unfiltered logits the no-speech probe reads: the last fc2 leaves the position alone, the
-    // LM head's log-probability variant runs with an all-zero mask, and the probe's finish kernel advances the position
-    // `lang`: the prompt position whose logits language detection reads: the language head and its finish run before the probe (if
-    // the probe sits at the same position); the finish advances the position unless the probe's finish will
-    auto launch_step = [&](bool emits, bool embed_first, bool probe, bool lang = false) {
-        if (embed_first) {   // token + position embedding → x, raw slab, row sums (one "tile")
-            Prof pr(c, WH_KG_DEC_OTHER);
-            wh_launch_dec_embed(s, prec, m->tok_emb, m->dec_pos, c->feed, ld, c->pos, c->dx, c->dxs, c->lnpart, nb, (int)d, mpad,
-                                f8 ? m->dec[0].ln1_w : nullptr, c->dshift, d_off);
+    void gemm(bool out_f32, const SkinnyArgs& a) const {
+        if (c->dec_tile && wh_dec_tile_applicable(prec, a)) wh_launch_dec_tile(s, prec, out_f32, a);
+        else wh_launch_dec_gemm(s, prec, out_f32, a);
+    }
+    // a GEMM that consumes LN(x) of the residual stream: out [nb][N], row-major or (slab_out) slab layout
+    SkinnyArgs ln_consumer(const void* W, const float* bias, const float* wscale, const float* ln_s, long N, void* out, int ln_tiles, bool slab_out = false) const {
+        SkinnyArgs a;
+        a.X = c->dxs; a.x_mpad = mpad; a.W = W; a.bias = bias; a.wscale = wscale; a.C = out;
+        if (slab_out) a.c_mpad = mpad; else a.ldc = N;
+        a.M = nb; a.N = (int)N; a.K = (int)d;
+        a.ln_part = c->lnpart; a.ln_tiles = ln_tiles; a.ln_s = ln_s; a.shift_io = c->dshift;
+        return a;
+    }
+    // a GEMM that adds to the residual stream: x += X W^T + bias, plus the raw slab copy and the partial sums of the next LayerNorm
+    // (next_gamma: that LayerNorm's γ, applied on the activation side in fp8 mode)
+    SkinnyArgs residual_producer(const void* W, const float* bias, const float* wscale, const void* X, long K, const float* next_gamma) const {
+        SkinnyArgs a;
+        a.X = X; a.x_mpad = mpad; a.W = W; a.bias = bias; a.wscale = wscale; a.R = c->dx; a.ldr = d; a.C = c->dx; a.ldc = d;
+        a.M = nb; a.N = (int)d; a.K = (int)K; a.xslab_out = c->dxs; a.stats_out = c->lnpart; a.row_shift = c->dshift;
+        if (f8) a.xgamma = next_gamma;
+        return a;
+    }
+    // final LN ∘ tied LM head: what the emitting step and the no-speech probe share (they differ in the masks and what they record)
+    SkinnyArgs lm_head_common() const {
+        SkinnyArgs a;
+        a.W = m->lm_w; a.bias = m->lm_c; a.ln_s = m->lm_s; a.ln_part = c->lnpart; a.ln_tiles = ln_tiles_d;
+        a.M = nb; a.N = D.vocab; a.K = (int)d;
+        a.X = c->dxs; a.x_mpad = mpad;
+        a.pos_p = c->pos; a.n_prompt = k.n_prompt;
+        a.part_val = c->part_val; a.part_idx = c->part_idx;
+        return a;
+    }
+
+    // `advance`: nothing follows the layers at this position (a prompt position without a head), so this fc2 advances the position
+    void layer(int l, bool advance) const {
+        const DecLayerDev& L = m->dec[l];
+        const long cache_l = (long)nb * D.n_heads * D.n_text_ctx * WH_HEAD_DIM * m->esz;   // bytes per layer
+        const long kv_stride = (long)nb * S * d;  // elements between consecutive [nb][S][d] planes
+        {   // LN1 ∘ Q|K|V projection
+            Prof pr(c, WH_KG_DEC_GEMM);
+            gemm(false, ln_consumer(L.qkv_w, L.qkv_b, L.qkv_sc, L.qkv_s, 3 * d, c->dqkv, (l == 0) ? 1 : ln_tiles_d));
         }
-        for (int l = 0; l < D.dec_layers; l++) {
-            const DecLayerDev& L = m->dec[l];
-            SkinnyArgs a;
-            {   // LN1 ∘ Q|K|V projection
+        {
+            Prof pr(c, WH_KG_DEC_OTHER);
+            wh_launch_dec_self_attn(s, prec, c->dqkv, (char*)c->self_k + l * cache_l, (char*)c->self_v + l * cache_l, c->datt, c->pos, (int)d, D.n_heads,
+                                    D.n_text_ctx, nb, mpad, d_off);
+        }
+        {   // self-attention out-proj + residual → x, raw slab, LN2 partials
+            Prof pr(c, WH_KG_DEC_GEMM);
+            gemm(true, residual_producer(L.o_w, L.o_b, L.o_sc, c->datt, d, L.ln2_w));
+        }
+        if (c->cross_es) {
+            // the attention runs on the encoder states (wh_cross_es.hip): W_k moves to the query side, W_v behind the attention
+            {   // LN2 ∘ cross-attention query, kept in f32
                 Prof pr(c, WH_KG_DEC_GEMM);
-                a = SkinnyArgs();
-                a.X = c->dxs; a.x_mpad = mpad; a.W = L.qkv_w; a.bias = L.qkv_b; a.wscale = L.qkv_sc; a.C = c->dqkv; a.ldc = 3 * d;
-                a.M = nb; a.N = (int)(3 * d); a.K = (int)d;
-                a.ln_part = c->lnpart; a.ln_tiles = (l == 0) ? 1 : ln_tiles_d; a.ln_s = L.qkv_s; a.shift_io = c->dshift;
-                dec_gemm(false, a);
-            }
-            {
-                Prof pr(c, WH_KG_DEC_OTHER);
-                wh_launch_dec_self_attn(s, prec, c->dqkv, (char*)c->self_k + l * cache_l * esz,
-                                        (char*)c->self_v + l * cache_l * esz, c->datt, c->pos, (int)d, D.n_heads,
-                                        D.n_text_ctx, nb, mpad, d_off);
-            }
-            {   // self-attention out-proj + residual → x, raw slab, LN2 partials
-                Prof pr(c, WH_KG_DEC_GEMM);
-                a = SkinnyArgs();
-                a.X = c->datt; a.x_mpad = mpad; a.W = L.o_w; a.bias = L.o_b; a.wscale = L.o_sc; a.R = c->dx; a.ldr = d; a.C = c->dx; a.ldc = d;
-                a.M = nb; a.N = (int)d; a.K = (int)d; a.xslab_out = c->dxs; a.stats_out = c->lnpart; a.row_shift = c->dshift;
-                if (f8) a.xgamma = L.ln2_w;
-                dec_gemm(true, a);
-            }
-            if (c->cross_es) {
-                // the attention runs on the encoder states (wh_cross_es.hip): W_k moves to the query side, W_v behind the attention
-                {   // LN2 ∘ cross-attention query, kept in f32
-                    Prof pr(c, WH_KG_DEC_GEMM);
-                    a = SkinnyArgs();
-                    a.X = c->dxs; a.x_mpad = mpad; a.W = L.cq_w; a.bias = L.cq_b; a.wscale = L.cq_sc; a.C = c->dq32; a.ldc = d; a.M = nb; a.N = (int)d; a.K = (int)d;
-                    a.ln_part = c->lnpart; a.ln_tiles = ln_tiles_d; a.ln_s = L.cq_s; a.shift_io = c->dshift;
-                    dec_gemm(true, a);
-                    // expanded queries qe[h] = W_k,h^T q_h: [nb][H][d] f32
-                    wh_launch_dec_qexpand(s, prec, c->dq32, L.cqx_w, c->dqe, nb, (int)d, D.n_heads);
-                }
-                {
-                    Prof pr(c, WH_KG_DEC_CROSS_ATTN);
-                    wh_launch_dec_cross_attn_es(s, prec, c->dqe, c->es_E, c->dctx, (int)S, c->es_rows, nb, mpad, kv_nt, c->dec_cus);
-                }
-                {   // per head: W_v,h ctx_h + b_v,h → the attention output the out-projection below expects (slab layout)
-                    Prof pr(c, WH_KG_DEC_GEMM);
-                    a = SkinnyArgs();
-                    a.X = c->dctx; a.x_mpad = mpad; a.W = L.cv_w; a.bias = L.cv_b; a.C = c->datt; a.c_mpad = mpad;
-                    a.M = nb; a.N = WH_HEAD_DIM; a.K = (int)d;
-                    a.zn = D.n_heads; a.x_zs = (long)(d / 32) * mpad * 32; a.w_zs = (long)WH_HEAD_DIM * d; a.c_zs = (long)(WH_HEAD_DIM / 32) * mpad * 32;
-                    a.bias_zs = WH_HEAD_DIM;
-                    if (f8) wh_launch_dec_gemm(s, WH_PREC_BF16, false, a);   // (fp8 mode: cv_w is the quantised model's W_v, code x row scale, as bf16 — wh_model.cpp)
-                    else dec_gemm(false, a);
-                }
-            } else {
-            {   // LN2 ∘ cross-attention query
-                Prof pr(c, WH_KG_DEC_GEMM);
-                a = SkinnyArgs();
-                a.X = c->dxs; a.x_mpad = mpad; a.W = L.cq_w; a.bias = L.cq_b; a.wscale = L.cq_sc; a.C = c->dq; a.ldc = d; a.M = nb; a.N = (int)d; a.K = (int)d;
-                a.ln_part = c->lnpart; a.ln_tiles = ln_tiles_d; a.ln_s = L.cq_s; a.shift_io = c->dshift;
-                dec_gemm(false, a);
+                gemm(true, ln_consumer(L.cq_w, L.cq_b, L.cq_sc, L.cq_s, d, c->dq32, ln_tiles_d));
+                // expanded queries qe[h] = W_k,h^T q_h: [nb][H][d] f32
+                wh_launch_dec_qexpand(s, prec, c->dq32, L.cqx_w, c->dqe, nb, (int)d, D.n_heads);
             }
             {
                 Prof pr(c, WH_KG_DEC_CROSS_ATTN);
-                if (f8)
-                    wh_launch_dec_cross_attn8(s, c->dq, (char*)c->cross_kv8 + (2 * l) * kv_stride, (char*)c->cross_kv8 + (2 * l + 1) * kv_stride,
-                                              c->kv_amax + (long)(2 * l) * nb * D.n_heads, c->kv_amax + (long)(2 * l + 1) * nb * D.n_heads,
-                                              c->cpart, c->cml, (int)S, (int)d, D.n_heads, c->cross_splits, nb, c->datt, mpad, kv_nt);
-                else
-                    wh_launch_dec_cross_attn(s, prec, c->dq, (char*)c->cross_kv + (2 * l) * kv_stride * esz,
-                                             (char*)c->cross_kv + (2 * l + 1) * kv_stride * esz, c->cpart, c->cml,
-                                             (int)S, (int)d, D.n_heads, c->cross_splits, nb, c->datt, mpad, kv_nt);
+                wh_launch_dec_cross_attn_es(s, prec, c->dqe, c->es_E, c->dctx, (int)S, c->es_rows, nb, mpad, kv_nt, c->dec_cus);
             }
-            }
-            {   // merge of the key ranges ∘ cross-attention out-proj + residual → x, raw slab, LN3 partials
-                Prof pr(c, WH_KG_DEC_GEMM);
-                a = SkinnyArgs();
-                if (c->cross_splits == 1 || c->cross_es) a.X = c->datt;  // one key range per clip: the attention kernel wrote its output itself
-                else { a.xpart = c->cpart; a.xml = c->cml; a.x_splits = c->cross_splits; a.x_heads = D.n_heads; }
-                a.x_mpad = mpad; a.W = L.co_w; a.bias = L.co_b; a.wscale = L.co_sc; a.R = c->dx; a.ldr = d; a.C = c->dx; a.ldc = d;
-                a.M = nb; a.N = (int)d; a.K = (int)d; a.xslab_out = c->dxs; a.stats_out = c->lnpart; a.row_shift = c->dshift;
-                if (f8) a.xgamma = L.ln3_w;
-                dec_gemm(true, a);
-            }
-            {   // LN3 ∘ fc1 + GELU (slab output)
-                Prof pr(c, WH_KG_DEC_GEMM);
-                a = SkinnyArgs();
-                a.X = c->dxs; a.x_mpad = mpad; a.W = L.fc1_w; a.bias = L.fc1_b; a.wscale = L.fc1_sc; a.act = 1; a.C = c->dh; a.c_mpad = mpad;
-                a.M = nb; a.N = (int)F; a.K = (int)d;
-                a.ln_part = c->lnpart; a.ln_tiles = ln_tiles_d; a.ln_s = L.fc1_s; a.shift_io = c->dshift;
-                dec_gemm(false, a);
-            }
-            {   // fc2 + residual → x, raw slab, partials for the next layer's LN1 / the final LN
-                Prof pr(c, WH_KG_DEC_GEMM);
-                a = SkinnyArgs();
-                a.X = c->dh; a.x_mpad = mpad; a.W = L.fc2_w; a.bias = L.fc2_b; a.wscale = L.fc2_sc; a.R = c->dx; a.ldr = d; a.C = c->dx; a.ldc = d;
-                a.M = nb; a.N = (int)d; a.K = (int)F; a.xslab_out = c->dxs; a.stats_out = c->lnpart; a.row_shift = c->dshift;
-                if (f8) a.xgamma = (l + 1 < D.dec_layers) ? m->dec[l + 1].ln1_w : m->dec_ln_w;  // next consumer's LayerNorm
-                if (!emits && !probe && !lang && l == D.dec_layers - 1) { a.ticket = c->step_ticket; a.pos_w = c->pos; }  // prompt position: advance here
-                dec_gemm(true, a);
-            }
-        }
-        if (emits) {  // final LN ∘ tied LM head + masked argmax; the finish kernel advances the position
-            {
+            {   // per head: W_v,h ctx_h + b_v,h → the attention output the out-projection below expects (slab layout)
                 Prof pr(c, WH_KG_DEC_GEMM);
                 SkinnyArgs a;
-                a.W = m->lm_w; a.bias = m->lm_c; a.ln_s = m->lm_s; a.ln_part = c->lnpart; a.ln_tiles = ln_tiles_d;
-                a.M = nb; a.N = D.vocab; a.K = (int)d;
-                a.X = c->dxs; a.x_mpad = mpad;
-                a.pos_p = c->pos; a.n_prompt = PP; a.mask_first = c->mask_first; a.mask_base = c->mask_base;
-                a.logits = d_logits; a.logits_rows = (int)logits_rows; a.logits_sel = d_sel; a.part_val = c->part_val; a.part_idx = c->part_idx;
-                if (c->ts_on) {
-                    a.ts_state = c->ts_state; a.ts_logits = c->ts_logits; a.ts_ld = c->ts_ld;
-                    a.ts_begin = (int)c->ts_begin; a.ts_max_init = c->ts_max_init;
-                }
-                if (lp) a.part_sum = c->lp_part_sum;
-                if (rep_on) { a.rep_bits = c->rep_bits; a.rep_side = c->rep_side; a.rep_words = c->rep_words; }
-                wh_launch_lm_head(s, prec, a);
-                lm_parts = wh_lm_head_parts(prec, a);
+                a.X = c->dctx; a.x_mpad = mpad; a.W = L.cv_w; a.bias = L.cv_b; a.C = c->datt; a.c_mpad = mpad;
+                a.M = nb; a.N = WH_HEAD_DIM; a.K = (int)d;
+                a.zn = D.n_heads; a.x_zs = (long)(d / 32) * mpad * 32; a.w_zs = (long)WH_HEAD_DIM * d; a.c_zs = (long)(WH_HEAD_DIM / 32) * mpad * 32;
+                a.bias_zs = WH_HEAD_DIM;
+                if (f8) wh_launch_dec_gemm(s, WH_PREC_BF16, false, a);   // (fp8 mode: cv_w is the quantised model's W_v, code x row scale, as bf16 — wh_model.cpp)
+                else gemm(false, a);
             }
-            {   // argmax finish + greedy bookkeeping + the next position's embedding
-                Prof pr(c, WH_KG_DEC_OTHER);
-                NextEmbed ne;
-                ne.tok_emb = m->tok_emb; ne.pos_emb = m->dec_pos; ne.x = c->dx; ne.xslab = c->dxs; ne.stats = c->lnpart;
-                ne.xgamma = f8 ? m->dec[0].ln1_w : nullptr; ne.d = (int)d; ne.mpad = mpad; ne.shift = c->dshift; ne.off = d_off;
-                TsFinish tf;
-                if (c->ts_on) {
-                    tf.rules = true; tf.ts_logits = c->ts_logits; tf.ts_ld = c->ts_ld; tf.state = c->ts_state;
-                    tf.ts_begin = (int)c->ts_begin; tf.vocab = D.vocab;
-                }
-                RepFinish rf;
-                if (rep_on) {
-                    rf.on = true; rf.bits = c->rep_bits; rf.side = c->rep_side; rf.words = c->rep_words; rf.vocab = D.vocab;
-                    rf.p = c->rep_p; rf.inv = c->rep_inv; rf.ngram = c->rep_n;
-                    if (c->ts_on) rf.exempt_from = (int)c->ts_begin;   // timestamps repeat in pairs and the rules own them
-                    rf.mask_first = c->mask_first; rf.mask_base = c->mask_base;
-                }
-                wh_launch_argmax_finish(s, prec, c->part_val, c->part_idx, lm_parts, mpad, c->pos, c->step_ticket, st, nb, ne, tf, lp ? c->lp_part_sum : nullptr, rf);
-            }
-        }
-        if (lang) {   // the listed ids' unfiltered logits of this prompt position -> each row's language token at the next one
-            {
+        } else {
+            {   // LN2 ∘ cross-attention query
                 Prof pr(c, WH_KG_DEC_GEMM);
-                LangHeadArgs a;
-                a.X = c->dxs; a.x_mpad = mpad; a.W = m->lm_w; a.bias = m->lm_c; a.ln_s = m->lm_s; a.ln_part = c->lnpart; a.ln_tiles = ln_tiles_d;
-                a.ids = c->lang_d_ids; a.n_lang = (int)c->lang_ids.size(); a.M = nb; a.K = (int)d; a.out = c->lang_logits;
-                wh_launch_lang_head(s, prec, a);
+                gemm(false, ln_consumer(L.cq_w, L.cq_b, L.cq_sc, L.cq_s, d, c->dq, ln_tiles_d));
             }
-            Prof pr(c, WH_KG_DEC_OTHER);
-            wh_launch_lang_finish(s, c->lang_logits, c->lang_d_ids, (int)c->lang_ids.size(), c->lang_bcast ? 0 : -1, c->lang_probs, c->lang_chosen,
-                                  c->feed, c->out_tokens, ld, Nmax + lang_slot, nb, probe ? nullptr : c->pos);
+            Prof pr(c, WH_KG_DEC_CROSS_ATTN);
+            if (f8)
+                wh_launch_dec_cross_attn8(s, c->dq, (char*)c->cross_kv8 + (2 * l) * kv_stride, (char*)c->cross_kv8 + (2 * l + 1) * kv_stride,
+                                          c->kv_amax + (long)(2 * l) * nb * D.n_heads, c->kv_amax + (long)(2 * l + 1) * nb * D.n_heads,
+                                          c->cpart, c->cml, (int)S, (int)d, D.n_heads, c->cross_splits, nb, c->datt, mpad, kv_nt);
+            else
+                wh_launch_dec_cross_attn(s, prec, c->dq, (char*)c->cross_kv + (2 * l) * kv_stride * m->esz, (char*)c->cross_kv + (2 * l + 1) * kv_stride * m->esz,
+                                         c->cpart, c->cml, (int)S, (int)d, D.n_heads, c->cross_splits, nb, c->datt, mpad, kv_nt);
         }
-        if (probe) {   // softmax(v)[no_speech] over this prompt position's unfiltered logits (no mask, no rules, nothing recorded)
-            int parts;
-            {
-                Prof pr(c, WH_KG_DEC_GEMM);
-                SkinnyArgs a;
-                a.W = m->lm_w; a.bias = m->lm_c; a.ln_s = m->lm_s; a.ln_part = c->lnpart; a.ln_tiles = ln_tiles_d;
-                a.M = nb; a.N = D.vocab; a.K = (int)d;
-                a.X = c->dxs; a.x_mpad = mpad;
-                a.pos_p = c->pos; a.n_prompt = PP; a.mask_first = c->lp_mask_zero; a.mask_base = c->lp_mask_zero;
-                a.part_val = c->part_val; a.part_idx = c->part_idx; a.part_sum = c->lp_part_sum;
-                a.probe_id = (int)c->lp_no_speech; a.probe_out = c->lp_probe_v;
-                wh_launch_lm_head(s, prec, a);
-                parts = wh_lm_head_parts(prec, a);
+        {   // merge of the key ranges ∘ cross-attention out-proj + residual → x, raw slab, LN3 partials
+            Prof pr(c, WH_KG_DEC_GEMM);
+            const bool merged = c->cross_splits == 1 || c->cross_es;   // one key range per clip: the attention kernel wrote its output itself
+            SkinnyArgs a = residual_producer(L.co_w, L.co_b, L.co_sc, merged ? c->datt : nullptr, d, L.ln3_w);
+            if (!merged) { a.xpart = c->cpart; a.xml = c->cml; a.x_splits = c->cross_splits; a.x_heads = D.n_heads; }
+            gemm(true, a);
+        }
+        {   // LN3 ∘ fc1 + GELU (slab output)
+            Prof pr(c, WH_KG_DEC_GEMM);
+            SkinnyArgs a = ln_consumer(L.fc1_w, L.fc1_b, L.fc1_sc, L.fc1_s, D.ffn, c->dh, ln_tiles_d, true);
+            a.act = 1;
+            gemm(false, a);
+        }
+        {   // fc2 + residual → x, raw slab, partials for the next layer's LN1 / the final LN
+            Prof pr(c, WH_KG_DEC_GEMM);
+            SkinnyArgs a = residual_producer(L.fc2_w, L.fc2_b, L.fc2_sc, c->dh, D.ffn, (l + 1 < D.dec_layers) ? m->dec[l + 1].ln1_w : m->dec_ln_w);
+            if (advance) { a.ticket = c->step_ticket; a.pos_w = c->pos; }
+            gemm(true, a);
+        }
+    }
+
+    // final LN ∘ tied LM head + masked argmax; the finish kernel records the token, advances the position and embeds the next one
+    void emit() const {
+        int lm_parts;
+        {
+            Prof pr(c, WH_KG_DEC_GEMM);
+            SkinnyArgs a = lm_head_common();
+            a.mask_first = c->mask_first; a.mask_base = c->mask_base;
+            a.logits = k.d_logits; a.logits_rows = k.logits_rows; a.logits_sel = k.d_sel;
+            if (rules) {
+                a.ts_state = c->ts_state; a.ts_logits = c->ts_logits; a.ts_ld = D.vocab - k.ts_begin;
+                a.ts_begin = k.ts_begin; a.ts_max_init = k.ts_max_init;
             }
-            Prof pr(c, WH_KG_DEC_OTHER);
-            wh_launch_nospeech_finish(s, c->part_val, c->lp_part_sum, parts, mpad, c->lp_probe_v, c->lp_ns, nb, c->pos);
+            a.part_sum = k.lp_sum;
+            if (k.rep) { a.rep_bits = c->rep_bits; a.rep_side = c->rep_side; a.rep_words = c->rep_words; }
+            wh_launch_lm_head(s, prec, a);
+            lm_parts = wh_lm_head_parts(prec, a);
         }
-    };
-    // Positions 0 .. P-1 (the prompt, the last of which emits the first token) are launched eagerly;
-    // the remaining NEW-1 positions replay ONE captured hipGraph of an emitting step — every kernel
-    // reads the position from device memory, so the graph is position-independent.  The host then
-    // pays one graph launch per token instead of ~50 kernel launches (src/main.rs:793-826 is one ORT
-    // Run per token in the reference).
-    for (int step = 0; step < std::min(PP, total_pos); step++)
-        launch_step(step >= PP - 1, true, lp_probe && step == Nmax + c->lp_sot_index, lang_det && step == Nmax + c->lang_sot_index);
-    const int remaining = total_pos - PP;
+        Prof pr(c, WH_KG_DEC_OTHER);   // argmax finish + greedy bookkeeping + the next position's embedding
+        DecodeState st;
+        st.feed = c->feed; st.out_tokens = c->out_tokens; st.n_out = c->n_out; st.done = c->done;
+        st.forced = c->forced; st.n_forced = k.n_forced; st.n_prompt = k.n_prompt; st.eot = k.eot; st.tok_ld = c->tok_ld;
+        if (k.lp_sum) st.logprob = c->lp_tok;
+        NextEmbed ne;
+        ne.tok_emb = m->tok_emb; ne.pos_emb = m->dec_pos; ne.x = c->dx; ne.xslab = c->dxs; ne.stats = c->lnpart;
+        ne.xgamma = f8 ? m->dec[0].ln1_w : nullptr; ne.d = (int)d; ne.mpad = mpad; ne.shift = c->dshift; ne.off = d_off;
+        TsFinish tf;
+        if (rules) {
+            tf.rules = true; tf.ts_logits = c->ts_logits; tf.ts_ld = D.vocab - k.ts_begin; tf.state = c->ts_state;
+            tf.ts_begin = k.ts_begin; tf.vocab = D.vocab;
+        }
+        RepFinish rf;
+        if (k.rep) {
+            rf.on = true; rf.bits = c->rep_bits; rf.side = c->rep_side; rf.words = c->rep_words; rf.vocab = D.vocab;
+            rf.p = k.rep_p; rf.inv = 1.0f / k.rep_p; rf.ngram = k.rep_n;
+            if (rules) rf.exempt_from = k.ts_begin;   // timestamps repeat in pairs and the rules own them
+            rf.mask_first = c->mask_first; rf.mask_base = c->mask_base;
+        }
+        wh_launch_argmax_finish(s, prec, c->part_val, c->part_idx, lm_parts, mpad, c->pos, c->step_ticket, st, nb, ne, tf, k.lp_sum, rf);
+    }
+
+    // the listed ids' unfiltered logits of this prompt position -> each row's language token in column tok_col of the next one; the
+    // finish advances the position unless the probe's finish will
+    void lang(int tok_col, bool advance) const {
+        {
+            Prof pr(c, WH_KG_DEC_GEMM);
+            const SkinnyArgs h = lm_head_common();   // the LM head's operands, the weight rows gathered by id
+            LangHeadArgs a;
+            a.X = h.X; a.x_mpad = h.x_mpad; a.W = h.W; a.bias = h.bias; a.ln_s = h.ln_s; a.ln_part = h.ln_part; a.ln_tiles = h.ln_tiles; a.M = h.M; a.K = h.K;
+            a.ids = c->lang_d_ids; a.n_lang = (int)c->lang_ids.size(); a.out = c->lang_logits;
+            wh_launch_lang_head(s, prec, a);
+        }
+        Prof pr(c, WH_KG_DEC_OTHER);
+        wh_launch_lang_finish(s, c->lang_logits, c->lang_d_ids, (int)c->lang_ids.size(), c->lang_bcast ? 0 : -1, c->lang_probs, c->lang_chosen,
+                              c->feed, c->out_tokens, c->tok_ld, tok_col, nb, advance ? c->pos : nullptr);
+    }
+
+    // softmax(v)[no_speech] over this prompt position's unfiltered logits: the LM head's log-probability variant with an all-zero mask,
+    // no rules, nothing recorded; the probe's finish kernel advances the position
+    void probe() const {
+        int parts;
+        {
+            Prof pr(c, WH_KG_DEC_GEMM);
+            SkinnyArgs a = lm_head_common();
+            a.mask_first = c->lp_mask_zero; a.mask_base = c->lp_mask_zero;
+            a.part_sum = c->lp_part_sum;
+            a.probe_id = (int)c->lp_no_speech; a.probe_out = c->lp_probe_v;
+            wh_launch_lm_head(s, prec, a);
+            parts = wh_lm_head_parts(prec, a);
+        }
+        Prof pr(c, WH_KG_DEC_OTHER);
+        wh_launch_nospeech_finish(s, c->part_val, c->lp_part_sum, parts, mpad, c->lp_probe_v, c->lp_ns, nb, c->pos);
+    }
+};
+
+// One decoder position.  prompt == nullptr: a generated position — the emitting step that is captured into the graph; it sees the
+// context and its key, nothing else (wh_ctx::StepKey).
+void launch_step(wh_ctx* c, const wh_ctx::StepKey& k, const PromptStep* prompt = nullptr) {
+    const Step t{c, k};
+    const bool emits = !prompt || prompt->emits, lang = prompt && prompt->lang, probe = prompt && prompt->probe;
+    if (prompt) {   // token + position embedding → x, raw slab, row sums (one "tile")
+        Prof pr(c, WH_KG_DEC_OTHER);
+        wh_launch_dec_embed(t.s, t.prec, t.m->tok_emb, t.m->dec_pos, c->feed, c->tok_ld, c->pos, c->dx, c->dxs, c->lnpart, t.nb, (int)t.d, t.mpad,
+                            t.f8 ? t.m->dec[0].ln1_w : nullptr, c->dshift, t.d_off);
+    }
+    for (int l = 0; l < t.D.dec_layers; l++) t.layer(l, l == t.D.dec_layers - 1 && !emits && !lang && !probe);
+    if (emits) t.emit();
+    if (lang) t.lang(prompt->lang_col, !probe);   // (before the probe, if the probe sits at the same position)
+    if (probe) t.probe();
+}
+
+// the instantiated graph of launch_step(c, key): kept from the last call if the key is the same, else captured now
+int ensure_step_graph(wh_ctx* c, const wh_ctx::StepKey& key) {
+    if (c->step_exec && c->step_key == key) return WH_OK;
+    hipStream_t s = c->stream;
+    drop_step_graph(c);   // nothing of it is in flight: every call ends with a stream synchronisation
+    c->capturing = true;  // no event records inside the captured step
+    hipGraph_t graph = nullptr;
+    hipError_t ce = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
+    if (ce == hipSuccess) {
+        launch_step(c, key);
+        ce = hipStreamEndCapture(s, &graph);
+    }
+    c->capturing = false;
+    if (ce != hipSuccess) {
+        if (graph) hipGraphDestroy(graph);
+        return fail(c, WH_ERR_HIP, "graph capture of the decode step failed: %s", hipGetErrorString(ce));
+    }
+    hipGraphExec_t gexec = nullptr;
+    ce = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
+    if (ce != hipSuccess) {
+        hipGraphDestroy(graph);
+        return fail(c, WH_ERR_HIP, "hipGraphInstantiate of the decode step failed: %s", hipGetErrorString(ce));
+    }
+    c->step_graph = graph;
+    c->step_exec = gexec;
+    c->step_key = key;
+    return WH_OK;
+}
+
+// The `remaining` generated positions after the prompt replay ONE captured hipGraph of an emitting step — every kernel reads the
+// position from device memory, so the graph is position-independent.  The host then pays one graph launch per token instead of ~50
+// kernel launches (src/main.rs:793-826 is one ORT Run per token in the reference).
+int run_token_loop(wh_ctx* c, const wh_ctx::StepKey& key, int remaining, bool poll_eot) {
+    hipStream_t s = c->stream;
     // with event timing on: every position is launched eagerly (stride 0/1), or only every stride-th one
     // (sampled live timing) while the others replay the graph
     const int stride = c->prof ? c->prof_stride : 0;
     const bool use_graph = remaining > 1 && !c->no_graph && (!c->prof || stride > 1);
     if (use_graph) {
-        wh_ctx::StepKey key;
-        key.nb = nb; key.n_prompt = PP; key.pfx = pfx; key.eot = (int)p->eot; key.n_forced = (int)p->n_forced;
-        key.logits_rows = (int)logits_rows; key.d_logits = d_logits; key.d_sel = d_sel;
-        if (c->ts_on) { key.ts_begin = (int)c->ts_begin; key.ts_max_init = c->ts_max_init; }
-        if (lp) key.lp_sum = c->lp_part_sum;
-        if (rep_on) { key.rep = true; key.rep_p = c->rep_p; key.rep_n = c->rep_n; }
-        if (!c->step_exec || !(c->step_key == key)) {
-            drop_step_graph(c);   // nothing of it is in flight: every call ends with a stream synchronisation
-            c->capturing = true;  // no event records inside the captured step
-            hipGraph_t graph = nullptr;
-            hipError_t ce = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-            if (ce == hipSuccess) {
-                launch_step(true, false, false);
-                ce = hipStreamEndCapture(s, &graph);
-            }
-            c->capturing = false;
-            if (ce != hipSuccess) {
-                if (graph) hipGraphDestroy(graph);
-                return fail(c, WH_ERR_HIP, "graph capture of the decode step failed: %s", hipGetErrorString(ce));
-            }
-            hipGraphExec_t gexec = nullptr;
-            ce = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
-            if (ce != hipSuccess) {
-                hipGraphDestroy(graph);
-                return fail(c, WH_ERR_HIP, "hipGraphInstantiate of the decode step failed: %s", hipGetErrorString(ce));
-            }
-            c->step_graph = graph;
-            c->step_exec = gexec;
-            c->step_key = key;
-        }
+        int rc = ensure_step_graph(c, key);
+        if (rc) return rc;
     }
+    std::vector<int> done_h(key.nb);
     for (int r = 0; r < remaining; r++) {
         const bool sampled = c->prof && stride > 1 && (r % stride) == stride / 2;
         if (use_graph && !sampled) {
@@ -728,54 +778,55 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
                 return fail(c, WH_ERR_HIP, "hipGraphLaunch failed: %s", hipGetErrorString(ge));
             }
         } else {
-            launch_step(true, false, false);
+            launch_step(c, key);
         }
         // diagnostic (profiles/README.md, rocprofv3 --pmc at whisper-large-v3 size): bound the number of dispatches in flight
         if (c->sync_every_pos) hipStreamSynchronize(s);
         // EOT early-out (src/main.rs:781-783, 820-822): poll the done flags every 16 generated tokens
         const int gen = r + 1;
-        if ((gen & 15) == 15 && r + 1 < remaining && p->n_forced == 0) {
-            hipError_t e1 = hipMemcpyAsync(done_h.data(), c->done, nb * 4, hipMemcpyDeviceToHost, s);
+        if ((gen & 15) == 15 && r + 1 < remaining && poll_eot) {
+            hipError_t e1 = hipMemcpyAsync(done_h.data(), c->done, key.nb * 4, hipMemcpyDeviceToHost, s);
             hipError_t e2 = hipStreamSynchronize(s);
             if (e1 != hipSuccess || e2 != hipSuccess)
                 return fail(c, WH_ERR_HIP, "decode: polling the done flags failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
             bool all = true;
-            for (int b = 0; b < nb; b++) all = all && done_h[b];
+            for (int b = 0; b < key.nb; b++) all = all && done_h[b];
             if (all) break;
         }
     }
-    CTX_HIP(c, hipEventRecord(c->ev[3], s));
-    // results
-    std::vector<int> toks((size_t)nb * ld);
-    const double t0 = now_s();
-    CTX_HIP(c, hipMemcpyAsync(toks.data(), c->out_tokens, toks.size() * 4, hipMemcpyDeviceToHost, s));
-    CTX_HIP(c, hipMemcpyAsync(nout.data(), c->n_out, nb * 4, hipMemcpyDeviceToHost, s));
-    std::vector<float> lps, nsp;
-    if (lp) {
-        lps.resize((size_t)nb * ld);
-        CTX_HIP(c, hipMemcpyAsync(lps.data(), c->lp_tok, lps.size() * 4, hipMemcpyDeviceToHost, s));
-        if (lp_probe) {
-            nsp.resize(nb);
-            CTX_HIP(c, hipMemcpyAsync(nsp.data(), c->lp_ns, nb * 4, hipMemcpyDeviceToHost, s));
-        }
-    }
+    return WH_OK;
+}
+
+// tokens, counts, log-probabilities, no-speech, languages, logits; keeps what wh_get_logprobs / wh_get_languages return
+int read_back(wh_ctx* c, const DecodePlan& pl, int64_t* tokens_out, size_t tok_stride, size_t* n_tokens_out, float* logits_out, const int32_t* sel) {
+    hipStream_t s = c->stream;
+    const int nb = pl.key.nb, ld = c->tok_ld, Nmax = pl.Nmax, PP = pl.key.n_prompt, vocab = c->m->dims.vocab;
+    const size_t logits_rows = pl.key.logits_rows;
+    const bool lp = c->lp_on;
     const size_t n_lang = c->lang_ids.size();
-    std::vector<int> lch;
-    std::vector<float> lpr;
-    if (lang_det) {
-        lch.resize(nb);
-        lpr.resize((size_t)nb * n_lang);
-        CTX_HIP(c, hipMemcpyAsync(lch.data(), c->lang_chosen, nb * 4, hipMemcpyDeviceToHost, s));
-        CTX_HIP(c, hipMemcpyAsync(lpr.data(), c->lang_probs, lpr.size() * 4, hipMemcpyDeviceToHost, s));
+    std::vector<int> toks, nout, lch;
+    std::vector<float> lps, nsp, lpr;
+    const double t0 = now_s();
+    auto fetch = [&](auto& v, const void* src, size_t n) {   // (4-byte elements)
+        v.resize(n);
+        return hipMemcpyAsync(v.data(), src, n * 4, hipMemcpyDeviceToHost, s);
+    };
+    CTX_HIP(c, fetch(toks, c->out_tokens, (size_t)nb * ld));
+    CTX_HIP(c, fetch(nout, c->n_out, nb));
+    if (lp) CTX_HIP(c, fetch(lps, c->lp_tok, (size_t)nb * ld));
+    if (pl.lp_probe) CTX_HIP(c, fetch(nsp, c->lp_ns, nb));
+    if (pl.lang_det) {
+        CTX_HIP(c, fetch(lch, c->lang_chosen, nb));
+        CTX_HIP(c, fetch(lpr, c->lang_probs, (size_t)nb * n_lang));
     }
     CTX_HIP(c, hipStreamSynchronize(s));
     CTX_HIP(c, hipGetLastError());
-    if (lang_fix) {   // the file's language and window 0's probabilities (the first rows kept), once per window of this batch
+    if (pl.lang_fix) {   // the file's language and window 0's probabilities (the first rows kept), once per window of this batch
         for (int b = 0; b < nb; b++) {
             c->lang_rows.push_back(c->lang_fixed);
             for (size_t j = 0; j < n_lang; j++) { const float pj = c->lang_prob_rows[j]; c->lang_prob_rows.push_back(pj); }
         }
-    } else if (lang_det) {
+    } else if (pl.lang_det) {
         for (int b = 0; b < nb; b++) c->lang_rows.push_back(lch[b]);
         c->lang_prob_rows.insert(c->lang_prob_rows.end(), lpr.begin(), lpr.end());
         c->lang_have = true;
@@ -785,22 +836,50 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
         for (int b = 0; b < nb; b++) c->lp_rows.emplace_back(lps.begin() + (size_t)b * ld + PP, lps.begin() + (size_t)b * ld + nout[b]);
         c->lp_ns_rows.insert(c->lp_ns_rows.end(), nsp.begin(), nsp.end());
         c->lp_have = true;
-        c->lp_have_ns = lp_probe;
+        c->lp_have_ns = pl.lp_probe;
     }
     for (int b = 0; b < nb; b++) {
         n_tokens_out[b] = (size_t)(nout[b] - Nmax);   // the prefix columns are not echoed: shared prompt ++ generated, as without prefixes
         for (int i = Nmax; i < nout[b]; i++) tokens_out[(size_t)b * tok_stride + i - Nmax] = toks[(size_t)b * ld + i];
     }
     if (logits_out) {
-        for (size_t i = 0; i < n_lrows; i++) {
+        for (size_t i = 0; i < pl.n_lrows; i++) {
             const int b = sel ? sel[i] : (int)i;
             const size_t rows = (size_t)nout[b] - PP;
-            CTX_HIP(c, hipMemcpy(logits_out + i * logits_rows * D.vocab, d_logits + i * logits_rows * D.vocab,
-                                 std::min(rows, logits_rows) * D.vocab * 4, hipMemcpyDeviceToHost));
+            CTX_HIP(c, hipMemcpy(logits_out + i * logits_rows * vocab, pl.key.d_logits + i * logits_rows * vocab, std::min(rows, logits_rows) * vocab * 4,
+                                 hipMemcpyDeviceToHost));
         }
     }
     c->timing.d2h_s = now_s() - t0;
     return WH_OK;
+}
+
+// `sel` (optional, with logits_out): the n_sel batch rows whose logits are read back — logits_out is then [n_sel][logits_rows][vocab]
+int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out, size_t tok_stride,
+               size_t* n_tokens_out, float* logits_out, size_t logits_rows, const std::function<int()>& after_kv = nullptr,
+               const int32_t* sel = nullptr, size_t n_sel = 0) {
+    hipStream_t s = c->stream;
+    c->cur = s;
+    DecodePlan pl;
+    int rc = plan_decode(c, nb, p, logits_out != nullptr, logits_rows, sel, n_sel, pl);
+    if (rc) return rc;
+    const wh_ctx::StepKey& key = pl.key;
+    // the encoder states come from the encoder stream
+    if (c->s_enc != s) CTX_HIP(c, hipStreamWaitEvent(s, c->ev_enc_done, 0));
+    CTX_HIP(c, hipEventRecord(c->ev[5], s));   // decode start (stage timing)
+    if ((rc = upload_token_state(c, p, pl)) || (rc = prepare_logits(c, pl)) || (rc = project_cross_kv(c, nb, after_kv))) return rc;
+    // Positions 0 .. PP-1 (the prompt, the last of which emits the first token) are launched eagerly; the rest is the token loop's
+    const int PP = key.n_prompt, total_pos = PP + pl.NEW - 1;
+    for (int step = 0; step < std::min(PP, total_pos); step++) {
+        PromptStep ps;
+        ps.emits = step >= PP - 1;
+        ps.lang = step == pl.lang_pos; ps.lang_col = pl.Nmax + pl.lang_slot;
+        ps.probe = step == pl.probe_pos;
+        launch_step(c, key, &ps);
+    }
+    if ((rc = run_token_loop(c, key, total_pos - PP, p->n_forced == 0))) return rc;
+    CTX_HIP(c, hipEventRecord(c->ev[3], s));
+    return read_back(c, pl, tokens_out, tok_stride, n_tokens_out, logits_out, sel);
 }
 
 // mel of nb clips resident at `pcm` ([nb][480000] f32, n samples each in c->d_nsamp) → conv1 operand in c->melT
@@ -1229,6 +1308,19 @@ int wh_ctx_placement(const wh_ctx* c, float* first_us, float* kept_us) {
     return c->place_tries;
 }
 
+// An option setter's buffer: `bytes` zeroed bytes on the context's device, or nullptr with the setter's error recorded (the caller returns
+// WH_ERR_NOMEM).
+static void* setter_alloc(wh_ctx* c, const char* setter, size_t bytes) {
+    hipSetDevice(c->m->device);
+    void* buf = nullptr;
+    hipError_t e = hipMalloc(&buf, bytes);
+    if (e == hipSuccess) e = hipMemset(buf, 0, bytes);
+    if (e == hipSuccess) return buf;
+    if (buf) hipFree(buf);
+    fail(c, WH_ERR_NOMEM, "%s: hipMalloc: %s", setter, hipGetErrorString(e));
+    return nullptr;
+}
+
 // Whisper's timestamp rules on every decode entry of the ctx.  The buffers — the rows' timestamp logits and a per-row state —
 // are allocated when rules are turned on (the logits again for another timestamp_begin); the captured decode step is recaptured when the
 // key changes (and before a buffer it holds is freed).
@@ -1246,14 +1338,11 @@ int wh_ctx_set_timestamp_rules(wh_ctx* c, const wh_timestamp_rules* r) {
         return fail(c, WH_ERR_ARG, "wh_ctx_set_timestamp_rules: no_timestamps %lld outside the vocabulary", (long long)r->no_timestamps);
     const int ld = vocab - (int)r->timestamp_begin;
     if (!c->ts_logits || c->ts_ld != ld) {
-        hipSetDevice(c->m->device);
-        float* tl = nullptr; int* st = c->ts_state;
-        hipError_t e = hipMalloc((void**)&tl, (size_t)c->mpad * ld * 4);
-        if (e == hipSuccess && !st) e = hipMalloc((void**)&st, (size_t)c->mpad * 16);
-        if (e != hipSuccess) {
+        float* tl = (float*)setter_alloc(c, "wh_ctx_set_timestamp_rules", (size_t)c->mpad * ld * 4);
+        int* st = c->ts_state ? c->ts_state : (int*)(tl ? setter_alloc(c, "wh_ctx_set_timestamp_rules", (size_t)c->mpad * 16) : nullptr);
+        if (!tl || !st) {
             if (tl) hipFree(tl);
-            if (st && st != c->ts_state) hipFree(st);
-            return fail(c, WH_ERR_NOMEM, "wh_ctx_set_timestamp_rules: hipMalloc: %s", hipGetErrorString(e));
+            return WH_ERR_NOMEM;
         }
         drop_step_graph(c);   // (a captured step may hold the old buffer's address)
         if (c->ts_logits) hipFree(c->ts_logits);
@@ -1283,14 +1372,8 @@ int wh_ctx_set_logprobs(wh_ctx* c, const wh_logprob_opts* o) {
         auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
         const size_t MP = (size_t)c->mpad, B = (size_t)c->max_batch, n_tiles = ((size_t)vocab + 15) / 16;
         const size_t b_sum = up(MP * (n_tiles + 4) * 4), b_tok = up(B * c->tok_ld * 4), b_mask = up(((size_t)vocab / 32 + 1) * 4), b_pv = up(MP * 4), b_ns = up(B * 4);
-        hipSetDevice(c->m->device);
-        char* buf = nullptr;
-        hipError_t e = hipMalloc((void**)&buf, b_sum + b_tok + b_mask + b_pv + b_ns);
-        if (e == hipSuccess) e = hipMemset(buf, 0, b_sum + b_tok + b_mask + b_pv + b_ns);
-        if (e != hipSuccess) {
-            if (buf) hipFree(buf);
-            return fail(c, WH_ERR_NOMEM, "wh_ctx_set_logprobs: hipMalloc: %s", hipGetErrorString(e));
-        }
+        char* buf = (char*)setter_alloc(c, "wh_ctx_set_logprobs", b_sum + b_tok + b_mask + b_pv + b_ns);
+        if (!buf) return WH_ERR_NOMEM;
         c->lp_buf = buf;
         c->lp_part_sum = (float*)buf;
         c->lp_tok = (float*)(buf + b_sum);
@@ -1312,7 +1395,7 @@ static void rep_release(wh_ctx* c) {
     if (c->rep_bits) hipFree(c->rep_bits);
     if (c->rep_side) hipFree(c->rep_side);
     c->rep_bits = nullptr; c->rep_side = nullptr;
-    c->rep_on = false; c->rep_p = c->rep_inv = 1.0f; c->rep_n = 0;
+    c->rep_on = false; c->rep_p = 1.0f; c->rep_n = 0;
 }
 int wh_ctx_set_repetition(wh_ctx* c, const wh_repetition_opts* o) {
     if (!c) return WH_ERR_ARG;
@@ -1329,22 +1412,17 @@ int wh_ctx_set_repetition(wh_ctx* c, const wh_repetition_opts* o) {
         return WH_OK;
     }
     if (!c->rep_bits) {
-        hipSetDevice(c->m->device);
         const size_t vocab = (size_t)c->m->dims.vocab, words = (vocab + 31) / 32, B = (size_t)c->max_batch;
-        unsigned* bits = nullptr; float* side = nullptr;
-        hipError_t e = hipMalloc((void**)&bits, B * words * 4);
-        if (e == hipSuccess) e = hipMalloc((void**)&side, B * vocab * 4);
-        if (e == hipSuccess) e = hipMemset(bits, 0, B * words * 4);
-        if (e != hipSuccess) {
+        unsigned* bits = (unsigned*)setter_alloc(c, "wh_ctx_set_repetition", B * words * 4);
+        float* side = (float*)(bits ? setter_alloc(c, "wh_ctx_set_repetition", B * vocab * 4) : nullptr);
+        if (!side) {
             if (bits) hipFree(bits);
-            if (side) hipFree(side);
-            return fail(c, WH_ERR_NOMEM, "wh_ctx_set_repetition: hipMalloc: %s", hipGetErrorString(e));
+            return WH_ERR_NOMEM;
         }
         c->rep_bits = bits; c->rep_side = side; c->rep_words = (int)words;
     }
     c->rep_on = true;
     c->rep_p = o->repetition_penalty;
-    c->rep_inv = 1.0f / o->repetition_penalty;
     c->rep_n = o->no_repeat_ngram_size;
     return WH_OK;
 }
@@ -1371,14 +1449,7 @@ int wh_ctx_set_language_detection(wh_ctx* c, const wh_language_opts* o) {
     auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
     const size_t MP = (size_t)c->mpad, B = (size_t)c->max_batch;
     const size_t b_ids = up(WH_LANG_LD * 4), b_log = up(MP * WH_LANG_LD * 4), b_pr = up(B * WH_LANG_LD * 4), b_ch = up(B * 4);
-    if (!buf) {
-        hipError_t e = hipMalloc((void**)&buf, b_ids + b_log + b_pr + b_ch);
-        if (e == hipSuccess) e = hipMemset(buf, 0, b_ids + b_log + b_pr + b_ch);
-        if (e != hipSuccess) {
-            if (buf) hipFree(buf);
-            return fail(c, WH_ERR_NOMEM, "wh_ctx_set_language_detection: hipMalloc: %s", hipGetErrorString(e));
-        }
-    }
+    if (!buf && !(buf = (char*)setter_alloc(c, "wh_ctx_set_language_detection", b_ids + b_log + b_pr + b_ch))) return WH_ERR_NOMEM;
     int ids[WH_LANG_LD];
     for (int i = 0; i < WH_LANG_LD; i++) ids[i] = (int)o->lang_ids[(size_t)i < o->n_lang ? i : 0];
     hipError_t e = hipMemcpy(buf, ids, sizeof ids, hipMemcpyHostToDevice);   // (nothing of the ctx is in flight: every call ends with a stream synchronisation)
@@ -1421,15 +1492,7 @@ int wh_ctx_set_prefixes(wh_ctx* c, const wh_prefix_opts* o) {
     for (size_t i = 0; i < n_ids; i++)
         if (o->ids[i] < 0 || o->ids[i] >= vocab) return fail(c, WH_ERR_ARG, "wh_ctx_set_prefixes: id %lld outside the vocabulary (%d)", (long long)o->ids[i], vocab);
     if (!c->pfx_off) {
-        hipSetDevice(c->m->device);
-        int* buf = nullptr;
-        hipError_t e = hipMalloc((void**)&buf, (size_t)c->max_batch * 4);
-        if (e == hipSuccess) e = hipMemset(buf, 0, (size_t)c->max_batch * 4);
-        if (e != hipSuccess) {
-            if (buf) hipFree(buf);
-            return fail(c, WH_ERR_NOMEM, "wh_ctx_set_prefixes: hipMalloc: %s", hipGetErrorString(e));
-        }
-        c->pfx_off = buf;
+        if (!(c->pfx_off = (int*)setter_alloc(c, "wh_ctx_set_prefixes", (size_t)c->max_batch * 4))) return WH_ERR_NOMEM;
     }
     c->pfx_ids.assign(o->ids, o->ids + n_ids);
     c->pfx_offsets.assign(o->offsets, o->offsets + o->n_clips + 1);

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include <type_traits>
+
 #include "../../include/whisper_hip.h"
 
 typedef __bf16 bf16;
@@ -444,3 +446,33 @@ int wh_fail_hip(hipError_t e, const char* what, const char* file, int line);
 // recorded through wh_set_error (the launch that follows then fails and surfaces at the call's hipGetLastError).
 bool wh_ensure_dyn_lds(const void* kernel, size_t bytes);
 void wh_set_error(const char* fmt, ...);
+
+// Runtime choices -> template arguments, for the launchers of kernels with variant flags.
+// wh_with_flags(f, b0, b1, ...) calls the generic lambda f with one std::bool_constant per flag, in order:
+//   wh_with_flags([&](auto R, auto L) { launch(k<decltype(R)::value, decltype(L)::value>); }, rules, lp);
+// Every combination is instantiated; one more flag is one more argument.
+template <typename F>
+void wh_with_flags(F&& f) { f(); }
+template <typename F, typename... Bs>
+void wh_with_flags(F&& f, bool b, Bs... rest) {
+    if (b) wh_with_flags([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+    else wh_with_flags([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
+// the element type of a precision mode's operands where it is {WH_PREC_F32: float, WH_PREC_F16X3: h2, else bf16}: f(wh_type_tag<T>{})
+template <typename T> struct wh_type_tag { typedef T type; };
+template <typename F>
+void wh_with_dtype(int prec, F&& f) {
+    if (prec == WH_PREC_F32) f(wh_type_tag<float>{});
+    else if (prec == WH_PREC_F16X3) f(wh_type_tag<h2>{});
+    else f(wh_type_tag<bf16>{});
+}
+// 1 .. 4 as an std::integral_constant (the LM heads' row groups per workgroup; anything above 4 counts as 4)
+template <typename F>
+void wh_with_1to4(int n, F&& f) {
+    switch (n) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        default: f(std::integral_constant<int, 4>{}); break;
+    }
+}

@@ -1767,27 +1767,21 @@ void wh_launch_dec_gemm(hipStream_t s, int prec, bool out_f32, const SkinnyArgs&
     else launch_dec_gemm_split<bf16, bf16, bf16>(s, a);
 }
 
-template <bool PFX>
-void launch_dec_embed_t(hipStream_t s, int prec, const void* tok_emb, const float* pos_emb, const int* feed, int feed_ld,
-                        const int* pos_p, float* x, void* xslab, float* stats, int rows, int d, int mpad, const float* xgamma, float* shift, const int* off) {
-    dim3 grid((rows + 3) / 4);
-    if (prec == WH_PREC_F16X3)
-        hipLaunchKernelGGL((k_dec_embed<h2, PFX>), grid, dim3(256), 0, s, (const h2*)tok_emb, pos_emb, feed, feed_ld, pos_p, x, (h2*)xslab, stats, rows, d, mpad, xgamma, shift, off);
-    else if (prec == WH_PREC_F32)
-        hipLaunchKernelGGL((k_dec_embed<float, PFX>), grid, dim3(256), 0, s, (const float*)tok_emb, pos_emb, feed, feed_ld, pos_p, x, (float*)xslab, stats, rows, d, mpad, xgamma, shift, off);
-    else
-        hipLaunchKernelGGL((k_dec_embed<bf16, PFX>), grid, dim3(256), 0, s, (const bf16*)tok_emb, pos_emb, feed, feed_ld, pos_p, x, (bf16*)xslab, stats, rows, d, mpad, xgamma, shift, off);
-}
-
 // off != nullptr (here and in wh_launch_argmax_finish / wh_launch_dec_self_attn): the prefix-aware instantiations
 void wh_launch_dec_embed(hipStream_t s, int prec, const void* tok_emb, const float* pos_emb, const int* feed, int feed_ld,
                          const int* pos_p, float* x, void* xslab, float* stats, int rows, int d, int mpad, const float* xgamma, float* shift, const int* off) {
-    if (off) launch_dec_embed_t<true>(s, prec, tok_emb, pos_emb, feed, feed_ld, pos_p, x, xslab, stats, rows, d, mpad, xgamma, shift, off);
-    else launch_dec_embed_t<false>(s, prec, tok_emb, pos_emb, feed, feed_ld, pos_p, x, xslab, stats, rows, d, mpad, xgamma, shift, off);
+    dim3 grid((rows + 3) / 4);
+    wh_with_dtype(prec, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        wh_with_flags([&](auto PFX) {
+            hipLaunchKernelGGL((k_dec_embed<T, decltype(PFX)::value>), grid, dim3(256), 0, s, (const T*)tok_emb, pos_emb, feed, feed_ld, pos_p, x, (T*)xslab, stats, rows, d, mpad, xgamma, shift, off);
+        }, off != nullptr);
+    });
 }
 
-template <typename T, bool RULES = false, bool LP = false, bool REP = false>
-void launch_lm_head_t(hipStream_t s, const SkinnyArgs& a, int* n_parts_out = nullptr) {
+// row groups per workgroup (mt), dynamic LDS and grid of k_lm_head<T, mt, ...> for this shape
+template <typename T>
+static dim3 lm_head_geometry(const SkinnyArgs& a, int* mt_out, size_t* sm_out) {
     const int n_tiles = (a.N + 15) / 16;
     int mt = std::min(wh_dbg_lm_mt, (a.M + 15) / 16);
     auto lds = [&](int t) { return (size_t)t * 16 * a.K * sizeof(T) + (size_t)t * 16 * 2 * 4 * 5; };  // X tile + LN stats (+ 4 quarter sums)
@@ -1797,21 +1791,9 @@ void launch_lm_head_t(hipStream_t s, const SkinnyArgs& a, int* n_parts_out = nul
     if (mt > 4) mt = 4;
     const size_t sm = lds(mt);
     const int per_cu = std::max<int>(1, (int)(150 * 1024 / sm));
-    dim3 grid(std::min((n_tiles + 3) / 4, 256 * std::min(per_cu, wh_dbg_lm_blocks_per_cu) / ((a.M + 16 * mt - 1) / (16 * mt))), (a.M + 16 * mt - 1) / (16 * mt));
-    if (n_parts_out) { *n_parts_out = (int)grid.x * 4; return; }  // query only: partials per row = waves per row group
-#define WH_LM(MT_)                                                \
-    {                                                             \
-        auto kfn = k_lm_head<T, MT_, RULES, LP, REP>;             \
-        set_max_smem(kfn, sm);                                    \
-        hipLaunchKernelGGL(kfn, grid, dim3(256), sm, s, a);       \
-    }
-    switch (mt) {
-        case 1: WH_LM(1) break;
-        case 2: WH_LM(2) break;
-        case 3: WH_LM(3) break;
-        default: WH_LM(4) break;
-    }
-#undef WH_LM
+    *mt_out = mt;
+    *sm_out = sm;
+    return dim3(std::min((n_tiles + 3) / 4, 256 * std::min(per_cu, wh_dbg_lm_blocks_per_cu) / ((a.M + 16 * mt - 1) / (16 * mt))), (a.M + 16 * mt - 1) / (16 * mt));
 }
 
 // a.X = final-LayerNorm'ed rows [M][K] in the compute dtype
@@ -1820,18 +1802,16 @@ void launch_lm_head_t(hipStream_t s, const SkinnyArgs& a, int* n_parts_out = nul
 // a.rep_bits != nullptr: the repetition variants (same logits, same partial count)
 template <typename T>
 static void launch_lm_head_v(hipStream_t s, const SkinnyArgs& a) {
-    const bool r = a.ts_logits != nullptr, l = a.part_sum != nullptr;
-    if (a.rep_bits) {
-        if (r && l) launch_lm_head_t<T, true, true, true>(s, a);
-        else if (r) launch_lm_head_t<T, true, false, true>(s, a);
-        else if (l) launch_lm_head_t<T, false, true, true>(s, a);
-        else launch_lm_head_t<T, false, false, true>(s, a);
-        return;
-    }
-    if (r && l) launch_lm_head_t<T, true, true>(s, a);
-    else if (r) launch_lm_head_t<T, true>(s, a);
-    else if (l) launch_lm_head_t<T, false, true>(s, a);
-    else launch_lm_head_t<T>(s, a);
+    int mt;
+    size_t sm;
+    const dim3 grid = lm_head_geometry<T>(a, &mt, &sm);
+    wh_with_flags([&](auto RULES, auto LP, auto REP) {
+        wh_with_1to4(mt, [&](auto MT) {
+            auto kfn = k_lm_head<T, decltype(MT)::value, decltype(RULES)::value, decltype(LP)::value, decltype(REP)::value>;
+            set_max_smem(kfn, sm);
+            hipLaunchKernelGGL(kfn, grid, dim3(256), sm, s, a);
+        });
+    }, a.ts_logits != nullptr, a.part_sum != nullptr, a.rep_bits != nullptr);
 }
 void wh_launch_lm_head(hipStream_t s, int prec, const SkinnyArgs& a) {
     if (prec == WH_PREC_F32) launch_lm_head_v<float>(s, a);
@@ -1843,42 +1823,25 @@ void wh_launch_lm_head(hipStream_t s, int prec, const SkinnyArgs& a) {
     else launch_lm_head_v<bf16>(s, a);
 }
 
-// number of argmax partials per row the LM head writes for this shape (its layout is [part][x_mpad])
+// number of argmax partials per row the LM head writes for this shape (its layout is [part][x_mpad]): k_lm_head's waves per row group
 int wh_lm_head_parts(int prec, const SkinnyArgs& a) {
-    int n = 0;
-    if (prec == WH_PREC_F16X3 && wh_lm_head_tile_x3_applicable(a)) n = wh_lm_head_tile_x3_parts(a);
-    else if (prec == WH_PREC_F32 || prec == WH_PREC_F16X3) launch_lm_head_t<float>(nullptr, a, &n);
-    else if (wh_lm_head_tile_applicable(a)) n = wh_lm_head_tile_parts(a);
-    else launch_lm_head_t<bf16>(nullptr, a, &n);
-    return n;
-}
-
-template <bool RULES, bool LP, bool PFX, bool REP>
-void launch_argmax_finish_p(hipStream_t s, int prec, const float* part_val, const int* part_idx, int n_parts, int mpad, int* pos_p,
-                            int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts, const float* part_sum, const RepFinish& rp) {
-    if (prec == WH_PREC_F16X3) hipLaunchKernelGGL((k_argmax_finish<h2, RULES, LP, PFX, REP>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum, rp);
-    else if (prec == WH_PREC_F32) hipLaunchKernelGGL((k_argmax_finish<float, RULES, LP, PFX, REP>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum, rp);
-    else hipLaunchKernelGGL((k_argmax_finish<bf16, RULES, LP, PFX, REP>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum, rp);
-}
-
-template <bool RULES, bool LP>
-void launch_argmax_finish_t(hipStream_t s, int prec, const float* part_val, const int* part_idx, int n_parts, int mpad, int* pos_p,
-                            int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts, const float* part_sum, const RepFinish& rp) {
-    const bool pfx = ne.tok_emb && ne.off;
-    if (rp.on) {   // the repetition variants
-        if (pfx) launch_argmax_finish_p<RULES, LP, true, true>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum, rp);
-        else launch_argmax_finish_p<RULES, LP, false, true>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum, rp);
-    }
-    else if (pfx) launch_argmax_finish_p<RULES, LP, true, false>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum, rp);
-    else launch_argmax_finish_p<RULES, LP, false, false>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum, rp);
+    int mt;
+    size_t sm;
+    if (prec == WH_PREC_F16X3 && wh_lm_head_tile_x3_applicable(a)) return wh_lm_head_tile_x3_parts(a);
+    if (prec == WH_PREC_F32 || prec == WH_PREC_F16X3) return (int)lm_head_geometry<float>(a, &mt, &sm).x * 4;
+    if (wh_lm_head_tile_applicable(a)) return wh_lm_head_tile_parts(a);
+    return (int)lm_head_geometry<bf16>(a, &mt, &sm).x * 4;
 }
 
 void wh_launch_argmax_finish(hipStream_t s, int prec, const float* part_val, const int* part_idx, int n_parts, int mpad, int* pos_p,
                              int* ticket, const DecodeState& st, int B, const NextEmbed& ne, const TsFinish& ts, const float* part_sum, const RepFinish& rp) {
-    if (ts.rules && part_sum) launch_argmax_finish_t<true, true>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum, rp);
-    else if (ts.rules) launch_argmax_finish_t<true, false>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum, rp);
-    else if (part_sum) launch_argmax_finish_t<false, true>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum, rp);
-    else launch_argmax_finish_t<false, false>(s, prec, part_val, part_idx, n_parts, mpad, pos_p, ticket, st, B, ne, ts, part_sum, rp);
+    wh_with_dtype(prec, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        wh_with_flags([&](auto RULES, auto LP, auto PFX, auto REP) {   // REP: the repetition variants
+            hipLaunchKernelGGL((k_argmax_finish<T, decltype(RULES)::value, decltype(LP)::value, decltype(PFX)::value, decltype(REP)::value>), dim3(B), dim3(256), 0, s,
+                               part_val, part_idx, n_parts, mpad, pos_p, ticket, st, ne, ts, part_sum, rp);
+        }, ts.rules, part_sum != nullptr, ne.tok_emb && ne.off, rp.on);
+    });
 }
 
 void wh_launch_nospeech_finish(hipStream_t s, const float* part_val, const float* part_sum, int n_parts, int mpad, const float* probe_v,
@@ -1888,32 +1851,22 @@ void wh_launch_nospeech_finish(hipStream_t s, const float* part_val, const float
 
 template <typename T>
 static void launch_lang_head_t(hipStream_t s, const LangHeadArgs& a) {
-    // row groups as launch_lm_head_t forms them (the pitch of the slab covers whole groups)
+    // row groups as lm_head_geometry forms them (the pitch of the slab covers whole groups)
     int mt = std::min(wh_dbg_lm_mt, (a.M + 15) / 16);
     auto lds = [&](int t) { return (size_t)t * 16 * a.K * sizeof(T) + (size_t)t * 16 * 2 * 4 * 5; };
     while (mt > 1 && lds(mt) > 150 * 1024) mt--;
     if (mt > 4) mt = 4;
     const size_t sm = lds(mt);
     dim3 grid(((a.n_lang + 15) / 16 + 3) / 4, (a.M + 16 * mt - 1) / (16 * mt));
-#define WH_LH(MT_)                                          \
-    {                                                       \
-        auto kfn = k_lang_head<T, MT_>;                     \
-        set_max_smem(kfn, sm);                              \
-        hipLaunchKernelGGL(kfn, grid, dim3(256), sm, s, a); \
-    }
-    switch (mt) {
-        case 1: WH_LH(1) break;
-        case 2: WH_LH(2) break;
-        case 3: WH_LH(3) break;
-        default: WH_LH(4) break;
-    }
-#undef WH_LH
+    wh_with_1to4(mt, [&](auto MT) {
+        auto kfn = k_lang_head<T, decltype(MT)::value>;
+        set_max_smem(kfn, sm);
+        hipLaunchKernelGGL(kfn, grid, dim3(256), sm, s, a);
+    });
 }
 
 void wh_launch_lang_head(hipStream_t s, int prec, const LangHeadArgs& a) {
-    if (prec == WH_PREC_F32) launch_lang_head_t<float>(s, a);
-    else if (prec == WH_PREC_F16X3) launch_lang_head_t<h2>(s, a);
-    else launch_lang_head_t<bf16>(s, a);   // (fp8 mode: the embedding is bf16)
+    wh_with_dtype(prec, [&](auto tag) { launch_lang_head_t<typename decltype(tag)::type>(s, a); });   // (fp8 mode: the embedding is bf16)
 }
 
 void wh_launch_lang_finish(hipStream_t s, const float* logits, const int* ids, int n_lang, int src_row, float* probs, int* chosen, int* feed,
@@ -1921,22 +1874,18 @@ void wh_launch_lang_finish(hipStream_t s, const float* logits, const int* ids, i
     hipLaunchKernelGGL(k_lang_finish, dim3(B), dim3(64), 0, s, logits, ids, n_lang, src_row, probs, chosen, feed, out_tokens, tok_ld, tok_pos, pos_p);
 }
 
-template <bool PFX>
-void launch_dec_self_attn_t(hipStream_t s, int prec, const void* qkv, void* kc, void* vc, void* out, const int* pos_p,
-                            int d, int n_heads, int tc, int B, int mpad, const int* off) {
-    dim3 grid(n_heads, B);
-    if (prec == WH_PREC_F16X3)   // f32 q/k/v and caches (no matrix-core work here), the output as the out-projection's fp16-limb operand
-        hipLaunchKernelGGL((k_dec_self_attn<float, h2, PFX>), grid, dim3(64), 0, s, (const float*)qkv, (float*)kc, (float*)vc, (h2*)out, pos_p, d, n_heads, tc, mpad, off);
-    else if (prec == WH_PREC_F32)
-        hipLaunchKernelGGL((k_dec_self_attn<float, float, PFX>), grid, dim3(64), 0, s, (const float*)qkv, (float*)kc, (float*)vc, (float*)out, pos_p, d, n_heads, tc, mpad, off);
-    else
-        hipLaunchKernelGGL((k_dec_self_attn<bf16, bf16, PFX>), grid, dim3(64), 0, s, (const bf16*)qkv, (bf16*)kc, (bf16*)vc, (bf16*)out, pos_p, d, n_heads, tc, mpad, off);
-}
-
 void wh_launch_dec_self_attn(hipStream_t s, int prec, const void* qkv, void* kc, void* vc, void* out, const int* pos_p,
                              int d, int n_heads, int tc, int B, int mpad, const int* off) {
-    if (off) launch_dec_self_attn_t<true>(s, prec, qkv, kc, vc, out, pos_p, d, n_heads, tc, B, mpad, off);
-    else launch_dec_self_attn_t<false>(s, prec, qkv, kc, vc, out, pos_p, d, n_heads, tc, B, mpad, off);
+    dim3 grid(n_heads, B);
+    wh_with_flags([&](auto pfx) {
+        constexpr bool PFX = decltype(pfx)::value;
+        if (prec == WH_PREC_F16X3)   // f32 q/k/v and caches (no matrix-core work here), the output as the out-projection's fp16-limb operand
+            hipLaunchKernelGGL((k_dec_self_attn<float, h2, PFX>), grid, dim3(64), 0, s, (const float*)qkv, (float*)kc, (float*)vc, (h2*)out, pos_p, d, n_heads, tc, mpad, off);
+        else if (prec == WH_PREC_F32)
+            hipLaunchKernelGGL((k_dec_self_attn<float, float, PFX>), grid, dim3(64), 0, s, (const float*)qkv, (float*)kc, (float*)vc, (float*)out, pos_p, d, n_heads, tc, mpad, off);
+        else
+            hipLaunchKernelGGL((k_dec_self_attn<bf16, bf16, PFX>), grid, dim3(64), 0, s, (const bf16*)qkv, (bf16*)kc, (bf16*)vc, (bf16*)out, pos_p, d, n_heads, tc, mpad, off);
+    }, off != nullptr);
 }
 
 // Occupancy cap of the cross-attention stream.  With more than two workgroups resident per CU (1024 clips = 4 per CU) every one

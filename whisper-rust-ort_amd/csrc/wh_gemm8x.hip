@@ -567,21 +567,10 @@ void wh_launch_lm_head_tile_x3(hipStream_t s, const SkinnyArgs& a) {
     const size_t sm = (size_t)NSLOT * SLOT + (size_t)BM * 2 * 4 * 5 + ((a.ts_logits || a.rep_bits) ? (size_t)BM * 16 : 0) +
                       (a.rep_bits ? (size_t)BM * 32 : 0);   // ring + LayerNorm statistics ([256][2] + four quarter sums) + RULES: the rows' ranges ([256][4]) + REP: the rows' touched bits ([256][8], behind the ranges' place)
     dim3 grid(((a.N + BN - 1) / BN) * ((a.M + BM - 1) / BM));
-#define WH_LM_TILE(R_, L_, P_)                                                         \
-    {                                                                                  \
-        wh_ensure_dyn_lds((const void*)k_lm_head_tile_x3<R_, L_, P_>, sm);               \
-        hipLaunchKernelGGL((k_lm_head_tile_x3<R_, L_, P_>), grid, dim3(512), sm, s, a);  \
-    }
     // a.ts_logits: the timestamp-rules variants; a.part_sum: the log-probability variants; a.rep_bits: the repetition variants
-    if (a.rep_bits) {
-        if (a.ts_logits && a.part_sum) WH_LM_TILE(true, true, true)
-        else if (a.ts_logits) WH_LM_TILE(true, false, true)
-        else if (a.part_sum) WH_LM_TILE(false, true, true)
-        else WH_LM_TILE(false, false, true)
-    }
-    else if (a.ts_logits && a.part_sum) WH_LM_TILE(true, true, false)
-    else if (a.ts_logits) WH_LM_TILE(true, false, false)
-    else if (a.part_sum) WH_LM_TILE(false, true, false)
-    else WH_LM_TILE(false, false, false)
-#undef WH_LM_TILE
+    wh_with_flags([&](auto RULES, auto LP, auto REP) {
+        auto kfn = k_lm_head_tile_x3<decltype(RULES)::value, decltype(LP)::value, decltype(REP)::value>;
+        wh_ensure_dyn_lds((const void*)kfn, sm);
+        hipLaunchKernelGGL(kfn, grid, dim3(512), sm, s, a);
+    }, a.ts_logits != nullptr, a.part_sum != nullptr, a.rep_bits != nullptr);
 }

@@ -4,6 +4,7 @@
 
 #include <map>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/whisper_hip.h"
@@ -197,24 +198,25 @@ struct wh_ctx {
     int cross_splits = 1;
     // the decode GEMMs as LDS-DMA tile GEMMs (wh_dec_tile.hip): decided at creation from the model and the context's capacity
     bool dec_tile = false;
-    // The captured decode step, kept across calls: every kernel argument the step bakes in is either a fixed workspace
-    // address or one of the values below, so a call with the same key replays the instantiated graph as it is.
-    // Destroyed in wh_ctx_free (after the stream has drained) or when the key changes.
+    // The decode step's key: every call-dependent value an emitting decoder position bakes into kernel arguments.  launch_step (wh_api.cpp)
+    // sees the context and this struct and nothing else of the call, so a value that is not listed here cannot reach the captured step; the
+    // context supplies only fixed workspace addresses and the option buffers.  A call with the same key replays the instantiated graph as it
+    // is; the graph is destroyed in wh_ctx_free (after the stream has drained) or when the key changes.
+    // The rule for the option buffers: a setter that frees or reallocates a buffer the step holds calls drop_step_graph first.
+    // What follows from the members needs no entry of its own: 1 / rep_p, the repetition exemption from ts_begin (and ts_ld = vocab -
+    // ts_begin), the non-temporal cross-K/V loads and the cache strides from nb, the LM head's partial count from the shape.
     struct StepKey {
         int nb = 0, n_prompt = 0, eot = 0, n_forced = 0, logits_rows = 0;
-        const float* d_logits = nullptr;
+        float* d_logits = nullptr;
         const int* d_sel = nullptr;
-        int ts_begin = -1, ts_max_init = -1;   // timestamp rules: -1 = off (other kernels, other arguments)
-        const float* lp_sum = nullptr;         // token log-probabilities: nullptr = off (other kernels, other arguments)
+        int ts_begin = -1, ts_max_init = -1;   // timestamp rules: ts_begin -1 = off (other kernels, other arguments)
+        float* lp_sum = nullptr;               // token log-probabilities: nullptr = off (other kernels, other arguments)
         bool pfx = false;                      // per-clip prefixes with a non-empty one in the batch: the prefix-aware kernels
         bool rep = false;                      // repetition penalty / no-repeat n-grams: other kernels, other arguments
         float rep_p = 1.0f;
         int rep_n = 0;
-        bool operator==(const StepKey& o) const {
-            return nb == o.nb && n_prompt == o.n_prompt && eot == o.eot && n_forced == o.n_forced && logits_rows == o.logits_rows &&
-                   d_logits == o.d_logits && d_sel == o.d_sel && ts_begin == o.ts_begin && ts_max_init == o.ts_max_init && lp_sum == o.lp_sum && pfx == o.pfx &&
-                   rep == o.rep && rep_p == o.rep_p && rep_n == o.rep_n;
-        }
+        auto members() const { return std::tie(nb, n_prompt, eot, n_forced, logits_rows, d_logits, d_sel, ts_begin, ts_max_init, lp_sum, pfx, rep, rep_p, rep_n); }
+        bool operator==(const StepKey& o) const { return members() == o.members(); }
     } step_key;
     // Whisper's timestamp rules (wh_ctx_set_timestamp_rules): off unless ts_on.  The timestamp logits and the per-row state
     // are allocated when rules are set (not part of the workspace carve; the logits again when timestamp_begin changes) and freed in wh_ctx_free.
@@ -242,7 +244,7 @@ struct wh_ctx {
     std::vector<float> lp_ns_rows;
     // Language detection (wh_ctx_set_language_detection): off unless lang_on.  One allocation made by the setter (not part of the
     // workspace carve), freed in wh_ctx_free: the id list, the listed ids' logits, the probabilities and the chosen ids.  Lives in the eagerly
-    // launched prompt positions only: the captured step and its key know nothing of it.
+    // launched prompt positions only (launch_step's PromptStep): the captured step and its key know nothing of it.
     bool lang_on = false;
     int lang_sot_index = 0;
     std::vector<int64_t> lang_ids;  // the caller's list, in the caller's order
@@ -261,7 +263,7 @@ struct wh_ctx {
     std::vector<int64_t> lang_rows;
     std::vector<float> lang_prob_rows;   // [clips][lang_have_n]
     // Per-clip prompt prefixes (wh_ctx_set_prefixes): off unless pfx_on.  pfx_off is allocated by the first setter call (not part
-    // of the workspace carve) and freed in wh_ctx_free; run_decode fills it per call.  A call whose rows all have empty prefixes passes no
+    // of the workspace carve) and freed in wh_ctx_free; upload_token_state fills it per call.  A call whose rows all have empty prefixes passes no
     // offsets to the kernels and launches what a context without prefixes launches.
     bool pfx_on = false;
     std::vector<int64_t> pfx_ids;      // the clips' prefixes back to back (the setter's copy)
@@ -270,10 +272,10 @@ struct wh_ctx {
     int* pfx_off = nullptr;            // [max_batch] device: first live global position of each row (Nmax - n_b)
     long pfx_win_base = -1;            // long-form: index of the device batch's first window (row b is window pfx_win_base + b); -1: rows are clips
     // Repetition penalty / no-repeat n-grams (wh_ctx_set_repetition): off unless rep_on.  The bitmap and the side buffer are
-    // allocated by the setter (not part of the workspace carve) and freed when the option is cleared and in wh_ctx_free; run_decode clears the
-    // bitmap at the start of a call.
+    // allocated by the setter (not part of the workspace carve) and freed when the option is cleared and in wh_ctx_free; upload_token_state clears
+    // the bitmap at the start of a call.
     bool rep_on = false;
-    float rep_p = 1.0f, rep_inv = 1.0f;
+    float rep_p = 1.0f;
     int rep_n = 0;
     int rep_words = 0;                 // ceil(vocab / 32)
     unsigned* rep_bits = nullptr;      // [max_batch][rep_words] touched ids of each row's current position
