@@ -247,6 +247,24 @@ __device__ __forceinline__ float xrow_sum(float v) {
     t = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     return __uint_as_float(t.x) + __uint_as_float(t.y);
 }
+// (value, index) argmax the same way: every lane ends with the largest value of its four rows and that value's index, the lowest
+// index on ties (the LM heads' reduction over the four lane groups that share a row of the MFMA result)
+__device__ __forceinline__ void xrow_argmax(float& bv, int& bi) {
+    wh_u32x2 tv = __builtin_amdgcn_permlane16_swap(__float_as_uint(bv), __float_as_uint(bv), false, false);
+    wh_u32x2 ti = __builtin_amdgcn_permlane16_swap((unsigned)bi, (unsigned)bi, false, false);
+    float v0 = __uint_as_float(tv.x), v1 = __uint_as_float(tv.y);
+    int i0 = (int)ti.x, i1 = (int)ti.y;
+    bool take1 = v1 > v0 || (v1 == v0 && i1 < i0);
+    bv = take1 ? v1 : v0;
+    bi = take1 ? i1 : i0;
+    tv = __builtin_amdgcn_permlane32_swap(__float_as_uint(bv), __float_as_uint(bv), false, false);
+    ti = __builtin_amdgcn_permlane32_swap((unsigned)bi, (unsigned)bi, false, false);
+    v0 = __uint_as_float(tv.x); v1 = __uint_as_float(tv.y);
+    i0 = (int)ti.x; i1 = (int)ti.y;
+    take1 = v1 > v0 || (v1 == v0 && i1 < i0);
+    bv = take1 ? v1 : v0;
+    bi = take1 ? i1 : i0;
+}
 
 typedef __attribute__((ext_vector_type(4))) unsigned wh_u32x4;
 // NOTE: hipcc (ROCm 7.2) miscompiles __builtin_bit_cast(bf16x2, <element of a uint vector>) — every

@@ -759,20 +759,7 @@ __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
     for (int t = 0; t < MT; t++) {
         float bv = bvw[t];
         int bi = biw[t];
-        wh_u32x2 tv = __builtin_amdgcn_permlane16_swap(__float_as_uint(bv), __float_as_uint(bv), false, false);
-        wh_u32x2 ti = __builtin_amdgcn_permlane16_swap((unsigned)bi, (unsigned)bi, false, false);
-        float v0 = __uint_as_float(tv.x), v1 = __uint_as_float(tv.y);
-        int i0 = (int)ti.x, i1 = (int)ti.y;
-        bool take1 = v1 > v0 || (v1 == v0 && i1 < i0);
-        bv = take1 ? v1 : v0;
-        bi = take1 ? i1 : i0;
-        tv = __builtin_amdgcn_permlane32_swap(__float_as_uint(bv), __float_as_uint(bv), false, false);
-        ti = __builtin_amdgcn_permlane32_swap((unsigned)bi, (unsigned)bi, false, false);
-        v0 = __uint_as_float(tv.x); v1 = __uint_as_float(tv.y);
-        i0 = (int)ti.x; i1 = (int)ti.y;
-        take1 = v1 > v0 || (v1 == v0 && i1 < i0);
-        bv = take1 ? v1 : v0;
-        bi = take1 ? i1 : i0;
+        xrow_argmax(bv, bi);
         const int m = m0 + t * 16 + fl;
         if constexpr (LP) {   // this lane's sum moved to the row's maximum, then the four lane groups' sums added
             const float ls = lp_row_sum(lp_rescale(lsw[t], bvw[t], bv));

@@ -37,6 +37,7 @@
 
 #include "wh_common.h"
 #include "wh_kernels.h"
+#include "wh_lm_tile.h"
 
 namespace {
 
@@ -424,10 +425,14 @@ __global__ __launch_bounds__(512, Geo<BN>::WAVES_PER_SIMD) void k_gemm8(GemmArgs
 // SkinnyArgs::rep_bits enters no partial and no sum, its raw logit goes to SkinnyArgs::rep_side; m < M, nn < N keep both inside row m's slice).
 // The tile's 256 rows x 8 bitmap words are staged in LDS after the main loop (one global load round per workgroup), so a row costs one 8-byte
 // LDS read.
+// This file has the kernel's ring and main loop; what surrounds them (the LDS behind the ring, the LayerNorm statistics, the rules' and the
+// bitmap's staging, the whole epilogue and the launcher) is WhLmTile, wh_lm_tile.h, shared with k_lm_head_tile_x3 (wh_gemm8x.hip).
+typedef WhLmTile<BM, Geo<256>::TM, Geo<256>::TN, Geo<256>::WN, Geo<256>::NSLOT * Geo<256>::SLOT> LmTile8;
+
 template <bool RULES = false, bool LP = false, bool REP = false>
 __global__ __launch_bounds__(512, 2) void k_lm_head_tile(SkinnyArgs a) {
     typedef Geo<256> G;
-    constexpr int BN = 256, TM = G::TM, TN = G::TN, NSLOT = G::NSLOT, SLOT = G::SLOT, SLOT_A = G::SLOT_A;
+    constexpr int BN = LmTile8::BN, TM = G::TM, TN = G::TN, NSLOT = G::NSLOT, SLOT = G::SLOT, SLOT_A = G::SLOT_A;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -443,31 +448,8 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile(SkinnyArgs a) {
     }
     const int ct = tile % nbn, m0 = (tile / nbn) * BM, n0 = ct * BN;
 
-    // final LayerNorm: quarter sums of the producer's per-tile partials, two quarters per thread (row tid & 255) — requested
-    // before the ring, so they are the oldest vector-memory requests
-    float* lnstat = reinterpret_cast<float*>(smem + (size_t)NSLOT * SLOT);   // [256][2] mean, rstd
-    float* lnq = lnstat + 2 * BM;                                            // [4][256][2]
-    int* tsr = reinterpret_cast<int*>(lnq + 4 * BM * 2);                     // RULES: [256][4] the rows' allowed ranges (written after the main loop)
-    unsigned* rbw = reinterpret_cast<unsigned*>(tsr + 4 * BM);               // REP: [256][8] the rows' touched bits of this tile's 256 columns (written after the main loop)
-    if (a.ln_part) {
-        const int r = tid & (BM - 1), h = tid >> 8, row = min(m0 + r, a.x_mpad - 1);
-        float s1a, s2a, s1b, s2b;
-        ln_partial_sum(a.ln_part, a.ln_tiles, a.x_mpad, row, h, 4, s1a, s2a);
-        ln_partial_sum(a.ln_part, a.ln_tiles, a.x_mpad, row, h + 2, 4, s1b, s2b);
-        lnq[(h * BM + r) * 2] = s1a;
-        lnq[(h * BM + r) * 2 + 1] = s2a;
-        lnq[((h + 2) * BM + r) * 2] = s1b;
-        lnq[((h + 2) * BM + r) * 2 + 1] = s2b;
-    }
-    // RULES: the rows' state, requested behind the LayerNorm partials without waiting on the position (gen 0 ignores it); it turns into
-    // the allowed ranges in LDS after the main loop, so the epilogue reads them from LDS instead of eight dependent global loads
-    int ts_raw[3] = {0, 0, 0};
-    if constexpr (RULES) {
-        if (tid < BM) {
-            const int* r = a.ts_state + 4 * min(m0 + tid, a.M - 1);
-            ts_raw[0] = r[0]; ts_raw[1] = r[1]; ts_raw[2] = r[2];
-        }
-    }
+    const auto lds = LmTile8::carve(smem);
+    const auto ts_raw = LmTile8::prologue<RULES>(a, lds, m0, tid);   // LayerNorm quarter sums (the oldest vector-memory requests), the rules' row state
 
     const int rl = lane >> 2, ps = lane & 3;
     const bf16* a_src[2];
@@ -522,14 +504,7 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile(SkinnyArgs a) {
     wait_stage(0, NSLOT - 1);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's quarter sums have left for LDS
     __builtin_amdgcn_s_barrier();          // stage 0 visible; the LayerNorm quarter sums are in LDS
-    if (a.ln_part && tid < BM) {
-        const float s1 = (lnq[tid * 2] + lnq[(BM + tid) * 2]) + (lnq[(2 * BM + tid) * 2] + lnq[(3 * BM + tid) * 2]);
-        const float s2 = (lnq[tid * 2 + 1] + lnq[(BM + tid) * 2 + 1]) + (lnq[(2 * BM + tid) * 2 + 1] + lnq[(3 * BM + tid) * 2 + 1]);
-        float mean, rstd;
-        wh_ln_mean_rstd(s1, s2, (float)a.K, false, mean, rstd);
-        lnstat[2 * tid] = mean;
-        lnstat[2 * tid + 1] = rstd;
-    }
+    LmTile8::ln_reduce(a, lds, tid);
     read_frags(0, 0);
     for (int kt = 0; kt < nk; kt += 2) {
 #pragma unroll
@@ -549,184 +524,9 @@ __global__ __launch_bounds__(512, 2) void k_lm_head_tile(SkinnyArgs a) {
             }
         }
     }
-    if constexpr (RULES) {
-        if (tid < BM) {
-            int lo = ts_raw[0], slo = ts_raw[1], shi = ts_raw[2];
-            const int gen0 = *a.pos_p - (a.n_prompt - 1);
-            if (gen0 == 0) ts_ranges(nullptr, 0, 0, a.ts_begin, a.ts_max_init, a.N, lo, slo, shi);   // rule 4
-            tsr[4 * tid] = lo; tsr[4 * tid + 1] = slo; tsr[4 * tid + 2] = shi;
-        }
-    }
-    if constexpr (REP) {
-        if (tid < BM) {   // row m0 + tid's words n0 / 32 .. + 7 (n0 is a multiple of 256: word-aligned); past the row's last word: 0
-            const unsigned* src = a.rep_bits + (long)min(m0 + tid, a.M - 1) * a.rep_words;
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const int w = (n0 >> 5) + k;
-                rbw[tid * 8 + k] = w < a.rep_words ? src[w] : 0u;
-            }
-        }
-    }
+    LmTile8::stage_rows<RULES, REP>(a, lds, ts_raw, m0, n0, tid);
     __syncthreads();   // lnstat written by the first 256 threads is visible to everyone (and every MFMA has its operands)
-
-    // ---- epilogue: final LayerNorm fold + masked argmax, one partial per (wave, row) ------------------------------------
-    const int pos = *a.pos_p;
-    const int gen = pos - (a.n_prompt - 1);  // index of the token this row generates
-    const unsigned* mask = (gen == 0) ? a.mask_first : a.mask_base;
-    const int nw0 = n0 + wn * 64;
-    float sv[TN][4], cv[TN][4];
-    unsigned mbits[TN];
-#pragma unroll
-    for (int j = 0; j < TN; j++) {
-        const int n = nw0 + j * 16 + 4 * fg;
-#pragma unroll
-        for (int e = 0; e < 4; e++) { sv[j][e] = 0.0f; cv[j][e] = 0.0f; }
-        if (a.ln_part) {
-#pragma unroll
-            for (int e = 0; e < 4; e++)
-                if (n + e < a.N) { sv[j][e] = a.ln_s[n + e]; cv[j][e] = a.bias[n + e]; }
-        }
-        mbits[j] = 0;
-        if (n < a.N) mbits[j] = mask[n >> 5] >> (n & 31);   // suppress bits of this lane's 4 columns
-    }
-    float* red_v = reinterpret_cast<float*>(smem);            // [4][256] — every wave is past the last barrier of the main loop
-    int* red_i = reinterpret_cast<int*>(smem) + G::WN * BM;
-    float* red_s = reinterpret_cast<float*>(smem) + 2 * G::WN * BM;   // LP: [4][256] sum of exp(v - red_v)
-    if constexpr (REP) {
-        // A lane with a touched id among its 16 columns of a row (rare: a row has at most one per history token) sends the raw logits of those
-        // ids (the same expression) to the row's side buffer and replaces their accumulators by NaN, which enters no argmax, no sum of exp and
-        // no log-probability pass: the loops below are the REP = false ones.  (With the touched bits as a second, row-dependent suppress mask
-        // inside them the rules variants spilled; inside their row loop this pass took the loop past the unroller's size limit and the
-        // accumulators went to scratch.)  With the rules on a touched id is never a timestamp, so the timestamp logits are not concerned.
-#pragma unroll
-        for (int i = 0; i < TM; i++) {
-            const int rloc = wm * (TM * 16) + i * 16 + fl, m = m0 + rloc;
-            const wh_u32x2 rw = *reinterpret_cast<const wh_u32x2*>(rbw + rloc * 8 + wn * 2);   // the two bitmap words of this wave's 64 columns of row m
-            if ((((rw.x | rw.y) >> (4 * fg)) & 0x000f000fu) != 0u && m < a.M) {
-                const float mean = a.ln_part ? lnstat[2 * rloc] : 0.0f, rstd = a.ln_part ? lnstat[2 * rloc + 1] : 1.0f;
-                int nf = nw0 + 4 * fg;   // (through an empty asm per row: the column tests are not hoisted out of the row loop as live lane masks, cf. lp_tile_row)
-                asm volatile("" : "+v"(nf));
-#pragma unroll
-                for (int j = 0; j < TN; j++) {
-                    const unsigned rb = ((j < 2) ? rw.x : rw.y) >> ((j & 1) * 16 + 4 * fg);
-#pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        const int nn = nf + j * 16 + e;
-                        const bool t = ((rb >> e) & 1u) && nn < a.N;
-                        if (t) a.rep_side[(long)m * a.N + nn] = a.ln_part ? wh_ln_fold(acc[i][j][e], mean, rstd, sv[j][e], cv[j][e]) : acc[i][j][e];
-                        acc[i][j][e] = t ? __builtin_nanf("") : acc[i][j][e];
-                    }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < TM; i++) {
-        const int rloc = wm * (TM * 16) + i * 16 + fl, m = m0 + rloc;
-        const float mean = a.ln_part ? lnstat[2 * rloc] : 0.0f, rstd = a.ln_part ? lnstat[2 * rloc + 1] : 1.0f;
-        float bv = -INFINITY;
-        int bi = 0x7fffffff;
-        int tlo = a.ts_begin, slo = a.N, shi = 0;
-        if constexpr (RULES) {
-            if (m < a.M) { tlo = tsr[4 * rloc]; slo = tsr[4 * rloc + 1]; shi = tsr[4 * rloc + 2]; }
-        }
-#pragma unroll
-        for (int j = 0; j < TN; j++) {
-            const int n = nw0 + j * 16 + 4 * fg;
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const int nn = n + e;
-                const float v = a.ln_part ? wh_ln_fold(acc[i][j][e], mean, rstd, sv[j][e], cv[j][e]) : acc[i][j][e];
-                if (nn < a.N && m < a.M) {
-                    if (a.logits && gen >= 0 && gen < a.logits_rows) {
-                        const int slot = a.logits_sel ? a.logits_sel[m] : m;
-                        if (slot >= 0) a.logits[((long)slot * a.logits_rows + gen) * a.N + nn] = v;
-                    }
-                    const bool sup = (mbits[j] >> e) & 1u;
-                    if constexpr (RULES) {
-                        if (nw0 + j * 16 + 16 <= a.ts_begin) { if (!sup && nn >= tlo && v > bv) { bv = v; bi = nn; } }   // text-only column group
-                        else ts_take(v, nn, sup, a.ts_begin, tlo, slo, shi, bv, bi, a.ts_logits + (long)m * a.ts_ld);
-                    } else if (!sup && v > bv) { bv = v; bi = nn; }  // strict >, columns ascending: lowest index on ties, NaN never wins
-                }
-            }
-        }
-        // argmax over the four lane groups of the row (k_lm_head's reduction)
-        wh_u32x2 tv = __builtin_amdgcn_permlane16_swap(__float_as_uint(bv), __float_as_uint(bv), false, false);
-        wh_u32x2 ti = __builtin_amdgcn_permlane16_swap((unsigned)bi, (unsigned)bi, false, false);
-        float v0 = __uint_as_float(tv.x), v1 = __uint_as_float(tv.y);
-        int i0 = (int)ti.x, i1 = (int)ti.y;
-        bool take1 = v1 > v0 || (v1 == v0 && i1 < i0);
-        bv = take1 ? v1 : v0;
-        bi = take1 ? i1 : i0;
-        tv = __builtin_amdgcn_permlane32_swap(__float_as_uint(bv), __float_as_uint(bv), false, false);
-        ti = __builtin_amdgcn_permlane32_swap((unsigned)bi, (unsigned)bi, false, false);
-        v0 = __uint_as_float(tv.x); v1 = __uint_as_float(tv.y);
-        i0 = (int)ti.x; i1 = (int)ti.y;
-        take1 = v1 > v0 || (v1 == v0 && i1 < i0);
-        bv = take1 ? v1 : v0;
-        bi = take1 ? i1 : i0;
-        if (fg == 0) {   // this wave's (max, index) of row rloc: the four waves that share the row meet in LDS (the ring is idle now)
-            red_v[wn * BM + rloc] = bv;
-            red_i[wn * BM + rloc] = bi;
-        }
-    }
-    if constexpr (REP) {
-        // parity path: the logits rows keep the raw values (the loop above stored NaN for the touched ids); no accumulator is read, so the
-        // row loop stays rolled
-        if (a.logits && gen >= 0 && gen < a.logits_rows) {
-#pragma unroll 1
-            for (int i = 0; i < TM; i++) {
-                const int rloc = wm * (TM * 16) + i * 16 + fl, m = m0 + rloc;
-                const wh_u32x2 rw = *reinterpret_cast<const wh_u32x2*>(rbw + rloc * 8 + wn * 2);
-                if ((((rw.x | rw.y) >> (4 * fg)) & 0x000f000fu) == 0u || m >= a.M) continue;
-                const int slot = a.logits_sel ? a.logits_sel[m] : m;
-                if (slot < 0) continue;
-                for (int c = 0; c < 16; c++) {
-                    const int j = c >> 2, e = c & 3, nn = nw0 + j * 16 + 4 * fg + e;
-                    const unsigned rb = ((j < 2) ? rw.x : rw.y) >> ((j & 1) * 16 + 4 * fg);
-                    if (((rb >> e) & 1u) && nn < a.N) a.logits[((long)slot * a.logits_rows + gen) * a.N + nn] = a.rep_side[(long)m * a.N + nn];
-                }
-            }
-        }
-    }
-    if constexpr (LP) {
-        // The rows' maxima are known: a second pass over the accumulators adds exp(v - max) over the same ids.  A loop of its own (inside the
-        // loop above the two passes of neighbouring rows overlap and the rules variant spills); each row's maximum comes back from LDS, where
-        // this wave's own lanes put it (the rules variant has no probe: the probe runs rules-off).
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < TM; i++) {
-            const int rloc = wm * (TM * 16) + i * 16 + fl, m = m0 + rloc;
-            const float mean = a.ln_part ? lnstat[2 * rloc] : 0.0f, rstd = a.ln_part ? lnstat[2 * rloc + 1] : 1.0f;
-            const float bv = red_v[wn * BM + rloc];
-            int tlo = 0;
-            if constexpr (RULES) tlo = tsr[4 * rloc];
-            const float ls = lp_row_sum(lp_tile_row<TN, !RULES>(acc[i], a.ln_part != nullptr, mean, rstd, sv, cv, mbits, nw0 + 4 * fg, tlo,
-                                                                RULES ? min(a.ts_begin, a.N) : a.N, bv, m < a.M ? a.probe_id : -1, a.probe_out + m));
-            if (fg == 0) red_s[wn * BM + rloc] = ls;
-        }
-    }
-    __syncthreads();
-    // one partial per (column tile, row): 203 instead of 812 partials per row for k_argmax_finish to read (strided by the row pitch)
-    if (tid < BM && m0 + tid < a.M) {
-        float bv = red_v[tid];
-        int bi = red_i[tid];
-        float ls = LP ? red_s[tid] : 0.0f;
-#pragma unroll
-        for (int w = 1; w < G::WN; w++) {
-            const float v1 = red_v[w * BM + tid];
-            const int i1 = red_i[w * BM + tid];
-            if constexpr (LP) ls = lp_merge(bv, ls, v1, red_s[w * BM + tid]);
-            const bool take1 = v1 > bv || (v1 == bv && i1 < bi);
-            bv = take1 ? v1 : bv;
-            bi = take1 ? i1 : bi;
-        }
-        a.part_val[(long)ct * a.x_mpad + m0 + tid] = bv;
-        a.part_idx[(long)ct * a.x_mpad + m0 + tid] = bi;
-        if constexpr (LP) a.part_sum[(long)ct * a.x_mpad + m0 + tid] = ls;
-    }
+    LmTile8::epilogue<RULES, LP, REP>(a, acc, smem, lds, ct, m0, wm, wn, tid);
 }
 
 
@@ -769,24 +569,11 @@ __global__ __launch_bounds__(256) void k_ln_stats(const float* __restrict__ part
     if (shift) shift[r] = (shift_in ? shift_in[r] : 0.0f) + mean;   // offset the producer used + the mean measured on its shifted rows = the row's true mean
 }
 
-// LM head at hundreds of rows (bf16 operands): argmax partials per row = column tiles x 4 (layout [part][x_mpad])
-bool wh_lm_head_tile_applicable(const SkinnyArgs& a) {
-    const char* e = getenv("WH_LM_TILE_MIN_ROWS");   // (0 disables: A/B runs and the parity test flip it between contexts)
-    const int min_rows = e ? atoi(e) : 256;
-    return min_rows > 0 && a.M >= min_rows && (a.K % BK) == 0 && a.K / BK >= 4 && a.X != nullptr && a.xpart == nullptr && a.wscale == nullptr;
-}
-int wh_lm_head_tile_parts(const SkinnyArgs& a) { return (a.N + 255) / 256; }
+// LM head at hundreds of rows (bf16 operands): one argmax partial per (256-column tile, row) — layout [part][x_mpad]
+bool wh_lm_head_tile_applicable(const SkinnyArgs& a) { return LmTile8::applicable(a, BK) && a.K / BK >= 4; }   // (the ring is primed with four k-steps)
+int wh_lm_head_tile_parts(const SkinnyArgs& a) { return LmTile8::parts(a); }
 void wh_launch_lm_head_tile(hipStream_t s, const SkinnyArgs& a) {
-    typedef Geo<256> G;
-    const size_t sm = (size_t)G::NSLOT * G::SLOT + (size_t)BM * 2 * 4 * 5 + ((a.ts_logits || a.rep_bits) ? (size_t)BM * 16 : 0) +
-                      (a.rep_bits ? (size_t)BM * 32 : 0);   // ring + LayerNorm statistics ([256][2] + four quarter sums) + RULES: the rows' ranges ([256][4]) + REP: the rows' touched bits ([256][8], behind the ranges' place)
-    dim3 grid(((a.N + 255) / 256) * ((a.M + BM - 1) / BM));
-    // a.ts_logits: the timestamp-rules variants; a.part_sum: the log-probability variants; a.rep_bits: the repetition variants
-    wh_with_flags([&](auto RULES, auto LP, auto REP) {
-        auto kfn = k_lm_head_tile<decltype(RULES)::value, decltype(LP)::value, decltype(REP)::value>;
-        wh_ensure_dyn_lds((const void*)kfn, sm);
-        hipLaunchKernelGGL(kfn, grid, dim3(512), sm, s, a);
-    }, a.ts_logits != nullptr, a.part_sum != nullptr, a.rep_bits != nullptr);
+    LmTile8::launch(s, a, [](auto RULES, auto LP, auto REP) { return k_lm_head_tile<decltype(RULES)::value, decltype(LP)::value, decltype(REP)::value>; });
 }
 
 void wh_launch_ln_stats(hipStream_t s, const float* partials, int groups, long rows, int d, float* stat, float* shift, const float* shift_in) {
