@@ -291,6 +291,42 @@ typedef struct {
     int32_t no_repeat_ngram_size; /* 0 = off; 1 .. WH_MAX_NGRAM */
 } wh_repetition_opts;
 int wh_ctx_set_repetition(wh_ctx* c, const wh_repetition_opts* o);
+/* Word-level timestamps: the frame at which each generated token is spoken, from the cross-attention of a few "alignment heads" and a
+ * dynamic-time-warping path (openai-whisper's word_timestamps=True / find_alignment + dtw, faster-whisper's word_timestamps, HF
+ * return_timestamps="word").  No reference entry corresponds.  With this set, every decode entry of the ctx keeps, at every generated
+ * position, the listed heads' cross-attention queries, and after the token loop computes per clip:
+ *   - rows g = 0 .. n_gen - 1: the decoder positions that emitted the clip's generated tokens (EOT included if hit; prompt and prefix
+ *     positions are not rows; timestamp tokens are ordinary rows); frames S_b = min(n_audio_ctx, max(8, (mel frames of the clip + 1) / 2));
+ *   - P[a][g][s] = softmax over s < S_b of q_g . k_s per listed head a: the model's own cross-attention probabilities over the cropped frames;
+ *   - per head and frame the mean and population standard deviation over the n_gen rows, W = (P - mean) / std (0 where std == 0), a median
+ *     filter of width 7 along s with reflect padding, the mean over the heads: M[g][s], all in f32;
+ *   - openai-whisper's dtw on -M in f32 (ties go to the step along the frames), backtraced from (n_gen, S_b);
+ *   - frame[g] = the smallest frame on the path within row g; its time is frame[g] * 0.02 s from the window start.  n_gen == 1: frame[0] = 0.
+ * Unlike openai-whisper (a second decoder pass over the text tokens alone, statistics over the prompt rows too) the rows come from the
+ * generating pass and the statistics run over the generated rows only, as HF's token timestamps do.
+ * Tokens, logits and every other output are the same with this on or off.
+ * Refused with WH_ERR_ARG (the ctx unchanged): a wrong struct_size, n_heads outside 1 .. WH_MAX_ALIGN_HEADS, a layer or head outside the
+ * model, a pair listed twice, more than WH_MAX_ALIGN_DEBUG_ROWS debug rows (or a negative one).  At decode time, before anything is launched:
+ * a debug row outside the batch -> WH_ERR_ARG; a WH_PREC_FP8 or WH_PREC_F16X3 model -> WH_ERR_UNSUPPORTED.  o == NULL turns it off (the default). */
+#define WH_MAX_ALIGN_HEADS 32
+#define WH_MAX_ALIGN_DEBUG_ROWS 8
+typedef struct {
+    size_t struct_size;         /* sizeof(wh_alignment_opts) */
+    const int32_t* heads;       /* [n_heads][2] as (layer, head); copied by the setter */
+    size_t n_heads;             /* 1 .. WH_MAX_ALIGN_HEADS */
+    const int32_t* debug_rows;  /* parity harness only (NULL/0 in production): batch rows whose P and M are kept for wh_get_alignment_debug */
+    size_t n_debug_rows;        /* 0 .. WH_MAX_ALIGN_DEBUG_ROWS */
+} wh_alignment_opts;
+int wh_ctx_set_alignment(wh_ctx* c, const wh_alignment_opts* o);
+/* Of the last decode call on the ctx (any decode entry; every clip / window it returned tokens for, in that order): frames [n][cap_tokens],
+ * entry i of clip b = the frame of its generated token i, 0 past the clip's end (cap_tokens must hold the longest clip's generated tokens);
+ * n_frames [n] (may be NULL) = S_b.  frames == NULL: only *n_clips_out.  WH_ERR_STATE if the call ran with alignment off; WH_ERR_ARG if
+ * cap_clips < n. */
+int wh_get_token_frames(const wh_ctx* c, int32_t* frames, size_t cap_tokens, int32_t* n_frames, size_t cap_clips, size_t* n_clips_out);
+/* Parity harness: debug row k (position in the setter's debug_rows) of the last decode call (a long-form call: of its last device batch).
+ * shape3 = {n_heads, n_gen, S_b}; probs [n_heads][n_gen][S_b] and matrix [n_gen][S_b] (either may be NULL; cap_floats must hold probs).
+ * probs == NULL and matrix == NULL: only the shape.  WH_ERR_STATE if that call kept no debug rows; WH_ERR_ARG for k outside them. */
+int wh_get_alignment_debug(const wh_ctx* c, size_t k, float* probs, float* matrix, size_t cap_floats, int32_t* shape3);
 const char* wh_last_error(const wh_ctx* c); /* c == NULL: last load/create error of this thread */
 int wh_get_timings(const wh_ctx* c, wh_timing* out);
 

@@ -35,7 +35,8 @@ EXPORTS = ("wh_model_load", "wh_model_create", "wh_model_free", "wh_model_get_di
            "wh_transcribe_batch_next", "wh_transcribe_batch_device", "wh_transcribe_batch_device_next", "wh_longform_plan", "wh_transcribe_longform", "wh_profile_enable",
            "wh_profile_get", "wh_synthetic_weights", "wh_e4m3_quantize", "wh_e4m3_dequantize", "wh_abi_version",
            "wh_device_count", "wh_ctx_set_timestamp_rules", "wh_ctx_set_logprobs", "wh_get_logprobs",
-           "wh_ctx_set_language_detection", "wh_get_languages", "wh_ctx_set_prefixes", "wh_ctx_set_repetition")
+           "wh_ctx_set_language_detection", "wh_get_languages", "wh_ctx_set_prefixes", "wh_ctx_set_repetition",
+           "wh_ctx_set_alignment", "wh_get_token_frames", "wh_get_alignment_debug")
 
 
 class WhisperHipError(RuntimeError):
@@ -93,6 +94,15 @@ WH_MAX_NGRAM = 32
 
 class WhRepetitionOpts(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32)]
+
+
+WH_MAX_ALIGN_HEADS = 32
+WH_MAX_ALIGN_DEBUG_ROWS = 8
+
+
+class WhAlignmentOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("heads", C.POINTER(C.c_int32)), ("n_heads", C.c_size_t), ("debug_rows", C.POINTER(C.c_int32)),
+                ("n_debug_rows", C.c_size_t)]
 
 
 def pack_prefixes(prefixes: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.ndarray]:
@@ -180,6 +190,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.wh_get_languages.argtypes = [vp, i64p, f32p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.wh_ctx_set_prefixes.argtypes = [vp, C.POINTER(WhPrefixOpts)]
     L.wh_ctx_set_repetition.argtypes = [vp, C.POINTER(WhRepetitionOpts)]
+    L.wh_ctx_set_alignment.argtypes = [vp, C.POINTER(WhAlignmentOpts)]
+    L.wh_get_token_frames.argtypes = [vp, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_int32), C.c_size_t, szp]
+    L.wh_get_alignment_debug.argtypes = [vp, C.c_size_t, f32p, f32p, C.c_size_t, C.POINTER(C.c_int32)]
     _lib = L
     return L
 
@@ -389,6 +402,44 @@ class Context:
 
     def clear_repetition(self):
         self._check(self.lib.wh_ctx_set_repetition(self.h, None))
+
+    def set_alignment(self, heads: Sequence[Tuple[int, int]], debug_rows: Sequence[int] = ()):
+        """wh_ctx_set_alignment: every decode entry of this context computes the frame at which each generated token is spoken, from the
+        cross-attention of the listed (layer, head) pairs and a dynamic-time-warping path.  debug_rows (parity harness): batch rows whose
+        probabilities and alignment matrix are kept for alignment_debug()."""
+        h = np.ascontiguousarray(list(heads), np.int32).reshape(-1, 2) if len(heads) else np.zeros((0, 2), np.int32)
+        d = np.ascontiguousarray(list(debug_rows), np.int32)
+        i32p = C.POINTER(C.c_int32)
+        o = WhAlignmentOpts(C.sizeof(WhAlignmentOpts), h.ctypes.data_as(i32p) if h.size else None, h.shape[0], d.ctypes.data_as(i32p) if d.size else None, d.size)
+        self._check(self.lib.wh_ctx_set_alignment(self.h, C.byref(o)))
+
+    def clear_alignment(self):
+        self._check(self.lib.wh_ctx_set_alignment(self.h, None))
+
+    def token_frames(self) -> Tuple[List[np.ndarray], np.ndarray]:
+        """wh_get_token_frames of the last decode call: one int32 array per clip / window (the frame of each generated token, 0.02 s apart)
+        and the clips' frame counts S_b."""
+        n = C.c_size_t(0)
+        self._check(self.lib.wh_get_token_frames(self.h, None, 0, None, 0, C.byref(n)))
+        k = int(n.value)
+        lens = list(self._gen_lens)
+        assert len(lens) == k, (len(lens), k)
+        cap = max(1, max(lens, default=0))
+        fr = np.zeros((max(1, k), cap), np.int32)
+        nf = np.zeros(max(1, k), np.int32)
+        i32p = C.POINTER(C.c_int32)
+        self._check(self.lib.wh_get_token_frames(self.h, fr.ctypes.data_as(i32p), cap, nf.ctypes.data_as(i32p), k, C.byref(n)))
+        return [fr[i, : lens[i]].copy() for i in range(k)], nf[:k].copy()
+
+    def alignment_debug(self, k: int) -> Tuple[np.ndarray, np.ndarray]:
+        """wh_get_alignment_debug: (probs float32 [n_heads, n_gen, S_b], matrix float32 [n_gen, S_b]) of debug row k of the last decode call."""
+        shape = (C.c_int32 * 3)()
+        self._check(self.lib.wh_get_alignment_debug(self.h, k, None, None, 0, shape))
+        nh, ng, sb = int(shape[0]), int(shape[1]), int(shape[2])
+        probs = np.zeros((nh, ng, sb), np.float32)
+        matrix = np.zeros((ng, sb), np.float32)
+        self._check(self.lib.wh_get_alignment_debug(self.h, k, _f32(probs), _f32(matrix), max(1, probs.size), shape))
+        return probs, matrix
 
     def _took(self, toks: List[np.ndarray], params: "DecodeParams") -> List[np.ndarray]:
         self._gen_lens = [len(t) - len(params.prompt) for t in toks]   # (what logprobs() cuts its rows to)
@@ -680,6 +731,8 @@ def load_host_library(path: str = HOST_LIB_PATH) -> C.CDLL:
         L.whh_no_speech_token.restype = C.c_longlong
         L.whh_language_table.argtypes = [C.c_char_p, C.c_longlong, ll, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
         L.whh_language_table.restype = C.c_longlong
+        L.whh_words_json.argtypes = [ll, C.POINTER(C.c_int), C.c_size_t, C.c_longlong, C.c_longlong, C.c_double, C.c_double, C.c_char_p, C.c_char_p, C.c_size_t]
+        L.whh_words_json.restype = C.c_size_t
         _host = L
     return _host
 
@@ -729,6 +782,19 @@ def language_table(vocab: int, tokenizer_json: str = "") -> Tuple[List[str], Lis
     if n < 0:
         raise ValueError(err.value.decode())
     return codes.value.decode().split(","), [int(ids[i]) for i in range(n)]
+
+
+def words_from_tokens(generated: Sequence[int], frames: Sequence[int], tb: int, eot: int, duration: float, offset: float = 0.0,
+                      tokenizer_json: str = "") -> List[dict]:
+    """One window's generated tokens and their frames (Context.token_frames) -> [{word, start, end}]: openai-whisper's split on spaces;
+    timestamp tokens (ids >= tb; tb < 0: none), EOT and special tokens dropped; times in seconds, offset by the window's start."""
+    import json
+    n = min(len(generated), len(frames))
+    t = np.ascontiguousarray(list(generated)[:n] or [0], np.int64)
+    f = np.ascontiguousarray(list(frames)[:n] or [0], np.int32)
+    L = load_host_library()
+    return json.loads(_host_string(lambda o, c: L.whh_words_json(t.ctypes.data_as(C.POINTER(C.c_longlong)), f.ctypes.data_as(C.POINTER(C.c_int)), n, tb, eot,
+                                                                 duration, offset, tokenizer_json.encode(), o, c)))
 
 
 def split_segments(generated: Sequence[int], tb: int, eot: int, duration: float, avg_logprob: Optional[float] = None,

@@ -315,6 +315,20 @@ int prefix_check(wh_ctx* c, const wh_decode_params* p, int nb, bool longform) {
     return WH_OK;
 }
 
+// Word-level timestamps: what a decode entry refuses because of them, checked by every entry before it launches anything and
+// again by run_decode.
+int align_check(wh_ctx* c, int nb) {
+    if (!c->al_on) return WH_OK;
+    if (c->m->prec == WH_PREC_FP8 || c->m->prec == WH_PREC_F16X3)
+        return fail(c, WH_ERR_UNSUPPORTED, "decode: word-level timestamps are not supported in the %s mode (no score kernel for its keys and queries)",
+                    c->m->prec == WH_PREC_FP8 ? "fp8" : "f16x3");
+    if (c->cross_es && !wh_align_scores_supported(WH_ALIGN_ES_BF16, c->m->dims.d_model))
+        return fail(c, WH_ERR_UNSUPPORTED, "decode: word-level timestamps have no score kernel for encoder states %d wide", c->m->dims.d_model);
+    for (int r : c->al_debug)
+        if (r >= nb) return fail(c, WH_ERR_ARG, "decode: alignment debug row %d outside the batch (%d clips)", r, nb);
+    return WH_OK;
+}
+
 // ---- cross-KV + greedy loop for the nb clips whose encoder states are resident ------------------
 // run_decode (below) is a sequence of stages: plan_decode -> upload_token_state -> prepare_logits -> project_cross_kv -> the prompt
 // positions (launch_step, eagerly) -> run_token_loop (the captured step) -> read_back.
@@ -366,6 +380,7 @@ int plan_decode(wh_ctx* c, int nb, const wh_decode_params* p, bool want_logits, 
     if (pl.lp_probe && c->lp_sot_index >= P - 1)   // the probe reads a prompt position that emits nothing
         return fail(c, WH_ERR_ARG, "decode: the no-speech probe's sot_index %d is not below n_prompt - 1 (%d)", c->lp_sot_index, P - 1);
     if (int rc = prefix_check(c, p, nb, c->pfx_win_base >= 0)) return rc;
+    if (int rc = align_check(c, nb)) return rc;
     pl.plen.assign(nb, 0);
     pl.pids.assign(nb, nullptr);
     if (c->pfx_on)
@@ -390,6 +405,7 @@ int plan_decode(wh_ctx* c, int nb, const wh_decode_params* p, bool want_logits, 
     if (c->ts_on) { key.ts_begin = (int)c->ts_begin; key.ts_max_init = c->ts_max_init; }
     if (c->lp_on) key.lp_sum = c->lp_part_sum;
     if (c->rep_on) { key.rep = true; key.rep_p = c->rep_p; key.rep_n = c->rep_n; }
+    if (c->al_on) { key.al_cap = NEW; key.al_gen = c->al_gen; }   // (prepare_alignment completes it with the side buffer's address)
     return WH_OK;
 }
 
@@ -428,6 +444,15 @@ int upload_token_state(wh_ctx* c, const wh_decode_params* p, const DecodePlan& p
     }
     CTX_HIP(c, hipMemcpyAsync(c->mask_first, mfirst.data(), mfirst.size() * 4, hipMemcpyHostToDevice, s));
     CTX_HIP(c, hipMemcpyAsync(c->mask_base, mbase.data(), mbase.size() * 4, hipMemcpyHostToDevice, s));
+    std::vector<int> sb;
+    if (c->al_on) {   // frames of each clip: half its mel frames (the conv stride), at least 8, at most the audio context
+        sb.resize(nb);
+        for (int b = 0; b < nb; b++) {
+            const int nf = (size_t)b < c->enc_nframes.size() ? c->enc_nframes[b] : WH_N_FRAMES;
+            sb[b] = std::min(c->m->dims.n_audio_ctx, std::max(8, (nf + 1) / 2));
+        }
+        CTX_HIP(c, hipMemcpyAsync(c->al_sb, sb.data(), nb * 4, hipMemcpyHostToDevice, s));
+    }
     CTX_HIP(c, hipStreamSynchronize(s));  // host vectors above go out of scope
     return WH_OK;
 }
@@ -449,6 +474,94 @@ int prepare_logits(wh_ctx* c, DecodePlan& pl) {
         c->logits_cap = need;
     }
     pl.key.d_logits = c->logits;
+    return WH_OK;
+}
+
+// Word-level timestamps: the side buffer the captured step copies the alignment heads' queries into, [heads][nb][max_new_tokens][dk] f32 — sized
+// by the call, grown on demand; completes the key
+int align_dk(const wh_ctx* c) { return c->cross_es ? c->m->dims.d_model : WH_HEAD_DIM; }
+int prepare_alignment(wh_ctx* c, DecodePlan& pl) {
+    if (!c->al_on) return WH_OK;
+    const size_t need = c->al_heads.size() / 2 * (size_t)pl.key.nb * pl.NEW * align_dk(c);
+    if (need > c->al_q_cap) {
+        drop_step_graph(c);  // the captured step holds the old buffer's address
+        if (c->al_q) CTX_HIP(c, hipFree(c->al_q));
+        c->al_q = nullptr;
+        c->al_q_cap = 0;
+        CTX_HIP(c, hipMalloc((void**)&c->al_q, need * 4));
+        c->al_q_cap = need;
+    }
+    pl.key.al_q = c->al_q;
+    return WH_OK;
+}
+
+// The post-pass of a call with word-level timestamps, on the decode stream after the token loop: scores + softmax, filter, DTW for chunks of
+// clips sized so that the workspace (P, M and the DTW steps of a chunk) stays within WH_ALIGN_WS_BYTES; keeps the debug rows' P and M.
+constexpr size_t WH_ALIGN_WS_BYTES = (size_t)1 << 30;
+int run_alignment(wh_ctx* c, const DecodePlan& pl) {
+    if (!c->al_on) return WH_OK;
+    hipStream_t s = c->stream;
+    const wh_dims& D = c->m->dims;
+    const int nb = pl.key.nb, NEW = pl.NEW, nh = (int)(c->al_heads.size() / 2), S = D.n_audio_ctx, Sp = (S + 3) / 4 * 4;
+    c->al_dbg.clear();
+    CTX_HIP(c, hipMemsetAsync(c->al_frames, 0, (size_t)nb * D.n_text_ctx * 4, s));
+    if (NEW == 1) return WH_OK;   // one row per clip: frame 0, nothing to launch
+    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t b_p = (size_t)nh * NEW * Sp * 4, b_m = (size_t)NEW * Sp * 4, b_t = (size_t)(NEW + 1) * (S + 1), per_clip = b_p + b_m + b_t;
+    const int chunk = (int)std::min<size_t>((size_t)nb, std::max<size_t>(1, WH_ALIGN_WS_BYTES / per_clip));
+    const size_t ws_need = up(chunk * b_p) + up(chunk * b_m) + up(chunk * b_t);
+    if (ws_need > c->al_ws_cap) {
+        if (c->al_ws) CTX_HIP(c, hipFree(c->al_ws));
+        c->al_ws = nullptr;
+        c->al_ws_cap = 0;
+        CTX_HIP(c, hipMalloc((void**)&c->al_ws, ws_need));
+        c->al_ws_cap = ws_need;
+    }
+    AlignArgs a;
+    a.q = c->al_q; a.dk = align_dk(c);
+    const long kv_stride = (long)nb * S * D.d_model;
+    for (int i = 0; i < nh; i++) {
+        const int l = c->al_heads[2 * i], h = c->al_heads[2 * i + 1];
+        a.k_base[i] = c->cross_es ? c->es_E : (const void*)((const char*)c->cross_kv + ((long)(2 * l) * kv_stride + (long)h * WH_HEAD_DIM) * c->m->esz);
+    }
+    a.k_clip_pitch = (long)(c->cross_es ? c->es_rows : S) * D.d_model; a.k_row_pitch = D.d_model;
+    a.n_out = c->n_out; a.n_prompt = pl.key.n_prompt; a.cap = NEW; a.sb = c->al_sb;
+    a.nb = nb; a.n_heads = nh; a.S = S; a.Sp = Sp;
+    a.P = (float*)c->al_ws; a.M = (float*)(c->al_ws + up(chunk * b_p)); a.trace = (unsigned char*)(c->al_ws + up(chunk * b_p) + up(chunk * b_m));
+    a.frames = c->al_frames; a.frames_ld = D.n_text_ctx;
+    const int form = c->cross_es ? WH_ALIGN_ES_BF16 : c->m->prec == WH_PREC_F32 ? WH_ALIGN_KV_F32 : WH_ALIGN_KV_BF16;
+    c->al_dbg.resize(c->al_debug.size());
+    const bool tm = c->al_timing && !c->capturing;
+    hipEvent_t te[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (tm) for (auto& e : te) CTX_HIP(c, hipEventCreate(&e));
+    struct TeGuard { hipEvent_t* te; ~TeGuard() { for (int i = 0; i < 4; i++) if (te[i]) hipEventDestroy(te[i]); } } te_guard{te};
+    c->al_ms[0] = c->al_ms[1] = c->al_ms[2] = 0;
+    for (int c0 = 0; c0 < nb; c0 += chunk) {
+        const int nc = std::min(chunk, nb - c0);
+        a.clip0 = c0;
+        Prof pr(c, WH_KG_DEC_OTHER);
+        if (tm) CTX_HIP(c, hipEventRecord(te[0], s));
+        CTX_LAUNCH(c, wh_launch_align_scores(s, form, a, nc));
+        if (tm) CTX_HIP(c, hipEventRecord(te[1], s));
+        wh_launch_align_filter(s, a, nc);
+        if (tm) CTX_HIP(c, hipEventRecord(te[2], s));
+        wh_launch_align_dtw(s, a, nc);
+        if (tm) {   // (measurement runs only: the host waits for every chunk)
+            CTX_HIP(c, hipEventRecord(te[3], s));
+            CTX_HIP(c, hipEventSynchronize(te[3]));
+            for (int i = 0; i < 3; i++) { float ms = 0; hipEventElapsedTime(&ms, te[i], te[i + 1]); c->al_ms[i] += ms; }
+        }
+        for (size_t k = 0; k < c->al_debug.size(); k++) {   // parity harness: the whole slot; read_back cuts it to the row's n_gen and S_b
+            const int r = c->al_debug[k];
+            if (r < c0 || r >= c0 + nc) continue;
+            wh_ctx::AlignDebug& dbg = c->al_dbg[k];
+            dbg.probs.resize((size_t)nh * NEW * Sp);
+            dbg.matrix.resize((size_t)NEW * Sp);
+            CTX_HIP(c, hipMemcpyAsync(dbg.probs.data(), a.P + (size_t)(r - c0) * nh * NEW * Sp, dbg.probs.size() * 4, hipMemcpyDeviceToHost, s));
+            CTX_HIP(c, hipMemcpyAsync(dbg.matrix.data(), a.M + (size_t)(r - c0) * NEW * Sp, dbg.matrix.size() * 4, hipMemcpyDeviceToHost, s));
+            CTX_HIP(c, hipStreamSynchronize(s));
+        }
+    }
     return WH_OK;
 }
 
@@ -586,6 +699,10 @@ struct Step {
                 // expanded queries qe[h] = W_k,h^T q_h: [nb][H][d] f32
                 wh_launch_dec_qexpand(s, prec, c->dq32, L.cqx_w, c->dqe, nb, (int)d, D.n_heads);
             }
+            if (k.al_q && c->al_layer[l].n) {   // word-level timestamps: the listed heads' expanded queries of this position
+                Prof pr(c, WH_KG_DEC_OTHER);
+                wh_launch_align_copy(s, false, c->dqe, (long)D.n_heads * d, d, (int)d, c->al_layer[l], c->pos, k.n_prompt - 1, k.al_cap, nb, k.al_q);
+            }
             {
                 Prof pr(c, WH_KG_DEC_CROSS_ATTN);
                 wh_launch_dec_cross_attn_es(s, prec, c->dqe, c->es_E, c->dctx, (int)S, c->es_rows, nb, mpad, kv_nt, c->dec_cus);
@@ -604,6 +721,10 @@ struct Step {
             {   // LN2 ∘ cross-attention query
                 Prof pr(c, WH_KG_DEC_GEMM);
                 gemm(false, ln_consumer(L.cq_w, L.cq_b, L.cq_sc, L.cq_s, d, c->dq, ln_tiles_d));
+            }
+            if (k.al_q && c->al_layer[l].n) {   // word-level timestamps: the listed heads' queries of this position
+                Prof pr(c, WH_KG_DEC_OTHER);
+                wh_launch_align_copy(s, m->esz == 2, c->dq, d, WH_HEAD_DIM, WH_HEAD_DIM, c->al_layer[l], c->pos, k.n_prompt - 1, k.al_cap, nb, k.al_q);
             }
             Prof pr(c, WH_KG_DEC_CROSS_ATTN);
             if (f8)
@@ -804,7 +925,7 @@ int read_back(wh_ctx* c, const DecodePlan& pl, int64_t* tokens_out, size_t tok_s
     const size_t logits_rows = pl.key.logits_rows;
     const bool lp = c->lp_on;
     const size_t n_lang = c->lang_ids.size();
-    std::vector<int> toks, nout, lch;
+    std::vector<int> toks, nout, lch, afr, asb;
     std::vector<float> lps, nsp, lpr;
     const double t0 = now_s();
     auto fetch = [&](auto& v, const void* src, size_t n) {   // (4-byte elements)
@@ -819,8 +940,34 @@ int read_back(wh_ctx* c, const DecodePlan& pl, int64_t* tokens_out, size_t tok_s
         CTX_HIP(c, fetch(lch, c->lang_chosen, nb));
         CTX_HIP(c, fetch(lpr, c->lang_probs, (size_t)nb * n_lang));
     }
+    if (c->al_on) {
+        CTX_HIP(c, fetch(afr, c->al_frames, (size_t)nb * c->m->dims.n_text_ctx));
+        CTX_HIP(c, fetch(asb, c->al_sb, nb));
+    }
     CTX_HIP(c, hipStreamSynchronize(s));
     CTX_HIP(c, hipGetLastError());
+    if (c->al_on) {   // kept for wh_get_token_frames / wh_get_alignment_debug
+        const int tc = c->m->dims.n_text_ctx, nh = (int)(c->al_heads.size() / 2), Sp = (c->m->dims.n_audio_ctx + 3) / 4 * 4, NEW = pl.NEW;
+        for (int b = 0; b < nb; b++) {
+            c->al_rows.emplace_back(afr.begin() + (size_t)b * tc, afr.begin() + (size_t)b * tc + (nout[b] - PP));
+            c->al_nframes.push_back(asb[b]);
+        }
+        c->al_have = true;
+        c->al_dbg.resize(c->al_debug.size());
+        for (size_t k = 0; k < c->al_debug.size(); k++) {   // the debug rows' slots cut to [n_heads][n_gen][S_b] and [n_gen][S_b]
+            wh_ctx::AlignDebug& dbg = c->al_dbg[k];
+            const int r = c->al_debug[k], n = nout[r] - PP, sb = asb[r];
+            std::vector<float> pr((size_t)nh * n * sb, 0.0f), mt((size_t)n * sb, 0.0f);
+            if (!dbg.probs.empty() && n > 1)
+                for (int h = 0; h < nh; h++)
+                    for (int g = 0; g < n; g++) std::copy_n(dbg.probs.begin() + ((size_t)h * NEW + g) * Sp, sb, pr.begin() + ((size_t)h * n + g) * sb);
+            if (!dbg.matrix.empty() && n > 1)
+                for (int g = 0; g < n; g++) std::copy_n(dbg.matrix.begin() + (size_t)g * Sp, sb, mt.begin() + (size_t)g * sb);
+            dbg.n_heads = nh; dbg.n_gen = n; dbg.sb = sb;
+            dbg.probs.swap(pr);
+            dbg.matrix.swap(mt);
+        }
+    }
     if (pl.lang_fix) {   // the file's language and window 0's probabilities (the first rows kept), once per window of this batch
         for (int b = 0; b < nb; b++) {
             c->lang_rows.push_back(c->lang_fixed);
@@ -867,7 +1014,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
     // the encoder states come from the encoder stream
     if (c->s_enc != s) CTX_HIP(c, hipStreamWaitEvent(s, c->ev_enc_done, 0));
     CTX_HIP(c, hipEventRecord(c->ev[5], s));   // decode start (stage timing)
-    if ((rc = upload_token_state(c, p, pl)) || (rc = prepare_logits(c, pl)) || (rc = project_cross_kv(c, nb, after_kv))) return rc;
+    if ((rc = upload_token_state(c, p, pl)) || (rc = prepare_logits(c, pl)) || (rc = prepare_alignment(c, pl)) || (rc = project_cross_kv(c, nb, after_kv))) return rc;
     // Positions 0 .. PP-1 (the prompt, the last of which emits the first token) are launched eagerly; the rest is the token loop's
     const int PP = key.n_prompt, total_pos = PP + pl.NEW - 1;
     for (int step = 0; step < std::min(PP, total_pos); step++) {
@@ -877,7 +1024,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
         ps.probe = step == pl.probe_pos;
         launch_step(c, key, &ps);
     }
-    if ((rc = run_token_loop(c, key, total_pos - PP, p->n_forced == 0))) return rc;
+    if ((rc = run_token_loop(c, key, total_pos - PP, p->n_forced == 0)) || (rc = run_alignment(c, pl))) return rc;
     CTX_HIP(c, hipEventRecord(c->ev[3], s));
     return read_back(c, pl, tokens_out, tok_stride, n_tokens_out, logits_out, sel);
 }
@@ -942,6 +1089,10 @@ int check_params(wh_ctx* c, const wh_decode_params* p) {
     c->lang_have = false;
     c->lang_rows.clear();
     c->lang_prob_rows.clear();
+    c->al_have = false;
+    c->al_rows.clear();
+    c->al_nframes.clear();
+    c->al_dbg.clear();
     if (!p) return fail(c, WH_ERR_ARG, "decode params are NULL");
     if ((p->n_suppress && !p->suppress) || (p->n_begin_suppress && !p->begin_suppress) || (p->n_forced && !p->forced))
         return fail(c, WH_ERR_ARG, "decode params: NULL list with non-zero length");
@@ -1078,6 +1229,7 @@ static int ctx_create_impl(wh_model* m, const wh_ctx_opts* opts, wh_ctx** out) {
     c->dec_cus = dec_masked ? (int)mask_bits(opts->dec_cu_mask, opts->dec_cu_mask_words) : n_cus;   // compute units the token-loop stream may use
     c->no_graph = getenv("WH_NO_GRAPH") != nullptr;
     c->sync_every_pos = getenv("WH_SYNC_EVERY_POS") != nullptr;
+    c->al_timing = getenv("WH_ALIGN_TIMING") != nullptr;
     const wh_dims& D = m->dims;
     const size_t B = max_batch, d = D.d_model, S = D.n_audio_ctx, F = D.ffn, C = D.n_mels, esz = m->esz;
     const size_t Ld = D.dec_layers, H = D.n_heads, TC = D.n_text_ctx;
@@ -1501,6 +1653,84 @@ int wh_ctx_set_prefixes(wh_ctx* c, const wh_prefix_opts* o) {
     return WH_OK;
 }
 
+// Word-level timestamps on every decode entry of the ctx.  The setter copies the head list and allocates the frames; the side
+// buffer of the queries and the post-pass workspace are sized by the calls.  The captured decode step is keyed on the list's identity.
+int wh_ctx_set_alignment(wh_ctx* c, const wh_alignment_opts* o) {
+    if (!c) return WH_ERR_ARG;
+    if (!o) {
+        c->al_on = false;
+        return WH_OK;
+    }
+    if (o->struct_size != sizeof(wh_alignment_opts)) return fail(c, WH_ERR_ARG, "wh_ctx_set_alignment: struct_size %zu, expected %zu", o->struct_size, sizeof(wh_alignment_opts));
+    const wh_dims& D = c->m->dims;
+    if (o->n_heads < 1 || o->n_heads > WH_MAX_ALIGN_HEADS || !o->heads) return fail(c, WH_ERR_ARG, "wh_ctx_set_alignment: n_heads %zu outside 1..%d (or a NULL list)", o->n_heads, WH_MAX_ALIGN_HEADS);
+    if (o->n_debug_rows > WH_MAX_ALIGN_DEBUG_ROWS || (o->n_debug_rows && !o->debug_rows)) return fail(c, WH_ERR_ARG, "wh_ctx_set_alignment: more than %d debug rows (or a NULL list)", WH_MAX_ALIGN_DEBUG_ROWS);
+    for (size_t i = 0; i < o->n_heads; i++) {
+        const int l = o->heads[2 * i], h = o->heads[2 * i + 1];
+        if (l < 0 || l >= D.dec_layers || h < 0 || h >= D.n_heads) return fail(c, WH_ERR_ARG, "wh_ctx_set_alignment: (layer %d, head %d) outside the model (%d layers, %d heads)", l, h, D.dec_layers, D.n_heads);
+        for (size_t j = 0; j < i; j++)
+            if (o->heads[2 * j] == l && o->heads[2 * j + 1] == h) return fail(c, WH_ERR_ARG, "wh_ctx_set_alignment: (layer %d, head %d) listed twice", l, h);
+    }
+    for (size_t i = 0; i < o->n_debug_rows; i++)
+        if (o->debug_rows[i] < 0) return fail(c, WH_ERR_ARG, "wh_ctx_set_alignment: negative debug row");
+    if (!c->al_frames) {
+        int* fr = (int*)setter_alloc(c, "wh_ctx_set_alignment", (size_t)c->max_batch * D.n_text_ctx * 4);
+        int* sb = (int*)(fr ? setter_alloc(c, "wh_ctx_set_alignment", (size_t)c->max_batch * 4) : nullptr);
+        if (!sb) {
+            if (fr) hipFree(fr);
+            return WH_ERR_NOMEM;
+        }
+        c->al_frames = fr; c->al_sb = sb;
+    }
+    c->al_heads.assign(o->heads, o->heads + 2 * o->n_heads);
+    c->al_debug.assign(o->debug_rows, o->debug_rows + o->n_debug_rows);
+    c->al_layer.assign(D.dec_layers, AlignLayerHeads());
+    for (size_t i = 0; i < o->n_heads; i++) {
+        AlignLayerHeads& lh = c->al_layer[o->heads[2 * i]];
+        lh.slot[lh.n] = (unsigned char)i;
+        lh.head[lh.n] = (unsigned char)o->heads[2 * i + 1];
+        lh.n++;
+    }
+    c->al_gen++;
+    c->al_on = true;
+    return WH_OK;
+}
+
+int wh_get_token_frames(const wh_ctx* c, int32_t* frames, size_t cap_tokens, int32_t* n_frames, size_t cap_clips, size_t* n_clips_out) {
+    if (!c) return WH_ERR_ARG;
+    if (!c->al_have) return WH_ERR_STATE;
+    const size_t n = c->al_rows.size();
+    if (n_clips_out) *n_clips_out = n;
+    if ((frames || n_frames) && cap_clips < n) return WH_ERR_ARG;
+    if (frames) {
+        for (size_t b = 0; b < n; b++)
+            if (c->al_rows[b].size() > cap_tokens) return WH_ERR_ARG;
+        for (size_t b = 0; b < n; b++) {
+            std::fill(frames + b * cap_tokens, frames + (b + 1) * cap_tokens, 0);
+            std::copy(c->al_rows[b].begin(), c->al_rows[b].end(), frames + b * cap_tokens);
+        }
+    }
+    if (n_frames) std::copy(c->al_nframes.begin(), c->al_nframes.end(), n_frames);
+    return WH_OK;
+}
+
+int wh_get_alignment_debug(const wh_ctx* c, size_t k, float* probs, float* matrix, size_t cap_floats, int32_t* shape3) {
+    if (!c) return WH_ERR_ARG;
+    if (!c->al_have || c->al_dbg.empty()) return WH_ERR_STATE;
+    if (k >= c->al_dbg.size()) return WH_ERR_ARG;
+    const wh_ctx::AlignDebug& d = c->al_dbg[k];
+    if (shape3) { shape3[0] = d.n_heads; shape3[1] = d.n_gen; shape3[2] = d.sb; }
+    if (probs) {
+        if (cap_floats < d.probs.size()) return WH_ERR_ARG;
+        std::copy(d.probs.begin(), d.probs.end(), probs);
+    }
+    if (matrix) {
+        if (cap_floats < d.matrix.size()) return WH_ERR_ARG;
+        std::copy(d.matrix.begin(), d.matrix.end(), matrix);
+    }
+    return WH_OK;
+}
+
 int wh_get_languages(const wh_ctx* c, int64_t* lang_out, float* probs, size_t cap_clips, size_t* n_clips_out) {
     if (!c) return WH_ERR_ARG;
     if (!c->lang_have) return WH_ERR_STATE;
@@ -1561,6 +1791,10 @@ void wh_ctx_free(wh_ctx* c) {
     if (c->pfx_off) hipFree(c->pfx_off);
     if (c->rep_bits) hipFree(c->rep_bits);
     if (c->rep_side) hipFree(c->rep_side);
+    if (c->al_q) hipFree(c->al_q);
+    if (c->al_ws) hipFree(c->al_ws);
+    if (c->al_frames) hipFree(c->al_frames);
+    if (c->al_sb) hipFree(c->al_sb);
     if (c->s_copy) { hipStreamSynchronize(c->s_copy); hipStreamDestroy(c->s_copy); }
     if (c->ev_h2d) hipEventDestroy(c->ev_h2d);
     if (c->pcm2) hipFree(c->pcm2);
@@ -1575,6 +1809,14 @@ extern "C" int wh_debug_set_es_pad(wh_ctx* c, int pad_rows) {
     if (!c || !c->cross_es || pad_rows < 0 || c->m->dims.n_audio_ctx + pad_rows > c->es_rows_cap) return WH_ERR_ARG;
     c->es_rows = c->m->dims.n_audio_ctx + pad_rows;
     c->have_enc = false;
+    return WH_OK;
+}
+
+// measurement hook (tools/align_bench.py; not in the public header): milliseconds of the three post-pass kernels of the last call, summed over
+// its chunks — filled when the context was created under WH_ALIGN_TIMING=1
+extern "C" int wh_debug_align_times(const wh_ctx* c, double* ms3) {
+    if (!c || !ms3 || !c->al_timing) return WH_ERR_ARG;
+    for (int i = 0; i < 3; i++) ms3[i] = c->al_ms[i];
     return WH_OK;
 }
 
@@ -1692,6 +1934,7 @@ int wh_encode(wh_ctx* c, const float* mel, float* enc_out) {
                                    (bf16*)c->melT, (long)TOK_ROWS * D.n_mels);
     rc = run_encoder(c, 1, enc_out != nullptr);
     if (rc) return rc;
+    c->enc_nframes.assign(1, WH_N_FRAMES);
     CTX_HIP(c, hipEventRecord(c->ev[2], s));
     if (enc_out)
         CTX_HIP(c, hipMemcpyAsync(enc_out, c->enc_out_f32, (size_t)D.n_audio_ctx * D.d_model * 4, hipMemcpyDeviceToHost, s));
@@ -1730,6 +1973,7 @@ int wh_decode_greedy(wh_ctx* c, const wh_decode_params* p, int64_t* tokens_out, 
     if (logits_out && cap_logits_rows < p->max_new_tokens) return fail(c, WH_ERR_ARG, "logits_out needs max_new_tokens rows");
     rc = prefix_check(c, p, 1, false);
     if (rc) return rc;
+    if ((rc = align_check(c, 1))) return rc;
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -1753,6 +1997,7 @@ int wh_decode_greedy_batch(wh_ctx* c, const wh_decode_params* p, int64_t* tokens
     if (logits_out && cap_logits_rows < p->max_new_tokens) return fail(c, WH_ERR_ARG, "logits_out needs max_new_tokens rows per clip");
     rc = prefix_check(c, p, nb, false);
     if (rc) return rc;
+    if ((rc = align_check(c, nb))) return rc;
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -1777,6 +2022,7 @@ int wh_decode_greedy_rows(wh_ctx* c, const wh_decode_params* p, const int32_t* r
     if (cap_logits_rows < p->max_new_tokens) return fail(c, WH_ERR_ARG, "logits_out needs max_new_tokens rows per selected clip");
     rc = prefix_check(c, p, nb, false);
     if (rc) return rc;
+    if ((rc = align_check(c, nb))) return rc;
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -1838,6 +2084,7 @@ int wh_transcribe_batch(wh_ctx* c, const wh_clip* clips, size_t n_clips, const w
     if (n_clips == 0 || n_clips > (size_t)c->max_batch) return fail(c, WH_ERR_ARG, "n_clips must be 1..max_batch (%d)", c->max_batch);
     rc = prefix_check(c, p, (int)n_clips, false);
     if (rc) return rc;
+    if ((rc = align_check(c, (int)n_clips))) return rc;
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -1858,6 +2105,7 @@ int wh_transcribe_batch(wh_ctx* c, const wh_clip* clips, size_t n_clips, const w
     CTX_HIP(c, hipStreamSynchronize(s));
     c->timing = wh_timing{};
     c->timing.h2d_s = now_s() - t0;
+    c->enc_nframes = nf;
     return transcribe_resident(c, c->pcm, (int)n_clips, false, nullptr, 0, p, tokens_out, n_tokens_out, t0);
 }
 
@@ -1884,6 +2132,7 @@ int wh_transcribe_batch_next(wh_ctx* c, const wh_clip* clips, size_t n_clips, co
     if (n_clips == 0 || n_clips > (size_t)c->max_batch) return fail(c, WH_ERR_ARG, "n_clips must be 1..max_batch (%d)", c->max_batch);
     rc = prefix_check(c, p, (int)n_clips, false);
     if (rc) return rc;
+    if ((rc = align_check(c, (int)n_clips))) return rc;
     if (next_clips && (n_next == 0 || n_next > (size_t)c->max_batch)) return fail(c, WH_ERR_ARG, "n_next must be 1..max_batch (%d)", c->max_batch);
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
@@ -1935,6 +2184,7 @@ int wh_transcribe_batch_next(wh_ctx* c, const wh_clip* clips, size_t n_clips, co
             return WH_OK;
         };
     }
+    c->enc_nframes = nf;
     return transcribe_resident(c, d_pcm, (int)n_clips, false, nullptr, 0, p, tokens_out, n_tokens_out, t0, copy_next);
 }
 
@@ -1947,6 +2197,7 @@ int wh_transcribe_batch_device_next(wh_ctx* c, const float* d_pcm, size_t n_clip
     if (n_clips == 0 || n_clips > (size_t)c->max_batch) return fail(c, WH_ERR_ARG, "n_clips must be 1..max_batch (%d)", c->max_batch);
     rc = prefix_check(c, p, (int)n_clips, false);
     if (rc) return rc;
+    if ((rc = align_check(c, (int)n_clips))) return rc;
     if (d_pcm_next && (n_clips_next == 0 || n_clips_next > (size_t)c->max_batch))
         return fail(c, WH_ERR_ARG, "n_clips_next must be 1..max_batch (%d)", c->max_batch);
     CTX_HIP(c, hipSetDevice(c->m->device));
@@ -1962,6 +2213,7 @@ int wh_transcribe_batch_device_next(wh_ctx* c, const float* d_pcm, size_t n_clip
     }
     c->pre_valid = false;
     c->timing = wh_timing{};
+    c->enc_nframes.assign(std::max(n_clips, n_clips_next), WH_N_FRAMES);   // (device-resident clips are exactly 30 s, this batch's and the prefetched one's)
     return transcribe_resident(c, d_pcm, (int)n_clips, prefetched, d_pcm_next, (int)n_clips_next, p, tokens_out, n_tokens_out, t0);
 }
 
@@ -1999,6 +2251,11 @@ int wh_transcribe_longform(wh_ctx* c, const float* pcm, size_t n_samples, double
     if (!tokens_out || !n_tokens_out || !n_chunks_out) return fail(c, WH_ERR_ARG, "NULL argument");
     rc = prefix_check(c, p, 1, true);
     if (rc) return rc;
+    {   // (alignment debug rows are rows of a device batch: they must exist in every batch of the call, so in its last, smallest one)
+        size_t nw = 0;
+        wh_longform_plan(n_samples, chunk_length_s, overlap_s, nullptr, 0, &nw);
+        if ((rc = align_check(c, nw ? (int)(nw - (nw - 1) / c->max_batch * c->max_batch) : 1))) return rc;
+    }
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -2047,6 +2304,8 @@ int wh_transcribe_longform(wh_ctx* c, const float* pcm, size_t n_samples, double
         rc = run_encoder(c, nb, false);
         if (rc) return rc;
         CTX_HIP(c, hipEventRecord(c->ev[2], s));
+        c->enc_nframes.resize(nb);   // each window's valid mel frames
+        for (int i = 0; i < nb; i++) c->enc_nframes[i] = (int)std::min<size_t>(WH_N_FRAMES, nf - std::min<size_t>(nf, (size_t)fs[i]));
         c->pfx_win_base = (long)base;   // per-clip prefixes: which rows of this batch are window 0
         rc = run_decode(c, nb, p, tokens_out + base * stride, stride, n_tokens_out + base, nullptr, 0);
         if (rc) return rc;

@@ -215,7 +215,10 @@ struct wh_ctx {
         bool rep = false;                      // repetition penalty / no-repeat n-grams: other kernels, other arguments
         float rep_p = 1.0f;
         int rep_n = 0;
-        auto members() const { return std::tie(nb, n_prompt, eot, n_forced, logits_rows, d_logits, d_sel, ts_begin, ts_max_init, lp_sum, pfx, rep, rep_p, rep_n); }
+        float* al_q = nullptr;                 // word-level timestamps: nullptr = off (no launch); the side buffer the queries are copied to,
+        int al_cap = 0;                        // its rows per clip (the call's max_new_tokens) and the identity of the head list (al_gen)
+        unsigned al_gen = 0;
+        auto members() const { return std::tie(nb, n_prompt, eot, n_forced, logits_rows, d_logits, d_sel, ts_begin, ts_max_init, lp_sum, pfx, rep, rep_p, rep_n, al_q, al_cap, al_gen); }
         bool operator==(const StepKey& o) const { return members() == o.members(); }
     } step_key;
     // Whisper's timestamp rules (wh_ctx_set_timestamp_rules): off unless ts_on.  The timestamp logits and the per-row state
@@ -280,6 +283,29 @@ struct wh_ctx {
     int rep_words = 0;                 // ceil(vocab / 32)
     unsigned* rep_bits = nullptr;      // [max_batch][rep_words] touched ids of each row's current position
     float* rep_side = nullptr;         // [max_batch][vocab] raw logits of the touched ids (only those entries are written)
+    // Word-level timestamps (wh_ctx_set_alignment): off unless al_on.  The captured step copies the listed heads' queries into
+    // al_q (grown on demand by a call; the step graph is dropped when its address changes); the post-pass of a call works in al_ws, a chunk of
+    // clips at a time.  al_d (frames + per-clip frame counts) is allocated by the setter and freed in wh_ctx_free with the rest.
+    bool al_on = false;
+    unsigned al_gen = 0;                       // counts the setter's calls: the identity of the head list in the step's key
+    std::vector<int> al_heads;                 // [n][2] (layer, head), the caller's order
+    std::vector<int> al_debug;                 // batch rows whose P and M are kept
+    std::vector<AlignLayerHeads> al_layer;     // [dec_layers] the listed heads of each layer
+    float* al_q = nullptr;                     // [n_heads][nb][max_new_tokens][dk] f32
+    size_t al_q_cap = 0;                       // floats
+    char* al_ws = nullptr;                     // post-pass workspace: P, M, the DTW steps of one chunk of clips
+    size_t al_ws_cap = 0;                      // bytes
+    int* al_frames = nullptr;                  // [max_batch][n_text_ctx] frame of each generated token
+    int* al_sb = nullptr;                      // [max_batch] S_b of each row
+    bool al_timing = false;                    // WH_ALIGN_TIMING=1: events around the three post-pass kernels (tools/align_bench.py)
+    double al_ms[3] = {0, 0, 0};               // scores, filter, DTW of the last call, milliseconds
+    std::vector<int> enc_nframes;              // mel frames of each clip whose encoder states are resident (what S_b derives from)
+    // what wh_get_token_frames / wh_get_alignment_debug return: the last decode call's clips in the order their tokens were returned
+    bool al_have = false;
+    std::vector<std::vector<int>> al_rows;
+    std::vector<int> al_nframes;
+    struct AlignDebug { int n_heads = 0, n_gen = 0, sb = 0; std::vector<float> probs, matrix; };
+    std::vector<AlignDebug> al_dbg;
     hipGraph_t step_graph = nullptr;
     hipGraphExec_t step_exec = nullptr;
 };

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <vector>
 
+#include "../../include/whisper_hip.h"
+
 constexpr int WH_SMALL_CTX_CLIPS = 8;
 
 struct GemmArgs {
@@ -332,6 +334,38 @@ void wh_launch_kv_quant(hipStream_t s, const void* kv_bf16, unsigned* amax, void
 void wh_launch_dec_cross_attn8(hipStream_t s, const void* q, const void* ck, const void* cv, const float* amax_k,
                                const float* amax_v, float* part, float* ml, int S, int d, int n_heads, int splits, int B, void* out,
                                int mpad, bool stream_nt);
+
+// Word-level timestamps (wh_align.hip).
+// The listed alignment heads of one decoder layer: head[i] of the layer is entry slot[i] of the caller's list.
+struct AlignLayerHeads {
+    int n = 0;
+    unsigned char slot[WH_MAX_ALIGN_HEADS] = {0}, head[WH_MAX_ALIGN_HEADS] = {0};
+};
+// the token loop's copy: src row b, head h at src + b * row_pitch + h * head_pitch (dk values, bf16 or f32) -> dst [slot][nb][cap][dk] f32 at
+// index *pos_p - first_emit (nothing outside 0 .. cap - 1)
+void wh_launch_align_copy(hipStream_t s, bool src_bf16, const void* src, long row_pitch, long head_pitch, int dk, const AlignLayerHeads& hs, const int* pos_p,
+                          int first_emit, int cap, int nb, float* dst);
+// the post-pass over the clips clip0 .. clip0 + n_clips - 1 of a batch of nb (workspace slots 0 .. n_clips - 1)
+constexpr int WH_ALIGN_KV_F32 = 0, WH_ALIGN_KV_BF16 = 1, WH_ALIGN_ES_BF16 = 2;
+struct AlignArgs {
+    const float* q = nullptr;        // [n_heads][nb][cap][dk] f32 (the token loop's copy)
+    const void* k_base[WH_MAX_ALIGN_HEADS] = {nullptr};   // per listed head: its key rows of clip 0 (K plane + 64 h, or the encoder states)
+    long k_clip_pitch = 0, k_row_pitch = 0;                // elements from clip to clip and from frame to frame
+    int dk = 0;
+    const int* n_out = nullptr;      // [nb] tokens of each row, prompt included (DecodeState::n_out)
+    int n_prompt = 0, cap = 0;       // rows of clip b: clamp(n_out[b] - n_prompt, 0, cap)
+    const int* sb = nullptr;         // [nb] frames of each clip, 8 .. S
+    int nb = 0, n_heads = 0, S = 0, Sp = 0, clip0 = 0;
+    float* P = nullptr;              // [slot][n_heads][cap][Sp]
+    float* M = nullptr;              // [slot][cap][Sp]
+    unsigned char* trace = nullptr;  // [slot][cap + 1][S + 1]
+    int* frames = nullptr;           // [nb][frames_ld], zeroed by the caller
+    int frames_ld = 0;
+};
+bool wh_align_scores_supported(int form, int dk);   // a score kernel exists for this form and key width
+int wh_launch_align_scores(hipStream_t s, int form, const AlignArgs& a, int n_clips);
+void wh_launch_align_filter(hipStream_t s, const AlignArgs& a, int n_clips);
+void wh_launch_align_dtw(hipStream_t s, const AlignArgs& a, int n_clips);
 
 extern int wh_dbg_cross_unroll;
 extern int wh_dbg_lm_blocks_per_cu;

@@ -157,6 +157,7 @@ inline JVal stat_json(const StatBlock& s) {
 struct RowOut {
     std::string file; double duration_s, end_to_end_s, rtf; std::string text;
     std::string segments;   // JSON array of {start, end, text} (--timestamp-rules), empty: no key
+    std::string words, token_times;   // --word-timestamps: JSON arrays of {word, start, end} and of the generated tokens' times; empty: no key
     bool has_conf = false;  // --logprobs: avg_logprob and no_speech_prob keys
     double avg_logprob = 0, no_speech_prob = 0;
     bool has_lang = false;  // --language auto: the detected language code and its probability
@@ -227,6 +228,7 @@ inline std::string per_file_json(const std::vector<RowOut>& rows) {  // :1232 to
         if (rows[i].has_prompt) r.set("prompt_tokens", JVal::integer(rows[i].prompt_tokens));
         if (rows[i].has_conf) { JVal v; v.raw = fmt_conf(rows[i].avg_logprob); r.set("avg_logprob", v); v.raw = fmt_conf(rows[i].no_speech_prob); r.set("no_speech_prob", v); }
         if (!rows[i].segments.empty()) { JVal sg; sg.raw = rows[i].segments; r.set("segments", sg); }
+        if (!rows[i].words.empty()) { JVal w; w.raw = rows[i].words; r.set("words", w); w.raw = rows[i].token_times; r.set("token_times", w); }
         o += "  ";
         r.write(o, 2);
         o += (i + 1 < rows.size()) ? ",\n" : "\n";
@@ -675,6 +677,79 @@ inline std::string decode_tokens(const std::vector<int64_t>& tokens, const Token
 }
 
 // ---------------------------------------------------------------------------------------------
+// word-level timestamps (wh_ctx_set_alignment / wh_get_token_frames; no reference counterpart): a window's generated tokens and their
+// frames -> words, as openai-whisper's split_tokens_on_spaces does.  Timestamp tokens (ids >= tb, tb < 0: none), EOT and the tokenizer's
+// special tokens are dropped; of the kept tokens a new word begins where the decoded piece begins with a space (and at the first piece); a
+// piece that ends inside a UTF-8 sequence stays with the next one.  A word starts at its first token's frame x 0.02 s and ends where the
+// next kept token starts (the last word: at the window's duration); both are offset by the window's start.  Punctuation is not merged into
+// its neighbours.  Without a tokenizer the pieces are those of decode_tokens' "[TOKENS:a b c]" form (its first 200 ids), so that the words
+// of a window always concatenate to its text.
+// ---------------------------------------------------------------------------------------------
+struct Word {
+    std::string word;
+    double start = 0, end = 0;
+};
+
+inline bool utf8_complete(const std::string& s) {   // false when s ends inside a multi-byte sequence
+    size_t i = 0;
+    while (i < s.size()) {
+        const unsigned char c = (unsigned char)s[i];
+        const size_t len = c < 0x80 ? 1 : (c >> 5) == 6 ? 2 : (c >> 4) == 14 ? 3 : (c >> 3) == 30 ? 4 : 1;
+        if (i + len > s.size()) return false;
+        i += len;
+    }
+    return true;
+}
+
+inline std::vector<Word> words_from_tokens(const std::vector<int64_t>& tokens, const std::vector<int32_t>& frames, int64_t tb, int64_t eot,
+                                           double duration, double offset, const Tokenizer* tok) {
+    const bool have_tok = tok && tok->loaded;
+    std::vector<size_t> kept;   // rows that carry text
+    for (size_t i = 0; i < tokens.size() && i < frames.size(); i++) {
+        const int64_t t = tokens[i];
+        if (t == eot || (tb >= 0 && t >= tb) || t < 0) continue;
+        if (have_tok && ((size_t)t >= tok->id_to_tok.size() || tok->is_special[(size_t)t])) continue;
+        if (!have_tok && kept.size() == 200) break;
+        kept.push_back(i);
+    }
+    auto t_of = [&](size_t k) { return std::min(duration, std::max(0.0, frames[kept[k]] * 0.02)) + offset; };
+    std::vector<Word> words;
+    std::string pending;       // bytes of pieces that did not end on a character boundary yet
+    size_t pending_first = 0;  // kept index of the first token in `pending`
+    for (size_t k = 0; k < kept.size(); k++) {
+        std::string piece;
+        if (have_tok) piece = decode_tokens({tokens[kept[k]]}, tok);
+        else piece = (k == 0 ? "[TOKENS:" : " ") + std::to_string(tokens[kept[k]]) + (k + 1 == kept.size() ? "]" : "");
+        if (pending.empty()) pending_first = k;
+        pending += piece;
+        if (!utf8_complete(pending) && k + 1 < kept.size()) continue;
+        if (words.empty() || pending[0] == ' ') {
+            Word w;
+            w.word = pending;
+            w.start = t_of(pending_first);
+            words.push_back(w);
+        } else {
+            words.back().word += pending;
+        }
+        // the word ends where the next kept token starts
+        words.back().end = k + 1 < kept.size() ? t_of(k + 1) : duration + offset;
+        pending.clear();
+    }
+    for (Word& w : words) w.end = std::max(w.end, w.start);
+    return words;
+}
+
+inline std::string words_json(const std::vector<Word>& words) {   // [{"word": "...", "start": s, "end": s}] on one line
+    std::string o = "[";
+    char b[96];
+    for (size_t i = 0; i < words.size(); i++) {
+        snprintf(b, sizeof b, ", \"start\": %.2f, \"end\": %.2f}", words[i].start, words[i].end);
+        o += std::string(i ? ", " : "") + "{\"word\": " + json_escape(words[i].word) + b;
+    }
+    return o + "]";
+}
+
+// ---------------------------------------------------------------------------------------------
 // long-form stitcher — src/main.rs:659-696
 // ---------------------------------------------------------------------------------------------
 // Rust's str::split_whitespace / trim split on the Unicode White_Space property and str::to_lowercase maps every cased
@@ -797,6 +872,8 @@ inline std::string trim(const std::string& s) {   // str::trim
     }
     return s.substr(a, b - a);
 }
+inline std::string ltrim(const std::string& s) { return s.substr(s.size() - trim(s + "x").size() + 1); }   // leading white space only
+inline std::string rtrim(const std::string& s) { return s.substr(0, trim("x" + s).size() - 1); }            // trailing white space only
 inline size_t word_overlap(const std::string& a, const std::string& b, size_t max_words) {  // :686-696
     auto aw = split_ws(a), bw = split_ws(b);
     for (auto& w : aw) w = lower(w);

@@ -124,6 +124,14 @@ size_t whh_longform_segments_json(const long long* toks, const size_t* lens, siz
     }
     return put(segments_json(merge_window_segments(w, std::vector<double>(starts, starts + n_windows), overlap_s)), out, cap);
 }
+// word-level timestamps: a window's generated tokens and their frames -> [{"word", "start", "end"}] (wh_host.h words_from_tokens)
+size_t whh_words_json(const long long* toks, const int* frames, size_t n, long long tb, long long eot, double duration, double offset,
+                      const char* tokenizer_json, char* out, size_t cap) {
+    Tokenizer t;
+    if (tokenizer_json && *tokenizer_json) load_tokenizer(tokenizer_json, t);
+    return put(words_json(words_from_tokens(std::vector<int64_t>(toks, toks + n), std::vector<int32_t>(frames, frames + n), tb, eot, duration, offset,
+                                            t.loaded ? &t : nullptr)), out, cap);
+}
 static std::vector<Cue> cues_from(const double* starts, const double* ends, const char* texts, size_t n) {
     std::vector<Cue> c;
     for (size_t i = 0; i < n; i++) {

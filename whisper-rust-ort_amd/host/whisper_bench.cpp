@@ -55,6 +55,9 @@ struct Args {
     bool have_rep_penalty = false, have_rep_ngram = false;
     float rep_penalty = 1.0f;
     int rep_ngram = 0;
+    // additive: word-level timestamps (wh_ctx_set_alignment): words and token times in the per-file JSON; the alignment heads as "l:h,l:h,..."
+    bool word_timestamps = false;
+    std::string alignment_heads;
     bool prompts() const { return !prompt_ids.empty() || !prompt_ids_dir.empty(); }
 };
 
@@ -114,6 +117,7 @@ static bool parse_args(int argc, char** argv, Args& a) {
         else if (k == "--write-srt") a.write_srt = a.timestamp_rules = true;
         else if (k == "--write-vtt") a.write_vtt = a.timestamp_rules = true;
         else if (k == "--logprobs") a.logprobs = true;
+        else if (k == "--word-timestamps") a.word_timestamps = true;
         else if (k == "--print-plan") a.print_plan = true;
         else if (k == "--prompt-all-windows") a.prompt_all_windows = true;
         else if (k == "--help" || k == "-h") {
@@ -137,7 +141,12 @@ static bool parse_args(int argc, char** argv, Args& a) {
                    "  --prompt-all-windows     a file of several windows: the context conditions every window (default: the first one only)\n"
                    "  --logprobs               avg_logprob and no_speech_prob in every row of the per-file JSON (and in its segments)\n"
                    "  --no-speech-threshold X  with --logprob-threshold Y: a window with no_speech_prob > X and avg_logprob < Y becomes empty text and\n"
-                   "  --logprob-threshold Y    no segments (both off unless given, each implies --logprobs; openai-whisper's defaults are 0.6 and -1.0)\n");
+                   "  --logprob-threshold Y    no segments (both off unless given, each implies --logprobs; openai-whisper's defaults are 0.6 and -1.0)\n"
+                   "  --word-timestamps        words [{word, start, end}] and token_times in every row of the per-file JSON (cross-attention alignment + DTW);\n"
+                   "                           a one-window file's words concatenate to its text, a longer file's are its windows' words one after the other\n"
+                   "                           (the overlap of two windows is not removed from them as it is from the stitched text)\n"
+                   "  --alignment-heads L      its heads as \"layer:head,layer:head,...\" (default: alignment_heads of the model directory's generation_config.json,\n"
+                   "                           else every head of the upper half of the decoder layers, the topmost layers first, 32 heads at most)\n");
             exit(0);
         } else {
             if (!need(i, argv[i], v, inl)) return false;
@@ -170,6 +179,7 @@ static bool parse_args(int argc, char** argv, Args& a) {
             else if (k == "--logprob-threshold") { a.logprob_threshold = strtod(v.c_str(), nullptr); a.logprobs = true; }
             else if (k == "--seed") a.seed = strtoull(v.c_str(), nullptr, 10);
             else if (k == "--prompt-ids") a.prompt_ids = v;
+            else if (k == "--alignment-heads") a.alignment_heads = v;
             else if (k == "--prompt-ids-dir") a.prompt_ids_dir = v;
             else if (k == "--repetition-penalty") {   // what wh_ctx_set_repetition refuses is refused here, before any device is touched
                 char* end = nullptr;
@@ -242,7 +252,7 @@ static OrtCfg load_best_cfg_from_discovery(const std::string& path) {  // src/ma
     return c;
 }
 
-struct GenCfg { std::vector<int64_t> suppress, begin_suppress; };
+struct GenCfg { std::vector<int64_t> suppress, begin_suppress; std::vector<int32_t> alignment_heads; /* (layer, head) pairs */ };
 static GenCfg load_generation_cfg(const std::string& path) {  // src/main.rs:650-657
     GenCfg g;
     if (!is_file(path)) return g;
@@ -255,6 +265,9 @@ static GenCfg load_generation_cfg(const std::string& path) {  // src/main.rs:650
     if (!j) throw std::runtime_error(path + ": " + err);
     if (auto v = j->get("suppress_tokens")) for (auto& e : v->arr) g.suppress.push_back(e->as_i64());
     if (auto v = j->get("begin_suppress_tokens")) for (auto& e : v->arr) g.begin_suppress.push_back(e->as_i64());
+    if (auto v = j->get("alignment_heads"))
+        for (auto& e : v->arr)
+            if (e->arr.size() == 2) { g.alignment_heads.push_back((int32_t)e->arr[0]->as_i64()); g.alignment_heads.push_back((int32_t)e->arr[1]->as_i64()); }
     return g;
 }
 
@@ -341,6 +354,56 @@ struct Conf {
     double no_speech_prob() const { return windows ? sum_ns / (double)windows : 0.0; }
 };
 // the last decode call's log-probabilities ([n][max_new_tokens], 0 past a window's end) and no-speech probabilities
+// --word-timestamps: the alignment heads as (layer, head) pairs — --alignment-heads, else the model directory's generation_config.json, else
+// every head of the upper half of the decoder layers (openai-whisper's default), the topmost layers first, while they fit WH_MAX_ALIGN_HEADS
+static std::vector<int32_t> alignment_heads(const Args& a, const GenCfg& gen, const wh_dims& dims) {
+    std::vector<int32_t> h;
+    if (!a.alignment_heads.empty()) {
+        const char* p = a.alignment_heads.c_str();
+        while (*p) {
+            char* e = nullptr;
+            const long l = strtol(p, &e, 10);
+            if (e == p || *e != ':') throw std::runtime_error("--alignment-heads: expected layer:head,layer:head,... in '" + a.alignment_heads + "'");
+            p = e + 1;
+            const long hd = strtol(p, &e, 10);
+            if (e == p || (*e && *e != ',')) throw std::runtime_error("--alignment-heads: expected layer:head,layer:head,... in '" + a.alignment_heads + "'");
+            h.push_back((int32_t)l); h.push_back((int32_t)hd);
+            p = *e ? e + 1 : e;
+        }
+        if (h.empty()) throw std::runtime_error("--alignment-heads names no head");
+        return h;
+    }
+    if (!gen.alignment_heads.empty()) return gen.alignment_heads;
+    for (int l = dims.dec_layers - 1; l >= dims.dec_layers / 2 && (int)h.size() / 2 + dims.n_heads <= WH_MAX_ALIGN_HEADS; l--)
+        for (int hd = 0; hd < dims.n_heads; hd++) { h.push_back(l); h.push_back(hd); }
+    if (h.empty())   // (a model whose layers are wider than the limit: the first heads of the top layer)
+        for (int hd = 0; hd < std::min<int>(dims.n_heads, WH_MAX_ALIGN_HEADS); hd++) { h.push_back(dims.dec_layers - 1); h.push_back(hd); }
+    return h;
+}
+// the last decode call's token frames: frames [n][max_new], 0 past a window's end
+static void fetch_frames(wh_ctx* ctx, size_t n, size_t max_new, std::vector<int32_t>& frames) {
+    frames.assign(std::max<size_t>(1, n) * max_new, 0);
+    size_t got = 0;
+    if (int rc = wh_get_token_frames(ctx, frames.data(), max_new, nullptr, n, &got)) throw std::runtime_error(std::string("wh_get_token_frames: ") + std::to_string(rc));
+    if (got != n) throw std::runtime_error("wh_get_token_frames: " + std::to_string(got) + " windows, expected " + std::to_string(n));
+}
+// one window's words and token times (seconds from the start of the file) appended to the file's
+struct WordOut { std::vector<Word> words; std::vector<double> token_times; };
+static void window_words(const Args& a, const std::vector<int64_t>& g, const int32_t* frames, const WhisperSpecial& sp, double duration, double offset,
+                         const Tokenizer* tok, WordOut& out) {
+    const std::vector<int32_t> fr(frames, frames + g.size());
+    // (what the row's text keeps is a word: without --timestamp-rules the text keeps ids at and above timestamp_begin too)
+    std::vector<Word> w = words_from_tokens(g, fr, a.timestamp_rules ? sp.timestamp_begin : -1, sp.eot, duration, offset, tok);
+    out.words.insert(out.words.end(), w.begin(), w.end());
+    for (size_t i = 0; i < g.size(); i++) out.token_times.push_back(std::min(duration, fr[i] * 0.02) + offset);
+}
+static std::string times_json(const std::vector<double>& t) {
+    std::string o = "[";
+    char b[32];
+    for (size_t i = 0; i < t.size(); i++) { snprintf(b, sizeof b, "%s%.2f", i ? ", " : "", t[i]); o += b; }
+    return o + "]";
+}
+
 static void fetch_logprobs(wh_ctx* ctx, size_t n, size_t max_new, std::vector<float>& lp, std::vector<float>& ns) {
     lp.assign(std::max<size_t>(1, n) * max_new, 0.0f);
     ns.assign(std::max<size_t>(1, n), 0.0f);
@@ -381,7 +444,7 @@ static void cues_conf(std::vector<Cue>& cues, double avg_lp, double ns) {
 
 static std::string transcribe(wh_ctx* ctx, const std::vector<float>& audio, const Args& a, const Tokenizer* tok,
                               const GenCfg& gen, Timing& t, std::vector<Cue>* cues = nullptr, Conf* conf = nullptr,
-                              const LanguageTable* lt = nullptr, Lang* lang = nullptr, const std::vector<int64_t>* prefix = nullptr) {
+                              const LanguageTable* lt = nullptr, Lang* lang = nullptr, const std::vector<int64_t>* prefix = nullptr, WordOut* words = nullptr) {
     const double t0 = now_s();
     if (a.prompts()) {   // the file's text context, on its first window or on every one (no context: an empty prefix)
         const size_t offs[2] = {0, prefix ? prefix->size() : 0};
@@ -411,10 +474,12 @@ static std::string transcribe(wh_ctx* ctx, const std::vector<float>& audio, cons
     std::vector<float> lps, nss;
     if (a.logprobs) fetch_logprobs(ctx, got, a.max_new_tokens, lps, nss);
     if (lt && lang && got) *lang = fetch_languages(ctx, got, *lt)[0];   // the file's language: its first window's
+    std::vector<int32_t> frames;
+    if (a.word_timestamps) fetch_frames(ctx, got, a.max_new_tokens, frames);
     const double td0 = now_s();
     std::vector<std::string> texts;
     std::vector<size_t> offs(std::max<size_t>(1, got));
-    if (a.timestamp_rules) wh_longform_plan(audio.size(), a.chunk_length_s, a.overlap_s, offs.data(), offs.size(), &nch);
+    if (a.timestamp_rules || a.word_timestamps) wh_longform_plan(audio.size(), a.chunk_length_s, a.overlap_s, offs.data(), offs.size(), &nch);
     std::vector<std::vector<Segment>> wsegs;
     std::vector<double> wstart;
     for (size_t c = 0; c < got; c++) {  // :926-943
@@ -424,6 +489,10 @@ static std::string transcribe(wh_ctx* ctx, const std::vector<float>& audio, cons
         Conf unused;
         const bool skip = a.logprobs && window_conf(a, g, lps.data() + c * a.max_new_tokens, nss[c], sp.eot, conf ? *conf : unused, avg_lp);
         if (skip) g.clear();   // the silence rule: empty text, no segments
+        if (a.word_timestamps && words) {
+            const size_t wlen = std::min<size_t>(audio.size() - offs[c], (size_t)std::llround(a.chunk_length_s * 16000.0));
+            window_words(a, g, frames.data() + c * a.max_new_tokens, sp, (double)wlen / 16000.0, (double)offs[c] / 16000.0, tok, *words);
+        }
         if (!g.empty() && g.back() == sp.eot) g.pop_back();
         if (a.timestamp_rules) {
             const size_t len = std::min<size_t>(audio.size() - offs[c], (size_t)std::llround(a.chunk_length_s * 16000.0));
@@ -531,6 +600,14 @@ int main(int argc, char** argv) {
                     if (int rc = wh_ctx_set_repetition(c, &ro))
                         throw std::runtime_error(std::string("wh_ctx_set_repetition: ") + std::to_string(rc) + ": " + wh_last_error(c));
                 }
+                if (a.word_timestamps) {   // word-level timestamps on every context (no reference counterpart)
+                    wh_dims dims{};
+                    wh_model_get_dims(m, &dims);
+                    const std::vector<int32_t> heads = alignment_heads(a, gen, dims);
+                    wh_alignment_opts ao{sizeof(wh_alignment_opts), heads.data(), heads.size() / 2, nullptr, 0};
+                    if (int rc = wh_ctx_set_alignment(c, &ao))
+                        throw std::runtime_error(std::string("wh_ctx_set_alignment: ") + std::to_string(rc) + ": " + wh_last_error(c));
+                }
                 if (lang_auto) {   // each clip's language from the logits at <|startoftranscript|> (prompt position 0), decoded into position 1
                     wh_language_opts lo{sizeof(wh_language_opts), lang_table.ids.data(), lang_table.ids.size(), 0};
                     if (int rc = wh_ctx_set_language_detection(c, &lo))
@@ -602,7 +679,7 @@ int main(int argc, char** argv) {
                             return hipHostMalloc((void**)&p, (size_t)WH_CLIP_SAMPLES * sizeof(float), hipHostMallocDefault) == hipSuccess ? p : nullptr;
                         },
                         [](float* p) { (void)hipHostFree(p); });
-        struct Result { std::string text; double dur = 0, load_s = 0; Timing t; bool ok = false; std::vector<Cue> cues; Conf conf; Lang lang; };
+        struct Result { std::string text; double dur = 0, load_s = 0; Timing t; bool ok = false; std::vector<Cue> cues; Conf conf; Lang lang; WordOut words; };
         const size_t nfiles = files.size();
         std::vector<Result> results(nfiles);
         const unsigned hc = std::thread::hardware_concurrency();
@@ -618,7 +695,7 @@ int main(int argc, char** argv) {
             if (batch.size() == 1 && batch[0].n() > (size_t)WH_CLIP_SAMPLES) {
                 // a file longer than one window goes alone through the long-form entry (which batches its windows)
                 Result& r = results[batch[0].idx];
-                r.text = transcribe(ctx, batch[0].audio, a, &tok, gen, r.t, &r.cues, &r.conf, lang_auto ? &lang_table : nullptr, &r.lang, &file_prefix[batch[0].idx]);
+                r.text = transcribe(ctx, batch[0].audio, a, &tok, gen, r.t, &r.cues, &r.conf, lang_auto ? &lang_table : nullptr, &r.lang, &file_prefix[batch[0].idx], &r.words);
                 r.dur = batch[0].dur; r.load_s = batch[0].load_s; r.ok = true;
             } else {
                 // the per-window body of transcribe_longform_chunked (:870-915) for a batch of one-window files
@@ -652,6 +729,8 @@ int main(int argc, char** argv) {
                 if (a.logprobs) fetch_logprobs(ctx, batch.size(), a.max_new_tokens, lps, nss);
                 std::vector<Lang> langs;
                 if (lang_auto) langs = fetch_languages(ctx, batch.size(), lang_table);
+                std::vector<int32_t> frames;
+                if (a.word_timestamps) fetch_frames(ctx, batch.size(), a.max_new_tokens, frames);
                 for (size_t k = 0; k < batch.size(); k++) {   // :926-943
                     Result& r = results[batch[k].idx];
                     if (lang_auto) r.lang = langs[k];
@@ -661,6 +740,14 @@ int main(int argc, char** argv) {
                     double avg_lp = 0;
                     const bool skip = a.logprobs && window_conf(a, g, lps.data() + k * a.max_new_tokens, nss[k], sp.eot, r.conf, avg_lp);
                     if (skip) g.clear();   // the silence rule: empty text, no segments
+                    if (a.word_timestamps) {
+                        window_words(a, g, frames.data() + k * a.max_new_tokens, sp, batch[k].dur, 0.0, &tok, r.words);
+                        // a one-window file's text is trimmed: so are the ends of its words, which then concatenate to the text
+                        if (!r.words.words.empty()) {
+                            r.words.words.front().word = ltrim(r.words.words.front().word);
+                            r.words.words.back().word = rtrim(r.words.words.back().word);
+                        }
+                    }
                     if (!g.empty() && g.back() == sp.eot) g.pop_back();
                     if (a.timestamp_rules) {
                         if (!skip) r.cues = to_cues(window_segments(g, sp, batch[k].dur), &tok);
@@ -699,6 +786,7 @@ int main(int argc, char** argv) {
             const double end_to_end = r.load_s + r.t.end_to_end_s;   // :1190
             rows.push_back(make_row(files[i], r.dur, end_to_end, r.text));
             if (a.timestamp_rules) rows.back().segments = cues_json(r.cues);
+            if (a.word_timestamps) { rows.back().words = words_json(r.words.words); rows.back().token_times = times_json(r.words.token_times); }
             if (a.prompts()) { rows.back().has_prompt = true; rows.back().prompt_tokens = (long long)file_prefix[i].size(); }
             if (r.lang.has) { rows.back().has_lang = true; rows.back().language = r.lang.code; rows.back().language_probability = r.lang.prob; }
             if (r.conf.has) { rows.back().has_conf = true; rows.back().avg_logprob = r.conf.avg_logprob(); rows.back().no_speech_prob = r.conf.no_speech_prob(); }
