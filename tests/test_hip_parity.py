@@ -445,6 +445,18 @@ def test_split_fp16_encoder_state_kernels(gpu, golden_dir):
     assert r.returncode == 0, r.stdout + r.stderr
 
 
+def test_bf16_and_fp16_limb_encoder_state_kernels(gpu):
+    """k_dec_cross_attn_es (bf16 states) and k_dec_cross_attn_es2 (two fp16 limb planes) alone against a float64 host restatement (tools/es16_check):
+    fewer tiles than the ring is deep, the full context, the persistent walk over several clips per workgroup, a cut last tile."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = os.path.join(root, "tools", "es16_check")
+    assert os.path.exists(exe), f"{exe} missing: __graft_entry__.build() compiles it"
+    r = subprocess.run([exe, "64"], capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0 and "MISMATCH" not in r.stdout, r.stdout + r.stderr
+
+
 def test_bf16_batch_is_deterministic_and_permutation_invariant(gpu):
     b = bundle("micro", 11, wb.WH_PREC_BF16, max_batch=16)
     prompt, eot = small_prompt(b.dims)

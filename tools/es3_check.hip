@@ -16,6 +16,11 @@ static float e4m3(unsigned char b) {
 static unsigned rs = 777;
 static unsigned rnd() { rs = rs * 1664525u + 1013904223u; return rs >> 8; }
 static float frand(float a) { return ((int)(rnd() & 0xffff) - 32768) / 32768.0f * a; }
+static unsigned long long fnv1a(const void* p, size_t n) {   // 64-bit FNV-1a of the raw output buffer: equal across builds that compute the same bits
+    unsigned long long h = 1469598103934665603ull;
+    for (size_t i = 0; i < n; i++) { h ^= ((const unsigned char*)p)[i]; h *= 1099511628211ull; }
+    return h;
+}
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
 
 // f32 rows [rows][512] -> E3 rows (the conversion of k_layernorm_es3 without the LayerNorm)
@@ -71,7 +76,7 @@ static int check(int B, int S, int n_cus) {
         }
     }
     const bool ok = worst <= 2e-4 * scale + 1e-6;
-    printf("check B %3d S %4d on %3d workgroups: max |ctx - host| %.3e (|ctx| up to %.3f; the states' own rounding: %.2e)  %s\n", B, S, std::min(B, n_cus), worst, scale, quant, ok ? "ok" : "MISMATCH");
+    printf("check B %3d S %4d on %3d workgroups: max |ctx - host| %.3e (|ctx| up to %.3f; the states' own rounding: %.2e)  %s  hash %016llx\n", B, S, std::min(B, n_cus), worst, scale, quant, ok ? "ok" : "MISMATCH", fnv1a(out.data(), out_b));
     hipFree(dEf); hipFree(dE); hipFree(dq); hipFree(dout);
     return ok ? 0 : 1;
 }

@@ -17,6 +17,11 @@ static float e4m3(unsigned char b) {   // OCP e4m3fn
 }
 static unsigned rs = 4242;
 static unsigned rnd() { rs = rs * 1664525u + 1013904223u; return rs >> 8; }
+static unsigned long long fnv1a(const void* p, size_t n) {   // 64-bit FNV-1a of the raw output buffer: equal across builds that compute the same bits
+    unsigned long long h = 1469598103934665603ull;
+    for (size_t i = 0; i < n; i++) { h ^= ((const unsigned char*)p)[i]; h *= 1099511628211ull; }
+    return h;
+}
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
 
 static int check(int B, int S, int n_cus) {
@@ -58,7 +63,7 @@ static int check(int B, int S, int n_cus) {
             }
         }
     const bool ok = worst <= 0.02 * scale + 1e-3;
-    printf("check B %3d S %4d on %3d workgroups: max |ctx - host| %.3e (|ctx| up to %.3f)  %s\n", B, S, std::min(B, n_cus), worst, scale, ok ? "ok" : "MISMATCH");
+    printf("check B %3d S %4d on %3d workgroups: max |ctx - host| %.3e (|ctx| up to %.3f)  %s  hash %016llx\n", B, S, std::min(B, n_cus), worst, scale, ok ? "ok" : "MISMATCH", fnv1a(out.data(), out_n * 2));
     hipFree(dE); hipFree(dq); hipFree(dout);
     return ok ? 0 : 1;
 }

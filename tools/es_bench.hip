@@ -11,6 +11,10 @@
 bool wh_ensure_dyn_lds(const void* kernel, size_t bytes) {
     return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
 }
+// the other formats' kernels live in their own files: the dispatcher's references to them are never taken here (bf16 only)
+bool wh_es3_enabled() { return false; }
+void wh_launch_dec_cross_attn_es3(hipStream_t, const float*, const void*, void*, int, int, int, int, bool, int) { abort(); }
+void wh_launch_dec_cross_attn_es8(hipStream_t, const float*, const void*, void*, int, int, int, int, bool, int) { abort(); }
 
 int main(int argc, char** argv) {
     const int B = argc > 1 ? atoi(argv[1]) : 1024, reps = argc > 2 ? atoi(argv[2]) : 30, S = 1500, d = 512, H = 8;

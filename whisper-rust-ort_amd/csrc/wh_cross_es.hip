@@ -47,35 +47,17 @@
 #include <algorithm>
 
 #include "wh_common.h"
+#include "wh_es_common.h"
 #include "wh_kernels.h"
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
+using namespace wh_es;
 
-constexpr int ES_D = 512, ES_H = 8, ES_TK = 32, ES_NSTAGE = 4;
+constexpr int ES_D = D, ES_H = H;
 constexpr int ES_ROWB = ES_D * 2;                      // bytes per key row
-constexpr int ES_TILEB = ES_TK * ES_ROWB;              // 32 KiB
-constexpr int ES_SCP = 36;                             // floats per (dim half, head) row of the score exchange (32 keys + pad)
-constexpr int ES_SCB = 4 * ES_H * ES_SCP;             // floats per score-exchange buffer: [dim half][hi | lo of the query][head][ES_SCP]
-constexpr int ES_LDS = ES_NSTAGE * ES_TILEB + 2 * ES_SCB * 4 + ES_H * ES_D * 4;   // ring + score exchange + next queries = 153 KiB
-
-template <int N> __device__ __forceinline__ void es_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-template <int AUX>
-__device__ __forceinline__ void es_glds16(const void* src, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)lds_wave_base, 16, 0, AUX);
-}
-
-__device__ __forceinline__ float es_sum32(float v) {   // v(lane) + v(lane ^ 32), in every lane (tools/cross_es2_proto.hip.txt)
-    const wh_u32x2 t = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(t.x) + __uint_as_float(t.y);
-}
-
-__device__ __forceinline__ float es_ror8(float v) {    // v of lane ^ 8 (same 16-lane row): DPP row_ror:8
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, true));
-}
+// ring of four 32-key tiles of 32 KiB; exchange rows [dim half][hi | lo of the query][head][32 keys + pad]; 153 KiB with the next queries
+constexpr Format ES_F = {32, 32 * ES_ROWB, 4, true, 36};
 
 // qe : [B][8][512] f32 expanded queries (natural-log score units)        E: [B][e_rows][512] bf16 encoder states (final LayerNorm applied),
 // e_rows >= S: the clips' states sit e_rows rows apart (20 rows of padding take the lock-step streams off a common 4 KiB phase, wh_api.cpp)
@@ -96,74 +78,47 @@ __device__ __forceinline__ float es_ror8(float v) {    // v of lane ^ 8 (same 16
 template <int AUX, int NL, int ABL = 0>   // ABL (tools/es_bench.hip only): 1 = ring, waits and barriers only; 2 = phase stamps (s_memtime) of workgroup 0 into dbg
 __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es(const float* __restrict__ qe, const bf16* __restrict__ E,
                                                                          bf16* __restrict__ out, int S, int e_rows, int mpad, int B, unsigned long long* dbg) {
-    constexpr int NSTAGE = ES_NSTAGE, LA = NSTAGE - 1;   // LA tiles staged ahead of the one being consumed
-    static_assert(NSTAGE == 4 && (NL == 1 || NL == 2), "ring of four 32-key slots; one or two loader waves");
+    constexpr int TK = ES_F.tk, TILEB = ES_F.tileb, SCP = ES_F.scp;
+    static_assert(NL == 1 || NL == 2, "one or two loader waves");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* sc = reinterpret_cast<float*>(smem + NSTAGE * ES_TILEB);   // [2 tiles][ES_SCB]
-    float* Qs = sc + 2 * ES_SCB;                               // [8][512] f32: the next clip's expanded queries
+    float* sc = carve<ES_F>(smem).sc;
+    float* Qs = carve<ES_F>(smem).Qs;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ntile = (S + ES_TK - 1) / ES_TK;
-    const int G = gridDim.x;
-    const int n_my = (B - (int)blockIdx.x + G - 1) / G;   // clips of this workgroup
-    const int total = n_my * ntile;                        // tiles of this workgroup
+    Walk<ES_F> w(S, B);   // the walk of this workgroup: every wave of either role follows it
 
     if (wave >= 4) {
-        // ================================ loader ================================
-        constexpr int PPT = ES_TK / NL;          // pieces (1 KiB key rows) per loader wave and tile
-        constexpr int QPP = 16 / NL;             // pieces of a clip's 16 KiB of queries per loader wave
+        // ================================ loader: a piece is a key row ================================
+        constexpr int PPT = TK / NL;
         const int lw = wave - 4;
         int voff[PPT];   // byte offset of this lane's 16 bytes of row lw * PPT + j inside a tile (the same for every tile: 32 % 16 == 0)
 #pragma unroll
         for (int j = 0; j < PPT; j++) voff[j] = (lw * PPT + j) * ES_ROWB + ((lane ^ ((lw * PPT + j) & 15)) << 4);
-        int st_clip = blockIdx.x, st_t = 0, st_slot = 0;   // tiles are staged strictly in sequence
-        auto stage_next = [&]() {
-            char* base = smem + st_slot * ES_TILEB;
-            const char* Et = reinterpret_cast<const char*>(E) + ((long)st_clip * e_rows + (long)st_t * ES_TK) * ES_ROWB;   // wave-uniform
-            if (st_t * ES_TK + ES_TK <= S) {
+        auto issue = [&](char* base, int clip, int t) __attribute__((always_inline)) {
+            const char* Et = reinterpret_cast<const char*>(E) + ((long)clip * e_rows + (long)t * TK) * ES_ROWB;   // wave-uniform
+            if (t * TK + TK <= S) {
 #pragma unroll
-                for (int j = 0; j < PPT; j++) es_glds16<AUX>(Et + voff[j], base + (lw * PPT + j) * ES_ROWB);
+                for (int j = 0; j < PPT; j++) glds16<AUX>(Et + voff[j], base + (lw * PPT + j) * ES_ROWB);
             } else {   // the clip's last tile: rows past the end re-read the last key (finite; their scores are masked)
 #pragma unroll
                 for (int j = 0; j < PPT; j++) {
                     const int r = lw * PPT + j;
-                    const int key = min(st_t * ES_TK + r, S - 1);
-                    es_glds16<AUX>(reinterpret_cast<const char*>(E) + ((long)st_clip * e_rows + key) * ES_ROWB + ((lane ^ (r & 15)) << 4), base + r * ES_ROWB);
+                    const int key = min(t * TK + r, S - 1);
+                    glds16<AUX>(reinterpret_cast<const char*>(E) + ((long)clip * e_rows + key) * ES_ROWB + ((lane ^ (r & 15)) << 4), base + r * ES_ROWB);
                 }
             }
-            st_slot = st_slot + 1 == NSTAGE ? 0 : st_slot + 1;
-            if (++st_t == ntile) { st_t = 0; st_clip += G; }
         };
-        auto stage_q = [&](int clip) {
-            const float* src = qe + (long)clip * (ES_H * ES_D);
-#pragma unroll
-            for (int j = 0; j < QPP; j++) es_glds16<0>(src + ((lw * QPP + j) * 64 + lane) * 4, reinterpret_cast<char*>(Qs) + (lw * QPP + j) * 1024);
-        };
-        stage_q(blockIdx.x);
-#pragma unroll
-        for (int t = 0; t < LA; t++)
-            if (t < total) stage_next();
-        // vmcnt retires in issue order (and holds at most 63): "all but the last two tiles' pieces" covers the queries and tile 0
-        if (total >= LA) es_wait_vm<(PPT * (LA - 1) < 63 ? PPT * (LA - 1) : 63)>(); else es_wait_vm<0>();
-        __builtin_amdgcn_s_barrier();   // P1: the first clip's queries are in Qs
-        __builtin_amdgcn_s_barrier();   // P2: tile 0 is in the ring
-        int clip = blockIdx.x, t = 0;
-        unsigned long long lt[4] = {0, 0, 0, 0};
-        for (int g = 0; g < total; g++) {
-            unsigned long long c0 = 0, c1 = 0, c2 = 0;
-            if constexpr (ABL & 2) c0 = __builtin_amdgcn_s_memtime();
-            if (g + 1 < total) {   // tile g + 1 has landed; the younger tiles stay in flight.  Conservative where the next clip's
-                                   // queries are among the younger loads: the count then also covers a few pieces of tile g + 2.
-                if (total - 2 - g >= LA - 2) es_wait_vm<PPT*(LA - 2)>(); else es_wait_vm<0>();
+        // ABL & 2: cycles of the vmcnt wait, the barrier and the piece issue, and the tile count
+        unsigned long long lt[4] = {0, 0, 0, 0}, last = 0;
+        auto stamp = [&](int phase) {
+            if constexpr (ABL & 2) {
+                const unsigned long long now = __builtin_amdgcn_s_memtime();
+                if (phase > 0) lt[phase - 1] += now - last;
+                if (phase == 3) lt[3] += 1;
+                last = now;
             }
-            if constexpr (ABL & 2) c1 = __builtin_amdgcn_s_memtime();
-            __builtin_amdgcn_s_barrier();
-            if constexpr (ABL & 2) c2 = __builtin_amdgcn_s_memtime();
-            if (g + LA < total) stage_next();
-            if (t == 0 && clip + G < B) stage_q(clip + G);   // Qs was read (if at all) before this barrier
-            if (++t == ntile) { t = 0; clip += G; }
-            if constexpr (ABL & 2) { lt[0] += c1 - c0; lt[1] += c2 - c1; lt[2] += __builtin_amdgcn_s_memtime() - c2; lt[3] += 1; }
-        }
+        };
+        loader<ES_F, NL>(smem, qe, lw, lane, B, w, issue, stamp);
         if constexpr (ABL & 2) {
             if (blockIdx.x == 0 && lane == 0 && dbg) { for (int i = 0; i < 4; i++) dbg[8 + 4 * (wave - 4) + i] = lt[i]; }
         }
@@ -177,32 +132,19 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es(const fl
     // rows 8-15 the bf16 remainders (qe = hi + lo to ~16 mantissa bits)
     bf16x8 qa[8];
     auto qa_from_lds = [&]() {
-        const float* qp = Qs + (fl & 7) * ES_D + 256 * hf + 8 * fg;
         const bool lo = fl >= 8;
+        read_queries<true>(Qs, fl, fg, hf, [&](int s, const float (&v)[8]) {
 #pragma unroll
-        for (int s0 = 0; s0 < 8; s0 += 4) {   // eight reads in flight at a time (left alone, the compiler keeps two)
-            f32x4 q[4][2];
-#pragma unroll
-            for (int s = 0; s < 4; s++) {
-                q[s][0] = *reinterpret_cast<const f32x4*>(qp + 32 * (s0 + s));
-                q[s][1] = *reinterpret_cast<const f32x4*>(qp + 32 * (s0 + s) + 4);
+            for (int u = 0; u < 8; u++) {
+                const bf16 h = (bf16)v[u];
+                qa[s][u] = lo ? (bf16)(v[u] - (float)h) : h;
             }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int s = 0; s < 4; s++)
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    const float v = q[s][u >> 2][u & 3] * 1.44269504088896341f;   // scores in log2 units: p = exp2(s - m)
-                    const bf16 h = (bf16)v;
-                    qa[s0 + s][u] = lo ? (bf16)(v - (float)h) : h;
-                }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        });
     };
     // ---- scores of the tile in slot `sl` for keys 16 kt + fl over dims 256 hf ..: rows 4 fg + i of D; partials to sc buffer `buf`
     auto score_reads = [&](int sl, bf16x8 (&ef)[8]) {
         const int r = 16 * kt + fl;
-        const char* rp = smem + sl * ES_TILEB + r * ES_ROWB;
+        const char* rp = smem + sl * TILEB + r * ES_ROWB;
 #pragma unroll
         for (int s = 0; s < 8; s++) {
             const int c = 32 * hf + 4 * s + fg;
@@ -218,52 +160,42 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es(const fl
         }
         // rows 0-7 (lane groups 0, 1) carry hi(qe), rows 8-15 (groups 2, 3) lo(qe): both go to the exchange buffer as they are (the
         // readers add the four partials of a score: two dim halves x {hi, lo}) — cheaper than adding lane and lane ^ 32 here
-        float* dst = sc + buf * ES_SCB + ((hf * 2 + (fg >> 1)) * ES_H + 4 * (fg & 1)) * ES_SCP + 16 * kt + fl;
+        float* dst = exch_dst<ES_F>(sc, buf, hf * 2 + (fg >> 1), fg, 16 * kt + fl);
 #pragma unroll
-        for (int i = 0; i < 4; i++) dst[i * ES_SCP] = d0[i] + d1[i];
+        for (int i = 0; i < 4; i++) dst[i * SCP] = d0[i] + d1[i];
     };
 
     f32x4 acc[8];   // rows 4 fg + i: heads 4 fg + i in lane groups 0 and 1 (the P operand's rows 8-15 are zero)
     float m_run = -INFINITY, l_run = 0.0f;
     const int kb = 16 * (fg & 1) + 8 * (fg >> 1);   // first key (within a tile) of this lane's contraction slots
-    int clip = blockIdx.x, t = 0, slot = 0;          // the tile being consumed: tile t of `clip`, ring slot `slot`
 
-    __builtin_amdgcn_s_barrier();   // P1
-    qa_from_lds();
-    __builtin_amdgcn_s_barrier();   // P2
+    prologue_barriers<ES_F>(qa_from_lds);
     if constexpr (!(ABL & 1)) {     // scores of tile 0
         bf16x8 ef[8];
         score_reads(0, ef);
         score_mfma(ef, 0);
     }
-#pragma unroll
-    for (int e = 0; e < 8; e++) acc[e] = f32x4{0, 0, 0, 0};
+    clear(acc);
     unsigned long long ct[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int g = 0; g < total; g++) {
-        const bool more = g + 1 < total;
+    for (; !w.done(); w.next()) {
+        const bool more = w.more();
         unsigned long long c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0;
         if constexpr (ABL & 2) c0 = __builtin_amdgcn_s_memtime();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();   // tile g + 1 and the scores of tile g visible to all; every wave is done with tile g - 1
+        tile_barrier();
         if constexpr (ABL & 2) c1 = __builtin_amdgcn_s_memtime();
-        const int nslot = slot + 1 == NSTAGE ? 0 : slot + 1;
         if constexpr (ABL & 1) {
-            slot = nslot;
-            if (++t == ntile) { t = 0; clip += G; }
+            if (w.advance()) w.next_clip();
             continue;
         }
-        // the next clip's first tile is scored with the next clip's queries (in Qs since a clip ago)
-        if (t == ntile - 1 && more) qa_from_lds();
-        const char* tb = smem + slot * ES_TILEB;
+        if (w.next_queries()) qa_from_lds();   // (in Qs since a clip ago)
+        const char* tb = smem + w.slot * TILEB;
         // ---- every LDS read of this iteration up front, in the order of use (LDS returns in order, so each consumer waits only
         // for what it needs): scores of tile g (softmax), score operands of tile g + 1, the 8 x 8 blocks of tile g (output)
         // lanes fl and fl + 8 share a head (the operand's rows 8-15 are zero): each takes four of the lane group's eight keys
         const int h = fl & 7, kq = kb + 4 * (fl >> 3);
-        const float* s0 = sc + (g & 1) * ES_SCB + h * ES_SCP + kq;
-        const f32x4 a0 = *reinterpret_cast<const f32x4*>(s0), a1 = *reinterpret_cast<const f32x4*>(s0 + ES_H * ES_SCP);
-        const f32x4 b0 = *reinterpret_cast<const f32x4*>(s0 + 2 * ES_H * ES_SCP), b1 = *reinterpret_cast<const f32x4*>(s0 + 3 * ES_H * ES_SCP);
+        const Partials sp = exch_read<ES_F>(sc, w.g & 1, h, kq);
         bf16x8 ef[8];
-        if (more) score_reads(nslot, ef);
+        if (more) score_reads(w.nslot(), ef);
         wh_u32x4 blk[8];
         {
             const int cs = (16 * wave + fl);
@@ -279,60 +211,26 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es(const fl
         bf16x8 pa;
         {
             float sv[4];
-            float tmax = -INFINITY;
-            const int key0 = t * ES_TK + kq;
 #pragma unroll
-            for (int u = 0; u < 4; u++) sv[u] = (a0[u] + a1[u]) + (b0[u] + b1[u]);
-            if (t == ntile - 1) {   // (wave-uniform) keys past the end of the clip
-#pragma unroll
-                for (int u = 0; u < 4; u++) sv[u] = (key0 + u < S) ? sv[u] : -INFINITY;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) tmax = fmaxf(tmax, sv[u]);
-            tmax = fmaxf(tmax, es_ror8(tmax));   // the head's other four keys of this lane group
-            tmax = xrow_max(tmax);               // over the four lane groups: all 32 keys of the tile
-            const float m_new = fmaxf(m_run, tmax);
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // first tile: exp2(-inf) = 0
-            float ps = 0.0f;
-            float pv[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                pv[u] = __builtin_amdgcn_exp2f(sv[u] - m_new);   // masked key: exp2(-inf) = 0
-                ps += pv[u];
-            }
+            for (int u = 0; u < 4; u++) sv[u] = (sp.p[0][u] + sp.p[1][u]) + (sp.p[2][u] + sp.p[3][u]);
+            const Soft sm = softmax_tile(sv, w.t * TK + kq, S, w.last_tile(), m_run);
             // rows 0-7 carry bf16(p) of keys kb .. kb + 7: this lane's four and, through DPP, its partner's; rows 8-15 stay zero (a
             // remainder row would be lost in the bf16 rounding of the output anyway)
             {
-                const bf16x2 p01 = {(bf16)pv[0], (bf16)pv[1]}, p23 = {(bf16)pv[2], (bf16)pv[3]};
+                const bf16x2 p01 = {(bf16)sm.pv[0], (bf16)sm.pv[1]}, p23 = {(bf16)sm.pv[2], (bf16)sm.pv[3]};
                 unsigned own0, own1;
                 __builtin_memcpy(&own0, &p01, 4);
                 __builtin_memcpy(&own1, &p23, 4);
-                const unsigned oth0 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)own0, 0x128, 0xF, 0xF, true);   // row_ror:8 = lane fl ^ 8 of the row
-                const unsigned oth1 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)own1, 0x128, 0xF, 0xF, true);
+                const unsigned oth0 = ror8u(own0), oth1 = ror8u(own1);   // lane fl ^ 8 of the row
                 const bool hi = fl < 8;
                 const wh_u32x4 pw = {hi ? own0 : 0u, hi ? own1 : 0u, hi ? oth0 : 0u, hi ? oth1 : 0u};
                 __builtin_memcpy(&pa, &pw, 16);
             }
-            l_run = l_run * alpha + ps;
-            m_run = m_new;
-            // the accumulators hold rows 4 fg + i = heads 4 fg + i (fg < 2); head h's factor sits in lane h: through SGPRs (v_readlane),
-            // and only when some running maximum moved (wave-uniform)
-            if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
-                float ah[8];
-#pragma unroll
-                for (int q = 0; q < 8; q++) ah[q] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, alpha), q));
-                const bool up = fg & 1;
-                const float a4[4] = {up ? ah[4] : ah[0], up ? ah[5] : ah[1], up ? ah[6] : ah[2], up ? ah[7] : ah[3]};
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-#pragma unroll
-                    for (int i = 0; i < 4; i++) acc[e][i] *= a4[i];
-                }
-            }
+            rescale(sm, fg, l_run, acc);
         }
         if constexpr (ABL & 2) { asm volatile("" :: "v"(pa) : "memory"); c3 = __builtin_amdgcn_s_memtime(); }
         // ---- scores of tile g + 1 (independent of everything above: fills the matrix pipe while the VALU transposes)
-        if (more) score_mfma(ef, (g + 1) & 1);
+        if (more) score_mfma(ef, (w.g + 1) & 1);
         if constexpr (ABL & 2) { asm volatile("" ::: "memory"); c4 = __builtin_amdgcn_s_memtime(); }
         // ---- output of tile g: dims 128 wave + 8 fl + e, contraction over the tile's 32 keys
 #pragma unroll
@@ -351,35 +249,26 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es(const fl
             asm volatile("" :: "v"(acc[7]) : "memory");
             ct[0] += c1 - c0; ct[1] += c2 - c1; ct[2] += c3 - c2; ct[3] += c4 - c3; ct[4] += __builtin_amdgcn_s_memtime() - c4; ct[5] += 1;
         }
-        slot = nslot;
-        if (++t < ntile) continue;
+        if (!w.advance()) continue;
         // ---- the clip ends: normalise and store (rows 0-7 = lane groups 0 and 1)
         {
-            const float lh = l_run + es_ror8(l_run);   // the head's two key quartets
-            const float inv = 1.0f / xrow_sum(lh);
-            float ih[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++) ih[q] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inv), q));
+            float inv4[4];
+            clip_inv4(l_run, fg, inv4);
             if (fg < 2) {
-                const bool up = fg & 1;
-                const float inv4[4] = {up ? ih[4] : ih[0], up ? ih[5] : ih[1], up ? ih[6] : ih[2], up ? ih[7] : ih[3]};
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
-                    const int k = (4 * fg + i) * ES_D + 128 * wave + 8 * fl;
                     bf16x8 ov;
 #pragma unroll
                     for (int e = 0; e < 8; e++) ov[e] = (bf16)(acc[e][i] * inv4[i]);
-                    *reinterpret_cast<bf16x8*>(out + ((long)(k >> 5) * mpad + clip) * 32 + (k & 31)) = ov;
+                    *reinterpret_cast<bf16x8*>(slab_dst(out, fg, i, wave, fl, mpad, w.clip)) = ov;
                 }
             }
         }
         // the next clip starts from nothing
-#pragma unroll
-        for (int e = 0; e < 8; e++) acc[e] = f32x4{0, 0, 0, 0};
+        clear(acc);
         m_run = -INFINITY;
         l_run = 0.0f;
-        t = 0;
-        clip += G;
+        w.next_clip();
     }
     if constexpr (ABL & 2) {
         if (blockIdx.x == 0 && tid == 0 && dbg) { for (int i = 0; i < 6; i++) dbg[i] = ct[i]; }
@@ -439,32 +328,25 @@ __global__ __launch_bounds__(256) void k_dec_qexpand(const float* __restrict__ q
 // lo.lo term; rows h and h + 8 are added where they leave the matrix core.  Per 32 KiB tile (16 keys) the work of a wave is what the
 // bf16 kernel does per 32 KiB tile (32 keys): 8 + 8 MFMAs, 4 exp2, the same LDS reads — twice the time per clip for twice the bytes.
 // =====================================================================================================================================
-constexpr int E2_TK = 16;
 constexpr int E2_ROWB = 2 * ES_D * 2;                  // bytes per key row: hi plane, lo plane
-constexpr int E2_TILEB = E2_TK * E2_ROWB;              // 32 KiB
-constexpr int E2_SCP = 20;                             // floats per (wave, head) row of the score exchange (16 keys + pad)
-constexpr int E2_SCB = 4 * ES_H * E2_SCP;              // floats per score-exchange buffer: [wave = quarter of the 1,024 dims][head][E2_SCP]
-constexpr int E2_LDS = ES_NSTAGE * E2_TILEB + 2 * E2_SCB * 4 + ES_H * ES_D * 4;   // ring + score exchange + next queries = 149 KiB
+// ring of four 16-key tiles of 32 KiB; exchange rows [wave = quarter of the 1,024 dims][head][16 keys + pad]; 149 KiB with the next queries
+constexpr Format E2_F = {16, 16 * E2_ROWB, 4, true, 20};
 
 template <int AUX, int NL>
 __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es2(const float* __restrict__ qe, const _Float16* __restrict__ E,
                                                                           h2* __restrict__ out, int S, int e_rows, int mpad, int B) {
-    constexpr int NSTAGE = ES_NSTAGE, LA = NSTAGE - 1;
-    static_assert(NSTAGE == 4 && (NL == 1 || NL == 2), "ring of four 16-key slots; one or two loader waves");
+    constexpr int TK = E2_F.tk, TILEB = E2_F.tileb, SCP = E2_F.scp;
+    static_assert(NL == 1 || NL == 2, "one or two loader waves");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* sc = reinterpret_cast<float*>(smem + NSTAGE * E2_TILEB);   // [2 tiles][E2_SCB]
-    float* Qs = sc + 2 * E2_SCB;                                      // [8][512] f32: the next clip's expanded queries
+    float* sc = carve<E2_F>(smem).sc;
+    float* Qs = carve<E2_F>(smem).Qs;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ntile = (S + E2_TK - 1) / E2_TK;
-    const int G = gridDim.x;
-    const int n_my = (B - (int)blockIdx.x + G - 1) / G;
-    const int total = n_my * ntile;
+    Walk<E2_F> w(S, B);
 
     if (wave >= 4) {
-        // ================================ loader: 32 pieces of 1 KiB (half a key row) per tile ================================
-        constexpr int PPT = 2 * E2_TK / NL;
-        constexpr int QPP = 16 / NL;
+        // ================================ loader: a piece is half a key row ================================
+        constexpr int PPT = 2 * TK / NL;
         const int lw = wave - 4;
         int voff[PPT];   // byte offset of this lane's 16 bytes inside a tile: LDS chunk p of tile row r holds chunk p ^ r of the key row
 #pragma unroll
@@ -472,46 +354,20 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es2(const f
             const int pi = lw * PPT + j, r = pi >> 1, p = (pi & 1) * 64 + lane;
             voff[j] = r * E2_ROWB + ((p ^ r) << 4);
         }
-        int st_clip = blockIdx.x, st_t = 0, st_slot = 0;
-        auto stage_next = [&]() {
-            char* base = smem + st_slot * E2_TILEB;
-            const char* Et = reinterpret_cast<const char*>(E) + ((long)st_clip * e_rows + (long)st_t * E2_TK) * E2_ROWB;   // wave-uniform
-            if (st_t * E2_TK + E2_TK <= S) {
+        loader<E2_F, NL>(smem, qe, lw, lane, B, w, [&](char* base, int clip, int t) __attribute__((always_inline)) {
+            const char* Et = reinterpret_cast<const char*>(E) + ((long)clip * e_rows + (long)t * TK) * E2_ROWB;   // wave-uniform
+            if (t * TK + TK <= S) {
 #pragma unroll
-                for (int j = 0; j < PPT; j++) es_glds16<AUX>(Et + voff[j], base + (lw * PPT + j) * 1024);
+                for (int j = 0; j < PPT; j++) glds16<AUX>(Et + voff[j], base + (lw * PPT + j) * 1024);
             } else {   // the clip's last tile: rows past the end re-read the last key (finite; their scores are masked)
 #pragma unroll
                 for (int j = 0; j < PPT; j++) {
                     const int pi = lw * PPT + j, r = pi >> 1, p = (pi & 1) * 64 + lane;
-                    const int key = min(st_t * E2_TK + r, S - 1);
-                    es_glds16<AUX>(reinterpret_cast<const char*>(E) + ((long)st_clip * e_rows + key) * E2_ROWB + ((p ^ r) << 4), base + pi * 1024);
+                    const int key = min(t * TK + r, S - 1);
+                    glds16<AUX>(reinterpret_cast<const char*>(E) + ((long)clip * e_rows + key) * E2_ROWB + ((p ^ r) << 4), base + pi * 1024);
                 }
             }
-            st_slot = st_slot + 1 == NSTAGE ? 0 : st_slot + 1;
-            if (++st_t == ntile) { st_t = 0; st_clip += G; }
-        };
-        auto stage_q = [&](int clip) {
-            const float* src = qe + (long)clip * (ES_H * ES_D);
-#pragma unroll
-            for (int j = 0; j < QPP; j++) es_glds16<0>(src + ((lw * QPP + j) * 64 + lane) * 4, reinterpret_cast<char*>(Qs) + (lw * QPP + j) * 1024);
-        };
-        stage_q(blockIdx.x);
-#pragma unroll
-        for (int t = 0; t < LA; t++)
-            if (t < total) stage_next();
-        if (total >= LA) es_wait_vm<(PPT * (LA - 1) < 63 ? PPT * (LA - 1) : 63)>(); else es_wait_vm<0>();
-        __builtin_amdgcn_s_barrier();   // P1: the first clip's queries are in Qs
-        __builtin_amdgcn_s_barrier();   // P2: tile 0 is in the ring
-        int clip = blockIdx.x, t = 0;
-        for (int g = 0; g < total; g++) {
-            if (g + 1 < total) {   // tile g + 1 has landed; the younger tiles stay in flight
-                if (total - 2 - g >= LA - 2) es_wait_vm<PPT*(LA - 2)>(); else es_wait_vm<0>();
-            }
-            __builtin_amdgcn_s_barrier();
-            if (g + LA < total) stage_next();
-            if (t == 0 && clip + G < B) stage_q(clip + G);   // Qs was read (if at all) before this barrier
-            if (++t == ntile) { t = 0; clip += G; }
-        }
+        });
         return;
     }
 
@@ -521,31 +377,18 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es2(const f
     // expanded queries as the MFMA row operand: row fl -> head fl & 7, rows 0-7 the fp16 hi limbs, rows 8-15 the lo limbs
     f16x8 qa[8];
     auto qa_from_lds = [&]() {
-        const float* qp = Qs + (fl & 7) * ES_D + 256 * hf + 8 * fg;
         const bool lo = fl >= 8;
+        read_queries<true>(Qs, fl, fg, hf, [&](int s, const float (&v)[8]) {
 #pragma unroll
-        for (int s0 = 0; s0 < 8; s0 += 4) {
-            f32x4 q[4][2];
-#pragma unroll
-            for (int s = 0; s < 4; s++) {
-                q[s][0] = *reinterpret_cast<const f32x4*>(qp + 32 * (s0 + s));
-                q[s][1] = *reinterpret_cast<const f32x4*>(qp + 32 * (s0 + s) + 4);
+            for (int u = 0; u < 8; u++) {
+                const _Float16 h = (_Float16)v[u];
+                qa[s][u] = lo ? (_Float16)(v[u] - (float)h) : h;
             }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int s = 0; s < 4; s++)
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    const float v = q[s][u >> 2][u & 3] * 1.44269504088896341f;   // scores in log2 units: p = exp2(s - m)
-                    const _Float16 h = (_Float16)v;
-                    qa[s0 + s][u] = lo ? (_Float16)(v - (float)h) : h;
-                }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        });
     };
     // scores of the tile in slot `sl`: keys fl, the 256 "dims" 256 wave .. of the 1,024 (8 contraction steps)
     auto score_reads = [&](int sl, f16x8 (&ef)[8]) {
-        const char* rp = smem + sl * E2_TILEB + fl * E2_ROWB;
+        const char* rp = smem + sl * TILEB + fl * E2_ROWB;
 #pragma unroll
         for (int s = 0; s < 8; s++) {
             const int c = 32 * wave + 4 * s + fg;
@@ -561,43 +404,35 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es2(const f
         }
         // rows 4 fg + i: the hi-limb rows of heads 0-7 in lane groups 0, 1, the lo-limb rows in groups 2, 3 (lane + 32): added here, so the
         // exchange buffer holds one partial per (wave, head, key) and the softmax adds four
-        float* dst = sc + buf * E2_SCB + (wave * ES_H + 4 * (fg & 1)) * E2_SCP + fl;
+        float* dst = exch_dst<E2_F>(sc, buf, wave, fg, fl);
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            const float v = es_sum32(d0[i] + d1[i]);
-            if (fg < 2) dst[i * E2_SCP] = v;
+            const float v = sum32(d0[i] + d1[i]);
+            if (fg < 2) dst[i * SCP] = v;
         }
     };
 
     f32x4 acc[8];   // rows 4 fg + i (hi-limb probability rows in groups 0, 1; lo-limb rows in groups 2, 3), column fl <-> dim 128 wave + 8 fl + e
     float m_run = -INFINITY, l_run = 0.0f;
     const int kb = 8 * (fg >> 1), pl = fg & 1;        // this lane group's contraction slots: keys kb .. kb + 7 of plane pl
-    int clip = blockIdx.x, t = 0, slot = 0;
 
-    __builtin_amdgcn_s_barrier();   // P1
-    qa_from_lds();
-    __builtin_amdgcn_s_barrier();   // P2
+    prologue_barriers<E2_F>(qa_from_lds);
     {
         f16x8 ef[8];
         score_reads(0, ef);
         score_mfma(ef, 0);
     }
-#pragma unroll
-    for (int e = 0; e < 8; e++) acc[e] = f32x4{0, 0, 0, 0};
-    for (int g = 0; g < total; g++) {
-        const bool more = g + 1 < total;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();   // tile g + 1 and the scores of tile g visible to all; every wave is done with tile g - 1
-        const int nslot = slot + 1 == NSTAGE ? 0 : slot + 1;
-        if (t == ntile - 1 && more) qa_from_lds();   // the next clip's first tile is scored with the next clip's queries
-        const char* tb = smem + slot * E2_TILEB;
+    clear(acc);
+    for (; !w.done(); w.next()) {
+        const bool more = w.more();
+        tile_barrier();
+        if (w.next_queries()) qa_from_lds();
+        const char* tb = smem + w.slot * TILEB;
         // every LDS read of this iteration up front, in the order of use
         const int h = fl & 7, kq = kb + 4 * (fl >> 3);   // lanes fl and fl + 8 share a head: each takes four of the lane group's eight keys
-        const float* s0 = sc + (g & 1) * E2_SCB + h * E2_SCP + kq;
-        const f32x4 a0 = *reinterpret_cast<const f32x4*>(s0), a1 = *reinterpret_cast<const f32x4*>(s0 + ES_H * E2_SCP);
-        const f32x4 b0 = *reinterpret_cast<const f32x4*>(s0 + 2 * ES_H * E2_SCP), b1 = *reinterpret_cast<const f32x4*>(s0 + 3 * ES_H * E2_SCP);
+        const Partials sp = exch_read<E2_F>(sc, w.g & 1, h, kq);
         f16x8 ef[8];
-        if (more) score_reads(nslot, ef);
+        if (more) score_reads(w.nslot(), ef);
         wh_u32x4 blk[8];
         {
             const int cs = pl * 64 + 16 * wave + fl;
@@ -612,27 +447,10 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es2(const f
         f16x8 pa;
         {
             float sv[4];
-            float tmax = -INFINITY;
-            const int key0 = t * E2_TK + kq;
 #pragma unroll
-            for (int u = 0; u < 4; u++) sv[u] = (a0[u] + a1[u]) + (b0[u] + b1[u]);
-            if (t == ntile - 1) {
-#pragma unroll
-                for (int u = 0; u < 4; u++) sv[u] = (key0 + u < S) ? sv[u] : -INFINITY;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) tmax = fmaxf(tmax, sv[u]);
-            tmax = fmaxf(tmax, es_ror8(tmax));
-            tmax = xrow_max(tmax);               // over the lane groups: all 16 keys of the tile
-            const float m_new = fmaxf(m_run, tmax);
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-            float ps = 0.0f;
-            float pv[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                pv[u] = __builtin_amdgcn_exp2f(sv[u] - m_new);
-                ps += pv[u];
-            }
+            for (int u = 0; u < 4; u++) sv[u] = (sp.p[0][u] + sp.p[1][u]) + (sp.p[2][u] + sp.p[3][u]);
+            const Soft sm = softmax_tile(sv, w.t * TK + kq, S, w.last_tile(), m_run);
+            const float (&pv)[4] = sm.pv;
             // the probability operand, rows 0-7 the hi limbs, rows 8-15 the lo limbs of keys kb .. kb + 7: a lane's own four keys are
             // slots 0-3 (fl < 8) or 4-7 (fl >= 8) of its row; the other four come from lane fl ^ 8, which holds the other limb row of
             // the same head — it sends the limb this row wants
@@ -647,27 +465,13 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es2(const f
                 __builtin_memcpy(&ul0, &l01, 4); __builtin_memcpy(&ul1, &l23, 4);
                 const bool hi = fl < 8;
                 const unsigned send0 = hi ? ul0 : uh0, send1 = hi ? ul1 : uh1;
-                const unsigned recv0 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)send0, 0x128, 0xF, 0xF, true);   // row_ror:8 = lane fl ^ 8
-                const unsigned recv1 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)send1, 0x128, 0xF, 0xF, true);
+                const unsigned recv0 = ror8u(send0), recv1 = ror8u(send1);   // from lane fl ^ 8
                 const wh_u32x4 pw = {hi ? uh0 : recv0, hi ? uh1 : recv1, hi ? recv0 : ul0, hi ? recv1 : ul1};
                 __builtin_memcpy(&pa, &pw, 16);
             }
-            l_run = l_run * alpha + ps;
-            m_run = m_new;
-            if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {   // a running maximum moved: rescale (head q's factor sits in lane q)
-                float ah[8];
-#pragma unroll
-                for (int q = 0; q < 8; q++) ah[q] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, alpha), q));
-                const bool up = fg & 1;   // rows 4 fg + i belong to head 4 (fg & 1) + i in either limb half
-                const float a4[4] = {up ? ah[4] : ah[0], up ? ah[5] : ah[1], up ? ah[6] : ah[2], up ? ah[7] : ah[3]};
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-#pragma unroll
-                    for (int i = 0; i < 4; i++) acc[e][i] *= a4[i];
-                }
-            }
+            rescale(sm, fg, l_run, acc);   // rows 4 fg + i belong to head 4 (fg & 1) + i in either limb half
         }
-        if (more) score_mfma(ef, (g + 1) & 1);
+        if (more) score_mfma(ef, (w.g + 1) & 1);
         // ---- output of tile g: dims 128 wave + 8 fl + e, contraction over the tile's 16 keys x 2 planes
 #pragma unroll
         for (int e = 0; e < 8; e++) {
@@ -681,61 +485,35 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es2(const f
             __builtin_memcpy(&ob, &op, 16);
             acc[e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pa, ob, acc[e], 0, 0, 0);
         }
-        slot = nslot;
-        if (++t < ntile) continue;
+        if (!w.advance()) continue;
         // ---- the clip ends: add the two limb rows of every head, normalise, store as the V projection's fp16-limb operand
         {
-            const float lh = l_run + es_ror8(l_run);          // the head's two key quartets of this lane group
-            const float inv = 1.0f / (xrow_sum(lh) * 0.5f);   // lane groups fg and fg ^ 1 hold the same eight keys: every key counted twice, exactly
-            float ih[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++) ih[q] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inv), q));
-            const bool up = fg & 1;
-            const float inv4[4] = {up ? ih[4] : ih[0], up ? ih[5] : ih[1], up ? ih[6] : ih[2], up ? ih[7] : ih[3]};
+            float inv4[4];
+            clip_inv4<true>(l_run, fg, inv4);
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 f32x8 ov;
 #pragma unroll
-                for (int e = 0; e < 8; e++) ov[e] = es_sum32(acc[e][i]) * inv4[i];   // row 4 fg + i (hi limbs) + row 8 + 4 fg + i (lo limbs)
-                if (fg < 2) {
-                    const int k = (4 * fg + i) * ES_D + 128 * wave + 8 * fl;
-                    store8(out + ((long)(k >> 5) * mpad + clip) * 32 + (k & 31), ov);
-                }
+                for (int e = 0; e < 8; e++) ov[e] = sum32(acc[e][i]) * inv4[i];   // row 4 fg + i (hi limbs) + row 8 + 4 fg + i (lo limbs)
+                if (fg < 2) store8(slab_dst(out, fg, i, wave, fl, mpad, w.clip), ov);
             }
         }
-#pragma unroll
-        for (int e = 0; e < 8; e++) acc[e] = f32x4{0, 0, 0, 0};
+        clear(acc);
         m_run = -INFINITY;
         l_run = 0.0f;
-        t = 0;
-        clip += G;
+        w.next_clip();
     }
 }
 
-// The encoder's final LayerNorm into the limb planes E2 [clip][es_rows][hi 512 | lo 512] (d_model 512): one wave per row, 8 columns per lane.
-// [3P] torch LayerNorm eps 1e-5, biased variance, two-pass in f32 — k_layernorm's arithmetic (wh_gemm.hip).
+// The encoder's final LayerNorm (wh_es_common.h) into the limb planes E2 [clip][es_rows][hi 512 | lo 512]
 __global__ __launch_bounds__(256) void k_layernorm_es2(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
                                                        _Float16* __restrict__ y, long rows, int in_blk, int out_blk) {
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int lane = threadIdx.x & 63, c = lane * 8;
-    const float* xr = x + row * ES_D;
-    const f32x4 v0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(xr + c)), v1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(xr + c + 4));
-    const float mean = dpp_wave_sum((v0[0] + v0[1] + v0[2] + v0[3]) + (v1[0] + v1[1] + v1[2] + v1[3])) / (float)ES_D;
-    float q = 0.0f;
-#pragma unroll
-    for (int e = 0; e < 4; e++) { const float t0 = v0[e] - mean, t1 = v1[e] - mean; q += t0 * t0; q += t1 * t1; }
-    const float rstd = rsqrtf(dpp_wave_sum(q) / (float)ES_D + 1e-5f);
-    const f32x4 w0 = *reinterpret_cast<const f32x4*>(w + c), w1 = *reinterpret_cast<const f32x4*>(w + c + 4);
-    const f32x4 b0 = *reinterpret_cast<const f32x4*>(b + c), b1 = *reinterpret_cast<const f32x4*>(b + c + 4);
-    f32x8 o;
-#pragma unroll
-    for (int e = 0; e < 4; e++) { o[e] = (v0[e] - mean) * rstd * w0[e] + b0[e]; o[4 + e] = (v1[e] - mean) * rstd * w1[e] + b1[e]; }
-    const xfrag f = x3_split(o);
-    const long orow = in_blk > 0 ? (row / in_blk) * out_blk + row % in_blk : row;
-    _Float16* yr = y + orow * (2 * ES_D) + c;
-    *reinterpret_cast<f16x8*>(yr) = f.hi;
-    *reinterpret_cast<f16x8*>(yr + ES_D) = f.lo;
+    layernorm_row(x, w, b, rows, in_blk, out_blk, [&](long orow, int c, const f32x8& o) {
+        const xfrag f = x3_split(o);
+        _Float16* yr = y + orow * (2 * ES_D) + c;
+        *reinterpret_cast<f16x8*>(yr) = f.hi;
+        *reinterpret_cast<f16x8*>(yr + ES_D) = f.lo;
+    });
 }
 
 // expanded queries, WH_PREC_F16X3: the same products with both operands as fp16 limbs (wkT stored as h2, q split in registers)
@@ -768,47 +546,38 @@ __global__ __launch_bounds__(256) void k_dec_qexpand_x3(const float* __restrict_
 unsigned long long* wh_es_bench_dbg = nullptr;
 #endif
 
-bool wh_cross_es_geometry(int d, int n_heads, int S) { return d == ES_D && n_heads == ES_H && S >= 4 * ES_TK; }
+bool wh_cross_es_geometry(int d, int n_heads, int S) { return d == ES_D && n_heads == ES_H && S >= 4 * ES_F.tk; }
 
 void wh_launch_layernorm_es2(hipStream_t s, const float* x, const float* w, const float* b, void* y, long rows, int in_blk, int out_blk) {
     hipLaunchKernelGGL(k_layernorm_es2, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, w, b, (_Float16*)y, rows, in_blk, out_blk);
 }
 
 void wh_launch_dec_cross_attn_es(hipStream_t s, int prec, const float* qe, const void* E, void* out, int S, int e_rows, int B, int mpad, bool stream_nt, int n_cus) {
-    static const int nt_env = [] { const char* e = getenv("WH_CROSS_NT"); return e ? atoi(e) : -1; }();
-    static const int nl = [] { const char* e = getenv("WH_ES_LOADERS"); return e ? atoi(e) : 1; }();        // (A/B runs) loader waves per workgroup
-    static const int persist = [] { const char* e = getenv("WH_ES_PERSIST"); return e ? atoi(e) : 1; }();   // (A/B runs) 0: one workgroup per clip
+    static const int nt_env = env_int("WH_CROSS_NT", -1);
+    static const int nl = env_int("WH_ES_LOADERS", 1);        // (A/B runs) loader waves per workgroup
+    static const int persist = env_int("WH_ES_PERSIST", 1);   // (A/B runs) 0: one workgroup per clip
     if (prec == WH_PREC_FP8) { wh_launch_dec_cross_attn_es8(s, qe, E, out, S, e_rows, B, mpad, stream_nt, n_cus); return; }   // e4m3 states (wh_cross_es8.hip)
     if (prec == WH_PREC_F16X3 && wh_es3_enabled()) { wh_launch_dec_cross_attn_es3(s, qe, E, out, S, e_rows, B, mpad, stream_nt, n_cus); return; }   // fp16 + e4m3 remainder (wh_cross_es3.hip)
-    if (n_cus <= 0) n_cus = 256;   // (the context passes the population of its decode stream's CU mask, else its device's CU count)
     if (nt_env >= 0) stream_nt = nt_env != 0;
-    const int grid = persist ? std::min(B, n_cus) : B;   // one workgroup per CU walks its clips
-    if (prec == WH_PREC_F16X3) {   // fp16 limb planes (k_dec_cross_attn_es2)
-#define WH_ES2_LAUNCH(AUX_, NL_)                                                                                                                       \
-        do {                                                                                                                                           \
-            wh_ensure_dyn_lds((const void*)k_dec_cross_attn_es2<AUX_, NL_>, E2_LDS);                                                                   \
-            hipLaunchKernelGGL((k_dec_cross_attn_es2<AUX_, NL_>), dim3(grid), dim3(256 + 64 * NL_), E2_LDS, s, qe, (const _Float16*)E, (h2*)out, S, e_rows, mpad, B); \
-        } while (0)
-        if (nl == 2) { if (stream_nt) WH_ES2_LAUNCH(2, 2); else WH_ES2_LAUNCH(0, 2); }
-        else { if (stream_nt) WH_ES2_LAUNCH(2, 1); else WH_ES2_LAUNCH(0, 1); }
-#undef WH_ES2_LAUNCH
+    // (the context passes the population of its decode stream's CU mask, else its device's CU count)
+    const int grid = persist ? persistent_grid(B, n_cus) : B;
+    if (prec == WH_PREC_F16X3) {   // fp16 limb planes
+        launch(s, grid, nl == 2, stream_nt, E2_F.lds(), [](auto AUX, auto NL) { return k_dec_cross_attn_es2<decltype(AUX)::value, decltype(NL)::value>; },
+               qe, (const _Float16*)E, (h2*)out, S, e_rows, mpad, B);
         return;
     }
     unsigned long long* es_dbg = nullptr;
 #ifdef WH_ES_BENCH
     es_dbg = wh_es_bench_dbg;
+    if (const char* e = getenv("WH_ES_ABL")) {   // always <AUX 2, one loader>
+        const bool stamps = atoi(e) == 2;
+        launch(s, grid, false, true, ES_F.lds(), [stamps](auto, auto) { return stamps ? k_dec_cross_attn_es<2, 1, 2> : k_dec_cross_attn_es<2, 1, 1>; },
+               qe, (const bf16*)E, (bf16*)out, S, e_rows, mpad, B, es_dbg);
+        return;
+    }
 #endif
-#define WH_ES_LAUNCH(AUX_, NL_, ...)                                                                                                \
-    do {                                                                                                                            \
-        wh_ensure_dyn_lds((const void*)k_dec_cross_attn_es<AUX_, NL_, ##__VA_ARGS__>, ES_LDS);                                      \
-        hipLaunchKernelGGL((k_dec_cross_attn_es<AUX_, NL_, ##__VA_ARGS__>), dim3(grid), dim3(256 + 64 * NL_), ES_LDS, s, qe, (const bf16*)E, (bf16*)out, S, e_rows, mpad, B, es_dbg); \
-    } while (0)
-#ifdef WH_ES_BENCH
-    if (const char* e = getenv("WH_ES_ABL")) { if (atoi(e) == 2) WH_ES_LAUNCH(2, 1, 2); else WH_ES_LAUNCH(2, 1, 1); return; }
-#endif
-    if (nl == 2) { if (stream_nt) WH_ES_LAUNCH(2, 2); else WH_ES_LAUNCH(0, 2); }
-    else { if (stream_nt) WH_ES_LAUNCH(2, 1); else WH_ES_LAUNCH(0, 1); }
-#undef WH_ES_LAUNCH
+    launch(s, grid, nl == 2, stream_nt, ES_F.lds(), [](auto AUX, auto NL) { return k_dec_cross_attn_es<decltype(AUX)::value, decltype(NL)::value>; },
+           qe, (const bf16*)E, (bf16*)out, S, e_rows, mpad, B, es_dbg);
 }
 
 void wh_launch_dec_qexpand(hipStream_t s, int prec, const float* q, const void* wkT, float* qe, int M, int d, int n_heads) {

@@ -21,20 +21,18 @@
 #include <algorithm>
 
 #include "wh_common.h"
-#include "wh_es_fp8.h"
+#include "wh_es_common.h"
 #include "wh_kernels.h"
 
 namespace {
 
-using namespace wh_es_fp8;
+using namespace wh_es;
 
-constexpr int E3_D = 512, E3_H = 8, E3_TK = 32, E3_NSTAGE = 3;
+constexpr int E3_D = D, E3_H = H;
 constexpr int E3_ROWB = E3_D * 3;                      // bytes per key row in memory: 1 KiB of fp16, 512 B of e4m3
-constexpr int E3_LO = E3_TK * E3_D * 2;                // offset of the e4m3 rows inside an LDS tile
-constexpr int E3_TILEB = E3_TK * E3_ROWB;              // 48 KiB
-constexpr int E3_SCP = 36;                             // floats per (dim half, limb, head) row of the score exchange (32 keys + pad)
-constexpr int E3_SCB = 4 * E3_H * E3_SCP;              // floats per score-exchange buffer
-constexpr int E3_LDS = E3_NSTAGE * E3_TILEB + 2 * E3_SCB * 4;   // 153 KiB
+// ring of three 32-key tiles of 48 KiB, no query prefetch; exchange rows [dim half][hi | lo of the query][head][32 keys + pad]; 153 KiB
+constexpr Format E3_F = {32, 32 * E3_ROWB, 3, false, 36};
+constexpr int E3_LO = E3_F.tk * E3_D * 2;              // offset of the e4m3 rows inside an LDS tile
 constexpr float E3_S8 = 1.0f / 4096.0f;                // the e4m3 plane's weight (states' remainders are stored x 2^12)
 
 // two fp16 as one dword (lo half = a)
@@ -51,50 +49,34 @@ __device__ __forceinline__ unsigned e3_h2(float a, float b) {
 template <int AUX, int NL>
 __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es3(const float* __restrict__ qe, const unsigned char* __restrict__ E, h2* __restrict__ out,
                                                                 int S, int e_rows, int mpad, int B) {
-    constexpr int NSTAGE = E3_NSTAGE, LA = NSTAGE - 1;
+    constexpr int TK = E3_F.tk, TILEB = E3_F.tileb, SCP = E3_F.scp;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* sc = reinterpret_cast<float*>(smem + NSTAGE * E3_TILEB);   // [2 tiles][E3_SCB]
+    float* sc = carve<E3_F>(smem).sc;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ntile = (S + E3_TK - 1) / E3_TK;
-    const int G = gridDim.x;
-    const int n_my = (B - (int)blockIdx.x + G - 1) / G;
-    const int total = n_my * ntile;
+    Walk<E3_F> w(S, B);   // the walk of this workgroup: every wave of either role follows it
 
     if (wave >= 4) {
         // ================================ loaders: 32 + 16 pieces of 1 KiB per tile, shared by NL waves ================================
         // (an LDS-DMA piece costs its issuer ~100 cycles: one wave issuing all 48 takes longer than the tile's 4,000 cycles of HBM time)
+        // Two tiles ahead: the prologue's wait leaves the younger tile's 48 / NL pieces in flight, an iteration's wait nothing.
         const int lw = wave - 4;
-        int st_clip = blockIdx.x, st_t = 0, st_slot = 0;
-        auto stage_next = [&]() {
-            char* base = smem + st_slot * E3_TILEB;
-            const unsigned char* Ec = E + (long)st_clip * e_rows * E3_ROWB;
+        loader<E3_F, NL>(smem, qe, lw, lane, B, w, [&](char* base, int clip, int t) __attribute__((always_inline)) {
+            const unsigned char* Ec = E + (long)clip * e_rows * E3_ROWB;
 #pragma unroll
-            for (int jj = 0; jj < E3_TK / NL; jj++) {   // fp16 rows: a piece is one key's 1 KiB, LDS chunk p holds dim-chunk p ^ (r & 15)
-                const int j = lw * (E3_TK / NL) + jj;
-                const int key = min(st_t * E3_TK + j, S - 1);   // rows past the clip's end re-read its last key (finite; their scores are masked)
+            for (int jj = 0; jj < TK / NL; jj++) {   // fp16 rows: a piece is one key's 1 KiB, LDS chunk p holds dim-chunk p ^ (r & 15)
+                const int j = lw * (TK / NL) + jj;
+                const int key = min(t * TK + j, S - 1);   // rows past the clip's end re-read its last key (finite; their scores are masked)
                 glds16<AUX>(Ec + (long)key * E3_ROWB + ((lane ^ (j & 15)) << 4), base + j * 1024);
             }
 #pragma unroll
-            for (int jj = 0; jj < E3_TK / 2 / NL; jj++) {   // e4m3 rows: a piece is two keys' 512 bytes
-                const int j = lw * (E3_TK / 2 / NL) + jj;
+            for (int jj = 0; jj < TK / 2 / NL; jj++) {   // e4m3 rows: a piece is two keys' 512 bytes
+                const int j = lw * (TK / 2 / NL) + jj;
                 const int r = 2 * j + (lane >> 5);
-                const int key = min(st_t * E3_TK + r, S - 1);
+                const int key = min(t * TK + r, S - 1);
                 glds16<AUX>(Ec + (long)key * E3_ROWB + 2 * E3_D + (((lane & 31) ^ swz8(r)) << 4), base + E3_LO + j * 1024);
             }
-        st_slot = st_slot + 1 == NSTAGE ? 0 : st_slot + 1;
-            if (++st_t == ntile) { st_t = 0; st_clip += G; }
-        };
-#pragma unroll
-        for (int t = 0; t < LA; t++)
-            if (t < total) stage_next();
-        if (total >= LA) wait_vm<48 / NL>(); else wait_vm<0>();   // tile 0 (the older of two) has landed
-        __builtin_amdgcn_s_barrier();   // P: tile 0 is in the ring
-        for (int g = 0; g < total; g++) {
-            if (g + 1 < total) wait_vm<0>();   // tile g + 1 has landed (nothing younger is in flight at this point)
-            __builtin_amdgcn_s_barrier();
-            if (g + LA < total) stage_next();
-        }
+        });
         return;
     }
 
@@ -107,35 +89,21 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es3(const f
     // (read from global memory where they are needed — once per clip, at its predecessor's last tile: the registers a prefetch would hold, 64 per lane,
     // are not there beside two planes' accumulators, operands and blocks)
     auto q_load = [&](int clip) {
-        const float* qp = qe + (long)clip * (E3_H * E3_D) + (fl & 7) * E3_D + 256 * hf + 8 * fg;
         const bool lo = fl >= 8;
+        read_queries<false>(qe + (long)clip * (E3_H * E3_D), fl, fg, hf, [&](int s, const float (&v)[8]) {
+            f16x8 h, r;
 #pragma unroll
-        for (int s0 = 0; s0 < 8; s0 += 4) {
-            f32x4 q[4][2];
-#pragma unroll
-            for (int s = 0; s < 4; s++) {
-                q[s][0] = *reinterpret_cast<const f32x4*>(qp + 32 * (s0 + s));
-                q[s][1] = *reinterpret_cast<const f32x4*>(qp + 32 * (s0 + s) + 4);
-            }
-#pragma unroll
-            for (int s = 0; s < 4; s++) {
-                float v[8];
-#pragma unroll
-                for (int u = 0; u < 8; u++) v[u] = q[s][u >> 2][u & 3] * 1.44269504088896341f;   // log2 units: p = exp2(s - m)
-                f16x8 h, r;
-#pragma unroll
-                for (int u = 0; u < 8; u++) { h[u] = (_Float16)v[u]; r[u] = (_Float16)(v[u] - (float)h[u]); }
-                qa16[s0 + s] = lo ? r : h;
-                const unsigned h0 = pack4(v[0], v[1], v[2], v[3]), h1 = pack4(v[4], v[5], v[6], v[7]);
-                const unsigned r0 = rem4(h0, v[0], v[1], v[2], v[3]), r1 = rem4(h1, v[4], v[5], v[6], v[7]);
-                qa8[s0 + s] = lo ? join(r0, r1) : join(h0, h1);
-            }
-        }
+            for (int u = 0; u < 8; u++) { h[u] = (_Float16)v[u]; r[u] = (_Float16)(v[u] - (float)h[u]); }
+            qa16[s] = lo ? r : h;
+            const unsigned h0 = pack4(v[0], v[1], v[2], v[3]), h1 = pack4(v[4], v[5], v[6], v[7]);
+            const unsigned r0 = rem4(h0, v[0], v[1], v[2], v[3]), r1 = rem4(h1, v[4], v[5], v[6], v[7]);
+            qa8[s] = lo ? join(r0, r1) : join(h0, h1);
+        });
     };
     // ---- scores of the tile in slot `sl` for keys 16 kt + fl over dims 256 hf ..
     auto score_reads = [&](int sl, f16x8 (&e16)[8]) {   // the fp16 plane's operands (the e4m3 plane's are read inside score_mfma, once these are spent)
         const int r = 16 * kt + fl;
-        const char* rp16 = smem + sl * E3_TILEB + r * 1024;
+        const char* rp16 = smem + sl * TILEB + r * 1024;
 #pragma unroll
         for (int s = 0; s < 8; s++) e16[s] = *reinterpret_cast<const f16x8*>(rp16 + (((32 * hf + 4 * s + fg) ^ (r & 15)) << 4));
     };
@@ -149,7 +117,7 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es3(const f
         }
         {
             const int r = 16 * kt + fl;
-            const char* rp8 = smem + sl * E3_TILEB + E3_LO + r * 512 + (fg & 1) * 8;
+            const char* rp8 = smem + sl * TILEB + E3_LO + r * 512 + (fg & 1) * 8;
             const int sw = swz8(r);
             long e8[8];
 #pragma unroll
@@ -161,36 +129,30 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es3(const f
             }
         }
         // rows 0-7 (lane groups 0, 1) and rows 8-15 (groups 2, 3) both go to the exchange buffer; the readers add the four partials of a score
-        float* dst = sc + buf * E3_SCB + ((hf * 2 + (fg >> 1)) * E3_H + 4 * (fg & 1)) * E3_SCP + 16 * kt + fl;
+        float* dst = exch_dst<E3_F>(sc, buf, hf * 2 + (fg >> 1), fg, 16 * kt + fl);
 #pragma unroll
-        for (int i = 0; i < 4; i++) dst[i * E3_SCP] = (d0[i] + d1[i]) + (c0[i] + c1[i]) * w8;
+        for (int i = 0; i < 4; i++) dst[i * SCP] = (d0[i] + d1[i]) + (c0[i] + c1[i]) * w8;
     };
 
     f32x4 acc16[8], acc8[8];   // rows 4 fg + i: heads 4 (fg & 1) + i; lane groups 0, 1 from the head limbs of p, 2, 3 from its remainders
     float m_run = -INFINITY, l_run = 0.0f;
     const int kb = 16 * (fg & 1) + 8 * (fg >> 1);   // first key (within a tile) of this lane's contraction slots
-    int clip = blockIdx.x, t = 0, slot = 0;
 
-    q_load(blockIdx.x);
-    __builtin_amdgcn_s_barrier();   // P
+    prologue_barriers<E3_F>([&]() { q_load(blockIdx.x); });
     {
         f16x8 e16[8];
         score_reads(0, e16);
         score_mfma(0, e16, 0);
     }
-#pragma unroll
-    for (int e = 0; e < 8; e++) { acc16[e] = f32x4{0, 0, 0, 0}; acc8[e] = f32x4{0, 0, 0, 0}; }
-    for (int g = 0; g < total; g++) {
-        const bool more = g + 1 < total;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();   // tile g + 1 and the scores of tile g visible to all; every wave is done with tile g - 1
-        const int nslot = slot + 1 == NSTAGE ? 0 : slot + 1;
-        if (t == ntile - 1 && more) q_load(clip + G);   // the next clip's first tile is scored with the next clip's queries
-        const char* tb = smem + slot * E3_TILEB;
+    clear(acc16, acc8);
+    for (; !w.done(); w.next()) {
+        const bool more = w.more();
+        tile_barrier();
+        const int nslot = w.nslot();
+        if (w.next_queries()) q_load(w.clip + w.G);
+        const char* tb = smem + w.slot * TILEB;
         const int h = fl & 7, kq = kb + 4 * (fl >> 3);
-        const float* s0 = sc + (g & 1) * E3_SCB + h * E3_SCP + kq;
-        const f32x4 a0 = *reinterpret_cast<const f32x4*>(s0), a1 = *reinterpret_cast<const f32x4*>(s0 + E3_H * E3_SCP);
-        const f32x4 b0 = *reinterpret_cast<const f32x4*>(s0 + 2 * E3_H * E3_SCP), b1 = *reinterpret_cast<const f32x4*>(s0 + 3 * E3_H * E3_SCP);
+        const Partials sp = exch_read<E3_F>(sc, w.g & 1, h, kq);
         f16x8 e16[8];
         if (more) score_reads(nslot, e16);
         __builtin_amdgcn_sched_barrier(0);
@@ -199,27 +161,10 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es3(const f
         long pa8;
         {
             float sv[4];
-            float tmax = -INFINITY;
-            const int key0 = t * E3_TK + kq;
 #pragma unroll
-            for (int u = 0; u < 4; u++) sv[u] = (a0[u] + a1[u]) + (b0[u] + b1[u]);
-            if (t == ntile - 1) {
-#pragma unroll
-                for (int u = 0; u < 4; u++) sv[u] = (key0 + u < S) ? sv[u] : -INFINITY;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) tmax = fmaxf(tmax, sv[u]);
-            tmax = fmaxf(tmax, ror8(tmax));
-            tmax = xrow_max(tmax);
-            const float m_new = fmaxf(m_run, tmax);
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-            float ps = 0.0f;
-            float pv[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                pv[u] = __builtin_amdgcn_exp2f(sv[u] - m_new);
-                ps += pv[u];
-            }
+            for (int u = 0; u < 4; u++) sv[u] = (sp.p[0][u] + sp.p[1][u]) + (sp.p[2][u] + sp.p[3][u]);
+            const Soft sm = softmax_tile(sv, w.t * TK + kq, S, w.last_tile(), m_run);
+            const float (&pv)[4] = sm.pv;
             {   // fp16 operand: rows 0-7 fp16(p) of keys kb .. kb + 7, rows 8-15 fp16(p - hi); lane fl < 8 owns keys kb .. kb + 3, lane fl + 8 keys kb + 4 ..
                 const _Float16 q0 = (_Float16)pv[0], q1 = (_Float16)pv[1], q2 = (_Float16)pv[2], q3 = (_Float16)pv[3];
                 const unsigned oh0 = e3_h2((float)q0, (float)q1), oh1 = e3_h2((float)q2, (float)q3);
@@ -232,23 +177,10 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es3(const f
                 const unsigned oth_hi = ror8u(own_hi), oth_lo = ror8u(own_lo);
                 pa8 = fl < 8 ? join(own_hi, oth_hi) : join(oth_lo, own_lo);
             }
-            l_run = l_run * alpha + ps;
-            m_run = m_new;
-            if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
-                float ah[8];
-#pragma unroll
-                for (int q = 0; q < 8; q++) ah[q] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, alpha), q));
-                const bool up = fg & 1;
-                const float a4[4] = {up ? ah[4] : ah[0], up ? ah[5] : ah[1], up ? ah[6] : ah[2], up ? ah[7] : ah[3]};
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-#pragma unroll
-                    for (int i = 0; i < 4; i++) { acc16[e][i] *= a4[i]; acc8[e][i] *= a4[i]; }
-                }
-            }
+            rescale(sm, fg, l_run, acc16, acc8);
         }
         // ---- scores of tile g + 1 (their operands leave the registers before the output blocks are read: both sets at once do not fit 256 registers)
-        if (more) score_mfma(nslot, e16, (g + 1) & 1);
+        if (more) score_mfma(nslot, e16, (w.g + 1) & 1);
         // ---- output of tile g: dims 128 wave + 8 fl + e, contraction over the tile's 32 keys; the 8 keys x 8 dims blocks are transposed in registers.
         // One plane after the other: the blocks of both at once do not fit the register budget either.
         {   // fp16 plane (wh_cross_es.hip's transposition of 2-byte elements)
@@ -296,68 +228,42 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es3(const f
                 acc8[e] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(pa8, join(k03, k47), acc8[e], 0, 0, 0);
             }
         }
-        slot = nslot;
-        if (++t < ntile) continue;
+        if (!w.advance()) continue;
         // ---- the clip ends: rows h and 8 + h (lanes l and l ^ 32) and the two planes are added, normalised, stored as an h2 slab
         {
-            const float lh = l_run + ror8(l_run);
-            const float inv = 1.0f / xrow_sum(lh);
-            float ih[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++) ih[q] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inv), q));
-            const bool up = fg & 1;
-            const float inv4[4] = {up ? ih[4] : ih[0], up ? ih[5] : ih[1], up ? ih[6] : ih[2], up ? ih[7] : ih[3]};
+            float inv4[4];
+            clip_inv4(l_run, fg, inv4);
+            // (the rows' slab addresses are worked out here, once per clip: as loop invariants they are four more register pairs that live through
+            // the tile loop, which has none to spare and sent them to scratch)
+            int fl_c = fl;
+            asm volatile("" : "+v"(fl_c));
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 f32x8 ov;
 #pragma unroll
-                for (int e = 0; e < 8; e++) {
-                    const float mine = acc16[e][i] + acc8[e][i] * w8;
-                    const wh_u32x2 sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mine), __float_as_uint(mine), false, false);
-                    ov[e] = (__uint_as_float(sw.x) + __uint_as_float(sw.y)) * inv4[i];
-                }
-                if (fg < 2) {
-                    const int k = (4 * fg + i) * E3_D + 128 * wave + 8 * fl;
-                    store8(out + ((long)(k >> 5) * mpad + clip) * 32 + (k & 31), ov);
-                }
+                for (int e = 0; e < 8; e++) ov[e] = sum32(acc16[e][i] + acc8[e][i] * w8) * inv4[i];
+                if (fg < 2) store8(slab_dst(out, fg, i, wave, fl_c, mpad, w.clip), ov);
             }
         }
-#pragma unroll
-        for (int e = 0; e < 8; e++) { acc16[e] = f32x4{0, 0, 0, 0}; acc8[e] = f32x4{0, 0, 0, 0}; }
+        clear(acc16, acc8);
         m_run = -INFINITY;
         l_run = 0.0f;
-        t = 0;
-        clip += G;
+        w.next_clip();
     }
 }
 
-// The encoder's final LayerNorm into key rows of [512 fp16 | 512 e4m3 remainders x 2^12]: one wave per row, 8 columns per lane
-// ([3P] torch LayerNorm eps 1e-5, biased variance, two-pass in f32 — k_layernorm_es2's arithmetic)
+// The encoder's final LayerNorm (wh_es_common.h) into key rows of [512 fp16 | 512 e4m3 remainders x 2^12]
 __global__ __launch_bounds__(256) void k_layernorm_es3(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
                                                        unsigned char* __restrict__ y, long rows, int in_blk, int out_blk) {
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int lane = threadIdx.x & 63, c = lane * 8;
-    const float* xr = x + row * E3_D;
-    const f32x4 v0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(xr + c)), v1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(xr + c + 4));
-    const float mean = dpp_wave_sum((v0[0] + v0[1] + v0[2] + v0[3]) + (v1[0] + v1[1] + v1[2] + v1[3])) / (float)E3_D;
-    float q = 0.0f;
+    layernorm_row(x, w, b, rows, in_blk, out_blk, [&](long orow, int c, const f32x8& o) {
+        f16x8 hi;
+        float rm[8];
 #pragma unroll
-    for (int e = 0; e < 4; e++) { const float t0 = v0[e] - mean, t1 = v1[e] - mean; q += t0 * t0; q += t1 * t1; }
-    const float rstd = rsqrtf(dpp_wave_sum(q) / (float)E3_D + 1e-5f);
-    const f32x4 w0 = *reinterpret_cast<const f32x4*>(w + c), w1 = *reinterpret_cast<const f32x4*>(w + c + 4);
-    const f32x4 b0 = *reinterpret_cast<const f32x4*>(b + c), b1 = *reinterpret_cast<const f32x4*>(b + c + 4);
-    float o[8];
-#pragma unroll
-    for (int e = 0; e < 4; e++) { o[e] = (v0[e] - mean) * rstd * w0[e] + b0[e]; o[4 + e] = (v1[e] - mean) * rstd * w1[e] + b1[e]; }
-    f16x8 hi;
-    float rm[8];
-#pragma unroll
-    for (int e = 0; e < 8; e++) { hi[e] = (_Float16)o[e]; rm[e] = fminf(fmaxf((o[e] - (float)hi[e]) * 4096.0f, -448.0f), 448.0f); }   // (|o| < 256 never reaches the clamp)
-    const long orow = in_blk > 0 ? (row / in_blk) * out_blk + row % in_blk : row;
-    unsigned char* yr = y + orow * E3_ROWB;
-    *reinterpret_cast<f16x8*>(yr + c * 2) = hi;
-    *reinterpret_cast<wh_u32x2*>(yr + 2 * E3_D + c) = wh_u32x2{pack4(rm[0], rm[1], rm[2], rm[3]), pack4(rm[4], rm[5], rm[6], rm[7])};
+        for (int e = 0; e < 8; e++) { hi[e] = (_Float16)o[e]; rm[e] = fminf(fmaxf((o[e] - (float)hi[e]) * 4096.0f, -448.0f), 448.0f); }   // (|o| < 256 never reaches the clamp)
+        unsigned char* yr = y + orow * E3_ROWB;
+        *reinterpret_cast<f16x8*>(yr + c * 2) = hi;
+        *reinterpret_cast<wh_u32x2*>(yr + 2 * E3_D + c) = wh_u32x2{pack4(rm[0], rm[1], rm[2], rm[3]), pack4(rm[4], rm[5], rm[6], rm[7])};
+    });
 }
 
 }  // namespace
@@ -369,17 +275,9 @@ bool wh_es3_enabled() {
 }
 
 void wh_launch_dec_cross_attn_es3(hipStream_t s, const float* qe, const void* E, void* out, int S, int e_rows, int B, int mpad, bool stream_nt, int n_cus) {
-    static const int nl = [] { const char* e = getenv("WH_ES3_LOADERS"); return e ? atoi(e) : 2; }();   // (A/B runs) loader waves per workgroup
-    if (n_cus <= 0) n_cus = 256;
-    const int grid = std::min(B, n_cus);   // one workgroup per CU walks its clips
-#define WH_ES3_LAUNCH(AUX_, NL_)                                                                                                                      \
-    do {                                                                                                                                              \
-        wh_ensure_dyn_lds((const void*)k_dec_cross_attn_es3<AUX_, NL_>, E3_LDS);                                                                      \
-        hipLaunchKernelGGL((k_dec_cross_attn_es3<AUX_, NL_>), dim3(grid), dim3(256 + 64 * NL_), E3_LDS, s, qe, (const unsigned char*)E, (h2*)out, S, e_rows, mpad, B); \
-    } while (0)
-    if (stream_nt) { if (nl == 1) WH_ES3_LAUNCH(2, 1); else WH_ES3_LAUNCH(2, 2); }
-    else { if (nl == 1) WH_ES3_LAUNCH(0, 1); else WH_ES3_LAUNCH(0, 2); }
-#undef WH_ES3_LAUNCH
+    static const int nl = env_int("WH_ES3_LOADERS", 2);   // (A/B runs) loader waves per workgroup
+    launch(s, persistent_grid(B, n_cus), nl != 1, stream_nt, E3_F.lds(), [](auto AUX, auto NL) { return k_dec_cross_attn_es3<decltype(AUX)::value, decltype(NL)::value>; },
+           qe, (const unsigned char*)E, (h2*)out, S, e_rows, mpad, B);
 }
 
 void wh_launch_layernorm_es3(hipStream_t s, const float* x, const float* w, const float* b, void* y, long rows, int in_blk, int out_blk) {

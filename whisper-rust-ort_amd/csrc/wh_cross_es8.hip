@@ -22,83 +22,47 @@
 #include <algorithm>
 
 #include "wh_common.h"
-#include "wh_es_fp8.h"
+#include "wh_es_common.h"
 #include "wh_kernels.h"
 
 namespace {
 
-using namespace wh_es_fp8;
+using namespace wh_es;
 
-constexpr int E8_D = 512, E8_H = 8, E8_TK = 32;
+constexpr int E8_D = D;
 constexpr int E8_ROWB = E8_D;                          // bytes per key row
-constexpr int E8_TILEB = E8_TK * E8_ROWB;              // 16 KiB
-constexpr int E8_SCP = 36;                             // floats per (dim half, limb, head) row of the score exchange (32 keys + pad)
-constexpr int E8_SCB = 4 * E8_H * E8_SCP;              // floats per score-exchange buffer: [dim half][hi | lo of the query][head][E8_SCP]
-constexpr int e8_lds(int nstage) { return nstage * E8_TILEB + 2 * E8_SCB * 4 + E8_H * E8_D * 4; }   // ring + score exchange + next queries
+// ring of five 32-key tiles of 16 KiB; exchange rows [dim half][hi | lo of the query][head][32 keys + pad]
+constexpr Format E8_F = {32, 32 * E8_ROWB, 5, true, 36};
 
 // qe : [B][8][512] f32 expanded queries (natural-log score units)        E: [B][e_rows][512] e4m3 encoder states (final LayerNorm applied)
 // out: ctx as the decode GEMM's operand, slab layout [8 * 512 / 32][mpad][32] bf16, column h * 512 + dim
-template <int AUX, int NSTAGE, int NL>
+template <int AUX, int NL>
 __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es8(const float* __restrict__ qe, const unsigned char* __restrict__ E, bf16* __restrict__ out,
                                                                 int S, int e_rows, int mpad, int B) {
-    constexpr int LA = NSTAGE - 1;   // LA tiles staged ahead of the one being consumed
+    constexpr int TK = E8_F.tk, TILEB = E8_F.tileb, SCP = E8_F.scp;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* sc = reinterpret_cast<float*>(smem + NSTAGE * E8_TILEB);   // [2 tiles][E8_SCB]
-    float* Qs = sc + 2 * E8_SCB;                                       // [8][512] f32: the next clip's expanded queries
+    float* sc = carve<E8_F>(smem).sc;
+    float* Qs = carve<E8_F>(smem).Qs;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int ntile = (S + E8_TK - 1) / E8_TK;
-    const int G = gridDim.x;
-    const int n_my = (B - (int)blockIdx.x + G - 1) / G;   // clips of this workgroup
-    const int total = n_my * ntile;                        // tiles of this workgroup
+    Walk<E8_F> w(S, B);   // the walk of this workgroup: every wave of either role follows it
 
     if (wave >= 4) {
-        // ================================ loader ================================
-        constexpr int PPT = E8_TILEB / 1024 / NL;   // pieces of 1 KiB = 2 key rows per tile and loader wave (an LDS-DMA piece costs its issuer ~100 cycles:
-                                                    // one wave issuing all 16 takes longer than the 1,350 cycles a tile has at the HBM rate)
+        // ================================ loader: a piece is two key rows ================================
+        // (an LDS-DMA piece costs its issuer ~100 cycles: one wave issuing all 16 takes longer than the 1,350 cycles a tile has at the HBM rate)
+        constexpr int PPT = E8_F.pieces() / NL;
         const int lw = wave - 4;
         const int rsub = lane >> 5, pc = lane & 31;   // row inside a piece, physical 16-byte chunk of the row
-        int st_clip = blockIdx.x, st_t = 0, st_slot = 0;   // tiles are staged strictly in sequence
-        auto stage_next = [&]() {
-            char* base = smem + st_slot * E8_TILEB;
-            const unsigned char* Ec = E + (long)st_clip * e_rows * E8_ROWB;
+        loader<E8_F, NL>(smem, qe, lw, lane, B, w, [&](char* base, int clip, int t) __attribute__((always_inline)) {
+            const unsigned char* Ec = E + (long)clip * e_rows * E8_ROWB;
 #pragma unroll
             for (int jj = 0; jj < PPT; jj++) {
                 const int j = lw * PPT + jj;
                 const int r = 2 * j + rsub;
-                const int key = min(st_t * E8_TK + r, S - 1);   // rows past the clip's end re-read its last key (finite; their scores are masked)
+                const int key = min(t * TK + r, S - 1);   // rows past the clip's end re-read its last key (finite; their scores are masked)
                 glds16<AUX>(Ec + (long)key * E8_ROWB + ((pc ^ swz8(r)) << 4), base + j * 1024);
             }
-            st_slot = st_slot + 1 == NSTAGE ? 0 : st_slot + 1;
-            if (++st_t == ntile) { st_t = 0; st_clip += G; }
-        };
-        constexpr int QPP = 16 / NL;
-        auto stage_q = [&](int clip) {
-            const float* src = qe + (long)clip * (E8_H * E8_D);
-#pragma unroll
-            for (int jj = 0; jj < QPP; jj++) {
-                const int j = lw * QPP + jj;
-                glds16<0>(src + (j * 64 + lane) * 4, reinterpret_cast<char*>(Qs) + j * 1024);
-            }
-        };
-        stage_q(blockIdx.x);
-#pragma unroll
-        for (int t = 0; t < LA; t++)
-            if (t < total) stage_next();
-        // vmcnt retires in issue order (and holds at most 63): "all but the last LA - 1 tiles' pieces" covers the queries and tile 0
-        if (total >= LA) wait_vm<(PPT * (LA - 1) < 63 ? PPT * (LA - 1) : 63)>(); else wait_vm<0>();
-        __builtin_amdgcn_s_barrier();   // P1: the first clip's queries are in Qs
-        __builtin_amdgcn_s_barrier();   // P2: tile 0 is in the ring
-        int clip = blockIdx.x, t = 0;
-        for (int g = 0; g < total; g++) {
-            if (g + 1 < total) {   // tile g + 1 has landed; the younger tiles stay in flight (conservative where the next clip's queries are among them)
-                if (total - 2 - g >= LA - 2) wait_vm<PPT*(LA - 2)>(); else wait_vm<0>();
-            }
-            __builtin_amdgcn_s_barrier();
-            if (g + LA < total) stage_next();
-            if (t == 0 && clip + G < B) stage_q(clip + G);   // Qs was read (if at all) before this barrier
-            if (++t == ntile) { t = 0; clip += G; }
-        }
+        });
         return;
     }
 
@@ -108,23 +72,17 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es8(const f
     // ---- expanded queries of this wave's dim half as the MFMA row operand: row fl -> head fl & 7, rows 0-7 the e4m3 heads, rows 8-15 the remainders
     long qa[8];
     auto qa_from_lds = [&]() {
-        const float* qp = Qs + (fl & 7) * E8_D + 256 * hf + 8 * fg;
         const bool lo = fl >= 8;
-#pragma unroll
-        for (int s = 0; s < 8; s++) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(qp + 32 * s), b = *reinterpret_cast<const f32x4*>(qp + 32 * s + 4);
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) v[u] = (u < 4 ? a[u & 3] : b[u & 3]) * 1.44269504088896341f;   // scores in log2 units: p = exp2(s - m)
+        read_queries<false>(Qs, fl, fg, hf, [&](int s, const float (&v)[8]) {
             const unsigned h0 = pack4(v[0], v[1], v[2], v[3]), h1 = pack4(v[4], v[5], v[6], v[7]);
             const unsigned r0 = rem4(h0, v[0], v[1], v[2], v[3]), r1 = rem4(h1, v[4], v[5], v[6], v[7]);
             qa[s] = lo ? join(r0, r1) : join(h0, h1);
-        }
+        });
     };
     // ---- scores of the tile in slot `sl` for keys 16 kt + fl over dims 256 hf ..: rows 4 fg + i of D; partials to sc buffer `buf`
     auto score_reads = [&](int sl, long (&ef)[8]) {
         const int r = 16 * kt + fl;
-        const char* rp = smem + sl * E8_TILEB + r * E8_ROWB + (fg & 1) * 8;
+        const char* rp = smem + sl * TILEB + r * E8_ROWB + (fg & 1) * 8;
         const int sw = swz8(r);
 #pragma unroll
         for (int s = 0; s < 8; s++) {
@@ -140,42 +98,33 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es8(const f
             d1 = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(qa[s + 1], ef[s + 1], d1, 0, 0, 0);
         }
         // rows 0-7 (lane groups 0, 1) carry the head limbs, rows 8-15 (groups 2, 3) the remainders: both go to the exchange buffer as they are
-        float* dst = sc + buf * E8_SCB + ((hf * 2 + (fg >> 1)) * E8_H + 4 * (fg & 1)) * E8_SCP + 16 * kt + fl;
+        float* dst = exch_dst<E8_F>(sc, buf, hf * 2 + (fg >> 1), fg, 16 * kt + fl);
 #pragma unroll
-        for (int i = 0; i < 4; i++) dst[i * E8_SCP] = d0[i] + d1[i];
+        for (int i = 0; i < 4; i++) dst[i * SCP] = d0[i] + d1[i];
     };
 
     f32x4 acc[8];   // rows 4 fg + i: heads 4 (fg & 1) + i; lane groups 0, 1 from the probabilities' head limbs, 2, 3 from their remainders
     float m_run = -INFINITY, l_run = 0.0f;
     const int kb = 16 * (fg & 1) + 8 * (fg >> 1);   // first key (within a tile) of this lane's contraction slots
-    int clip = blockIdx.x, t = 0, slot = 0;          // the tile being consumed: tile t of `clip`, ring slot `slot`
 
-    __builtin_amdgcn_s_barrier();   // P1
-    qa_from_lds();
-    __builtin_amdgcn_s_barrier();   // P2
+    prologue_barriers<E8_F>(qa_from_lds);
     {   // scores of tile 0
         long ef[8];
         score_reads(0, ef);
         score_mfma(ef, 0);
     }
-#pragma unroll
-    for (int e = 0; e < 8; e++) acc[e] = f32x4{0, 0, 0, 0};
-    for (int g = 0; g < total; g++) {
-        const bool more = g + 1 < total;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();   // tile g + 1 and the scores of tile g visible to all; every wave is done with tile g - 1
-        const int nslot = slot + 1 == NSTAGE ? 0 : slot + 1;
-        // the next clip's first tile is scored with the next clip's queries (in Qs since a clip ago)
-        if (t == ntile - 1 && more) qa_from_lds();
-        const char* tb = smem + slot * E8_TILEB;
+    clear(acc);
+    for (; !w.done(); w.next()) {
+        const bool more = w.more();
+        tile_barrier();
+        if (w.next_queries()) qa_from_lds();   // (in Qs since a clip ago)
+        const char* tb = smem + w.slot * TILEB;
         // ---- every LDS read of this iteration up front, in the order of use: scores of tile g (softmax), score operands of tile g + 1,
         // the 8 x 8 blocks of tile g (output).  Lanes fl and fl + 8 share a head: each takes four of the lane group's eight keys
         const int h = fl & 7, kq = kb + 4 * (fl >> 3);
-        const float* s0 = sc + (g & 1) * E8_SCB + h * E8_SCP + kq;
-        const f32x4 a0 = *reinterpret_cast<const f32x4*>(s0), a1 = *reinterpret_cast<const f32x4*>(s0 + E8_H * E8_SCP);
-        const f32x4 b0 = *reinterpret_cast<const f32x4*>(s0 + 2 * E8_H * E8_SCP), b1 = *reinterpret_cast<const f32x4*>(s0 + 3 * E8_H * E8_SCP);
+        const Partials sp = exch_read<E8_F>(sc, w.g & 1, h, kq);
         long ef[8];
-        if (more) score_reads(nslot, ef);
+        if (more) score_reads(w.nslot(), ef);
         wh_u32x2 blk[8];
         {
             const int c = 8 * wave + (fl >> 1);
@@ -190,27 +139,10 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es8(const f
         long pa;
         {
             float sv[4];
-            float tmax = -INFINITY;
-            const int key0 = t * E8_TK + kq;
 #pragma unroll
-            for (int u = 0; u < 4; u++) sv[u] = (a0[u] + b0[u]) + (a1[u] + b1[u]) * REM_INV;   // two dim halves x {head limb, remainder / 16}
-            if (t == ntile - 1) {   // (wave-uniform) keys past the end of the clip
-#pragma unroll
-                for (int u = 0; u < 4; u++) sv[u] = (key0 + u < S) ? sv[u] : -INFINITY;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) tmax = fmaxf(tmax, sv[u]);
-            tmax = fmaxf(tmax, ror8(tmax));   // the head's other four keys of this lane group
-            tmax = xrow_max(tmax);               // over the four lane groups: all 32 keys of the tile
-            const float m_new = fmaxf(m_run, tmax);
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // first tile: exp2(-inf) = 0
-            float ps = 0.0f;
-            float pv[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                pv[u] = __builtin_amdgcn_exp2f(sv[u] - m_new);   // masked key: exp2(-inf) = 0
-                ps += pv[u];
-            }
+            for (int u = 0; u < 4; u++) sv[u] = (sp.p[0][u] + sp.p[2][u]) + (sp.p[1][u] + sp.p[3][u]) * REM_INV;   // two dim halves x {head limb, remainder / 16}
+            const Soft sm = softmax_tile(sv, w.t * TK + kq, S, w.last_tile(), m_run);
+            const float (&pv)[4] = sm.pv;
             // operand rows 0-7: e4m3(p) of keys kb .. kb + 7 (this lane's four and, through DPP, its partner's); rows 8-15: their remainders x 16
             {
                 const unsigned own_hi = pack4(pv[0], pv[1], pv[2], pv[3]);
@@ -219,24 +151,10 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es8(const f
                 // lane fl < 8 (row h) owns keys kb .. kb + 3, lane fl + 8 (row 8 + h) keys kb + 4 .. kb + 7
                 pa = fl < 8 ? join(own_hi, oth_hi) : join(oth_lo, own_lo);
             }
-            l_run = l_run * alpha + ps;
-            m_run = m_new;
-            // head h's factor sits in lane h: through SGPRs (v_readlane), and only when some running maximum moved (wave-uniform)
-            if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
-                float ah[8];
-#pragma unroll
-                for (int q = 0; q < 8; q++) ah[q] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, alpha), q));
-                const bool up = fg & 1;
-                const float a4[4] = {up ? ah[4] : ah[0], up ? ah[5] : ah[1], up ? ah[6] : ah[2], up ? ah[7] : ah[3]};
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-#pragma unroll
-                    for (int i = 0; i < 4; i++) acc[e][i] *= a4[i];
-                }
-            }
+            rescale(sm, fg, l_run, acc);
         }
         // ---- scores of tile g + 1 (independent of everything above: fills the matrix pipe while the VALU transposes)
-        if (more) score_mfma(ef, (g + 1) & 1);
+        if (more) score_mfma(ef, (w.g + 1) & 1);
         // ---- output of tile g: dims 128 wave + 8 fl + e, contraction over the tile's 32 keys.  The 8 keys x 8 dims block of bytes is
         // transposed in registers: byte pairs of key pairs first (16 v_perm_b32), then the four keys of a contraction half (16 more)
         {
@@ -256,40 +174,25 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es8(const f
                 acc[e] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(pa, join(k03, k47), acc[e], 0, 0, 0);
             }
         }
-        slot = nslot;
-        if (++t < ntile) continue;
+        if (!w.advance()) continue;
         // ---- the clip ends: rows h and 8 + h (lanes l and l ^ 32) are the head limb's and the remainder's share of head h — add, normalise, store
         {
-            const float lh = l_run + ror8(l_run);   // the head's two key quartets
-            const float inv = 1.0f / xrow_sum(lh);
-            float ih[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++) ih[q] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inv), q));
-            const bool up = fg & 1;
-            const float inv4[4] = {up ? ih[4] : ih[0], up ? ih[5] : ih[1], up ? ih[6] : ih[2], up ? ih[7] : ih[3]};
+            float inv4[4];
+            clip_inv4(l_run, fg, inv4);
             const float wgt = fg < 2 ? 1.0f : REM_INV;
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 bf16x8 ov;
 #pragma unroll
-                for (int e = 0; e < 8; e++) {
-                    const float mine = acc[e][i] * wgt;
-                    const wh_u32x2 sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mine), __float_as_uint(mine), false, false);
-                    ov[e] = (bf16)((__uint_as_float(sw.x) + __uint_as_float(sw.y)) * inv4[i]);
-                }
-                if (fg < 2) {
-                    const int k = (4 * fg + i) * E8_D + 128 * wave + 8 * fl;
-                    *reinterpret_cast<bf16x8*>(out + ((long)(k >> 5) * mpad + clip) * 32 + (k & 31)) = ov;
-                }
+                for (int e = 0; e < 8; e++) ov[e] = (bf16)(sum32(acc[e][i] * wgt) * inv4[i]);
+                if (fg < 2) *reinterpret_cast<bf16x8*>(slab_dst(out, fg, i, wave, fl, mpad, w.clip)) = ov;
             }
         }
         // the next clip starts from nothing
-#pragma unroll
-        for (int e = 0; e < 8; e++) acc[e] = f32x4{0, 0, 0, 0};
+        clear(acc);
         m_run = -INFINITY;
         l_run = 0.0f;
-        t = 0;
-        clip += G;
+        w.next_clip();
     }
 }
 
@@ -328,17 +231,9 @@ __global__ __launch_bounds__(256) void k_layernorm_es8(const float* __restrict__
 // tools/runs/gpu_r04as.sh — one workgroup per CU stays)
 void wh_launch_dec_cross_attn_es8(hipStream_t s, const float* qe, const void* E, void* out, int S, int e_rows, int B, int mpad, bool stream_nt, int n_cus) {
     // (A/B runs) loader waves per workgroup — measured in the pipeline at 2048 clips (tools/runs/gpu_r04ao.sh): no difference (214.6 vs 215.6 ms of cross-attention), so one
-    static const int nl = [] { const char* e = getenv("WH_ES8_LOADERS"); return e ? atoi(e) : 1; }();
-    if (n_cus <= 0) n_cus = 256;
-    const int grid = std::min(B, n_cus);   // one workgroup per CU walks its clips
-#define WH_ES8_LAUNCH(AUX_, NL_)                                                                                                                         \
-    do {                                                                                                                                                 \
-        wh_ensure_dyn_lds((const void*)k_dec_cross_attn_es8<AUX_, 5, NL_>, e8_lds(5));                                                                   \
-        hipLaunchKernelGGL((k_dec_cross_attn_es8<AUX_, 5, NL_>), dim3(grid), dim3(256 + 64 * NL_), e8_lds(5), s, qe, (const unsigned char*)E, (bf16*)out, S, e_rows, mpad, B); \
-    } while (0)
-    if (stream_nt) { if (nl == 1) WH_ES8_LAUNCH(2, 1); else WH_ES8_LAUNCH(2, 2); }
-    else { if (nl == 1) WH_ES8_LAUNCH(0, 1); else WH_ES8_LAUNCH(0, 2); }
-#undef WH_ES8_LAUNCH
+    static const int nl = env_int("WH_ES8_LOADERS", 1);
+    launch(s, persistent_grid(B, n_cus), nl != 1, stream_nt, E8_F.lds(), [](auto AUX, auto NL) { return k_dec_cross_attn_es8<decltype(AUX)::value, decltype(NL)::value>; },
+           qe, (const unsigned char*)E, (bf16*)out, S, e_rows, mpad, B);
 }
 
 void wh_launch_layernorm_es8(hipStream_t s, const float* x, const float* gamma, const float* beta, void* out, long rows, int S, int e_rows) {
