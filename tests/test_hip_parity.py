@@ -457,6 +457,20 @@ def test_bf16_and_fp16_limb_encoder_state_kernels(gpu):
     assert r.returncode == 0 and "MISMATCH" not in r.stdout, r.stdout + r.stderr
 
 
+def test_decode_gemm_kernels_alone(gpu):
+    """k_dec_gemm, k_dec_gemm_wide and k_dec_tile alone against a float64 host restatement of the SkinnyArgs contract (tools/dec_gemm_check): bf16, f32,
+    fp16 limb pairs and e4m3 weights; plain, LayerNorm-consumer, LayerNorm-producer, grouped and ticket calls; one k-step per wave, a cut row tile,
+    a K tail past the prefetch depth, X merged from attention partials with an empty key range, the ring wrapping.  Every wide case runs again
+    through k_dec_gemm and the two must agree bit for bit, statistics included."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = os.path.join(root, "tools", "dec_gemm_check")
+    assert os.path.exists(exe), f"{exe} missing: __graft_entry__.build() compiles it"
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0 and "MISMATCH" not in r.stdout, r.stdout + r.stderr
+
+
 def test_bf16_batch_is_deterministic_and_permutation_invariant(gpu):
     b = bundle("micro", 11, wb.WH_PREC_BF16, max_batch=16)
     prompt, eot = small_prompt(b.dims)

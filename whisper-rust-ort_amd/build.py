@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libwhisper_hip.so")
 SOURCES = ["wh_mel.hip", "wh_gemm.hip", "wh_gemm8.hip", "wh_gemm8x.hip", "wh_gemm8_mx.hip", "wh_mlp.hip", "wh_attn.hip", "wh_decode.hip", "wh_dec_tile.hip", "wh_cross_es.hip", "wh_cross_es8.hip", "wh_cross_es3.hip", "wh_fp8.hip", "wh_align.hip", "wh_model.cpp", "wh_api.cpp"]
-HEADERS = ["wh_common.h", "wh_es_common.h", "wh_kernels.h", "wh_lm_tile.h", "wh_internal.h", "wh_json.h", "../../include/whisper_hip.h"]
+HEADERS = ["wh_common.h", "wh_es_common.h", "wh_dec_epilogue.h", "wh_kernels.h", "wh_lm_tile.h", "wh_internal.h", "wh_json.h", "../../include/whisper_hip.h"]
 # -amdgpu-mfma-vgpr-form: MFMA accumulators live in VGPRs (gfx950's register file is unified).  With the default
 # heuristic the attention kernel kept its score and output tiles in AGPRs and spent 160 of ~400 VALU instructions
 # per key tile on v_accvgpr_read/write copies around the softmax.
@@ -68,13 +68,21 @@ def build_tools(verbose: bool = False, force: bool = False) -> None:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     for name, kernel_src in (("mx_mfma_check", "wh_gemm8_mx.hip"), ("mx_gemm_check", "wh_gemm8_mx.hip"), ("mlp_check", "wh_mlp.hip"), ("es16_check", "wh_cross_es.hip"), ("es8_check", "wh_cross_es8.hip"), ("es3_check", "wh_cross_es3.hip"), ("align_check", "wh_align.hip")):
         src, exe = os.path.join(TOOLS, name + ".hip"), os.path.join(TOOLS, name)
-        deps = [src, os.path.join(CSRC, kernel_src), os.path.join(CSRC, "wh_common.h"), os.path.join(CSRC, "wh_es_common.h"), os.path.join(CSRC, "wh_kernels.h")]
+        deps = [src, os.path.join(CSRC, kernel_src), os.path.join(CSRC, "wh_common.h"), os.path.join(CSRC, "wh_es_common.h"), os.path.join(CSRC, "wh_dec_epilogue.h"), os.path.join(CSRC, "wh_kernels.h")]
         if force or _stale(exe, deps):
             # the kernel source's own extra flags: a tool checks the kernel binary that ships
             cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-mllvm", "-amdgpu-mfma-vgpr-form=1"] + EXTRA_FLAGS.get(kernel_src, []) + ["-w", "-I", CSRC, src, "-o", exe]
             if verbose:
                 print(" ".join(cmd), flush=True)
             subprocess.check_call(cmd)
+    # tools/dec_gemm_check (tests/test_hip_parity.py) calls the library's own launchers instead: it links libwhisper_hip.so, so it checks
+    # the kernels of whichever library it is built against
+    src, exe = os.path.join(TOOLS, "dec_gemm_check.cpp"), os.path.join(TOOLS, "dec_gemm_check")
+    if force or _stale(exe, [src, OUT, os.path.join(CSRC, "wh_kernels.h")]):
+        cmd = [hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-w", src, "-o", exe, "-L" + HERE, "-lwhisper_hip", "-Wl,-rpath,$ORIGIN/../whisper-rust-ort_amd"]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
 
 
 HOST = os.path.join(HERE, "host")

@@ -346,6 +346,24 @@ __device__ __forceinline__ void wh_ln_mean_rstd(float s1, float s2, float inv_or
     const float var = ex2 - mean * mean;
     rstd = rsqrtf(fmaxf(var, 0.0f) + 1e-5f);
 }
+
+// {mean, rstd} of a row from the partials that ln_partial_sum reads, in the ONE term order that every kernel whose results must agree bit for
+// bit uses (k_dec_gemm / k_dec_gemm_wide; k_lm_head / k_lang_head / the LM-head tile kernels): thread (row r, quarter q) sums every 4th tile
+// with ln_partial_sum and leaves its pair in LDS, lnq [4][rows][2]; behind a barrier the quarters of a row are added as (q0 + q1) + (q2 + q3)
+// and wh_ln_mean_rstd finishes over the row's k columns.  (k_dec_tile adds two halves — a different sum, whose results are that kernel's own.)
+// The shape is deliberate: the row count is a template parameter, each sum is one expression and k arrives as an int, because with a
+// run-time row count, a sum built in two statements or the conversion of k at the call site the callers' instruction streams changed.
+template <int rows>
+__device__ __forceinline__ void ln_part_store(float* lnq, int r, int q, float s1, float s2) {
+    lnq[(q * rows + r) * 2] = s1;
+    lnq[(q * rows + r) * 2 + 1] = s2;
+}
+template <int rows>
+__device__ __forceinline__ void ln_row_stats(const float* lnq, int r, int k, float& mean, float& rstd) {
+    const float s1 = (lnq[r * 2] + lnq[(rows + r) * 2]) + (lnq[(2 * rows + r) * 2] + lnq[(3 * rows + r) * 2]);
+    const float s2 = (lnq[r * 2 + 1] + lnq[(rows + r) * 2 + 1]) + (lnq[(2 * rows + r) * 2 + 1] + lnq[(3 * rows + r) * 2 + 1]);
+    wh_ln_mean_rstd(s1, s2, (float)k, false, mean, rstd);
+}
 __device__ __forceinline__ float wh_scale(float acc, float ws) {   // acc * ws (fp8 weights: the channel scale; exact for ws = 1)
 #pragma clang fp contract(off)
     return acc * ws;
@@ -414,14 +432,6 @@ __device__ __forceinline__ float lp_merge(float m, float s, float m1, float s1) 
     const float mx = fmaxf(m, m1);
     return lp_rescale(s, m, mx) + lp_rescale(s1, m1, mx);
 }
-// sum over the four lane groups that share a row in the 16 x 16 MFMA result layout (lanes l, l + 16, l + 32, l + 48): every one of them gets it
-__device__ __forceinline__ float lp_row_sum(float s) {
-    typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
-    u32x2_t t = __builtin_amdgcn_permlane16_swap(__float_as_uint(s), __float_as_uint(s), false, false);
-    s = __uint_as_float(t.x) + __uint_as_float(t.y);
-    t = __builtin_amdgcn_permlane32_swap(__float_as_uint(s), __float_as_uint(s), false, false);
-    return __uint_as_float(t.x) + __uint_as_float(t.y);
-}
 // second pass over one row of a tile kernel's accumulators (still live after the argmax): the sum of exp(v - bv) over this lane's columns
 // that are not suppressed and lie in [lo, hi), bv = the row's maximum over exactly those columns.  Branch-free: one v_exp_f32 and a select per
 // logit.  The column tests do not depend on the row; left to themselves they are hoisted out of the caller's unrolled row loop as sixteen
@@ -483,6 +493,14 @@ void wh_with_dtype(int prec, F&& f) {
     if (prec == WH_PREC_F32) f(wh_type_tag<float>{});
     else if (prec == WH_PREC_F16X3) f(wh_type_tag<h2>{});
     else f(wh_type_tag<bf16>{});
+}
+// the smallest power of two in [LO, HI] that is >= n as an std::integral_constant (anything above HI counts as HI)
+template <int LO, int HI, typename F>
+void wh_with_pow2(int n, F&& f) {
+    if constexpr (LO < HI) {
+        if (n > LO) return wh_with_pow2<2 * LO, HI>(n, f);
+    }
+    f(std::integral_constant<int, LO>{});
 }
 // 1 .. 4 as an std::integral_constant (the LM heads' row groups per workgroup; anything above 4 counts as 4)
 template <typename F>

@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "wh_common.h"
+#include "wh_dec_epilogue.h"
 #include "wh_kernels.h"
 
 namespace {
@@ -52,8 +53,6 @@ template <> struct OT<h2> {
     }
 };
 
-__device__ __forceinline__ long slab_idx(int m, int k, int mpad) { return ((long)(k >> 5) * mpad + m) * 32 + (k & 31); }
-
 template <typename T, typename TO, int BN, int NSLOT>
 __global__ __launch_bounds__(256) void k_dec_tile(SkinnyArgs a) {
     typedef OT<T> O;
@@ -64,7 +63,8 @@ __global__ __launch_bounds__(256) void k_dec_tile(SkinnyArgs a) {
     constexpr int PER_STAGE = A_INSTR + W_INSTR;
     constexpr int TM = 4, TN = BN / 32;                              // 16 x 16 tiles per wave: 64 rows x BN / 2 columns
     extern __shared__ __attribute__((aligned(128))) char smem[];
-    {   // grouped launches (SkinnyArgs::zn): group blockIdx.z works on its own X, W, bias and C (a slab: type T)
+    {   // grouped launches (SkinnyArgs::zn): group blockIdx.z works on its own X, W, bias and C (a slab: type T).  dec_gemm_group
+        // (wh_dec_epilogue.h) written out: through the function this kernel's register allocation changes
         const long z = blockIdx.z;
         if (z) {
             a.X = (const T*)a.X + z * a.x_zs;
@@ -95,8 +95,7 @@ __global__ __launch_bounds__(256) void k_dec_tile(SkinnyArgs a) {
         const int r = tid & (BM - 1), h = tid >> 7, row = min(m0 + r, a.x_mpad - 1);
         float s1, s2;
         ln_partial_sum(a.ln_part, a.ln_tiles, a.x_mpad, row, h, 2, s1, s2);
-        lnq[(h * BM + r) * 2] = s1;
-        lnq[(h * BM + r) * 2 + 1] = s2;
+        ln_part_store<BM>(lnq, r, h, s1, s2);
     }
 
     // per-lane source addresses of this wave's share of a stage: lane i -> row i / CPR of the instruction's RPI rows, LDS chunk i % CPR
@@ -231,7 +230,8 @@ __global__ __launch_bounds__(256) void k_dec_tile(SkinnyArgs a) {
             }
         }
     }
-    if (a.ticket) {   // the last workgroup of the last kernel of a prompt step advances the device-side position
+    if (a.ticket) {   // the last workgroup of the last kernel of a prompt step advances the device-side position (advance_if_last,
+                      // wh_dec_epilogue.h, written out for the same reason; tickets are only used with zn == 1, so the counts agree)
         __syncthreads();
         if (tid == 0) {
             const int t = atomicAdd(a.ticket, 1);

@@ -24,6 +24,7 @@
 #include <stdlib.h>
 
 #include "wh_common.h"
+#include "wh_dec_epilogue.h"
 #include "wh_kernels.h"
 
 #include <algorithm>
@@ -40,27 +41,7 @@ int wh_dbg_wide = -1;  // column tiles per workgroup at > 256 rows: -1 heuristic
 
 namespace {
 
-// One workgroup arrives; the last one of the grid bumps *pos (every workgroup read *pos at its
-// start, so nobody can observe the new value within this launch) and re-arms the ticket.
-__device__ __forceinline__ void advance_if_last(int* ticket, int* pos_p, int n_blocks) {
-    if (!ticket) return;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int t = atomicAdd(ticket, 1);
-        if (t == n_blocks - 1) {
-            *ticket = 0;
-            *pos_p += 1;
-        }
-    }
-}
-
-// ---- decode activation layout ("k-slab major") ------------------------------------------------
-// Activations that feed a decode GEMM are stored [K/32][Mpad][32]: the 32-deep k-slab of 16
-// consecutive rows is one contiguous 1 KiB block, so the MFMA column-operand load of a wave (lane
-// (row fl, group fg) reads 8 consecutive k of row 16t+fl) is a single fully coalesced access — the
-// same shape as the weight-fragment loads — instead of 16 rows x 64 B scattered over a row-major
-// [M][K] buffer.  Producers (LayerNorm, attention, fc1 epilogue) write this layout directly.
-__device__ __forceinline__ long slab_idx(int m, int k, int mpad) { return ((long)(k >> 5) * mpad + m) * 32 + (k & 31); }
+// (advance_if_last, the position ticket, and slab_idx, the k-slab-major activation layout: wh_dec_epilogue.h)
 
 // Token embedding + learned position ([3P] :737, :757-766) for the rows of this position: writes the f32
 // residual stream, its raw copy in the compute dtype (slab layout) and each row's {sum x, sum x^2}
@@ -190,17 +171,6 @@ __device__ __forceinline__ void load_wfrags(const TW* p, typename FragT<T>::type
     }
 }
 
-// grouped launches (SkinnyArgs::zn): group blockIdx.z works on its own X, W, bias and C
-template <typename T, typename TO, typename TW>
-__device__ __forceinline__ void dec_gemm_group(SkinnyArgs& a) {
-    const long z = blockIdx.z;
-    if (z == 0) return;
-    a.X = (const T*)a.X + z * a.x_zs;
-    a.W = (const TW*)a.W + z * a.w_zs;
-    a.C = a.c_mpad ? (void*)((T*)a.C + z * a.c_zs) : (void*)((TO*)a.C + z * a.c_zs);
-    if (a.bias) a.bias += z * a.bias_zs;
-}
-
 template <typename T, typename TO, int MT, int NW, int XP, typename TW = T>  // XP > 0: X from XP-bounded attention partials
 __global__ __launch_bounds__(NW * 64) void k_dec_gemm(SkinnyArgs a) {
     extern __shared__ __attribute__((aligned(128))) char smem_raw[];   // 128: h2 tiles find their 32-blocks from the address
@@ -247,7 +217,8 @@ __global__ __launch_bounds__(NW * 64) void k_dec_gemm(SkinnyArgs a) {
     }
     // LayerNorm folded in: reduce the producer's per-tile partial sums of this row group to mean / rstd
     // (while the weight and activation fragments above are in flight)
-    float* lnred = reinterpret_cast<float*>(smem_raw) + (size_t)NW * MT * 64 * 4;  // [4][MT*16][2], then stat[MT*16][2]
+    typedef DecGemmLds<NW, MT, MT> Lds;
+    float* lnred = Lds::lnq(smem_raw);
     float ln_mean = 0.0f, ln_rstd = 1.0f, ln_sv[4] = {0, 0, 0, 0};
     if (a.ln_part) {
         constexpr int ROWS = MT * 16;
@@ -255,15 +226,11 @@ __global__ __launch_bounds__(NW * 64) void k_dec_gemm(SkinnyArgs a) {
             const int r = tid % ROWS, q = tid / ROWS;
             float s1, s2;
             ln_partial_sum(a.ln_part, a.ln_tiles, a.x_mpad, m0 + r, q, 4, s1, s2);
-            lnred[(q * ROWS + r) * 2] = s1;
-            lnred[(q * ROWS + r) * 2 + 1] = s2;
+            ln_part_store<ROWS>(lnred, r, q, s1, s2);
         }
         __syncthreads();
         if (ep_ok) {
-            const int r = wave * 16 + fl;
-            const float s1 = (lnred[r * 2] + lnred[(ROWS + r) * 2]) + (lnred[(2 * ROWS + r) * 2] + lnred[(3 * ROWS + r) * 2]);
-            const float s2 = (lnred[r * 2 + 1] + lnred[(ROWS + r) * 2 + 1]) + (lnred[(2 * ROWS + r) * 2 + 1] + lnred[(3 * ROWS + r) * 2 + 1]);
-            wh_ln_mean_rstd(s1, s2, (float)a.K, false, ln_mean, ln_rstd);
+            ln_row_stats<ROWS>(lnred, wave * 16 + fl, a.K, ln_mean, ln_rstd);
             const f32x4 sv = *reinterpret_cast<const f32x4*>(a.ln_s + en);
             ln_sv[0] = sv[0]; ln_sv[1] = sv[1]; ln_sv[2] = sv[2]; ln_sv[3] = sv[3];
         }
@@ -275,7 +242,7 @@ __global__ __launch_bounds__(NW * 64) void k_dec_gemm(SkinnyArgs a) {
         // X = merge of the key ranges' partials, built once per workgroup in LDS (slab layout [K/32][16][32]) with
         // row-contiguous 16-byte loads; the weight fragments above are in flight meanwhile (iters <= DEPTH here)
         static_assert(MT == 1, "merged-X variant runs 16-row groups");
-        T* Xs = reinterpret_cast<T*>(smem_raw + (size_t)NW * 64 * 16 + 4 * 16 * 2 * 4);
+        T* Xs = reinterpret_cast<T*>(smem_raw + Lds::BYTES);
         constexpr int NT = NW * 64, IF = XP <= 4 ? 4 : (XP <= 8 ? 2 : 1);    // items in flight per thread
         // 4-column chunks per row; only live rows are merged (a dead row of X feeds only its own, never stored,
         // output column of the MFMA tile)
@@ -337,7 +304,7 @@ __global__ __launch_bounds__(NW * 64) void k_dec_gemm(SkinnyArgs a) {
                     for (int t = 0; t < MT; t++) mma16(acc[t], wq[i][j], xq[i][j][t]);  // D rows = n (4*fg + r), col = m (fl)
             }
     }
-    f32x4* red = reinterpret_cast<f32x4*>(smem_raw);
+    f32x4* red = Lds::red(smem_raw);
 #pragma unroll
     for (int t = 0; t < MT; t++) red[(wave * MT + t) * 64 + lane] = acc[t];
     __syncthreads();
@@ -442,7 +409,8 @@ __global__ __launch_bounds__(NW * 64, 2) void k_dec_gemm_wide(SkinnyArgs a) {
         if (ep_ok[j] && a.R) pre_r[j] = *reinterpret_cast<const f32x4*>(a.R + (long)em[j] * a.ldr + en[j]);
         if (ep_ok[j] && a.row_shift) pre_sh[j] = a.row_shift[em[j]];
     }
-    float* lnred = reinterpret_cast<float*>(smem_raw) + (size_t)NW * TILES * 64 * 4;  // [4][MT*16][2]
+    typedef DecGemmLds<NW, MT, TILES> Lds;
+    float* lnred = Lds::lnq(smem_raw);
     if (a.ln_part) {
         constexpr int ROWS = MT * 16;
         static_assert(4 * ROWS <= NW * 64, "one thread per (quarter, row)");
@@ -450,15 +418,13 @@ __global__ __launch_bounds__(NW * 64, 2) void k_dec_gemm_wide(SkinnyArgs a) {
             const int r = tid % ROWS, q = tid / ROWS;
             float s1, s2;
             ln_partial_sum(a.ln_part, a.ln_tiles, a.x_mpad, m0 + r, q, 4, s1, s2);
-            lnred[(q * ROWS + r) * 2] = s1;
-            lnred[(q * ROWS + r) * 2 + 1] = s2;
+            ln_part_store<ROWS>(lnred, r, q, s1, s2);
         }
     }
     // per-column operands of the tiles this wave finishes: requested AFTER the main loop.  Requesting them before it where the
     // register file has room (two column tiles per workgroup) was measured slower in round 3 — the trace of the whole step reads
     // 9.68 instead of 8.74 us for the QKV / cross-Q launches, 7.17 instead of 6.97 us for the out-projections
     // (profiles/r03_kernel_stats_base_bf16_b1024.txt history) — they only lengthen the queue in front of the first fragments.
-    constexpr bool EARLY_COLS = false;
     f32x4 pre_bias[TPW], pre_ws[TPW], pre_g[TPW], pre_sv[TPW];
     auto load_cols = [&]() {
 #pragma unroll
@@ -472,7 +438,6 @@ __global__ __launch_bounds__(NW * 64, 2) void k_dec_gemm_wide(SkinnyArgs a) {
             }
         }
     };
-    if constexpr (EARLY_COLS) load_cols();
     f32x4 acc[NT][MT];
 #pragma unroll
     for (int nt = 0; nt < NT; nt++)
@@ -501,8 +466,8 @@ __global__ __launch_bounds__(NW * 64, 2) void k_dec_gemm_wide(SkinnyArgs a) {
             }
         }
     }
-    if constexpr (!EARLY_COLS) load_cols();
-    f32x4* red = reinterpret_cast<f32x4*>(smem_raw);
+    load_cols();
+    f32x4* red = Lds::red(smem_raw);
 #pragma unroll
     for (int nt = 0; nt < NT; nt++)
 #pragma unroll
@@ -523,11 +488,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_dec_gemm_wide(SkinnyArgs a) {
             }
             float ln_mean = 0.0f, ln_rstd = 1.0f;
             if (a.ln_part) {
-                constexpr int ROWS = MT * 16;
-                const int r = (t % MT) * 16 + fl;
-                const float s1 = (lnred[r * 2] + lnred[(ROWS + r) * 2]) + (lnred[(2 * ROWS + r) * 2] + lnred[(3 * ROWS + r) * 2]);
-                const float s2 = (lnred[r * 2 + 1] + lnred[(ROWS + r) * 2 + 1]) + (lnred[(2 * ROWS + r) * 2 + 1] + lnred[(3 * ROWS + r) * 2 + 1]);
-                wh_ln_mean_rstd(s1, s2, (float)a.K, false, ln_mean, ln_rstd);
+                ln_row_stats<MT * 16>(lnred, (t % MT) * 16 + fl, a.K, ln_mean, ln_rstd);
             }
 #pragma unroll
             for (int e = 0; e < 4; e++) {
@@ -618,15 +579,12 @@ __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
             const int r = tid % ROWS, q = tid / ROWS;
             float s1, s2;
             ln_partial_sum(a.ln_part, a.ln_tiles, a.x_mpad, m0 + r, q, 4, s1, s2);
-            lnq[(q * ROWS + r) * 2] = s1;
-            lnq[(q * ROWS + r) * 2 + 1] = s2;
+            ln_part_store<ROWS>(lnq, r, q, s1, s2);
         }
         __syncthreads();
         if (tid < ROWS) {
-            const float s1 = (lnq[tid * 2] + lnq[(ROWS + tid) * 2]) + (lnq[(2 * ROWS + tid) * 2] + lnq[(3 * ROWS + tid) * 2]);
-            const float s2 = (lnq[tid * 2 + 1] + lnq[(ROWS + tid) * 2 + 1]) + (lnq[(2 * ROWS + tid) * 2 + 1] + lnq[(3 * ROWS + tid) * 2 + 1]);
             float mean, rstd;
-            wh_ln_mean_rstd(s1, s2, (float)a.K, false, mean, rstd);
+            ln_row_stats<ROWS>(lnq, tid, a.K, mean, rstd);
             lnstat[2 * tid] = mean;
             lnstat[2 * tid + 1] = rstd;
         }
@@ -762,7 +720,7 @@ __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
         xrow_argmax(bv, bi);
         const int m = m0 + t * 16 + fl;
         if constexpr (LP) {   // this lane's sum moved to the row's maximum, then the four lane groups' sums added
-            const float ls = lp_row_sum(lp_rescale(lsw[t], bvw[t], bv));
+            const float ls = xrow_sum(lp_rescale(lsw[t], bvw[t], bv));
             if (fg == 0 && m < a.M) a.part_sum[(long)part * a.x_mpad + m] = ls;
         }
         if (fg == 0 && m < a.M) {
@@ -1089,15 +1047,12 @@ __global__ __launch_bounds__(256) void k_lang_head(LangHeadArgs a) {
             const int r = tid % ROWS, q = tid / ROWS;
             float s1, s2;
             ln_partial_sum(a.ln_part, a.ln_tiles, a.x_mpad, m0 + r, q, 4, s1, s2);
-            lnq[(q * ROWS + r) * 2] = s1;
-            lnq[(q * ROWS + r) * 2 + 1] = s2;
+            ln_part_store<ROWS>(lnq, r, q, s1, s2);
         }
         __syncthreads();
         if (tid < ROWS) {
-            const float s1 = (lnq[tid * 2] + lnq[(ROWS + tid) * 2]) + (lnq[(2 * ROWS + tid) * 2] + lnq[(3 * ROWS + tid) * 2]);
-            const float s2 = (lnq[tid * 2 + 1] + lnq[(ROWS + tid) * 2 + 1]) + (lnq[(2 * ROWS + tid) * 2 + 1] + lnq[(3 * ROWS + tid) * 2 + 1]);
             float mean, rstd;
-            wh_ln_mean_rstd(s1, s2, (float)a.K, false, mean, rstd);
+            ln_row_stats<ROWS>(lnq, tid, a.K, mean, rstd);
             lnstat[2 * tid] = mean;
             lnstat[2 * tid + 1] = rstd;
         }
@@ -1662,6 +1617,10 @@ void set_max_smem(K kernel, size_t bytes) {
 template <typename T, typename TO, int NW, typename TW>
 void launch_dec_gemm_mt(hipStream_t s, const SkinnyArgs& a) {
     const int n_tiles = (a.N + 15) / 16;
+    auto launch = [&](auto kernel, dim3 grid, size_t smem) {
+        set_max_smem(kernel, smem);
+        hipLaunchKernelGGL(kernel, grid, dim3(NW * 64), smem, s, a);
+    };
     // rows per workgroup: 64, or 32 when K is deep (every workgroup pulls its rows of X through L2; halving
     // them costs a second read of the 16-column weight tile but doubles the workgroups sharing the load)
     // measured (tools/microbench.cpp, M = 64): N = 512 → 16 rows best (2.6 vs 3.7 us), N = 1536 / 2048 → 32 rows
@@ -1692,31 +1651,22 @@ void launch_dec_gemm_mt(hipStream_t s, const SkinnyArgs& a) {
         else if (n_tiles % 2 == 0 && (n_tiles / 2) * rg * a.zn >= 128) nt = 2;
         if (wide == 2 || (wide == 4 && NW == 4)) nt = wide;
         if (wide != 0 && nt > 1 && n_tiles % nt == 0) {
-            const size_t smw = (size_t)NW * WMT * nt * 64 * 16 + (size_t)4 * WMT * 16 * 2 * 4;
-            dim3 gw(n_tiles / nt, rg, a.zn);
-            if (nt == 4) { set_max_smem(k_dec_gemm_wide<T, TO, WMT, 4, NW, TW>, smw); hipLaunchKernelGGL((k_dec_gemm_wide<T, TO, WMT, 4, NW, TW>), gw, dim3(NW * 64), smw, s, a); }
-            else { set_max_smem(k_dec_gemm_wide<T, TO, WMT, 2, NW, TW>, smw); hipLaunchKernelGGL((k_dec_gemm_wide<T, TO, WMT, 2, NW, TW>), gw, dim3(NW * 64), smw, s, a); }
+            wh_with_pow2<2, 4>(nt, [&](auto NT) {
+                launch(k_dec_gemm_wide<T, TO, WMT, decltype(NT)::value, NW, TW>, dim3(n_tiles / nt, rg, a.zn), DecGemmLds<NW, WMT, WMT * decltype(NT)::value>::BYTES);
+            });
             return;
         }
     }
     const int mt = std::min(mt_cap, (a.M + 15) / 16);
-    const size_t sm = (size_t)NW * mt * 64 * 16 + (size_t)4 * mt * 16 * 2 * 4;
-    dim3 grid(n_tiles, (a.M + 16 * mt - 1) / (16 * mt), a.zn);
     if (a.xpart) {  // X merged from attention partials: 16-row groups only (the merge is per-lane work)
-        dim3 g1(n_tiles, (a.M + 15) / 16);
-        const size_t sm1 = (size_t)NW * 64 * 16 + 4 * 16 * 2 * 4 + (size_t)16 * a.K * sizeof(T);  // + merged X tile
-        if (a.x_splits <= 4) { set_max_smem(k_dec_gemm<T, TO, 1, NW, 4, TW>, sm1); hipLaunchKernelGGL((k_dec_gemm<T, TO, 1, NW, 4, TW>), g1, dim3(NW * 64), sm1, s, a); }
-        else if (a.x_splits <= 8) { set_max_smem(k_dec_gemm<T, TO, 1, NW, 8, TW>, sm1); hipLaunchKernelGGL((k_dec_gemm<T, TO, 1, NW, 8, TW>), g1, dim3(NW * 64), sm1, s, a); }
-        else if (a.x_splits <= 16) { set_max_smem(k_dec_gemm<T, TO, 1, NW, 16, TW>, sm1); hipLaunchKernelGGL((k_dec_gemm<T, TO, 1, NW, 16, TW>), g1, dim3(NW * 64), sm1, s, a); }
-        else { set_max_smem(k_dec_gemm<T, TO, 1, NW, 32, TW>, sm1); hipLaunchKernelGGL((k_dec_gemm<T, TO, 1, NW, 32, TW>), g1, dim3(NW * 64), sm1, s, a); }
+        wh_with_pow2<4, 32>(a.x_splits, [&](auto XP) {   // + merged X tile
+            launch(k_dec_gemm<T, TO, 1, NW, decltype(XP)::value, TW>, dim3(n_tiles, (a.M + 15) / 16), DecGemmLds<NW, 1, 1>::BYTES + (size_t)16 * a.K * sizeof(T));
+        });
         return;
     }
-    switch (mt) {
-        case 1: hipLaunchKernelGGL((k_dec_gemm<T, TO, 1, NW, 0, TW>), grid, dim3(NW * 64), sm, s, a); break;
-        case 2: hipLaunchKernelGGL((k_dec_gemm<T, TO, 2, NW, 0, TW>), grid, dim3(NW * 64), sm, s, a); break;
-        case 3: hipLaunchKernelGGL((k_dec_gemm<T, TO, 3, NW, 0, TW>), grid, dim3(NW * 64), sm, s, a); break;
-        default: hipLaunchKernelGGL((k_dec_gemm<T, TO, 4, NW, 0, TW>), grid, dim3(NW * 64), sm, s, a); break;
-    }
+    wh_with_1to4(mt, [&](auto MT) {   // grid and LDS follow the run-time mt as they always did (the carve is linear in the row tiles)
+        launch(k_dec_gemm<T, TO, decltype(MT)::value, NW, 0, TW>, dim3(n_tiles, (a.M + 16 * mt - 1) / (16 * mt), a.zn), mt * DecGemmLds<NW, 1, 1>::BYTES);
+    });
 }
 
 // K split over the waves of a workgroup: 8 ways when K is deep, when X is merged from attention partials, or when the
@@ -1766,20 +1716,26 @@ void wh_launch_dec_embed(hipStream_t s, int prec, const void* tok_emb, const flo
     });
 }
 
-// row groups per workgroup (mt), dynamic LDS and grid of k_lm_head<T, mt, ...> for this shape
+// 16-row groups per workgroup (mt) and dynamic LDS of k_lm_head<T, mt, ...> / k_lang_head<T, mt> for M rows of K columns
 template <typename T>
-static dim3 lm_head_geometry(const SkinnyArgs& a, int* mt_out, size_t* sm_out) {
-    const int n_tiles = (a.N + 15) / 16;
-    int mt = std::min(wh_dbg_lm_mt, (a.M + 15) / 16);
-    auto lds = [&](int t) { return (size_t)t * 16 * a.K * sizeof(T) + (size_t)t * 16 * 2 * 4 * 5; };  // X tile + LN stats (+ 4 quarter sums)
+static int lm_row_groups(int M, int K, size_t* sm_out) {
+    int mt = std::min(wh_dbg_lm_mt, (M + 15) / 16);
+    auto lds = [&](int t) { return (size_t)t * 16 * K * sizeof(T) + (size_t)t * 16 * 2 * 4 * 5; };  // X tile + LN stats (+ 4 quarter sums)
     while (mt > 1 && lds(mt) > 150 * 1024) mt--;
     // (128-row groups — two instead of four at 256 clips, half the passes over the 53 MB embedding but one workgroup per CU —
     // measured no faster: 189.5 vs 188.0 ms per 256-clip step)
     if (mt > 4) mt = 4;
-    const size_t sm = lds(mt);
+    *sm_out = lds(mt);
+    return mt;
+}
+
+// the same and the grid of k_lm_head for this shape
+template <typename T>
+static dim3 lm_head_geometry(const SkinnyArgs& a, int* mt_out, size_t* sm_out) {
+    const int n_tiles = (a.N + 15) / 16;
+    const int mt = *mt_out = lm_row_groups<T>(a.M, a.K, sm_out);
+    const size_t sm = *sm_out;
     const int per_cu = std::max<int>(1, (int)(150 * 1024 / sm));
-    *mt_out = mt;
-    *sm_out = sm;
     return dim3(std::min((n_tiles + 3) / 4, 256 * std::min(per_cu, wh_dbg_lm_blocks_per_cu) / ((a.M + 16 * mt - 1) / (16 * mt))), (a.M + 16 * mt - 1) / (16 * mt));
 }
 
@@ -1839,11 +1795,8 @@ void wh_launch_nospeech_finish(hipStream_t s, const float* part_val, const float
 template <typename T>
 static void launch_lang_head_t(hipStream_t s, const LangHeadArgs& a) {
     // row groups as lm_head_geometry forms them (the pitch of the slab covers whole groups)
-    int mt = std::min(wh_dbg_lm_mt, (a.M + 15) / 16);
-    auto lds = [&](int t) { return (size_t)t * 16 * a.K * sizeof(T) + (size_t)t * 16 * 2 * 4 * 5; };
-    while (mt > 1 && lds(mt) > 150 * 1024) mt--;
-    if (mt > 4) mt = 4;
-    const size_t sm = lds(mt);
+    size_t sm;
+    const int mt = lm_row_groups<T>(a.M, a.K, &sm);
     dim3 grid(((a.n_lang + 15) / 16 + 3) / 4, (a.M + 16 * mt - 1) / (16 * mt));
     wh_with_1to4(mt, [&](auto MT) {
         auto kfn = k_lang_head<T, decltype(MT)::value>;

@@ -54,10 +54,8 @@ struct WhLmTile {
             float s1a, s2a, s1b, s2b;
             ln_partial_sum(a.ln_part, a.ln_tiles, a.x_mpad, row, h, 4, s1a, s2a);
             ln_partial_sum(a.ln_part, a.ln_tiles, a.x_mpad, row, h + 2, 4, s1b, s2b);
-            l.lnq[(h * BM + r) * 2] = s1a;
-            l.lnq[(h * BM + r) * 2 + 1] = s2a;
-            l.lnq[((h + 2) * BM + r) * 2] = s1b;
-            l.lnq[((h + 2) * BM + r) * 2 + 1] = s2b;
+            ln_part_store<BM>(l.lnq, r, h, s1a, s2a);
+            ln_part_store<BM>(l.lnq, r, h + 2, s1b, s2b);
         }
         TsRaw t = {0, 0, 0};
         if constexpr (RULES) {
@@ -72,11 +70,8 @@ struct WhLmTile {
     // left (s_waitcnt lgkmcnt(0) before that barrier), wherever the kernel's loop has it
     static __device__ __forceinline__ void ln_reduce(SkinnyArgs a, const Lds l, int tid) {
         if (a.ln_part && tid < BM) {
-            const float* lnq = l.lnq;
-            const float s1 = (lnq[tid * 2] + lnq[(BM + tid) * 2]) + (lnq[(2 * BM + tid) * 2] + lnq[(3 * BM + tid) * 2]);
-            const float s2 = (lnq[tid * 2 + 1] + lnq[(BM + tid) * 2 + 1]) + (lnq[(2 * BM + tid) * 2 + 1] + lnq[(3 * BM + tid) * 2 + 1]);
             float mean, rstd;
-            wh_ln_mean_rstd(s1, s2, (float)a.K, false, mean, rstd);
+            ln_row_stats<BM>(l.lnq, tid, a.K, mean, rstd);
             l.lnstat[2 * tid] = mean;
             l.lnstat[2 * tid + 1] = rstd;
         }
@@ -233,7 +228,7 @@ struct WhLmTile {
                 const float bv = red_v[wn * BM + rloc];
                 int tlo = 0;
                 if constexpr (RULES) tlo = tsr[4 * rloc];
-                const float ls = lp_row_sum(lp_tile_row<TN, !RULES>(acc[i], a.ln_part != nullptr, mean, rstd, sv, cv, mbits, nw0 + 4 * fg, tlo,
+                const float ls = xrow_sum(lp_tile_row<TN, !RULES>(acc[i], a.ln_part != nullptr, mean, rstd, sv, cv, mbits, nw0 + 4 * fg, tlo,
                                                                     RULES ? min(a.ts_begin, a.N) : a.N, bv, m < a.M ? a.probe_id : -1, a.probe_out + m));
                 if (fg == 0) red_s[wn * BM + rloc] = ls;
             }
