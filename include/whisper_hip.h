@@ -327,6 +327,61 @@ int wh_get_token_frames(const wh_ctx* c, int32_t* frames, size_t cap_tokens, int
  * shape3 = {n_heads, n_gen, S_b}; probs [n_heads][n_gen][S_b] and matrix [n_gen][S_b] (either may be NULL; cap_floats must hold probs).
  * probs == NULL and matrix == NULL: only the shape.  WH_ERR_STATE if that call kept no debug rows; WH_ERR_ARG for k outside them. */
 int wh_get_alignment_debug(const wh_ctx* c, size_t k, float* probs, float* matrix, size_t cap_floats, int32_t* shape3);
+/* Beam search in the token loop, with the n best hypotheses per clip (openai-whisper's BeamSearchDecoder and MaximumLikelihoodRanker;
+ * faster-whisper's beam_size / patience / length_penalty; HF generate's num_beams).  No reference entry corresponds: the reference keeps
+ * plain argmax (src/main.rs:709-735).  With this set, every decode entry of the ctx decodes each clip with K = beam_size beams, which are
+ * K adjacent batch rows (row = clip * K + beam), so a call may hold at most max_batch / K clips.  Per clip:
+ *   - C = round(K * patience) finished candidates are wanted.  Live beams j = 0 .. K-1 carry a generated history h_j and a score s_j (f32);
+ *     s_0 = 0, s_j = -inf for j >= 1 at the start.  A beam with s_j = -inf is dead: its row keeps running, none of its candidates is taken;
+ *   - at every generated position g, for each live row: v = the raw logits after the suppress masks (begin_suppress at g = 0) and, when set,
+ *     the timestamp rules 1-5 on h_j (rule 5 empties the text ids); NaN is never allowed; lp[i] = v[i] - (m + logf(sum_allowed expf(v - m)))
+ *     with m the largest allowed logit (what wh_get_logprobs reports); nothing allowed: the row yields no candidate;
+ *   - candidates (j, i) with score = s_j + lp[i] (one f32 addition), ordered by score descending, then j, then i ascending; scores of -inf
+ *     or NaN are no candidates.  Walking that order, a candidate with i == eot becomes a finished hypothesis h_j ++ [eot] with that score,
+ *     any other one the next live beam (its parent j recorded); the walk stops after K live ones; if fewer are available the rest are dead;
+ *   - finished hypotheses enter the clip's pool in walk order while the pool holds fewer than C; the clip is complete when it holds C, and
+ *     its rows then count as done for the loop's EOT poll.  The loop also ends at max_new_tokens;
+ *   - ranking, on the host in f32: the pool in insertion order, then — if it holds fewer than K — the live beams by descending score until
+ *     K; len = generated tokens not counting EOT, at least 1 (openai-whisper divides by zero there); rank = score / len when
+ *     length_penalty < 0 (openai's None), else score / powf((5 + len) / 6, length_penalty); best first, ties keep the order above.
+ * tokens_out / n_tokens_out return the best hypothesis, wh_get_logprobs its per-token lp values, wh_get_beams all of them.  Language
+ * detection and the no-speech probe read prompt positions, where the K rows of a clip are equal: their outputs are those of the clip's
+ * first row.  With the parity entries, logits_out / rows address the n * K physical rows: row g of a physical row holds what that row
+ * produced at generated position g (rows of a clip stop being recorded when the clip is complete).  wh_decode_greedy_batch's logits_out is then
+ * [n * K][cap_logits_rows][vocab] and its cap_clips must be at least n * K (WH_ERR_ARG otherwise); wh_decode_greedy, whose logits_out holds one
+ * row, refuses logits_out with K > 1 (WH_ERR_ARG): use wh_decode_greedy_rows.  beam_size == 1 runs this path too.
+ * The setter allocates a per-row logits scratch float [max_batch][vocab] (425 MB at 2048 whisper-base rows) and the search state, and
+ * frees both when the option is cleared.  With the option off the launches are what they were without this entry.
+ * Refused with WH_ERR_ARG (the ctx unchanged): a wrong struct_size, beam_size outside 1 .. WH_MAX_BEAMS, a patience that is not finite or
+ * <= 0 or whose round(K * patience) lies outside 1 .. WH_MAX_BEAM_CANDIDATES, a NaN length_penalty, more than WH_MAX_BEAM_TRACE_CLIPS trace
+ * clips or a negative one.  At decode time, before anything is launched: n_clips * beam_size > max_batch -> WH_ERR_ARG; forced tokens,
+ * repetition controls, alignment or a non-empty prefix set, or a WH_PREC_FP8 / WH_PREC_F16X3 model -> WH_ERR_UNSUPPORTED.
+ * o == NULL turns it off (the default). */
+#define WH_MAX_BEAMS 8
+#define WH_MAX_BEAM_CANDIDATES 16
+#define WH_MAX_BEAM_TRACE_CLIPS 8
+typedef struct {
+    size_t struct_size;         /* sizeof(wh_beam_opts) */
+    int32_t beam_size;          /* K: 1 .. WH_MAX_BEAMS */
+    float patience;             /* > 0; round(K * patience) in 1 .. WH_MAX_BEAM_CANDIDATES */
+    float length_penalty;       /* < 0: none (rank by score / len) */
+    const int32_t* trace_clips; /* parity harness only (NULL/0 in production): clips whose per-position decisions wh_get_beam_trace returns */
+    size_t n_trace_clips;       /* 0 .. WH_MAX_BEAM_TRACE_CLIPS */
+} wh_beam_opts;
+int wh_ctx_set_beam_search(wh_ctx* c, const wh_beam_opts* o);
+/* The ranked hypotheses of the last decode call (any decode entry; every clip / window it returned tokens for, in that order), best first:
+ * tokens [n][cap_hyp][cap_tokens] the generated tokens (no prompt; EOT included when finished), n_tokens [n][cap_hyp], sum_logprob /
+ * rank_score / finished [n][cap_hyp] (any may be NULL), n_hyp [n] (<= cap_hyp hypotheses are returned per clip).  tokens == NULL and
+ * n_hyp == NULL: only *n_clips_out.  WH_ERR_STATE if the call ran without beam search; WH_ERR_ARG if cap_clips < n or cap_tokens is too small. */
+int wh_get_beams(const wh_ctx* c, int64_t* tokens, size_t cap_tokens, size_t* n_tokens, float* sum_logprob, float* rank_score, int32_t* finished,
+                 size_t cap_hyp, size_t* n_hyp, size_t cap_clips, size_t* n_clips_out);
+/* Parity harness: trace clip k (position in the setter's trace_clips) of the last decode call (a long-form call: of its last device batch).
+ * parents / tokens / scores [steps][K]: at generated position g, live beam j continues beam parents[g][j] of position g - 1 with
+ * tokens[g][j] and has score scores[g][j] (a dead beam: its own index, -1, -inf); pool_size [steps]: the pool after position g.
+ * Any array may be NULL.  *n_steps: the positions the clip ran before it was complete.  WH_ERR_STATE if that call kept no trace;
+ * WH_ERR_ARG for k outside the trace clips or cap_steps < *n_steps. */
+int wh_get_beam_trace(const wh_ctx* c, size_t k, int32_t* parents, int32_t* tokens, float* scores, int32_t* pool_size, size_t cap_steps,
+                      size_t* n_steps);
 const char* wh_last_error(const wh_ctx* c); /* c == NULL: last load/create error of this thread */
 int wh_get_timings(const wh_ctx* c, wh_timing* out);
 

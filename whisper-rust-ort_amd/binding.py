@@ -36,7 +36,7 @@ EXPORTS = ("wh_model_load", "wh_model_create", "wh_model_free", "wh_model_get_di
            "wh_profile_get", "wh_synthetic_weights", "wh_e4m3_quantize", "wh_e4m3_dequantize", "wh_abi_version",
            "wh_device_count", "wh_ctx_set_timestamp_rules", "wh_ctx_set_logprobs", "wh_get_logprobs",
            "wh_ctx_set_language_detection", "wh_get_languages", "wh_ctx_set_prefixes", "wh_ctx_set_repetition",
-           "wh_ctx_set_alignment", "wh_get_token_frames", "wh_get_alignment_debug")
+           "wh_ctx_set_alignment", "wh_get_token_frames", "wh_get_alignment_debug", "wh_ctx_set_beam_search", "wh_get_beams", "wh_get_beam_trace")
 
 
 class WhisperHipError(RuntimeError):
@@ -103,6 +103,16 @@ WH_MAX_ALIGN_DEBUG_ROWS = 8
 class WhAlignmentOpts(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("heads", C.POINTER(C.c_int32)), ("n_heads", C.c_size_t), ("debug_rows", C.POINTER(C.c_int32)),
                 ("n_debug_rows", C.c_size_t)]
+
+
+WH_MAX_BEAMS = 8
+WH_MAX_BEAM_CANDIDATES = 16
+WH_MAX_BEAM_TRACE_CLIPS = 8
+
+
+class WhBeamOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("beam_size", C.c_int32), ("patience", C.c_float), ("length_penalty", C.c_float),
+                ("trace_clips", C.POINTER(C.c_int32)), ("n_trace_clips", C.c_size_t)]
 
 
 def pack_prefixes(prefixes: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.ndarray]:
@@ -193,6 +203,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.wh_ctx_set_alignment.argtypes = [vp, C.POINTER(WhAlignmentOpts)]
     L.wh_get_token_frames.argtypes = [vp, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_int32), C.c_size_t, szp]
     L.wh_get_alignment_debug.argtypes = [vp, C.c_size_t, f32p, f32p, C.c_size_t, C.POINTER(C.c_int32)]
+    i32p = C.POINTER(C.c_int32)
+    L.wh_ctx_set_beam_search.argtypes = [vp, C.POINTER(WhBeamOpts)]
+    L.wh_get_beams.argtypes = [vp, i64p, C.c_size_t, szp, f32p, f32p, i32p, C.c_size_t, szp, C.c_size_t, szp]
+    L.wh_get_beam_trace.argtypes = [vp, C.c_size_t, i32p, i32p, f32p, i32p, C.c_size_t, szp]
     _lib = L
     return L
 
@@ -289,6 +303,7 @@ class Context:
         cross_es: force the token loop's cross-attention onto the encoder states (True) or onto the projected K / V (False);
         None = the library's rule (bf16 whisper-base geometry, max_batch >= 256)."""
         self.model, self.lib, self.max_batch = model, model.lib, max_batch
+        self.beam_size_of_last = 1   # (beam_trace()'s row width: the beam_size of the last set_beam_search)
         self._gen_lens: List[int] = []
         h = C.c_void_p()
         flags = (WH_CTX_TWO_STREAMS if two_streams else 0) | (0 if cross_es is None else (WH_CTX_CROSS_ES_ON if cross_es else WH_CTX_CROSS_ES_OFF))
@@ -440,6 +455,65 @@ class Context:
         matrix = np.zeros((ng, sb), np.float32)
         self._check(self.lib.wh_get_alignment_debug(self.h, k, _f32(probs), _f32(matrix), max(1, probs.size), shape))
         return probs, matrix
+
+    def set_beam_search(self, beam_size: int, patience: float = 1.0, length_penalty: float = -1.0, trace_clips: Sequence[int] = ()):
+        """wh_ctx_set_beam_search: every decode entry of this context decodes each clip with `beam_size` beams (openai-whisper's
+        BeamSearchDecoder: round(beam_size * patience) finished candidates; length_penalty < 0 ranks by score / length).  trace_clips (parity
+        harness): clips whose per-position decisions beam_trace() returns."""
+        t = np.ascontiguousarray(list(trace_clips), np.int32)
+        o = WhBeamOpts(C.sizeof(WhBeamOpts), beam_size, patience, length_penalty, t.ctypes.data_as(C.POINTER(C.c_int32)) if t.size else None, t.size)
+        self._check(self.lib.wh_ctx_set_beam_search(self.h, C.byref(o)))
+        self.beam_size_of_last = beam_size
+
+    def clear_beam_search(self):
+        self._check(self.lib.wh_ctx_set_beam_search(self.h, None))
+
+    def beams(self, cap_hyp: int = WH_MAX_BEAM_CANDIDATES + WH_MAX_BEAMS) -> List[List[dict]]:
+        """wh_get_beams of the last decode call: per clip / window the ranked hypotheses, best first, as dicts {tokens (generated ids, EOT
+        included when finished), sum_logprob, rank_score, finished}."""
+        n = C.c_size_t(0)
+        self._check(self.lib.wh_get_beams(self.h, None, 0, None, None, None, None, 0, None, 0, C.byref(n)))
+        k, cap_t = max(1, int(n.value)), self.model.dims.n_text_ctx
+        toks = np.zeros((k, cap_hyp, cap_t), np.int64)
+        nt = np.zeros((k, cap_hyp), np.uint64)
+        sums = np.zeros((k, cap_hyp), np.float32)
+        rank = np.zeros((k, cap_hyp), np.float32)
+        fin = np.zeros((k, cap_hyp), np.int32)
+        nh = np.zeros(k, np.uint64)
+        szp = C.POINTER(C.c_size_t)
+        self._check(self.lib.wh_get_beams(self.h, _i64(toks), cap_t, nt.ctypes.data_as(szp), _f32(sums), _f32(rank), fin.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          cap_hyp, nh.ctypes.data_as(szp), k, C.byref(n)))
+        return [[{"tokens": toks[b, h, : int(nt[b, h])].copy(), "sum_logprob": float(sums[b, h]), "rank_score": float(rank[b, h]), "finished": bool(fin[b, h])}
+                 for h in range(int(nh[b]))] for b in range(int(n.value))]
+
+    def beam_trace(self, k: int) -> dict:
+        """wh_get_beam_trace of trace clip k: {parents, tokens int32 [steps, K], scores float32 [steps, K], pool_size int32 [steps]}."""
+        ns = C.c_size_t(0)
+        self._check(self.lib.wh_get_beam_trace(self.h, k, None, None, None, None, 0, C.byref(ns)))
+        steps, K = int(ns.value), self.beam_size_of_last
+        par = np.zeros((max(1, steps), K), np.int32)
+        tok = np.zeros((max(1, steps), K), np.int32)
+        sc = np.zeros((max(1, steps), K), np.float32)
+        pool = np.zeros(max(1, steps), np.int32)
+        i32p = C.POINTER(C.c_int32)
+        self._check(self.lib.wh_get_beam_trace(self.h, k, par.ctypes.data_as(i32p), tok.ctypes.data_as(i32p), _f32(sc), pool.ctypes.data_as(i32p), steps, C.byref(ns)))
+        return {"parents": par[:steps], "tokens": tok[:steps], "scores": sc[:steps], "pool_size": pool[:steps]}
+
+    def decode_resident_rows_raw(self, params: DecodeParams, rows: Sequence[int]) -> Tuple[List[np.ndarray], np.ndarray]:
+        """wh_decode_greedy_rows without cutting the logits: tokens of every clip and logits [len(rows)][max_new_tokens][vocab] (with beam
+        search `rows` are physical rows, clip * beam_size + beam, and a row's entries stop where its clip was complete: zeros after)."""
+        p, keep = params.to_c()
+        cap = len(params.prompt) + params.max_new_tokens
+        nb = self.max_batch
+        toks = np.zeros((nb, cap), np.int64)
+        n = (C.c_size_t * nb)()
+        got = C.c_size_t(0)
+        sel = np.ascontiguousarray(rows, np.int32)
+        logits = np.zeros((len(sel), params.max_new_tokens, self.model.dims.vocab), np.float32)
+        self._check(self.lib.wh_decode_greedy_rows(self.h, C.byref(p), sel.ctypes.data_as(C.POINTER(C.c_int32)), len(sel), _i64(toks), cap, n, nb,
+                                                   C.byref(got), _f32(logits), params.max_new_tokens))
+        k = int(got.value)
+        return self._took([toks[i, : n[i]].copy() for i in range(k)], params), logits
 
     def _took(self, toks: List[np.ndarray], params: "DecodeParams") -> List[np.ndarray]:
         self._gen_lens = [len(t) - len(params.prompt) for t in toks]   # (what logprobs() cuts its rows to)

@@ -329,6 +329,21 @@ int align_check(wh_ctx* c, int nb) {
     return WH_OK;
 }
 
+// Beam search: what a decode entry refuses because of it, checked by every entry before it launches anything and again by
+// run_decode.  nb = the call's clips (a long-form call: one device batch never holds more than max_batch / K windows).
+int beam_check(wh_ctx* c, const wh_decode_params* p, int nb) {
+    if (!c->bm_on) return WH_OK;
+    if ((long)nb * c->bm_k > c->max_batch)
+        return fail(c, WH_ERR_ARG, "decode: %d clips x beam_size %d exceed max_batch (%d rows)", nb, c->bm_k, c->max_batch);
+    if (c->m->prec == WH_PREC_FP8 || c->m->prec == WH_PREC_F16X3)
+        return fail(c, WH_ERR_UNSUPPORTED, "decode: beam search is not supported in the %s mode", c->m->prec == WH_PREC_FP8 ? "fp8" : "f16x3");
+    if (p->n_forced) return fail(c, WH_ERR_UNSUPPORTED, "decode: beam search with forced tokens is not supported");
+    if (c->rep_on) return fail(c, WH_ERR_UNSUPPORTED, "decode: beam search with repetition controls is not supported");
+    if (c->al_on) return fail(c, WH_ERR_UNSUPPORTED, "decode: beam search with word-level timestamps is not supported");
+    if (c->pfx_on && c->pfx_offsets.back() != 0) return fail(c, WH_ERR_UNSUPPORTED, "decode: beam search with a non-empty prefix is not supported");
+    return WH_OK;
+}
+
 // ---- cross-KV + greedy loop for the nb clips whose encoder states are resident ------------------
 // run_decode (below) is a sequence of stages: plan_decode -> upload_token_state -> prepare_logits -> project_cross_kv -> the prompt
 // positions (launch_step, eagerly) -> run_token_loop (the captured step) -> read_back.
@@ -352,11 +367,16 @@ struct DecodePlan {
     bool want_logits = false;
     size_t n_lrows = 0;
     std::vector<int> sel_map;
+    // beam search: key.nb rows = ncl clips x K beams (off: K == 1, ncl == key.nb)
+    int K = 1, ncl = 0;
 };
 
 // all validation; no HIP call
-int plan_decode(wh_ctx* c, int nb, const wh_decode_params* p, bool want_logits, size_t logits_rows, const int32_t* sel, size_t n_sel, DecodePlan& pl) {
+int plan_decode(wh_ctx* c, int ncl, const wh_decode_params* p, bool want_logits, size_t logits_rows, const int32_t* sel, size_t n_sel, DecodePlan& pl) {
     const wh_dims& D = c->m->dims;
+    if (int rc = beam_check(c, p, ncl)) return rc;
+    const int K = pl.K = c->bm_on ? c->bm_k : 1, nb = ncl * K;   // the rows of the device batch
+    pl.ncl = ncl;
     const int P = pl.P = (int)p->n_prompt, NEW = pl.NEW = (int)p->max_new_tokens;
     if (P <= 0 || NEW <= 0 || !p->prompt) return fail(c, WH_ERR_ARG, "decode: empty prompt or max_new_tokens == 0");
     if (P + NEW > D.n_text_ctx) return fail(c, WH_ERR_ARG, "decode: prompt (%d) + max_new_tokens (%d) exceeds %d positions", P, NEW, D.n_text_ctx);
@@ -379,13 +399,13 @@ int plan_decode(wh_ctx* c, int nb, const wh_decode_params* p, bool want_logits, 
     pl.lp_probe = c->lp_on && c->lp_no_speech >= 0;
     if (pl.lp_probe && c->lp_sot_index >= P - 1)   // the probe reads a prompt position that emits nothing
         return fail(c, WH_ERR_ARG, "decode: the no-speech probe's sot_index %d is not below n_prompt - 1 (%d)", c->lp_sot_index, P - 1);
-    if (int rc = prefix_check(c, p, nb, c->pfx_win_base >= 0)) return rc;
-    if (int rc = align_check(c, nb)) return rc;
+    if (int rc = prefix_check(c, p, ncl, c->pfx_win_base >= 0)) return rc;
+    if (int rc = align_check(c, ncl)) return rc;
     pl.plen.assign(nb, 0);
     pl.pids.assign(nb, nullptr);
     if (c->pfx_on)
         for (int b = 0; b < nb; b++) {
-            pl.pids[b] = prefix_of(c, c->pfx_win_base, b, &pl.plen[b]);
+            pl.pids[b] = prefix_of(c, c->pfx_win_base, b / K, &pl.plen[b]);
             pl.Nmax = std::max(pl.Nmax, pl.plen[b]);
         }
     if (pl.lang_det) pl.lang_pos = pl.Nmax + c->lang_sot_index;
@@ -406,6 +426,7 @@ int plan_decode(wh_ctx* c, int nb, const wh_decode_params* p, bool want_logits, 
     if (c->lp_on) key.lp_sum = c->lp_part_sum;
     if (c->rep_on) { key.rep = true; key.rep_p = c->rep_p; key.rep_n = c->rep_n; }
     if (c->al_on) { key.al_cap = NEW; key.al_gen = c->al_gen; }   // (prepare_alignment completes it with the side buffer's address)
+    if (c->bm_on) { key.beam_k = c->bm_k; key.beam_c = c->bm_c; key.beam_buf = c->bm_buf; }
     return WH_OK;
 }
 
@@ -432,6 +453,10 @@ int upload_token_state(wh_ctx* c, const wh_decode_params* p, const DecodePlan& p
     CTX_HIP(c, hipMemsetAsync(c->pos, 0, 4, s));
     CTX_HIP(c, hipMemsetAsync(c->step_ticket, 0, 4, s));
     if (c->rep_on) CTX_HIP(c, hipMemsetAsync(c->rep_bits, 0, (size_t)nb * c->rep_words * 4, s));   // no history yet: nothing is touched
+    if (pl.key.beam_k) {   // no position has run (the first one starts the scores and the pool itself)
+        CTX_HIP(c, hipMemsetAsync(c->bm_n_steps, 0, (size_t)pl.ncl * 4, s));
+        CTX_HIP(c, hipMemsetAsync(c->bm_pool_n, 0, (size_t)pl.ncl * 4, s));
+    }
     std::vector<int> forced(p->n_forced);
     for (size_t i = 0; i < p->n_forced; i++) forced[i] = (int)p->forced[i];
     if (!forced.empty()) CTX_HIP(c, hipMemcpyAsync(c->forced, forced.data(), forced.size() * 4, hipMemcpyHostToDevice, s));
@@ -634,9 +659,11 @@ struct Step {
     const int prec = m->prec, nb = k.nb, mpad = c->mpad, ln_tiles_d = D.d_model / 16;
     const long d = D.d_model, S = D.n_audio_ctx;
     const bool f8 = prec == WH_PREC_FP8, rules = k.ts_begin >= 0;
+    // beam search: the nb rows are the beams of ncl = nb / rpc clips, and the cross-attention of row b reads clip b / rpc (rpc == 1: ncl == nb)
+    const int rpc = k.beam_k ? k.beam_k : 1, ncl = nb / rpc;
     // the cross K/V of all layers are re-read at every position: below ~half the 256 MiB Infinity Cache they are served
     // from it; above, their stream only evicts the decode weights and activations — then they are loaded non-temporally
-    const bool kv_nt = (c->cross_es ? 1.0 : (double)D.dec_layers * 2.0) * nb * S * d * (f8 ? 1 : (double)m->esz) > 128.0 * 1024 * 1024;
+    const bool kv_nt = (c->cross_es ? 1.0 : (double)D.dec_layers * 2.0) * ncl * S * d * (f8 ? 1 : (double)m->esz) > 128.0 * 1024 * 1024;
     const int* d_off = k.pfx ? c->pfx_off : nullptr;
 
     // the decode GEMMs: tile GEMMs on contexts of a thousand clips and more (a property of the context, never of the call)
@@ -677,7 +704,7 @@ struct Step {
     void layer(int l, bool advance) const {
         const DecLayerDev& L = m->dec[l];
         const long cache_l = (long)nb * D.n_heads * D.n_text_ctx * WH_HEAD_DIM * m->esz;   // bytes per layer
-        const long kv_stride = (long)nb * S * d;  // elements between consecutive [nb][S][d] planes
+        const long kv_stride = (long)ncl * S * d;  // elements between consecutive [clips][S][d] planes
         {   // LN1 ∘ Q|K|V projection
             Prof pr(c, WH_KG_DEC_GEMM);
             gemm(false, ln_consumer(L.qkv_w, L.qkv_b, L.qkv_sc, L.qkv_s, 3 * d, c->dqkv, (l == 0) ? 1 : ln_tiles_d));
@@ -705,7 +732,7 @@ struct Step {
             }
             {
                 Prof pr(c, WH_KG_DEC_CROSS_ATTN);
-                wh_launch_dec_cross_attn_es(s, prec, c->dqe, c->es_E, c->dctx, (int)S, c->es_rows, nb, mpad, kv_nt, c->dec_cus);
+                wh_launch_dec_cross_attn_es(s, prec, c->dqe, c->es_E, c->dctx, (int)S, c->es_rows, nb, mpad, kv_nt, c->dec_cus, rpc);
             }
             {   // per head: W_v,h ctx_h + b_v,h → the attention output the out-projection below expects (slab layout)
                 Prof pr(c, WH_KG_DEC_GEMM);
@@ -733,7 +760,7 @@ struct Step {
                                           c->cpart, c->cml, (int)S, (int)d, D.n_heads, c->cross_splits, nb, c->datt, mpad, kv_nt);
             else
                 wh_launch_dec_cross_attn(s, prec, c->dq, (char*)c->cross_kv + (2 * l) * kv_stride * m->esz, (char*)c->cross_kv + (2 * l + 1) * kv_stride * m->esz,
-                                         c->cpart, c->cml, (int)S, (int)d, D.n_heads, c->cross_splits, nb, c->datt, mpad, kv_nt);
+                                         c->cpart, c->cml, (int)S, (int)d, D.n_heads, c->cross_splits, nb, c->datt, mpad, kv_nt, rpc);
         }
         {   // merge of the key ranges ∘ cross-attention out-proj + residual → x, raw slab, LN3 partials
             Prof pr(c, WH_KG_DEC_GEMM);
@@ -758,6 +785,7 @@ struct Step {
 
     // final LN ∘ tied LM head + masked argmax; the finish kernel records the token, advances the position and embeds the next one
     void emit() const {
+        if (k.beam_k) return emit_beam();
         int lm_parts;
         {
             Prof pr(c, WH_KG_DEC_GEMM);
@@ -794,6 +822,39 @@ struct Step {
             rf.mask_first = c->mask_first; rf.mask_base = c->mask_base;
         }
         wh_launch_argmax_finish(s, prec, c->part_val, c->part_idx, lm_parts, mpad, c->pos, c->step_ticket, st, nb, ne, tf, k.lp_sum, rf);
+    }
+
+    // Beam search: the LM head leaves the rows' raw logits of this position in the scratch (its argmax partials are not read);
+    // k_beam_select chooses the next beams of every clip and embeds their tokens; k_beam_reorder permutes the self-attention caches and
+    // advances the position.  One chain, no parallel branches.
+    void emit_beam() const {
+        {
+            Prof pr(c, WH_KG_DEC_GEMM);
+            SkinnyArgs a = lm_head_common();
+            a.mask_first = c->mask_first; a.mask_base = c->mask_base;
+            a.logits = c->bm_logits; a.logits_rows = 1; a.logits_cur = true;
+            wh_launch_lm_head(s, prec, a);
+        }
+        Prof pr(c, WH_KG_DEC_OTHER);
+        BeamArgs b;
+        b.K = k.beam_k; b.C = k.beam_c; b.n_clips = ncl; b.vocab = D.vocab;
+        b.logits = c->bm_logits; b.pos_p = c->pos; b.n_prompt = k.n_prompt; b.eot = k.eot; b.tok_ld = c->tok_ld;
+        b.mask_first = c->mask_first; b.mask_base = c->mask_base;
+        if (rules) { b.ts_begin = k.ts_begin; b.ts_max_init = k.ts_max_init; }
+        b.scores = c->bm_scores; b.parent = c->bm_parent; b.state = c->bm_state; b.pool_n = c->bm_pool_n; b.n_steps = c->bm_n_steps; b.pool = c->bm_pool;
+        b.tr_parent = c->bm_tr_parent; b.tr_token = c->bm_tr_token; b.tr_score = c->bm_tr_score; b.tr_lp = c->bm_tr_lp; b.tr_pool = c->bm_tr_pool;
+        b.rows_ld = c->max_batch; b.done = c->done; b.feed = c->feed;
+        b.logits_out = k.d_logits; b.logits_rows = k.logits_rows; b.logits_sel = k.d_sel;
+        NextEmbed ne;
+        ne.tok_emb = m->tok_emb; ne.pos_emb = m->dec_pos; ne.x = c->dx; ne.xslab = c->dxs; ne.stats = c->lnpart;
+        ne.d = (int)d; ne.mpad = mpad; ne.shift = c->dshift;
+        const bool tm = c->bm_timing && !c->capturing;   // (measurement runs only: positions launched eagerly)
+        std::array<hipEvent_t, 3> te = {nullptr, nullptr, nullptr};
+        if (tm) { for (auto& e : te) hipEventCreate(&e); hipEventRecord(te[0], s); }
+        wh_launch_beam_select(s, prec, b, ne);
+        if (tm) hipEventRecord(te[1], s);
+        wh_launch_beam_reorder(s, (int)m->esz, c->self_k, c->self_v, c->bm_parent, c->done, k.beam_k, ncl, D.dec_layers, D.n_heads, D.n_text_ctx, c->pos, c->step_ticket);
+        if (tm) { hipEventRecord(te[2], s); c->bm_events.push_back(te); }
     }
 
     // the listed ids' unfiltered logits of this prompt position -> each row's language token in column tok_col of the next one; the
@@ -1001,6 +1062,142 @@ int read_back(wh_ctx* c, const DecodePlan& pl, int64_t* tokens_out, size_t tok_s
     return WH_OK;
 }
 
+// read_back of a call with beam search: the pool and the trace come back, the parents are walked back into hypotheses, the
+// hypotheses are ranked (f32), and the best one of each clip is returned as its tokens (and log-probabilities); keeps what wh_get_beams /
+// wh_get_beam_trace return.  Language detection and the no-speech probe: the clip's first row.
+int read_back_beam(wh_ctx* c, const DecodePlan& pl, int64_t* tokens_out, size_t tok_stride, size_t* n_tokens_out, float* logits_out, const int32_t* sel) {
+    hipStream_t s = c->stream;
+    const int R = pl.key.nb, K = pl.K, ncl = pl.ncl, ld = c->max_batch, PP = pl.key.n_prompt, vocab = c->m->dims.vocab, NEW = pl.NEW;
+    const size_t n_lang = c->lang_ids.size();
+    std::vector<int> trp, trt, trpool, pool, pool_n, nsteps, feed, lch;
+    std::vector<float> trs, trl, nsp, lpr;
+    const double t0 = now_s();
+    auto fetch = [&](auto& v, const void* src, size_t n) {   // (4-byte elements)
+        v.resize(n);
+        return hipMemcpyAsync(v.data(), src, n * 4, hipMemcpyDeviceToHost, s);
+    };
+    const size_t ntr = (size_t)NEW * ld;   // (the trace is [position][max_batch]: the call's positions are its first NEW rows)
+    CTX_HIP(c, fetch(trp, c->bm_tr_parent, ntr));
+    CTX_HIP(c, fetch(trt, c->bm_tr_token, ntr));
+    CTX_HIP(c, fetch(trs, c->bm_tr_score, ntr));
+    CTX_HIP(c, fetch(trl, c->bm_tr_lp, ntr));
+    CTX_HIP(c, fetch(trpool, c->bm_tr_pool, ntr));
+    CTX_HIP(c, fetch(pool, c->bm_pool, (size_t)ncl * WH_MAX_BEAM_CANDIDATES * 4));
+    CTX_HIP(c, fetch(pool_n, c->bm_pool_n, ncl));
+    CTX_HIP(c, fetch(nsteps, c->bm_n_steps, ncl));
+    CTX_HIP(c, fetch(feed, c->feed, (size_t)R * c->tok_ld));   // (the prompt as it was fed: the detected language token)
+    if (pl.lp_probe) CTX_HIP(c, fetch(nsp, c->lp_ns, R));
+    if (pl.lang_det) {
+        CTX_HIP(c, fetch(lch, c->lang_chosen, R));
+        CTX_HIP(c, fetch(lpr, c->lang_probs, (size_t)R * n_lang));
+    }
+    CTX_HIP(c, hipStreamSynchronize(s));
+    CTX_HIP(c, hipGetLastError());
+    c->bm_ms[0] = c->bm_ms[1] = 0;
+    c->bm_timed = (long)c->bm_events.size();
+    for (auto& te : c->bm_events) {
+        for (int i = 0; i < 2; i++) { float ms = 0; hipEventElapsedTime(&ms, te[i], te[i + 1]); c->bm_ms[i] += ms; }
+        for (auto& e : te) hipEventDestroy(e);
+    }
+    c->bm_events.clear();
+    if (pl.lang_fix) {
+        for (int b = 0; b < ncl; b++) {
+            c->lang_rows.push_back(c->lang_fixed);
+            for (size_t j = 0; j < n_lang; j++) { const float pj = c->lang_prob_rows[j]; c->lang_prob_rows.push_back(pj); }
+        }
+    } else if (pl.lang_det) {
+        for (int b = 0; b < ncl; b++) {
+            c->lang_rows.push_back(lch[(size_t)b * K]);
+            c->lang_prob_rows.insert(c->lang_prob_rows.end(), lpr.begin() + (size_t)b * K * n_lang, lpr.begin() + ((size_t)b * K + 1) * n_lang);
+        }
+        c->lang_have = true;
+        c->lang_have_n = n_lang;
+    }
+    c->bm_traces.assign(c->bm_trace_clips.size(), wh_ctx::BeamTrace());
+    for (int clip = 0; clip < ncl; clip++) {
+        const int ns = nsteps[clip], r0 = clip * K;
+        // the history of beam j after position g (g == -1: empty), newest token last
+        auto chain = [&](int g, int j, std::vector<int>& toks, std::vector<float>& lps) {
+            for (; g >= 0; g--) {
+                const size_t t = (size_t)g * ld + r0 + j;
+                toks.push_back(trt[t]);
+                lps.push_back(trl[t]);
+                j = trp[t];
+            }
+            std::reverse(toks.begin(), toks.end());
+            std::reverse(lps.begin(), lps.end());
+        };
+        std::vector<wh_ctx::BeamHyp> hyps;
+        for (int e = 0; e < pool_n[clip]; e++) {   // the pool, in insertion order
+            const int* pe = pool.data() + ((size_t)clip * WH_MAX_BEAM_CANDIDATES + e) * 4;
+            wh_ctx::BeamHyp h;
+            chain(pe[0] - 1, pe[1], h.tokens, h.lps);
+            float lp;
+            memcpy(&h.sum, &pe[2], 4);
+            memcpy(&lp, &pe[3], 4);
+            h.tokens.push_back(pl.key.eot);
+            h.lps.push_back(lp);
+            h.finished = true;
+            hyps.push_back(std::move(h));
+        }
+        if ((int)hyps.size() < K && ns > 0) {   // fewer than K: the live, non-dead beams by descending score (ties: the lower beam)
+            std::vector<int> live;
+            for (int j = 0; j < K; j++)
+                if (trs[(size_t)(ns - 1) * ld + r0 + j] > -INFINITY) live.push_back(j);
+            std::stable_sort(live.begin(), live.end(), [&](int x, int y) { return trs[(size_t)(ns - 1) * ld + r0 + x] > trs[(size_t)(ns - 1) * ld + r0 + y]; });
+            for (int j : live) {
+                if ((int)hyps.size() >= K) break;
+                wh_ctx::BeamHyp h;
+                chain(ns - 1, j, h.tokens, h.lps);
+                h.sum = trs[(size_t)(ns - 1) * ld + r0 + j];
+                hyps.push_back(std::move(h));
+            }
+        }
+        for (auto& h : hyps) {
+            const float len = (float)std::max<size_t>(1, h.tokens.size() - (h.finished ? 1 : 0));
+            h.rank = c->bm_length_penalty < 0.0f ? h.sum / len : h.sum / powf((5.0f + len) / 6.0f, c->bm_length_penalty);
+        }
+        std::stable_sort(hyps.begin(), hyps.end(), [](const wh_ctx::BeamHyp& x, const wh_ctx::BeamHyp& y) { return x.rank > y.rank; });
+        // the clip's tokens: the prompt as fed, then the best hypothesis
+        for (int i = pl.Nmax; i < PP; i++) tokens_out[(size_t)clip * tok_stride + i - pl.Nmax] = feed[(size_t)r0 * c->tok_ld + i];
+        size_t n = (size_t)(PP - pl.Nmax);
+        if (!hyps.empty())
+            for (int t : hyps[0].tokens) tokens_out[(size_t)clip * tok_stride + n++] = t;
+        n_tokens_out[clip] = n;
+        if (c->lp_on) {
+            c->lp_rows.emplace_back(hyps.empty() ? std::vector<float>() : hyps[0].lps);
+            if (pl.lp_probe) c->lp_ns_rows.push_back(nsp[r0]);
+        }
+        for (size_t k = 0; k < c->bm_trace_clips.size(); k++) {
+            if (c->bm_trace_clips[k] != clip) continue;
+            wh_ctx::BeamTrace& tr = c->bm_traces[k];
+            tr.K = K; tr.n_steps = ns;
+            tr.parents.clear(); tr.tokens.clear(); tr.scores.clear(); tr.pool.clear();
+            for (int g = 0; g < ns; g++) {
+                for (int j = 0; j < K; j++) {
+                    const size_t t = (size_t)g * ld + r0 + j;
+                    tr.parents.push_back(trp[t]); tr.tokens.push_back(trt[t]); tr.scores.push_back(trs[t]);
+                }
+                tr.pool.push_back(trpool[(size_t)g * ld + clip]);
+            }
+        }
+        c->bm_hyps.push_back(std::move(hyps));
+    }
+    c->bm_have = true;
+    if (c->lp_on) { c->lp_have = true; c->lp_have_ns = pl.lp_probe; }
+    if (logits_out) {
+        const size_t logits_rows = pl.key.logits_rows;
+        for (size_t i = 0; i < pl.n_lrows; i++) {   // physical rows: what each produced at the positions its clip ran
+            const int r = sel ? sel[i] : (int)i;
+            const size_t rows = (size_t)nsteps[r / K];
+            CTX_HIP(c, hipMemcpy(logits_out + i * logits_rows * vocab, pl.key.d_logits + i * logits_rows * vocab, std::min(rows, logits_rows) * vocab * 4,
+                                 hipMemcpyDeviceToHost));
+        }
+    }
+    c->timing.d2h_s = now_s() - t0;
+    return WH_OK;
+}
+
 // `sel` (optional, with logits_out): the n_sel batch rows whose logits are read back — logits_out is then [n_sel][logits_rows][vocab]
 int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out, size_t tok_stride,
                size_t* n_tokens_out, float* logits_out, size_t logits_rows, const std::function<int()>& after_kv = nullptr,
@@ -1026,6 +1223,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
     }
     if ((rc = run_token_loop(c, key, total_pos - PP, p->n_forced == 0)) || (rc = run_alignment(c, pl))) return rc;
     CTX_HIP(c, hipEventRecord(c->ev[3], s));
+    if (key.beam_k) return read_back_beam(c, pl, tokens_out, tok_stride, n_tokens_out, logits_out, sel);
     return read_back(c, pl, tokens_out, tok_stride, n_tokens_out, logits_out, sel);
 }
 
@@ -1093,6 +1291,12 @@ int check_params(wh_ctx* c, const wh_decode_params* p) {
     c->al_rows.clear();
     c->al_nframes.clear();
     c->al_dbg.clear();
+    c->bm_have = false;
+    c->bm_hyps.clear();
+    c->bm_traces.clear();
+    for (auto& te : c->bm_events)   // (timing events of a call that failed before its read-back)
+        for (auto& e : te) hipEventDestroy(e);
+    c->bm_events.clear();
     if (!p) return fail(c, WH_ERR_ARG, "decode params are NULL");
     if ((p->n_suppress && !p->suppress) || (p->n_begin_suppress && !p->begin_suppress) || (p->n_forced && !p->forced))
         return fail(c, WH_ERR_ARG, "decode params: NULL list with non-zero length");
@@ -1230,6 +1434,7 @@ static int ctx_create_impl(wh_model* m, const wh_ctx_opts* opts, wh_ctx** out) {
     c->no_graph = getenv("WH_NO_GRAPH") != nullptr;
     c->sync_every_pos = getenv("WH_SYNC_EVERY_POS") != nullptr;
     c->al_timing = getenv("WH_ALIGN_TIMING") != nullptr;
+    c->bm_timing = getenv("WH_BEAM_TIMING") != nullptr;
     const wh_dims& D = m->dims;
     const size_t B = max_batch, d = D.d_model, S = D.n_audio_ctx, F = D.ffn, C = D.n_mels, esz = m->esz;
     const size_t Ld = D.dec_layers, H = D.n_heads, TC = D.n_text_ctx;
@@ -1696,6 +1901,113 @@ int wh_ctx_set_alignment(wh_ctx* c, const wh_alignment_opts* o) {
     return WH_OK;
 }
 
+// Beam search on every decode entry of the ctx.  The logits scratch and the search state are allocated when the option is turned
+// on and freed when it is cleared; the captured decode step is keyed on the setting and dropped before a buffer it holds is freed.
+static void beam_release(wh_ctx* c) {
+    if (c->bm_logits || c->bm_buf) drop_step_graph(c);   // (a captured step may hold the buffers' addresses)
+    if (c->bm_logits) hipFree(c->bm_logits);
+    if (c->bm_buf) hipFree(c->bm_buf);
+    c->bm_logits = nullptr; c->bm_buf = nullptr;
+    c->bm_on = false; c->bm_k = c->bm_c = 0;
+    c->bm_trace_clips.clear();
+}
+int wh_ctx_set_beam_search(wh_ctx* c, const wh_beam_opts* o) {
+    if (!c) return WH_ERR_ARG;
+    if (!o) {
+        hipSetDevice(c->m->device);
+        beam_release(c);
+        return WH_OK;
+    }
+    if (o->struct_size != sizeof(wh_beam_opts)) return fail(c, WH_ERR_ARG, "wh_ctx_set_beam_search: struct_size %zu, expected %zu", o->struct_size, sizeof(wh_beam_opts));
+    if (o->beam_size < 1 || o->beam_size > WH_MAX_BEAMS) return fail(c, WH_ERR_ARG, "wh_ctx_set_beam_search: beam_size %d outside 1 .. %d", (int)o->beam_size, WH_MAX_BEAMS);
+    if (!std::isfinite(o->patience) || !(o->patience > 0.0f)) return fail(c, WH_ERR_ARG, "wh_ctx_set_beam_search: patience %g is not a finite value above 0", (double)o->patience);
+    const long cand = lroundf((float)o->beam_size * o->patience);
+    if (cand < 1 || cand > WH_MAX_BEAM_CANDIDATES)
+        return fail(c, WH_ERR_ARG, "wh_ctx_set_beam_search: round(beam_size * patience) = %ld outside 1 .. %d", cand, WH_MAX_BEAM_CANDIDATES);
+    if (std::isnan(o->length_penalty)) return fail(c, WH_ERR_ARG, "wh_ctx_set_beam_search: length_penalty is NaN");
+    if (o->n_trace_clips > WH_MAX_BEAM_TRACE_CLIPS || (o->n_trace_clips && !o->trace_clips))
+        return fail(c, WH_ERR_ARG, "wh_ctx_set_beam_search: more than %d trace clips (or a NULL list)", WH_MAX_BEAM_TRACE_CLIPS);
+    for (size_t i = 0; i < o->n_trace_clips; i++)
+        if (o->trace_clips[i] < 0) return fail(c, WH_ERR_ARG, "wh_ctx_set_beam_search: negative trace clip");
+    if (!c->bm_logits) {
+        auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+        const size_t B = (size_t)c->max_batch, vocab = (size_t)c->m->dims.vocab, TL = (size_t)c->tok_ld;
+        const size_t b_row = up(B * 4), b_state = up(B * WH_BEAM_STATE * 4), b_pool = up(B * WH_MAX_BEAM_CANDIDATES * 4 * 4), b_tr = up(TL * B * 4);
+        float* lg = (float*)setter_alloc(c, "wh_ctx_set_beam_search", B * vocab * 4);
+        char* buf = (char*)(lg ? setter_alloc(c, "wh_ctx_set_beam_search", 4 * b_row + b_state + b_pool + 5 * b_tr) : nullptr);
+        if (!buf) {
+            if (lg) hipFree(lg);
+            return WH_ERR_NOMEM;
+        }
+        c->bm_logits = lg; c->bm_buf = buf;
+        char* q = buf;
+        c->bm_scores = (float*)q; q += b_row;
+        c->bm_parent = (int*)q; q += b_row;
+        c->bm_pool_n = (int*)q; q += b_row;
+        c->bm_n_steps = (int*)q; q += b_row;
+        c->bm_state = (int*)q; q += b_state;
+        c->bm_pool = (int*)q; q += b_pool;
+        c->bm_tr_parent = (int*)q; q += b_tr;
+        c->bm_tr_token = (int*)q; q += b_tr;
+        c->bm_tr_pool = (int*)q; q += b_tr;
+        c->bm_tr_score = (float*)q; q += b_tr;
+        c->bm_tr_lp = (float*)q;
+    }
+    c->bm_on = true;
+    c->bm_k = o->beam_size;
+    c->bm_c = (int)cand;
+    c->bm_length_penalty = o->length_penalty;
+    c->bm_trace_clips.assign(o->trace_clips, o->trace_clips + o->n_trace_clips);
+    return WH_OK;
+}
+
+int wh_get_beams(const wh_ctx* c, int64_t* tokens, size_t cap_tokens, size_t* n_tokens, float* sum_logprob, float* rank_score, int32_t* finished,
+                 size_t cap_hyp, size_t* n_hyp, size_t cap_clips, size_t* n_clips_out) {
+    if (!c) return WH_ERR_ARG;
+    if (!c->bm_have) return WH_ERR_STATE;
+    const size_t n = c->bm_hyps.size();
+    if (n_clips_out) *n_clips_out = n;
+    if (!tokens && !n_hyp) return WH_OK;
+    if (cap_clips < n) return WH_ERR_ARG;
+    for (size_t b = 0; b < n; b++) {
+        const size_t nh = std::min(cap_hyp, c->bm_hyps[b].size());
+        if (tokens)
+            for (size_t h = 0; h < nh; h++)
+                if (c->bm_hyps[b][h].tokens.size() > cap_tokens) return WH_ERR_ARG;
+    }
+    for (size_t b = 0; b < n; b++) {
+        const size_t nh = std::min(cap_hyp, c->bm_hyps[b].size());
+        if (n_hyp) n_hyp[b] = nh;
+        for (size_t h = 0; h < cap_hyp; h++) {
+            const size_t at = b * cap_hyp + h;
+            const wh_ctx::BeamHyp* hy = h < nh ? &c->bm_hyps[b][h] : nullptr;
+            if (tokens) {
+                std::fill(tokens + at * cap_tokens, tokens + (at + 1) * cap_tokens, (int64_t)0);
+                if (hy) std::copy(hy->tokens.begin(), hy->tokens.end(), tokens + at * cap_tokens);
+            }
+            if (n_tokens) n_tokens[at] = hy ? hy->tokens.size() : 0;
+            if (sum_logprob) sum_logprob[at] = hy ? hy->sum : 0.0f;
+            if (rank_score) rank_score[at] = hy ? hy->rank : 0.0f;
+            if (finished) finished[at] = hy && hy->finished ? 1 : 0;
+        }
+    }
+    return WH_OK;
+}
+
+int wh_get_beam_trace(const wh_ctx* c, size_t k, int32_t* parents, int32_t* tokens, float* scores, int32_t* pool_size, size_t cap_steps, size_t* n_steps) {
+    if (!c) return WH_ERR_ARG;
+    if (!c->bm_have || c->bm_traces.empty()) return WH_ERR_STATE;
+    if (k >= c->bm_traces.size()) return WH_ERR_ARG;
+    const wh_ctx::BeamTrace& t = c->bm_traces[k];
+    if (n_steps) *n_steps = (size_t)t.n_steps;
+    if ((parents || tokens || scores || pool_size) && cap_steps < (size_t)t.n_steps) return WH_ERR_ARG;
+    if (parents) std::copy(t.parents.begin(), t.parents.end(), parents);
+    if (tokens) std::copy(t.tokens.begin(), t.tokens.end(), tokens);
+    if (scores) std::copy(t.scores.begin(), t.scores.end(), scores);
+    if (pool_size) std::copy(t.pool.begin(), t.pool.end(), pool_size);
+    return WH_OK;
+}
+
 int wh_get_token_frames(const wh_ctx* c, int32_t* frames, size_t cap_tokens, int32_t* n_frames, size_t cap_clips, size_t* n_clips_out) {
     if (!c) return WH_ERR_ARG;
     if (!c->al_have) return WH_ERR_STATE;
@@ -1795,6 +2107,10 @@ void wh_ctx_free(wh_ctx* c) {
     if (c->al_ws) hipFree(c->al_ws);
     if (c->al_frames) hipFree(c->al_frames);
     if (c->al_sb) hipFree(c->al_sb);
+    if (c->bm_logits) hipFree(c->bm_logits);
+    if (c->bm_buf) hipFree(c->bm_buf);
+    for (auto& te : c->bm_events)
+        for (auto& e : te) hipEventDestroy(e);
     if (c->s_copy) { hipStreamSynchronize(c->s_copy); hipStreamDestroy(c->s_copy); }
     if (c->ev_h2d) hipEventDestroy(c->ev_h2d);
     if (c->pcm2) hipFree(c->pcm2);
@@ -1817,6 +2133,15 @@ extern "C" int wh_debug_set_es_pad(wh_ctx* c, int pad_rows) {
 extern "C" int wh_debug_align_times(const wh_ctx* c, double* ms3) {
     if (!c || !ms3 || !c->al_timing) return WH_ERR_ARG;
     for (int i = 0; i < 3; i++) ms3[i] = c->al_ms[i];
+    return WH_OK;
+}
+
+// measurement hook (tools/beam_bench.py; not in the public header): milliseconds of k_beam_select and k_beam_reorder of the last call, summed over
+// the positions that were launched eagerly (their count in *positions) — filled when the context was created under WH_BEAM_TIMING=1
+extern "C" int wh_debug_beam_times(const wh_ctx* c, double* ms2, long* positions) {
+    if (!c || !ms2 || !positions || !c->bm_timing) return WH_ERR_ARG;
+    ms2[0] = c->bm_ms[0]; ms2[1] = c->bm_ms[1];
+    *positions = c->bm_timed;
     return WH_OK;
 }
 
@@ -1971,9 +2296,12 @@ int wh_decode_greedy(wh_ctx* c, const wh_decode_params* p, int64_t* tokens_out, 
     if (!tokens_out || !n_tokens_out || cap_tokens < p->n_prompt + p->max_new_tokens)
         return fail(c, WH_ERR_ARG, "tokens_out needs capacity n_prompt + max_new_tokens");
     if (logits_out && cap_logits_rows < p->max_new_tokens) return fail(c, WH_ERR_ARG, "logits_out needs max_new_tokens rows");
+    // (beam search: the logits belong to beam_size physical rows, and this entry's logits_out holds one — read them through wh_decode_greedy_rows)
+    if (logits_out && c->bm_on && c->bm_k > 1)
+        return fail(c, WH_ERR_ARG, "wh_decode_greedy: logits_out holds one row's logits, beam search has %d rows per clip; use wh_decode_greedy_rows", c->bm_k);
     rc = prefix_check(c, p, 1, false);
     if (rc) return rc;
-    if ((rc = align_check(c, 1))) return rc;
+    if ((rc = align_check(c, 1)) || (rc = beam_check(c, p, 1))) return rc;
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -1995,9 +2323,12 @@ int wh_decode_greedy_batch(wh_ctx* c, const wh_decode_params* p, int64_t* tokens
     if (!tokens_out || !n_tokens_out || cap_clips < (size_t)nb || cap_tokens < p->n_prompt + p->max_new_tokens)
         return fail(c, WH_ERR_ARG, "tokens_out needs %d rows of capacity n_prompt + max_new_tokens", nb);
     if (logits_out && cap_logits_rows < p->max_new_tokens) return fail(c, WH_ERR_ARG, "logits_out needs max_new_tokens rows per clip");
+    // (beam search: logits_out is [n * beam_size][cap_logits_rows][vocab], one block per physical row — cap_clips must cover them)
+    if (logits_out && c->bm_on && cap_clips < (size_t)nb * c->bm_k)
+        return fail(c, WH_ERR_ARG, "wh_decode_greedy_batch: with beam search logits_out holds %d clips x %d beams: cap_clips must be at least %d", nb, c->bm_k, nb * c->bm_k);
     rc = prefix_check(c, p, nb, false);
     if (rc) return rc;
-    if ((rc = align_check(c, nb))) return rc;
+    if ((rc = align_check(c, nb)) || (rc = beam_check(c, p, nb))) return rc;
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -2016,13 +2347,14 @@ int wh_decode_greedy_rows(wh_ctx* c, const wh_decode_params* p, const int32_t* r
     if (c->pre_valid) return fail(c, WH_ERR_STATE, "the resident encoder states belong to a prefetched batch that has not been transcribed yet");
     const int nb = c->enc_batch;
     if (n_clips_out) *n_clips_out = (size_t)nb;
-    if (!rows || n_rows == 0 || n_rows > (size_t)nb || !logits_out) return fail(c, WH_ERR_ARG, "wh_decode_greedy_rows: need 1..%d rows and a logits buffer", nb);
+    const size_t phys = (size_t)nb * (c->bm_on ? c->bm_k : 1);   // (beam search: rows address the physical rows, clip * K + beam)
+    if (!rows || n_rows == 0 || n_rows > phys || !logits_out) return fail(c, WH_ERR_ARG, "wh_decode_greedy_rows: need 1..%zu rows and a logits buffer", phys);
     if (!tokens_out || !n_tokens_out || cap_clips < (size_t)nb || cap_tokens < p->n_prompt + p->max_new_tokens)
         return fail(c, WH_ERR_ARG, "tokens_out needs %d rows of capacity n_prompt + max_new_tokens", nb);
     if (cap_logits_rows < p->max_new_tokens) return fail(c, WH_ERR_ARG, "logits_out needs max_new_tokens rows per selected clip");
     rc = prefix_check(c, p, nb, false);
     if (rc) return rc;
-    if ((rc = align_check(c, nb))) return rc;
+    if ((rc = align_check(c, nb)) || (rc = beam_check(c, p, nb))) return rc;
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -2084,7 +2416,7 @@ int wh_transcribe_batch(wh_ctx* c, const wh_clip* clips, size_t n_clips, const w
     if (n_clips == 0 || n_clips > (size_t)c->max_batch) return fail(c, WH_ERR_ARG, "n_clips must be 1..max_batch (%d)", c->max_batch);
     rc = prefix_check(c, p, (int)n_clips, false);
     if (rc) return rc;
-    if ((rc = align_check(c, (int)n_clips))) return rc;
+    if ((rc = align_check(c, (int)n_clips)) || (rc = beam_check(c, p, (int)n_clips))) return rc;
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -2132,7 +2464,7 @@ int wh_transcribe_batch_next(wh_ctx* c, const wh_clip* clips, size_t n_clips, co
     if (n_clips == 0 || n_clips > (size_t)c->max_batch) return fail(c, WH_ERR_ARG, "n_clips must be 1..max_batch (%d)", c->max_batch);
     rc = prefix_check(c, p, (int)n_clips, false);
     if (rc) return rc;
-    if ((rc = align_check(c, (int)n_clips))) return rc;
+    if ((rc = align_check(c, (int)n_clips)) || (rc = beam_check(c, p, (int)n_clips))) return rc;
     if (next_clips && (n_next == 0 || n_next > (size_t)c->max_batch)) return fail(c, WH_ERR_ARG, "n_next must be 1..max_batch (%d)", c->max_batch);
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
@@ -2197,7 +2529,7 @@ int wh_transcribe_batch_device_next(wh_ctx* c, const float* d_pcm, size_t n_clip
     if (n_clips == 0 || n_clips > (size_t)c->max_batch) return fail(c, WH_ERR_ARG, "n_clips must be 1..max_batch (%d)", c->max_batch);
     rc = prefix_check(c, p, (int)n_clips, false);
     if (rc) return rc;
-    if ((rc = align_check(c, (int)n_clips))) return rc;
+    if ((rc = align_check(c, (int)n_clips)) || (rc = beam_check(c, p, (int)n_clips))) return rc;
     if (d_pcm_next && (n_clips_next == 0 || n_clips_next > (size_t)c->max_batch))
         return fail(c, WH_ERR_ARG, "n_clips_next must be 1..max_batch (%d)", c->max_batch);
     CTX_HIP(c, hipSetDevice(c->m->device));
@@ -2256,6 +2588,8 @@ int wh_transcribe_longform(wh_ctx* c, const float* pcm, size_t n_samples, double
         wh_longform_plan(n_samples, chunk_length_s, overlap_s, nullptr, 0, &nw);
         if ((rc = align_check(c, nw ? (int)(nw - (nw - 1) / c->max_batch * c->max_batch) : 1))) return rc;
     }
+    if ((rc = beam_check(c, p, 1))) return rc;
+    const size_t win_batch = (size_t)(c->bm_on ? c->max_batch / c->bm_k : c->max_batch);   // windows per device batch (beam search: K rows each)
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -2284,8 +2618,8 @@ int wh_transcribe_longform(wh_ctx* c, const float* pcm, size_t n_samples, double
         ~LangScope() { c->lang_bcast = false; c->lang_fixed = -1; c->pfx_win_base = -1; }   // (and the prefix's window scope)
     } lang_scope{c};
     c->lang_bcast = true;
-    for (size_t base = 0; base < nch; base += c->max_batch) {
-        const int nb = (int)std::min<size_t>(c->max_batch, nch - base);
+    for (size_t base = 0; base < nch; base += win_batch) {
+        const int nb = (int)std::min<size_t>(win_batch, nch - base);
         std::vector<int> src(nb, 0), fs(nb), nfs(1, (int)nf);
         for (int i = 0; i < nb; i++) fs[i] = (int)(offs[base + i] / 160);  // frame_start = pos / hop (:895, 950)
         rc = enc_begin(c);

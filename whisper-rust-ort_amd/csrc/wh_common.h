@@ -391,6 +391,19 @@ __device__ __forceinline__ void ts_ranges(const int* state, int m, int gen, int 
         ts_hi = state[4 * m + 2];
     }
 }
+// The ranges of the NEXT position from the history it will see (rules 2 and 3): `next` = the token fed next (seq[-1]), pen_ts = seq[-2] is a
+// timestamp or does not exist, prev_last_t = the last timestamp before `next` (-1: none).  Shared by k_argmax_finish<T, true> and k_beam_select.
+__device__ __forceinline__ void ts_next_state(int next, bool pen_ts, int prev_last_t, int tb, int eot, int vocab, int& text_lo, int& ts_lo, int& ts_hi,
+                                              int& last_t) {
+    const bool last_ts = next >= tb;
+    last_t = last_ts ? next : prev_last_t;
+    text_lo = 0;
+    ts_lo = tb;
+    if (last_ts && pen_ts) ts_lo = vocab;          // after a pair: no timestamp
+    else if (last_ts) text_lo = eot;               // after a single one: no text id below EOT
+    if (last_t >= 0 && ts_lo < vocab) ts_lo = max(ts_lo, (last_ts && !pen_ts) ? last_t : last_t + 1);
+    ts_hi = vocab - 1;
+}
 // exp(x) for x <= 0 as one v_exp_f32 (2^(x log2 e)): relative error ~1e-6 over the range that matters to a log-sum-exp
 __device__ __forceinline__ float ts_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
 // online (max, sum of exp(v - max), index of the max) over the allowed timestamp logits, columns ascending: strict >, so the lowest index keeps

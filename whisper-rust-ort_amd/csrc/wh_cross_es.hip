@@ -75,9 +75,12 @@ constexpr Format ES_F = {32, 32 * ES_ROWB, 4, true, 36};
 // Software pipeline, one barrier per tile: iteration g computes the SCORES of tile g + 1 and the softmax + output of tile g, so
 // the LDS round trips and MFMA chains of the two halves overlap inside a wave and the score exchange needs no barrier of its
 // own.  Tile g + 1 must therefore have landed at the top of iteration g: NSTAGE - 2 tiles stay in flight.
-template <int AUX, int NL, int ABL = 0>   // ABL (tools/es_bench.hip only): 1 = ring, waits and barriers only; 2 = phase stamps (s_memtime) of workgroup 0 into dbg
+// BEAM (beam search): the B rows are the beams of B / rows_per_clip clips — row `clip` of the walk streams the states of clip
+// clip / rows_per_clip; queries and output stay per row.  The BEAM = false instantiations do not read rows_per_clip.
+template <int AUX, int NL, int ABL = 0, bool BEAM = false>   // ABL (tools/es_bench.hip only): 1 = ring, waits and barriers only; 2 = phase stamps (s_memtime) of workgroup 0 into dbg
 __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es(const float* __restrict__ qe, const bf16* __restrict__ E,
-                                                                         bf16* __restrict__ out, int S, int e_rows, int mpad, int B, unsigned long long* dbg) {
+                                                                         bf16* __restrict__ out, int S, int e_rows, int mpad, int B, unsigned long long* dbg,
+                                                                         int rows_per_clip) {
     constexpr int TK = ES_F.tk, TILEB = ES_F.tileb, SCP = ES_F.scp;
     static_assert(NL == 1 || NL == 2, "one or two loader waves");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -94,7 +97,8 @@ __global__ __launch_bounds__(256 + 64 * NL, 1) void k_dec_cross_attn_es(const fl
         int voff[PPT];   // byte offset of this lane's 16 bytes of row lw * PPT + j inside a tile (the same for every tile: 32 % 16 == 0)
 #pragma unroll
         for (int j = 0; j < PPT; j++) voff[j] = (lw * PPT + j) * ES_ROWB + ((lane ^ ((lw * PPT + j) & 15)) << 4);
-        auto issue = [&](char* base, int clip, int t) __attribute__((always_inline)) {
+        auto issue = [&](char* base, int row, int t) __attribute__((always_inline)) {
+            const int clip = BEAM ? row / rows_per_clip : row;   // whose states the row streams
             const char* Et = reinterpret_cast<const char*>(E) + ((long)clip * e_rows + (long)t * TK) * ES_ROWB;   // wave-uniform
             if (t * TK + TK <= S) {
 #pragma unroll
@@ -552,7 +556,8 @@ void wh_launch_layernorm_es2(hipStream_t s, const float* x, const float* w, cons
     hipLaunchKernelGGL(k_layernorm_es2, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, w, b, (_Float16*)y, rows, in_blk, out_blk);
 }
 
-void wh_launch_dec_cross_attn_es(hipStream_t s, int prec, const float* qe, const void* E, void* out, int S, int e_rows, int B, int mpad, bool stream_nt, int n_cus) {
+void wh_launch_dec_cross_attn_es(hipStream_t s, int prec, const float* qe, const void* E, void* out, int S, int e_rows, int B, int mpad, bool stream_nt, int n_cus,
+                                 int rows_per_clip) {
     static const int nt_env = env_int("WH_CROSS_NT", -1);
     static const int nl = env_int("WH_ES_LOADERS", 1);        // (A/B runs) loader waves per workgroup
     static const int persist = env_int("WH_ES_PERSIST", 1);   // (A/B runs) 0: one workgroup per clip
@@ -572,12 +577,17 @@ void wh_launch_dec_cross_attn_es(hipStream_t s, int prec, const float* qe, const
     if (const char* e = getenv("WH_ES_ABL")) {   // always <AUX 2, one loader>
         const bool stamps = atoi(e) == 2;
         launch(s, grid, false, true, ES_F.lds(), [stamps](auto, auto) { return stamps ? k_dec_cross_attn_es<2, 1, 2> : k_dec_cross_attn_es<2, 1, 1>; },
-               qe, (const bf16*)E, (bf16*)out, S, e_rows, mpad, B, es_dbg);
+               qe, (const bf16*)E, (bf16*)out, S, e_rows, mpad, B, es_dbg, 1);
         return;
     }
 #endif
+    if (rows_per_clip != 1) {   // beam search: the rows of a clip share its states
+        launch(s, grid, nl == 2, stream_nt, ES_F.lds(), [](auto AUX, auto NL) { return k_dec_cross_attn_es<decltype(AUX)::value, decltype(NL)::value, 0, true>; },
+               qe, (const bf16*)E, (bf16*)out, S, e_rows, mpad, B, es_dbg, rows_per_clip);
+        return;
+    }
     launch(s, grid, nl == 2, stream_nt, ES_F.lds(), [](auto AUX, auto NL) { return k_dec_cross_attn_es<decltype(AUX)::value, decltype(NL)::value>; },
-           qe, (const bf16*)E, (bf16*)out, S, e_rows, mpad, B, es_dbg);
+           qe, (const bf16*)E, (bf16*)out, S, e_rows, mpad, B, es_dbg, 1);
 }
 
 void wh_launch_dec_qexpand(hipStream_t s, int prec, const float* q, const void* wkT, float* qe, int M, int d, int n_heads) {

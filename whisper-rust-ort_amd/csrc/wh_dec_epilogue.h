@@ -44,6 +44,51 @@ __device__ __forceinline__ void advance_if_last(int* ticket, int* pos_p, int n_b
 // [M][K] buffer.  Producers (LayerNorm, attention, fc1 epilogue) write this layout directly.
 __device__ __forceinline__ long slab_idx(int m, int k, int mpad) { return ((long)(k >> 5) * mpad + m) * 32 + (k & 31); }
 
+// Token + position embedding of row b's NEXT position by a 256-thread workgroup (k_dec_embed's work, fused into the kernel that chooses the
+// token: k_argmax_finish, k_beam_select): the f32 residual row, the slab copy and the row sums, with the row's mean first (k_dec_embed's
+// two passes: the slab copy and the sums are of the centred row).  sv: 12 floats of LDS nobody else uses until the call returns; every
+// thread of the workgroup calls it (barriers inside).  Thread 0 still reads sv when the call returns: a caller that calls it again, or reuses
+// sv, puts a __syncthreads() in between (k_beam_select's loop over a clip's rows).  The term order of the sums is fixed: a row's values do not depend on the caller.
+template <typename T>
+__device__ __forceinline__ void embed_next_row(const NextEmbed& ne, int b, int next, int mpos, float* sv) {
+    const int tid = threadIdx.x;
+    const T* er = (const T*)ne.tok_emb + (long)next * ne.d;
+    const float* pr = ne.pos_emb + (long)mpos * ne.d;
+    float mean = 0.0f;
+    if (ne.shift) {
+        float s0 = 0.0f;
+        for (int c = tid * 4; c < ne.d; c += 1024) {
+            const f32x4 v = load4_f32(er + c) + *reinterpret_cast<const f32x4*>(pr + c);
+            s0 += (v[0] + v[1]) + (v[2] + v[3]);
+        }
+        s0 = dpp_wave_sum(s0);
+        if ((tid & 63) == 0) sv[8 + (tid >> 6)] = s0;
+        __syncthreads();
+        mean = ((sv[8] + sv[9]) + (sv[10] + sv[11])) / (float)ne.d;
+    }
+    float s1 = 0.0f, s2 = 0.0f;
+    for (int c = tid * 4; c < ne.d; c += 1024) {
+        const f32x4 p4 = *reinterpret_cast<const f32x4*>(pr + c);
+        f32x4 v = load4_f32(er + c) + p4;
+        *reinterpret_cast<f32x4*>(ne.x + (long)b * ne.d + c) = v;
+        v -= mean;
+        f32x4 g = {1, 1, 1, 1};
+        if (ne.xgamma) g = *reinterpret_cast<const f32x4*>(ne.xgamma + c);
+        store4((T*)ne.xslab + slab_idx(b, c, ne.mpad), v[0] * g[0], v[1] * g[1], v[2] * g[2], v[3] * g[3]);
+        s1 += (v[0] + v[1]) + (v[2] + v[3]);
+        s2 += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+    }
+    s1 = dpp_wave_sum(s1);
+    s2 = dpp_wave_sum(s2);
+    if ((tid & 63) == 0) { sv[tid >> 6] = s1; sv[4 + (tid >> 6)] = s2; }
+    __syncthreads();
+    if (tid == 0) {
+        ne.stats[2 * b] = (sv[0] + sv[1]) + (sv[2] + sv[3]);
+        ne.stats[2 * b + 1] = (sv[4] + sv[5]) + (sv[6] + sv[7]);
+        if (ne.shift) ne.shift[b] = mean;
+    }
+}
+
 // grouped launches (SkinnyArgs::zn): group blockIdx.z works on its own X, W, bias and C (a slab: type T, else row-major TO)
 template <typename T, typename TO, typename TW>
 __device__ __forceinline__ void dec_gemm_group(SkinnyArgs& a) {

@@ -591,6 +591,7 @@ __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
     }
     const int pos = *a.pos_p;
     const int gen = pos - (a.n_prompt - 1);  // index of the token this row generates
+    const int lrow = a.logits_cur ? min(gen, 0) : gen;   // the row of a.logits this position's logits go to
     const unsigned* mask = (gen == 0) ? a.mask_first : a.mask_base;
     // Pipeline unit = (tile, 16-fragment chunk of K).  Two register sets: the next unit's weight
     // fragments are in flight while the current unit's MFMAs issue.
@@ -672,9 +673,9 @@ __global__ __launch_bounds__(256) void k_lm_head(SkinnyArgs a) {
                 const int nn = n + e;
                 const float v = a.ln_part ? wh_ln_fold(acc[t][e], mean, rstd, sv[e], cv[e]) : acc[t][e];
                 if (nn < a.N && m < a.M) {
-                    if (a.logits && gen >= 0 && gen < a.logits_rows) {
+                    if (a.logits && lrow >= 0 && lrow < a.logits_rows) {
                         const int slot = a.logits_sel ? a.logits_sel[m] : m;
-                        if (slot >= 0) a.logits[((long)slot * a.logits_rows + gen) * a.N + nn] = v;
+                        if (slot >= 0) a.logits[((long)slot * a.logits_rows + lrow) * a.N + nn] = v;
                     }
                     if constexpr (REP) {
                         if ((rbits >> e) & 1u) a.rep_side[(long)m * a.N + nn] = v;
@@ -893,16 +894,12 @@ __global__ __launch_bounds__(256) void k_argmax_finish(const float* __restrict__
         if constexpr (RULES) {
             // the next position's ranges from the history it sees (seq = the fed tokens, `next` its last one): rules 2 and 3
             const int tb = ts.ts_begin;
-            const bool last_ts = next >= tb;
             const bool pen_ts = gen == 0 || st.feed[b * st.tok_ld + pos] >= tb;   // (the token fed at this position is seq[-2])
-            const int last_t = last_ts ? next : (gen == 0 ? -1 : ts.state[4 * b + 3]);
-            int text_lo = 0, ts_lo = tb;
-            if (last_ts && pen_ts) ts_lo = ts.vocab;          // after a pair: no timestamp
-            else if (last_ts) text_lo = st.eot;               // after a single one: no text id below EOT
-            if (last_t >= 0 && ts_lo < ts.vocab) ts_lo = max(ts_lo, (last_ts && !pen_ts) ? last_t : last_t + 1);
+            int text_lo, ts_lo, ts_hi, last_t;
+            ts_next_state(next, pen_ts, gen == 0 ? -1 : ts.state[4 * b + 3], tb, st.eot, ts.vocab, text_lo, ts_lo, ts_hi, last_t);
             ts.state[4 * b] = text_lo;
             ts.state[4 * b + 1] = ts_lo;
-            ts.state[4 * b + 2] = ts.vocab - 1;
+            ts.state[4 * b + 2] = ts_hi;
             ts.state[4 * b + 3] = last_t;
         }
         si[0] = next;
@@ -935,44 +932,9 @@ __global__ __launch_bounds__(256) void k_argmax_finish(const float* __restrict__
         __syncthreads();
         const int next = si[0];
         __syncthreads();
-        const T* er = (const T*)ne.tok_emb + (long)next * ne.d;
         int mpos = pos + 1;   // the row's next model position
         if constexpr (PFX) mpos = max(pos + 1 - max(ne.off[b], 0), 0);
-        const float* pr = ne.pos_emb + (long)mpos * ne.d;
-        // the row's mean first (k_dec_embed's two passes): the slab copy and the sums are of the centred row
-        float mean = 0.0f;
-        if (ne.shift) {
-            float s0 = 0.0f;
-            for (int c = tid * 4; c < ne.d; c += 1024) {
-                const f32x4 v = load4_f32(er + c) + *reinterpret_cast<const f32x4*>(pr + c);
-                s0 += (v[0] + v[1]) + (v[2] + v[3]);
-            }
-            s0 = dpp_wave_sum(s0);
-            if ((tid & 63) == 0) sv[8 + (tid >> 6)] = s0;
-            __syncthreads();
-            mean = ((sv[8] + sv[9]) + (sv[10] + sv[11])) / (float)ne.d;
-        }
-        float s1 = 0.0f, s2 = 0.0f;
-        for (int c = tid * 4; c < ne.d; c += 1024) {
-            const f32x4 p4 = *reinterpret_cast<const f32x4*>(pr + c);
-            f32x4 v = load4_f32(er + c) + p4;
-            *reinterpret_cast<f32x4*>(ne.x + (long)b * ne.d + c) = v;
-            v -= mean;
-            f32x4 g = {1, 1, 1, 1};
-            if (ne.xgamma) g = *reinterpret_cast<const f32x4*>(ne.xgamma + c);
-            store4((T*)ne.xslab + slab_idx(b, c, ne.mpad), v[0] * g[0], v[1] * g[1], v[2] * g[2], v[3] * g[3]);
-            s1 += (v[0] + v[1]) + (v[2] + v[3]);
-            s2 += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-        }
-        s1 = dpp_wave_sum(s1);
-        s2 = dpp_wave_sum(s2);
-        if ((tid & 63) == 0) { sv[tid >> 6] = s1; sv[4 + (tid >> 6)] = s2; }
-        __syncthreads();
-        if (tid == 0) {
-            ne.stats[2 * b] = (sv[0] + sv[1]) + (sv[2] + sv[3]);
-            ne.stats[2 * b + 1] = (sv[4] + sv[5]) + (sv[6] + sv[7]);
-            if (ne.shift) ne.shift[b] = mean;
-        }
+        embed_next_row<T>(ne, b, next, mpos, sv);
     }
     advance_if_last(ticket, pos_p, gridDim.x);
 }
@@ -1326,7 +1288,7 @@ template <typename T, int NCH, int UNROLL, bool NT, typename TO = T>  // NCH = c
 __global__ __launch_bounds__(256) void k_dec_cross_attn(const T* __restrict__ q, const T* __restrict__ ck,
                                                         const T* __restrict__ cv, float* __restrict__ part,
                                                         float* __restrict__ ml, int S, int d, int n_heads,
-                                                        int splits, TO* __restrict__ out, int mpad) {
+                                                        int splits, TO* __restrict__ out, int mpad, int rows_per_clip) {
     constexpr int EPC = 16 / (int)sizeof(T);   // elements per 16-B chunk: 8 (bf16) / 4 (f32)
     constexpr int LPH = WH_HEAD_DIM / EPC;     // lanes per head: 8 / 16
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1356,8 +1318,10 @@ __global__ __launch_bounds__(256) void k_dec_cross_attn(const T* __restrict__ q,
             o[c][u] = 0.0f;
         }
     }
-    const T* kb = ck + (long)b * S * d;
-    const T* vb = cv + (long)b * S * d;
+    int kvb = b;   // the clip whose K / V this row reads: the row itself, or (beam search) clip b / rows_per_clip
+    if (rows_per_clip != 1) kvb = b / rows_per_clip;
+    const T* kb = ck + (long)kvb * S * d;
+    const T* vb = cv + (long)kvb * S * d;
     // Software pipeline, two register sets: the K and V rows of the next UNROLL keys are in flight
     // while the current UNROLL keys go through dot / online softmax / P·V.
     vec_t kA[UNROLL][NCH], vA[UNROLL][NCH], kB[UNROLL][NCH], vB[UNROLL][NCH];
@@ -1507,7 +1471,7 @@ template <int UNROLL, bool NT>
 __global__ __launch_bounds__(256) void k_dec_cross_attn_cg(const bf16* __restrict__ q, const bf16* __restrict__ ck,
                                                            const bf16* __restrict__ cv, float* __restrict__ part,
                                                            float* __restrict__ ml, int S, int d, int n_heads,
-                                                           int splits, bf16* __restrict__ out, int mpad) {
+                                                           int splits, bf16* __restrict__ out, int mpad, int rows_per_clip) {
     constexpr int CGW = 256, HPG = CGW / WH_HEAD_DIM;   // columns / heads per group
     __shared__ __attribute__((aligned(16))) float wm[8][HPG], wl[8][HPG], wo[8][CGW];
     typedef __attribute__((ext_vector_type(8))) bf16 vec_t;
@@ -1521,8 +1485,10 @@ __global__ __launch_bounds__(256) void k_dec_cross_attn_cg(const bf16* __restric
     float o[8], mrun = -INFINITY, lrun = 0.0f;
 #pragma unroll
     for (int e = 0; e < 8; e++) o[e] = 0.0f;
-    const bf16* kb = ck + (long)b * S * d + col0;
-    const bf16* vb = cv + (long)b * S * d + col0;
+    int kvb = b;   // (as in k_dec_cross_attn)
+    if (rows_per_clip != 1) kvb = b / rows_per_clip;
+    const bf16* kb = ck + (long)kvb * S * d + col0;
+    const bf16* vb = cv + (long)kvb * S * d + col0;
     vec_t kA[UNROLL], vA[UNROLL], kB[UNROLL], vB[UNROLL];
     auto load_set = [&](vec_t (&kk)[UNROLL], vec_t (&vv)[UNROLL], int j) {
 #pragma unroll
@@ -1842,14 +1808,14 @@ size_t wh_cross_lds_reserve(long total_wgs, size_t own_bytes) {
 }
 
 void wh_launch_dec_cross_attn(hipStream_t s, int prec, const void* q, const void* ck, const void* cv, float* part,
-                              float* ml, int S, int d, int n_heads, int splits, int B, void* out, int mpad, bool stream_nt) {
+                              float* ml, int S, int d, int n_heads, int splits, int B, void* out, int mpad, bool stream_nt, int rows_per_clip) {
     dim3 grid(splits, B);
     const bool f32_layout = prec == WH_PREC_F32 || prec == WH_PREC_F16X3;   // (no matrix-core work in this kernel: the f32 form serves both)
     const long wgs = (long)splits * B * ((!f32_layout && d > 512 && d % 256 == 0) ? d / 256 : 1);
     const size_t sm = wh_cross_lds_reserve(wgs, sizeof(float) * ((size_t)8 * n_heads + 4 * (size_t)d));
 #define WH_CA2(T_, N_, U_, NT_, TO_) do { set_max_smem(k_dec_cross_attn<T_, N_, U_, NT_, TO_>, sm);                                                 \
                                      hipLaunchKernelGGL((k_dec_cross_attn<T_, N_, U_, NT_, TO_>), grid, dim3(256), sm, s, (const T_*)q, (const T_*)ck, \
-                                             (const T_*)cv, part, ml, S, d, n_heads, splits, (TO_*)(splits == 1 ? out : nullptr), mpad); } while (0)
+                                             (const T_*)cv, part, ml, S, d, n_heads, splits, (TO_*)(splits == 1 ? out : nullptr), mpad, rows_per_clip); } while (0)
 #define WH_CA1(T_, N_, U_, NT_) WH_CA2(T_, N_, U_, NT_, T_)
     static const int nt_env = [] { const char* e = getenv("WH_CROSS_NT"); return e ? atoi(e) : -1; }();   // (A/B runs: force the non-temporal K/V loads off / on)
     if (nt_env >= 0) stream_nt = nt_env != 0;
@@ -1879,8 +1845,8 @@ void wh_launch_dec_cross_attn(hipStream_t s, int prec, const void* q, const void
             dim3 g3(splits, B, d / 256);
             bf16* o = (bf16*)(splits == 1 ? out : nullptr);
             const size_t smcg = wh_cross_lds_reserve(wgs, 12 * 1024) - 12 * 1024;   // (the kernel's own ~10 KB are static: only the reserve is dynamic)
-            if (stream_nt) { set_max_smem(k_dec_cross_attn_cg<4, true>, smcg); hipLaunchKernelGGL((k_dec_cross_attn_cg<4, true>), g3, dim3(256), smcg, s, (const bf16*)q, (const bf16*)ck, (const bf16*)cv, part, ml, S, d, n_heads, splits, o, mpad); }
-            else { set_max_smem(k_dec_cross_attn_cg<4, false>, smcg); hipLaunchKernelGGL((k_dec_cross_attn_cg<4, false>), g3, dim3(256), smcg, s, (const bf16*)q, (const bf16*)ck, (const bf16*)cv, part, ml, S, d, n_heads, splits, o, mpad); }
+            if (stream_nt) { set_max_smem(k_dec_cross_attn_cg<4, true>, smcg); hipLaunchKernelGGL((k_dec_cross_attn_cg<4, true>), g3, dim3(256), smcg, s, (const bf16*)q, (const bf16*)ck, (const bf16*)cv, part, ml, S, d, n_heads, splits, o, mpad, rows_per_clip); }
+            else { set_max_smem(k_dec_cross_attn_cg<4, false>, smcg); hipLaunchKernelGGL((k_dec_cross_attn_cg<4, false>), g3, dim3(256), smcg, s, (const bf16*)q, (const bf16*)ck, (const bf16*)cv, part, ml, S, d, n_heads, splits, o, mpad, rows_per_clip); }
         } else WH_CA(bf16, 3, 2);
     }
 #undef WH_CA

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <map>
 #include <string>
 #include <tuple>
@@ -218,7 +219,9 @@ struct wh_ctx {
         float* al_q = nullptr;                 // word-level timestamps: nullptr = off (no launch); the side buffer the queries are copied to,
         int al_cap = 0;                        // its rows per clip (the call's max_new_tokens) and the identity of the head list (al_gen)
         unsigned al_gen = 0;
-        auto members() const { return std::tie(nb, n_prompt, eot, n_forced, logits_rows, d_logits, d_sel, ts_begin, ts_max_init, lp_sum, pfx, rep, rep_p, rep_n, al_q, al_cap, al_gen); }
+        int beam_k = 0, beam_c = 0;            // beam search: beam_k 0 = off; nb then counts rows = clips x beam_k.  beam_buf: the identity of the
+        const void* beam_buf = nullptr;        // setter's buffers (logits scratch and search state: one allocation each, freed together)
+        auto members() const { return std::tie(nb, n_prompt, eot, n_forced, logits_rows, d_logits, d_sel, ts_begin, ts_max_init, lp_sum, pfx, rep, rep_p, rep_n, al_q, al_cap, al_gen, beam_k, beam_c, beam_buf); }
         bool operator==(const StepKey& o) const { return members() == o.members(); }
     } step_key;
     // Whisper's timestamp rules (wh_ctx_set_timestamp_rules): off unless ts_on.  The timestamp logits and the per-row state
@@ -306,6 +309,32 @@ struct wh_ctx {
     std::vector<int> al_nframes;
     struct AlignDebug { int n_heads = 0, n_gen = 0, sb = 0; std::vector<float> probs, matrix; };
     std::vector<AlignDebug> al_dbg;
+    // Beam search (wh_ctx_set_beam_search): off unless bm_on.  The logits scratch and the search state are allocated by the setter
+    // (not part of the workspace carve) and freed when the option is cleared and in wh_ctx_free; the captured step is dropped before that.
+    bool bm_on = false;
+    int bm_k = 0, bm_c = 0;
+    float bm_length_penalty = -1.0f;
+    std::vector<int> bm_trace_clips;
+    float* bm_logits = nullptr;       // [max_batch][vocab] raw logits of the current position
+    char* bm_buf = nullptr;           // the search state, carved into:
+    float* bm_scores = nullptr;       // [max_batch]
+    int* bm_parent = nullptr;         // [max_batch]
+    int* bm_state = nullptr;          // [max_batch][WH_BEAM_STATE]
+    int* bm_pool_n = nullptr;         // [max_batch] per clip
+    int* bm_n_steps = nullptr;        // [max_batch] per clip
+    int* bm_pool = nullptr;           // [max_batch][WH_MAX_BEAM_CANDIDATES][4] per clip
+    int *bm_tr_parent = nullptr, *bm_tr_token = nullptr, *bm_tr_pool = nullptr;   // [tok_ld][max_batch]
+    float *bm_tr_score = nullptr, *bm_tr_lp = nullptr;
+    // what wh_get_beams / wh_get_beam_trace return: the last decode call's clips in the order their tokens were returned
+    struct BeamHyp { std::vector<int> tokens; std::vector<float> lps; float sum = 0.0f, rank = 0.0f; bool finished = false; };
+    struct BeamTrace { int K = 0, n_steps = 0; std::vector<int> parents, tokens, pool; std::vector<float> scores; };
+    bool bm_timing = false;                    // WH_BEAM_TIMING=1: events around the two kernels of every eagerly launched position (tools/beam_bench.py)
+    std::vector<std::array<hipEvent_t, 3>> bm_events;
+    double bm_ms[2] = {0, 0};                  // k_beam_select, k_beam_reorder of the last call, milliseconds, over bm_timed positions
+    long bm_timed = 0;
+    bool bm_have = false;
+    std::vector<std::vector<BeamHyp>> bm_hyps;
+    std::vector<BeamTrace> bm_traces;
     hipGraph_t step_graph = nullptr;
     hipGraphExec_t step_exec = nullptr;
 };

@@ -134,6 +134,7 @@ struct SkinnyArgs {
     float* logits = nullptr;   // optional [M][logits_rows][N], or — logits_sel given — [selected][logits_rows][N]
     int logits_rows = 0;
     const int* logits_sel = nullptr;   // [M]: slot of row m in `logits`, -1 = this row's logits are not kept
+    bool logits_cur = false;           // the current position only: every generated position's logits go to row 0 (beam search's scratch, logits_rows == 1)
     float* part_val = nullptr;
     int* part_idx = nullptr;
     // Whisper's timestamp rules (the RULES variants of the LM head): ids >= ts_begin are timestamps.  part_val / part_idx
@@ -303,7 +304,8 @@ void wh_launch_dec_self_attn(hipStream_t s, int prec, const void* qkv, void* kc,
 // stream_nt: non-temporal K/V loads (set when the cross K/V of all layers exceed what the Infinity Cache can keep)
 // splits == 1: the normalised output goes straight to `out` (slab layout, row pitch mpad); else partials for the consumer's merge
 void wh_launch_dec_cross_attn(hipStream_t s, int prec, const void* q, const void* ck, const void* cv, float* part,
-                              float* ml, int S, int d, int n_heads, int splits, int B, void* out, int mpad, bool stream_nt);
+                              float* ml, int S, int d, int n_heads, int splits, int B, void* out, int mpad, bool stream_nt,
+                              int rows_per_clip = 1);   // beam search: row b reads the K / V of clip b / rows_per_clip (ck / cv hold B / rows_per_clip clips)
 
 // wh_cross_es.hip: the same attention computed on the encoder states themselves (bf16, whisper-base geometry): qe [B][H][d] f32
 // expanded queries, E [B][S][d] bf16, out = the H * d context values per clip as a decode-GEMM operand (slab layout, pitch mpad)
@@ -313,7 +315,9 @@ bool wh_cross_es_geometry(int d, int n_heads, int S);
 // (WH_PREC_F16X3: wkT as h2, E as fp16 limb planes [B][e_rows][hi d | lo d] written by wh_launch_layernorm_es2, out as an h2 slab)
 void wh_launch_dec_qexpand(hipStream_t s, int prec, const float* q, const void* wkT, float* qe, int M, int d, int n_heads);
 // e_rows >= S: rows between two clips' states; n_cus: compute units the launch stream may use (one persistent workgroup per CU)
-void wh_launch_dec_cross_attn_es(hipStream_t s, int prec, const float* qe, const void* E, void* out, int S, int e_rows, int B, int mpad, bool stream_nt, int n_cus);
+// rows_per_clip > 1 (beam search; bf16 states only): row b attends over the states of clip b / rows_per_clip
+void wh_launch_dec_cross_attn_es(hipStream_t s, int prec, const float* qe, const void* E, void* out, int S, int e_rows, int B, int mpad, bool stream_nt, int n_cus,
+                                 int rows_per_clip = 1);
 void wh_launch_layernorm_es2(hipStream_t s, const float* x, const float* w, const float* b, void* y, long rows, int in_blk, int out_blk);
 // (WH_PREC_F16X3, wh_cross_es3.hip: E as key rows of [d fp16 | d e4m3 remainders] = 3 bytes per element, written by wh_launch_layernorm_es3; the default of the
 // mode — wh_es3_enabled(), WH_ES3=0 keeps the two-fp16-limb form — and dispatched by wh_launch_dec_cross_attn_es)
@@ -366,6 +370,40 @@ bool wh_align_scores_supported(int form, int dk);   // a score kernel exists for
 int wh_launch_align_scores(hipStream_t s, int form, const AlignArgs& a, int n_clips);
 void wh_launch_align_filter(hipStream_t s, const AlignArgs& a, int n_clips);
 void wh_launch_align_dtw(hipStream_t s, const AlignArgs& a, int n_clips);
+
+// Beam search (wh_beam.hip).  A clip's K beams are the batch rows clip * K + j.
+constexpr int WH_BEAM_STATE = 8;   // ints of per-row state: {text_lo, ts_lo, ts_hi, last timestamp, last token, generated length, -, -}
+struct BeamArgs {
+    int K = 0, C = 0, n_clips = 0, vocab = 0;
+    const float* logits = nullptr;      // [n_clips * K][vocab] raw logits of the current position (SkinnyArgs::logits with logits_cur)
+    const int* pos_p = nullptr;
+    int n_prompt = 0, eot = 0, tok_ld = 0;
+    const unsigned* mask_first = nullptr;
+    const unsigned* mask_base = nullptr;
+    int ts_begin = -1, ts_max_init = -1;   // timestamp rules: ts_begin < 0 = off
+    float* scores = nullptr;            // [rows] s_j
+    int* parent = nullptr;              // [rows] this position's parents as beam indices 0 .. K-1 (k_beam_reorder reads them)
+    int* state = nullptr;               // [rows][WH_BEAM_STATE]
+    int* pool_n = nullptr;              // [n_clips]
+    int* n_steps = nullptr;             // [n_clips] positions the clip has run
+    int* pool = nullptr;                // [n_clips][WH_MAX_BEAM_CANDIDATES][4]: {position g, parent beam, score bits, lp bits}
+    int* tr_parent = nullptr;           // the trace, each [tok_ld][rows_ld]: parents, tokens, scores, lp of every position's live beams
+    int* tr_token = nullptr;
+    float* tr_score = nullptr;
+    float* tr_lp = nullptr;
+    int* tr_pool = nullptr;             // [tok_ld][rows_ld] (entry [g][clip]): pool size after position g
+    int rows_ld = 0;
+    int* done = nullptr;                // [rows] DecodeState::done
+    int* feed = nullptr;                // [rows][tok_ld]: the next position's input token
+    float* logits_out = nullptr;        // parity harness: SkinnyArgs::logits / logits_rows / logits_sel of a greedy call, filled by the select kernel
+    int logits_rows = 0;
+    const int* logits_sel = nullptr;
+};
+void wh_launch_beam_select(hipStream_t s, int prec, const BeamArgs& a, const NextEmbed& ne);
+// dst[j] = src[parent[j]] for the self-attention K and V caches [layers][rows][H][tc][64] of every clip, positions 0 .. *pos_p; the last workgroup
+// advances the position
+void wh_launch_beam_reorder(hipStream_t s, int esz, void* kc, void* vc, const int* parent, const int* done, int K, int n_clips, int layers, int n_heads, int tc,
+                            int* pos_p, int* ticket);
 
 extern int wh_dbg_cross_unroll;
 extern int wh_dbg_lm_blocks_per_cu;

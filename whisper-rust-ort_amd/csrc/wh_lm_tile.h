@@ -111,6 +111,7 @@ struct WhLmTile {
         const unsigned* rbw = l.rbw;
         const int pos = *a.pos_p;
         const int gen = pos - (a.n_prompt - 1);  // index of the token this row generates
+        const int lrow = a.logits_cur ? min(gen, 0) : gen;   // the row of a.logits this position's logits go to
         const unsigned* mask = (gen == 0) ? a.mask_first : a.mask_base;
         const int nw0 = n0 + wn * 64;
         float sv[TN][4], cv[TN][4];
@@ -177,9 +178,9 @@ struct WhLmTile {
                     const int nn = n + e;
                     const float v = a.ln_part ? wh_ln_fold(acc[i][j][e], mean, rstd, sv[j][e], cv[j][e]) : acc[i][j][e];
                     if (nn < a.N && m < a.M) {
-                        if (a.logits && gen >= 0 && gen < a.logits_rows) {
+                        if (a.logits && lrow >= 0 && lrow < a.logits_rows) {
                             const int slot = a.logits_sel ? a.logits_sel[m] : m;
-                            if (slot >= 0) a.logits[((long)slot * a.logits_rows + gen) * a.N + nn] = v;
+                            if (slot >= 0) a.logits[((long)slot * a.logits_rows + lrow) * a.N + nn] = v;
                         }
                         const bool sup = (mbits[j] >> e) & 1u;
                         if constexpr (RULES) {
@@ -198,7 +199,7 @@ struct WhLmTile {
         if constexpr (REP) {
             // parity path: the logits rows keep the raw values (the loop above stored NaN for the touched ids); no accumulator is read, so the
             // row loop stays rolled
-            if (a.logits && gen >= 0 && gen < a.logits_rows) {
+            if (a.logits && lrow >= 0 && lrow < a.logits_rows) {
 #pragma unroll 1
                 for (int i = 0; i < TM; i++) {
                     const int rloc = wm * (TM * 16) + i * 16 + fl, m = m0 + rloc;
@@ -209,7 +210,7 @@ struct WhLmTile {
                     for (int c = 0; c < 16; c++) {
                         const int j = c >> 2, e = c & 3, nn = nw0 + j * 16 + 4 * fg + e;
                         const unsigned rb = ((j < 2) ? rw.x : rw.y) >> ((j & 1) * 16 + 4 * fg);
-                        if (((rb >> e) & 1u) && nn < a.N) a.logits[((long)slot * a.logits_rows + gen) * a.N + nn] = a.rep_side[(long)m * a.N + nn];
+                        if (((rb >> e) & 1u) && nn < a.N) a.logits[((long)slot * a.logits_rows + lrow) * a.N + nn] = a.rep_side[(long)m * a.N + nn];
                     }
                 }
             }

@@ -163,6 +163,7 @@ struct RowOut {
     bool has_lang = false;  // --language auto: the detected language code and its probability
     std::string language;
     double language_probability = 0;
+    std::string hypotheses;   // --beam-size N >= 2: JSON array of the n best {text, sum_logprob, rank_score, finished}; empty: no key
     bool has_prompt = false;  // --prompt-ids / --prompt-ids-dir: the length of the file's text context (<|startofprev|> included; 0: none)
     long long prompt_tokens = 0;
 };
@@ -228,6 +229,7 @@ inline std::string per_file_json(const std::vector<RowOut>& rows) {  // :1232 to
         if (rows[i].has_prompt) r.set("prompt_tokens", JVal::integer(rows[i].prompt_tokens));
         if (rows[i].has_conf) { JVal v; v.raw = fmt_conf(rows[i].avg_logprob); r.set("avg_logprob", v); v.raw = fmt_conf(rows[i].no_speech_prob); r.set("no_speech_prob", v); }
         if (!rows[i].segments.empty()) { JVal sg; sg.raw = rows[i].segments; r.set("segments", sg); }
+        if (!rows[i].hypotheses.empty()) { JVal h; h.raw = rows[i].hypotheses; r.set("hypotheses", h); }
         if (!rows[i].words.empty()) { JVal w; w.raw = rows[i].words; r.set("words", w); w.raw = rows[i].token_times; r.set("token_times", w); }
         o += "  ";
         r.write(o, 2);
@@ -240,12 +242,14 @@ struct OrtCfg {  // :91-100 — CPU-EP knobs: accepted and echoed only, they hav
     long long intra_op = 1, inter_op = 1;
     std::string execution_mode = "SEQUENTIAL", graph_opt = "ENABLE_ALL";
     bool cpu_mem_arena = true, mem_pattern = true, allow_spinning = true;
+    long long beam_size = 1;   // additive (no reference counterpart: the reference is greedy): echoed only when >= 2, so a greedy run's config_used keeps the reference's keys
     JVal json(bool sorted) const {
         JVal j = JVal::obj(sorted);
         j.set("intra_op", JVal::integer(intra_op)).set("inter_op", JVal::integer(inter_op))
             .set("execution_mode", JVal::str(execution_mode)).set("graph_opt", JVal::str(graph_opt))
             .set("cpu_mem_arena", JVal::boolean(cpu_mem_arena)).set("mem_pattern", JVal::boolean(mem_pattern))
             .set("allow_spinning", JVal::boolean(allow_spinning));
+        if (beam_size >= 2) j.set("beam_size", JVal::integer(beam_size));
         return j;
     }
 };

@@ -45,7 +45,7 @@ size_t whh_per_file_json(const char* files, const char* texts, const double* dur
 }
 // the reference's summary object (src/main.rs:1235-1257) from per-file lists: lists = [end2end | load | preprocess | model_only | decode | rtf],
 // n values each; strs = NUL-separated model_id, onnx_dir, language, task, tokenizer_json, execution_mode, graph_opt;
-// ints = intra_op, inter_op, max_new_tokens; flags bit 0 timestamps, 1 cpu_mem_arena, 2 mem_pattern, 3 allow_spinning
+// ints = intra_op, inter_op, max_new_tokens; flags bit 0 timestamps, 1 cpu_mem_arena, 2 mem_pattern, 3 allow_spinning, bits 4-7 --beam-size (0: not given)
 size_t whh_summary_json(const double* lists, size_t n, const char* strs, const long long* ints, unsigned flags, char* out, size_t cap) {
     SummaryIn in;
     auto take = [&](int k) { return std::vector<double>(lists + (size_t)k * n, lists + (size_t)(k + 1) * n); };
@@ -55,6 +55,7 @@ size_t whh_summary_json(const double* lists, size_t n, const char* strs, const l
     for (auto* d : dst) { *d = std::string(strs); strs += d->size() + 1; }
     in.cfg.intra_op = ints[0]; in.cfg.inter_op = ints[1]; in.max_new_tokens = ints[2];
     in.timestamps = flags & 1; in.cfg.cpu_mem_arena = flags & 2; in.cfg.mem_pattern = flags & 4; in.cfg.allow_spinning = flags & 8;
+    if ((flags >> 4) & 15) in.cfg.beam_size = (flags >> 4) & 15;
     return put(reference_summary(in).pretty(), out, cap);
 }
 size_t whh_lower(const char* s, char* out, size_t cap) { return put(lower(s), out, cap); }

@@ -58,6 +58,10 @@ struct Args {
     // additive: word-level timestamps (wh_ctx_set_alignment): words and token times in the per-file JSON; the alignment heads as "l:h,l:h,..."
     bool word_timestamps = false;
     std::string alignment_heads;
+    // additive: beam search (wh_ctx_set_beam_search).  --beam-size 1 is the greedy path with the option not set
+    int beam_size = 1, n_best = 1;
+    float patience = 1.0f, length_penalty = -1.0f;
+    bool beam() const { return beam_size >= 2; }
     bool prompts() const { return !prompt_ids.empty() || !prompt_ids_dir.empty(); }
 };
 
@@ -128,7 +132,12 @@ static bool parse_args(int argc, char** argv, Args& a) {
                    "[--device 0] [--devices 0-7] [--streams-per-gpu 1] [--load-threads N] [--precision bf16|f32|fp8|f16x3] [--max-batch 16] "
                    "[--synthetic-clips N] [--seed 1000] [--print-plan] [--timestamp-rules] [--write-srt] [--write-vtt] "
                    "[--logprobs] [--no-speech-threshold X] [--logprob-threshold Y] [--prompt-ids a,b,c] [--prompt-ids-dir DIR] [--prompt-all-windows] "
-                   "[--repetition-penalty F] [--no-repeat-ngram-size N]\n"
+                   "[--repetition-penalty F] [--no-repeat-ngram-size N] [--beam-size N] [--patience F] [--length-penalty F] [--n-best M]\n"
+                   "  --beam-size N            beam search with N beams per window (1 .. 8; 1 = greedy, the default); a device batch then holds max-batch / N files\n"
+                   "  --patience F             round(N * F) finished hypotheses end a window's search (openai-whisper's patience; default 1)\n"
+                   "  --length-penalty F       rank by score / ((5 + len) / 6)^F; below 0 (the default): by score / len\n"
+                   "  --n-best M               hypotheses [{text, sum_logprob, rank_score, finished}] of the M best per file in the per-file JSON (a file of several windows:\n"
+                   "                           every window's M best one after the other, each with its window index)\n"
                    "  --repetition-penalty F   HF generate's repetition_penalty on each row's generated history (F > 0; 1 = off)\n"
                    "  --no-repeat-ngram-size N no n-gram of N ids is generated twice (0 = off, at most 32); timestamps are exempt from both\n"
                    "  --language auto          the language of every file is detected from its audio (its first window's, for a file of several) among\n"
@@ -199,8 +208,41 @@ static bool parse_args(int argc, char** argv, Args& a) {
                 a.rep_ngram = (int)n;
                 a.have_rep_ngram = true;
             }
+            else if (k == "--beam-size" || k == "--n-best") {   // what wh_ctx_set_beam_search refuses is refused here, before any device is touched
+                char* end = nullptr;
+                const long n = strtol(v.c_str(), &end, 10);
+                const long hi = k == "--beam-size" ? WH_MAX_BEAMS : WH_MAX_BEAMS + WH_MAX_BEAM_CANDIDATES;
+                if (v.empty() || *end || n < 1 || n > hi) {
+                    fprintf(stderr, "error: %s '%s' is outside 1 .. %ld\n", k.c_str(), v.c_str(), hi);
+                    return false;
+                }
+                (k == "--beam-size" ? a.beam_size : a.n_best) = (int)n;
+            } else if (k == "--patience" || k == "--length-penalty") {
+                char* end = nullptr;
+                const float f = strtof(v.c_str(), &end);
+                const bool pat = k == "--patience";
+                if (v.empty() || *end || std::isnan(f) || (pat && (!std::isfinite(f) || !(f > 0.0f)))) {
+                    fprintf(stderr, "error: %s '%s' is not %s\n", k.c_str(), v.c_str(), pat ? "a finite value above 0" : "a number");
+                    return false;
+                }
+                (pat ? a.patience : a.length_penalty) = f;
+            }
             else { fprintf(stderr, "error: unexpected argument '%s'\n", k.c_str()); return false; }
         }
+    }
+    if (a.beam()) {   // the combinations every decode call would refuse, and a candidate count outside the library's range
+        const long cand = lroundf((float)a.beam_size * a.patience);
+        if (cand < 1 || cand > WH_MAX_BEAM_CANDIDATES) {
+            fprintf(stderr, "error: round(--beam-size * --patience) = %ld is outside 1 .. %d\n", cand, WH_MAX_BEAM_CANDIDATES);
+            return false;
+        }
+        if (a.max_batch < a.beam_size) { fprintf(stderr, "error: --max-batch %d holds no file of --beam-size %d\n", a.max_batch, a.beam_size); return false; }
+        const char* clash = a.have_rep_penalty || a.have_rep_ngram ? "--repetition-penalty / --no-repeat-ngram-size" : a.word_timestamps ? "--word-timestamps"
+                            : a.prompts() ? "--prompt-ids / --prompt-ids-dir" : a.precision == "fp8" || a.precision == "f16x3" ? "--precision fp8 / f16x3" : nullptr;
+        if (clash) { fprintf(stderr, "error: --beam-size %d cannot be combined with %s\n", a.beam_size, clash); return false; }
+    } else if (a.n_best > 1) {
+        fprintf(stderr, "error: --n-best %d needs --beam-size 2 or more\n", a.n_best);
+        return false;
     }
     return true;
 }
@@ -442,9 +484,39 @@ static void cues_conf(std::vector<Cue>& cues, double avg_lp, double ns) {
     for (Cue& c : cues) { c.has_conf = true; c.avg_logprob = avg_lp; c.no_speech_prob = ns; }
 }
 
+// --beam-size N >= 2: the n best hypotheses of each of the n clips / windows of the last decode call as the comma-separated members of a JSON
+// array, {text, sum_logprob, rank_score, finished}, best first; with_window: a leading "window" key (the windows of a long file)
+static std::vector<std::string> fetch_hypotheses(wh_ctx* ctx, size_t n, const Args& a, const WhisperSpecial& sp, const Tokenizer* tok, bool with_window) {
+    const size_t nh = (size_t)a.n_best, cap = a.max_new_tokens;
+    std::vector<int64_t> ht(n * nh * cap);
+    std::vector<size_t> hn(n * nh), hcount(n);
+    std::vector<float> hs(n * nh), hr(n * nh);
+    std::vector<int32_t> hf(n * nh);
+    size_t got = 0;
+    if (int rc = wh_get_beams(ctx, ht.data(), cap, hn.data(), hs.data(), hr.data(), hf.data(), nh, hcount.data(), n, &got))
+        throw std::runtime_error(std::string("wh_get_beams: ") + std::to_string(rc));
+    std::vector<std::string> out(n);
+    for (size_t k = 0; k < n; k++)
+        for (size_t h = 0; h < hcount[k]; h++) {
+            const size_t at = k * nh + h;
+            std::vector<int64_t> g(ht.begin() + at * cap, ht.begin() + at * cap + hn[at]);
+            if (!g.empty() && g.back() == sp.eot) g.pop_back();
+            if (a.timestamp_rules) g = text_ids(g, sp.timestamp_begin);
+            JVal j = JVal::obj(false);
+            JVal s1, s2;
+            s1.raw = fmt_conf(hs[at]); s2.raw = fmt_conf(hr[at]);
+            if (with_window) j.set("window", JVal::integer((long long)k));
+            j.set("text", JVal::str(trim(decode_tokens(g, tok)))).set("sum_logprob", s1).set("rank_score", s2).set("finished", JVal::boolean(hf[at] != 0));
+            out[k] += (h ? ", " : "");
+            j.write(out[k], 4);
+        }
+    return out;
+}
+
 static std::string transcribe(wh_ctx* ctx, const std::vector<float>& audio, const Args& a, const Tokenizer* tok,
                               const GenCfg& gen, Timing& t, std::vector<Cue>* cues = nullptr, Conf* conf = nullptr,
-                              const LanguageTable* lt = nullptr, Lang* lang = nullptr, const std::vector<int64_t>* prefix = nullptr, WordOut* words = nullptr) {
+                              const LanguageTable* lt = nullptr, Lang* lang = nullptr, const std::vector<int64_t>* prefix = nullptr, WordOut* words = nullptr,
+                              std::string* hyps = nullptr) {
     const double t0 = now_s();
     if (a.prompts()) {   // the file's text context, on its first window or on every one (no context: an empty prefix)
         const size_t offs[2] = {0, prefix ? prefix->size() : 0};
@@ -476,6 +548,12 @@ static std::string transcribe(wh_ctx* ctx, const std::vector<float>& audio, cons
     if (lt && lang && got) *lang = fetch_languages(ctx, got, *lt)[0];   // the file's language: its first window's
     std::vector<int32_t> frames;
     if (a.word_timestamps) fetch_frames(ctx, got, a.max_new_tokens, frames);
+    if (a.beam() && hyps) {   // a long file: every window's n best, one after the other, each naming its window
+        std::string o;
+        for (const std::string& w : fetch_hypotheses(ctx, got, a, sp, tok, true))
+            if (!w.empty()) o += (o.empty() ? "" : ", ") + w;
+        *hyps = "[" + o + "]";
+    }
     const double td0 = now_s();
     std::vector<std::string> texts;
     std::vector<size_t> offs(std::max<size_t>(1, got));
@@ -526,6 +604,7 @@ int main(int argc, char** argv) {
         OrtCfg cfg = a.discovery_best_json.empty() ? suggested_optimum_cfg() : load_best_cfg_from_discovery(a.discovery_best_json);
         if (a.intra_op > 0) cfg.intra_op = a.intra_op;
         if (a.inter_op > 0) cfg.inter_op = a.inter_op;
+        if (a.beam()) cfg.beam_size = a.beam_size;   // (config_used gains beam_size only then: the greedy summaries keep their bytes)
 
         Tokenizer tok;  // resolve_tokenizer, src/main.rs:574-635: explicit path, model directories, then the Hugging Face cache
         if (!trim(a.tokenizer_json).empty()) {
@@ -561,6 +640,9 @@ int main(int argc, char** argv) {
             plan.set("devices", jd).set("models", JVal::integer((long long)devices.size())).set("contexts", jc)
                 .set("host_threads", JVal::integer((long long)(devices.size() * a.streams_per_gpu))).set("max_batch", JVal::integer(a.max_batch))
                 .set("precision", JVal::str(a.precision));
+            if (a.beam())
+                plan.set("beam_size", JVal::integer(a.beam_size)).set("patience", JVal::num(a.patience)).set("length_penalty", JVal::num(a.length_penalty))
+                    .set("n_best", JVal::integer(a.n_best)).set("files_per_batch", JVal::integer(a.max_batch / a.beam_size));
             printf("%s\n", plan.pretty().c_str());
             return 0;
         }
@@ -599,6 +681,11 @@ int main(int argc, char** argv) {
                     wh_repetition_opts ro{sizeof(wh_repetition_opts), a.rep_penalty, a.rep_ngram};
                     if (int rc = wh_ctx_set_repetition(c, &ro))
                         throw std::runtime_error(std::string("wh_ctx_set_repetition: ") + std::to_string(rc) + ": " + wh_last_error(c));
+                }
+                if (a.beam()) {   // beam search on every context (no reference counterpart)
+                    wh_beam_opts bo{sizeof(wh_beam_opts), a.beam_size, a.patience, a.length_penalty, nullptr, 0};
+                    if (int rc = wh_ctx_set_beam_search(c, &bo))
+                        throw std::runtime_error(std::string("wh_ctx_set_beam_search: ") + std::to_string(rc) + ": " + wh_last_error(c));
                 }
                 if (a.word_timestamps) {   // word-level timestamps on every context (no reference counterpart)
                     wh_dims dims{};
@@ -679,7 +766,7 @@ int main(int argc, char** argv) {
                             return hipHostMalloc((void**)&p, (size_t)WH_CLIP_SAMPLES * sizeof(float), hipHostMallocDefault) == hipSuccess ? p : nullptr;
                         },
                         [](float* p) { (void)hipHostFree(p); });
-        struct Result { std::string text; double dur = 0, load_s = 0; Timing t; bool ok = false; std::vector<Cue> cues; Conf conf; Lang lang; WordOut words; };
+        struct Result { std::string text; double dur = 0, load_s = 0; Timing t; bool ok = false; std::vector<Cue> cues; Conf conf; Lang lang; WordOut words; std::string hyps; };
         const size_t nfiles = files.size();
         std::vector<Result> results(nfiles);
         const unsigned hc = std::thread::hardware_concurrency();
@@ -695,7 +782,7 @@ int main(int argc, char** argv) {
             if (batch.size() == 1 && batch[0].n() > (size_t)WH_CLIP_SAMPLES) {
                 // a file longer than one window goes alone through the long-form entry (which batches its windows)
                 Result& r = results[batch[0].idx];
-                r.text = transcribe(ctx, batch[0].audio, a, &tok, gen, r.t, &r.cues, &r.conf, lang_auto ? &lang_table : nullptr, &r.lang, &file_prefix[batch[0].idx], &r.words);
+                r.text = transcribe(ctx, batch[0].audio, a, &tok, gen, r.t, &r.cues, &r.conf, lang_auto ? &lang_table : nullptr, &r.lang, &file_prefix[batch[0].idx], &r.words, &r.hyps);
                 r.dur = batch[0].dur; r.load_s = batch[0].load_s; r.ok = true;
             } else {
                 // the per-window body of transcribe_longform_chunked (:870-915) for a batch of one-window files
@@ -731,6 +818,10 @@ int main(int argc, char** argv) {
                 if (lang_auto) langs = fetch_languages(ctx, batch.size(), lang_table);
                 std::vector<int32_t> frames;
                 if (a.word_timestamps) fetch_frames(ctx, batch.size(), a.max_new_tokens, frames);
+                if (a.beam()) {   // the n best hypotheses of every file of the batch
+                    const std::vector<std::string> hy = fetch_hypotheses(ctx, batch.size(), a, sp, &tok, false);
+                    for (size_t k = 0; k < batch.size(); k++) results[batch[k].idx].hyps = "[" + hy[k] + "]";
+                }
                 for (size_t k = 0; k < batch.size(); k++) {   // :926-943
                     Result& r = results[batch[k].idx];
                     if (lang_auto) r.lang = langs[k];
@@ -770,9 +861,10 @@ int main(int argc, char** argv) {
         };
         // synthetic clips are one-window files by construction: allocate the page-locked staging pool now, outside the timed loop
         // (5.9 GB at --max-batch 1024; a directory of audio files allocates it when the first one-window file shows up)
-        if (a.synthetic_clips) pool.ensure(file_pipeline_pool_size((size_t)a.max_batch, ctxs.size(), n_loaders));
+        const size_t files_per_batch = (size_t)(a.max_batch / std::max(1, a.beam() ? a.beam_size : 1));   // beam search: a file takes beam_size rows
+        if (a.synthetic_clips) pool.ensure(file_pipeline_pool_size(files_per_batch, ctxs.size(), n_loaders));
         const double loop0 = now_s();
-        const std::string first_error = run_file_pipeline(nfiles, n_loaders, ctxs.size(), (size_t)a.max_batch, (size_t)WH_CLIP_SAMPLES, &pool, load, process);
+        const std::string first_error = run_file_pipeline(nfiles, n_loaders, ctxs.size(), files_per_batch, (size_t)WH_CLIP_SAMPLES, &pool, load, process);
         const double loop_s = now_s() - loop0;
         if (!first_error.empty()) throw std::runtime_error(first_error);
 
@@ -787,6 +879,7 @@ int main(int argc, char** argv) {
             rows.push_back(make_row(files[i], r.dur, end_to_end, r.text));
             if (a.timestamp_rules) rows.back().segments = cues_json(r.cues);
             if (a.word_timestamps) { rows.back().words = words_json(r.words.words); rows.back().token_times = times_json(r.words.token_times); }
+            if (!r.hyps.empty()) rows.back().hypotheses = r.hyps;
             if (a.prompts()) { rows.back().has_prompt = true; rows.back().prompt_tokens = (long long)file_prefix[i].size(); }
             if (r.lang.has) { rows.back().has_lang = true; rows.back().language = r.lang.code; rows.back().language_probability = r.lang.prob; }
             if (r.conf.has) { rows.back().has_conf = true; rows.back().avg_logprob = r.conf.avg_logprob(); rows.back().no_speech_prob = r.conf.no_speech_prob(); }
@@ -828,6 +921,7 @@ int main(int argc, char** argv) {
         if (a.logprobs) summary.set("logprobs", JVal::boolean(true));
         if (a.have_rep_penalty) summary.set("repetition_penalty", JVal::num(a.rep_penalty));
         if (a.have_rep_ngram) summary.set("no_repeat_ngram_size", JVal::integer(a.rep_ngram));
+        if (a.beam()) summary.set("patience", JVal::num(a.patience)).set("length_penalty", JVal::num(a.length_penalty)).set("n_best", JVal::integer(a.n_best));
         write_file(a.out_summary_json, summary.pretty());
         printf("DONE\n");  // :1261-1268
         printf("Config used:\n%s\n", cfg.json(false).pretty().c_str());
