@@ -382,6 +382,44 @@ int wh_get_beams(const wh_ctx* c, int64_t* tokens, size_t cap_tokens, size_t* n_
  * WH_ERR_ARG for k outside the trace clips or cap_steps < *n_steps. */
 int wh_get_beam_trace(const wh_ctx* c, size_t k, int32_t* parents, int32_t* tokens, float* scores, int32_t* pool_size, size_t cap_steps,
                       size_t* n_steps);
+/* Temperature sampling in the token loop (openai-whisper's GreedyDecoder at temperature > 0: Categorical(logits / T).sample(); the rungs
+ * of its temperature ladder, faster-whisper's and HF generate's too, are calls with this set).  No reference entry corresponds: the
+ * reference keeps plain argmax (src/main.rs:709-735).  With this set, batch row b of every decode entry of the ctx draws its token at
+ * generated position g with T = temperature[b] as follows (every draw can be replayed on the host from the row's logits):
+ *   - allowed set: v = the raw logits after the suppress masks (begin_suppress at g = 0) and, when set, the timestamp rules 1-5 on the
+ *     row's fed history; NaN (and -inf) is never allowed — exactly the set wh_get_logprobs sums over;
+ *   - uniform draw for id i: Philox4x32-10 with key (seed low 32 bits, seed high 32 bits) and counter (i >> 2, g, row_id low 32 bits,
+ *     row_id high 32 bits); x = word i & 3 of its output; u = ((x >> 9) + 0.5f) * 2^-23, exact in f32 and strictly inside (0, 1)
+ *     (23 bits: with 24, (x >> 8) + 0.5f is not representable above 2^23 and the largest draws would round to u = 1);
+ *   - gum_i = -logf(-logf(u_i));  z_i = v_i * invT with invT = 1.0f / T computed once in f32;
+ *   - the recorded token is the argmax over the allowed ids of z_i + gum_i (one f32 multiplication, one f32 addition, not fused), ties to
+ *     the lowest id; nothing allowed: token 0.  (Gumbel-max: the draw of an id depends on no reduction order.)
+ *   - its recorded log-probability is the untempered v[tok] - (m + logf(sum_allowed expf(v - m))), m the largest allowed logit
+ *     (openai-whisper sums log-softmax of the untempered logits).  Log-probabilities are recorded whenever sampling is on:
+ *     wh_get_logprobs works without wh_ctx_set_logprobs (the no-speech probe still needs it);
+ *   - T == 0: the row follows the greedy definition and returns the greedy call's tokens exactly;
+ *   - active[b] == 0: the row starts done — it records nothing, returns n_tokens_out = n_prompt, is fed the stop token and counts as done
+ *     for the loop's EOT poll;
+ *   - forced tokens: the recorded token is the sampled one, the fed one the forced one.
+ * row_ids name the rows' random streams, so a result does not depend on batching: the same clip with the same id and seed at another
+ * batch row, or in another device batch, draws the same tokens.  wh_transcribe_longform takes n_rows == 1: temperature[0] / active[0]
+ * for every window, the window index as its id.  With every temperature 0 and every row active the plain kernels are launched and every
+ * output is what it is without this entry.  Otherwise the LM head leaves the current position's raw logits in a float
+ * [max_batch][vocab] scratch (425 MB at 2048 whisper-base rows), which the setter allocates and frees again when the option is cleared.
+ * Works with suppress lists, timestamp rules, the no-speech probe, language detection, prefixes, forced tokens, all decode entries and
+ * all four precision modes.
+ * Refused with WH_ERR_ARG (the ctx unchanged): a wrong struct_size, n_rows outside 1 .. max_batch, a NULL temperature list, a temperature
+ * that is negative or not finite; at decode time, before anything is launched: n_rows different from the call's clip count (long-form:
+ * from 1) -> WH_ERR_ARG; beam search, repetition controls or alignment set -> WH_ERR_UNSUPPORTED.  o == NULL turns it off (the default). */
+typedef struct {
+    size_t struct_size;         /* sizeof(wh_sampling_opts) */
+    uint64_t seed;
+    const float* temperature;   /* [n_rows]; >= 0, finite; 0 = plain argmax for that row */
+    const uint8_t* active;      /* [n_rows] or NULL (all active); 0: the row starts done, generates nothing */
+    const uint64_t* row_ids;    /* [n_rows] or NULL (row index); names the row's random stream */
+    size_t n_rows;              /* 1 .. max_batch; must equal the call's clip count at decode time */
+} wh_sampling_opts;
+int wh_ctx_set_sampling(wh_ctx* c, const wh_sampling_opts* o);
 const char* wh_last_error(const wh_ctx* c); /* c == NULL: last load/create error of this thread */
 int wh_get_timings(const wh_ctx* c, wh_timing* out);
 

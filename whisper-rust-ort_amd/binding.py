@@ -36,7 +36,8 @@ EXPORTS = ("wh_model_load", "wh_model_create", "wh_model_free", "wh_model_get_di
            "wh_profile_get", "wh_synthetic_weights", "wh_e4m3_quantize", "wh_e4m3_dequantize", "wh_abi_version",
            "wh_device_count", "wh_ctx_set_timestamp_rules", "wh_ctx_set_logprobs", "wh_get_logprobs",
            "wh_ctx_set_language_detection", "wh_get_languages", "wh_ctx_set_prefixes", "wh_ctx_set_repetition",
-           "wh_ctx_set_alignment", "wh_get_token_frames", "wh_get_alignment_debug", "wh_ctx_set_beam_search", "wh_get_beams", "wh_get_beam_trace")
+           "wh_ctx_set_alignment", "wh_get_token_frames", "wh_get_alignment_debug", "wh_ctx_set_beam_search", "wh_get_beams", "wh_get_beam_trace",
+           "wh_ctx_set_sampling")
 
 
 class WhisperHipError(RuntimeError):
@@ -113,6 +114,11 @@ WH_MAX_BEAM_TRACE_CLIPS = 8
 class WhBeamOpts(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("beam_size", C.c_int32), ("patience", C.c_float), ("length_penalty", C.c_float),
                 ("trace_clips", C.POINTER(C.c_int32)), ("n_trace_clips", C.c_size_t)]
+
+
+class WhSamplingOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("seed", C.c_uint64), ("temperature", C.POINTER(C.c_float)), ("active", C.POINTER(C.c_uint8)),
+                ("row_ids", C.POINTER(C.c_uint64)), ("n_rows", C.c_size_t)]
 
 
 def pack_prefixes(prefixes: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.ndarray]:
@@ -205,7 +211,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.wh_get_alignment_debug.argtypes = [vp, C.c_size_t, f32p, f32p, C.c_size_t, C.POINTER(C.c_int32)]
     i32p = C.POINTER(C.c_int32)
     L.wh_ctx_set_beam_search.argtypes = [vp, C.POINTER(WhBeamOpts)]
-    L.wh_get_beams.argtypes = [vp, i64p, C.c_size_t, szp, f32p, f32p, i32p, C.c_size_t, szp, C.c_size_t, szp]
+    L.wh_ctx_set_sampling.argtypes = [vp, C.POINTER(WhSamplingOpts)]
+    L.wh_get_beams.argtypes =[vp, i64p, C.c_size_t, szp, f32p, f32p, i32p, C.c_size_t, szp, C.c_size_t, szp]
     L.wh_get_beam_trace.argtypes = [vp, C.c_size_t, i32p, i32p, f32p, i32p, C.c_size_t, szp]
     _lib = L
     return L
@@ -468,7 +475,22 @@ class Context:
     def clear_beam_search(self):
         self._check(self.lib.wh_ctx_set_beam_search(self.h, None))
 
-    def beams(self, cap_hyp: int = WH_MAX_BEAM_CANDIDATES + WH_MAX_BEAMS) -> List[List[dict]]:
+    def set_sampling(self, seed: int, temperatures: Sequence[float], active: Optional[Sequence[int]] = None, row_ids: Optional[Sequence[int]] = None):
+        """wh_ctx_set_sampling: batch row b of every decode entry of this context draws its tokens at temperatures[b] (0: plain argmax) by
+        Gumbel-max on Philox4x32-10 streams named by (seed, row_ids[b]); active[b] == 0: the row generates nothing.  Long-form: one row."""
+        t = np.ascontiguousarray(temperatures, np.float32)
+        a = np.ascontiguousarray(active, np.uint8) if active is not None else None
+        r = np.ascontiguousarray(row_ids, np.uint64) if row_ids is not None else None
+        if (a is not None and a.size != t.size) or (r is not None and r.size != t.size):
+            raise ValueError("set_sampling: active / row_ids must have one entry per temperature")
+        o = WhSamplingOpts(C.sizeof(WhSamplingOpts), seed, _f32(t) if t.size else None, a.ctypes.data_as(C.POINTER(C.c_uint8)) if a is not None else None,
+                           r.ctypes.data_as(C.POINTER(C.c_uint64)) if r is not None else None, t.size)
+        self._check(self.lib.wh_ctx_set_sampling(self.h, C.byref(o)))
+
+    def clear_sampling(self):
+        self._check(self.lib.wh_ctx_set_sampling(self.h, None))
+
+    def beams(self, cap_hyp: int =WH_MAX_BEAM_CANDIDATES + WH_MAX_BEAMS) -> List[List[dict]]:
         """wh_get_beams of the last decode call: per clip / window the ranked hypotheses, best first, as dicts {tokens (generated ids, EOT
         included when finished), sum_logprob, rank_score, finished}."""
         n = C.c_size_t(0)

@@ -9,7 +9,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libwhisper_hip.so")
-SOURCES = ["wh_mel.hip", "wh_gemm.hip", "wh_gemm8.hip", "wh_gemm8x.hip", "wh_gemm8_mx.hip", "wh_mlp.hip", "wh_attn.hip", "wh_decode.hip", "wh_dec_tile.hip", "wh_cross_es.hip", "wh_cross_es8.hip", "wh_cross_es3.hip", "wh_fp8.hip", "wh_align.hip", "wh_beam.hip", "wh_model.cpp", "wh_api.cpp"]
+SOURCES = ["wh_mel.hip", "wh_gemm.hip", "wh_gemm8.hip", "wh_gemm8x.hip", "wh_gemm8_mx.hip", "wh_mlp.hip", "wh_attn.hip", "wh_decode.hip", "wh_dec_tile.hip", "wh_cross_es.hip", "wh_cross_es8.hip", "wh_cross_es3.hip", "wh_fp8.hip", "wh_align.hip", "wh_beam.hip", "wh_sample.hip", "wh_model.cpp", "wh_api.cpp"]
 HEADERS = ["wh_common.h", "wh_es_common.h", "wh_dec_epilogue.h", "wh_kernels.h", "wh_lm_tile.h", "wh_internal.h", "wh_json.h", "../../include/whisper_hip.h"]
 # -amdgpu-mfma-vgpr-form: MFMA accumulators live in VGPRs (gfx950's register file is unified).  With the default
 # heuristic the attention kernel kept its score and output tiles in AGPRs and spent 160 of ~400 VALU instructions
@@ -94,17 +94,24 @@ def build_host(verbose: bool = False, force: bool = False) -> None:
     """The host side above the C ABI (C++, because the reference's host is compiled Rust and Rust is
     not in this image): the CLI `whisper_bench` and `libwh_host.so` (host helpers for the tests)."""
     gxx = os.environ.get("CXX", "g++")
-    hdr = [os.path.join(HOST, "wh_host.h"), os.path.join(HOST, "wh_unicode_lower.h"), os.path.join(CSRC, "wh_json.h"), os.path.join(HERE, "..", "include", "whisper_hip.h")]
+    # the temperature ladder's compression_ratio calls zlib, which the host code loads by its soname at the first use (dlopen("libz.so.1"):
+    # the development symlink libz.so is not needed to link).  Python's own zlib module depends on the same soname.
+    import ctypes
+    try:
+        ctypes.CDLL("libz.so.1")
+    except OSError as e:
+        raise RuntimeError(f"libz.so.1 is missing: whisper_bench --temperature and libwh_host.so's compression_ratio need zlib ({e})") from e
+    hdr =[os.path.join(HOST, "wh_host.h"), os.path.join(HOST, "wh_unicode_lower.h"), os.path.join(CSRC, "wh_json.h"), os.path.join(HERE, "..", "include", "whisper_hip.h")]
     src = os.path.join(HOST, "wh_host_capi.cpp")
     if force or _stale(HOST_SO, [src] + hdr):
-        cmd = [gxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-o", HOST_SO, src]
+        cmd = [gxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-o", HOST_SO, src, "-ldl"]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
     src = os.path.join(HOST, "whisper_bench.cpp")
     if force or _stale(CLI, [src, OUT] + hdr):
         cmd = [gxx, "-O2", "-std=c++17", "-Wall", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-o", CLI, src, "-L" + HERE, "-lwhisper_hip",
-               "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64"]
+               "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-ldl"]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)

@@ -344,6 +344,24 @@ int beam_check(wh_ctx* c, const wh_decode_params* p, int nb) {
     return WH_OK;
 }
 
+// Temperature sampling: what a decode entry refuses because of it, checked by every entry before it launches anything and again
+// by run_decode.  nb = the call's clips (a long-form call: the setter's one row stands for every window).
+int sample_check(wh_ctx* c, int nb, bool longform) {
+    if (!c->sm_on) return WH_OK;
+    if (c->sm_temp.size() != (size_t)(longform ? 1 : nb))
+        return fail(c, WH_ERR_ARG, "decode: wh_ctx_set_sampling was given %zu rows, this call has %d", c->sm_temp.size(), longform ? 1 : nb);
+    if (c->bm_on) return fail(c, WH_ERR_UNSUPPORTED, "decode: sampling with beam search is not supported (the search runs at temperature 0 only)");
+    if (c->rep_on) return fail(c, WH_ERR_UNSUPPORTED, "decode: sampling with repetition controls is not supported");
+    if (c->al_on) return fail(c, WH_ERR_UNSUPPORTED, "decode: sampling with word-level timestamps is not supported");
+    return WH_OK;
+}
+// every temperature 0 and every row active: the plain kernels are launched
+bool sample_trivial(const wh_ctx* c) {
+    for (size_t i = 0; i < c->sm_temp.size(); i++)
+        if (c->sm_temp[i] != 0.0f || !c->sm_active[i]) return false;
+    return true;
+}
+
 // ---- cross-KV + greedy loop for the nb clips whose encoder states are resident ------------------
 // run_decode (below) is a sequence of stages: plan_decode -> upload_token_state -> prepare_logits -> project_cross_kv -> the prompt
 // positions (launch_step, eagerly) -> run_token_loop (the captured step) -> read_back.
@@ -375,6 +393,7 @@ struct DecodePlan {
 int plan_decode(wh_ctx* c, int ncl, const wh_decode_params* p, bool want_logits, size_t logits_rows, const int32_t* sel, size_t n_sel, DecodePlan& pl) {
     const wh_dims& D = c->m->dims;
     if (int rc = beam_check(c, p, ncl)) return rc;
+    if (int rc = sample_check(c, ncl, c->pfx_win_base >= 0)) return rc;
     const int K = pl.K = c->bm_on ? c->bm_k : 1, nb = ncl * K;   // the rows of the device batch
     pl.ncl = ncl;
     const int P = pl.P = (int)p->n_prompt, NEW = pl.NEW = (int)p->max_new_tokens;
@@ -427,6 +446,7 @@ int plan_decode(wh_ctx* c, int ncl, const wh_decode_params* p, bool want_logits,
     if (c->rep_on) { key.rep = true; key.rep_p = c->rep_p; key.rep_n = c->rep_n; }
     if (c->al_on) { key.al_cap = NEW; key.al_gen = c->al_gen; }   // (prepare_alignment completes it with the side buffer's address)
     if (c->bm_on) { key.beam_k = c->bm_k; key.beam_c = c->bm_c; key.beam_buf = c->bm_buf; }
+    if (c->sm_on && !sample_trivial(c)) key.sample_buf = c->sm_buf;
     return WH_OK;
 }
 
@@ -450,6 +470,24 @@ int upload_token_state(wh_ctx* c, const wh_decode_params* p, const DecodePlan& p
     std::vector<int> nout(nb, pl.key.n_prompt);
     CTX_HIP(c, hipMemcpyAsync(c->n_out, nout.data(), nb * 4, hipMemcpyHostToDevice, s));
     CTX_HIP(c, hipMemsetAsync(c->done, 0, nb * 4, s));
+    std::vector<int> sm_done;
+    std::vector<float> sm_t;
+    std::vector<unsigned long long> sm_id;
+    if (pl.key.sample_buf) {   // this call's rows: temperatures, random streams, and the inactive rows start done (a long-form call: row 0 for every window, the window index as its id)
+        const bool lf = c->pfx_win_base >= 0;
+        sm_done.resize(nb); sm_t.resize(nb); sm_id.resize(nb);
+        for (int b = 0; b < nb; b++) {
+            sm_done[b] = c->sm_active[lf ? 0 : b] ? 0 : 1;
+            sm_t[b] = c->sm_temp[lf ? 0 : b];
+            sm_id[b] = lf ? (unsigned long long)(c->pfx_win_base + b) : (unsigned long long)c->sm_ids[b];
+        }
+        const unsigned long long seed = c->sm_seed;
+        CTX_HIP(c, hipMemcpyAsync(c->done, sm_done.data(), nb * 4, hipMemcpyHostToDevice, s));
+        CTX_HIP(c, hipMemcpyAsync(c->sm_d_temp, sm_t.data(), nb * 4, hipMemcpyHostToDevice, s));
+        CTX_HIP(c, hipMemcpyAsync(c->sm_d_ids, sm_id.data(), nb * 8, hipMemcpyHostToDevice, s));
+        CTX_HIP(c, hipMemcpyAsync(c->sm_d_seed, &seed, 8, hipMemcpyHostToDevice, s));
+        CTX_HIP(c, hipStreamSynchronize(s));   // (`seed` goes out of scope)
+    }
     CTX_HIP(c, hipMemsetAsync(c->pos, 0, 4, s));
     CTX_HIP(c, hipMemsetAsync(c->step_ticket, 0, 4, s));
     if (c->rep_on) CTX_HIP(c, hipMemsetAsync(c->rep_bits, 0, (size_t)nb * c->rep_words * 4, s));   // no history yet: nothing is touched
@@ -786,6 +824,7 @@ struct Step {
     // final LN ∘ tied LM head + masked argmax; the finish kernel records the token, advances the position and embeds the next one
     void emit() const {
         if (k.beam_k) return emit_beam();
+        if (k.sample_buf) return emit_sample();
         int lm_parts;
         {
             Prof pr(c, WH_KG_DEC_GEMM);
@@ -855,6 +894,37 @@ struct Step {
         if (tm) hipEventRecord(te[1], s);
         wh_launch_beam_reorder(s, (int)m->esz, c->self_k, c->self_v, c->bm_parent, c->done, k.beam_k, ncl, D.dec_layers, D.n_heads, D.n_text_ctx, c->pos, c->step_ticket);
         if (tm) { hipEventRecord(te[2], s); c->bm_events.push_back(te); }
+    }
+
+    // Temperature sampling: the LM head leaves the rows' raw logits of this position in the scratch (its argmax partials are not
+    // read; k_argmax_finish is not launched); k_sample_select chooses every row's token, does the finish kernel's bookkeeping, embeds the next
+    // position and advances.  One chain, no parallel branches.
+    void emit_sample() const {
+        {
+            Prof pr(c, WH_KG_DEC_GEMM);
+            SkinnyArgs a = lm_head_common();
+            a.mask_first = c->mask_first; a.mask_base = c->mask_base;
+            a.logits = c->sm_logits; a.logits_rows = 1; a.logits_cur = true;
+            wh_launch_lm_head(s, prec, a);
+        }
+        Prof pr(c, WH_KG_DEC_OTHER);
+        SampleArgs a;
+        a.logits = c->sm_logits; a.vocab = D.vocab; a.mask_first = c->mask_first; a.mask_base = c->mask_base;
+        if (rules) { a.ts_begin = k.ts_begin; a.ts_max_init = k.ts_max_init; a.ts_state = c->sm_state; }
+        a.temperature = c->sm_d_temp; a.row_ids = c->sm_d_ids; a.seed = c->sm_d_seed;
+        a.logits_out = k.d_logits; a.logits_rows = k.logits_rows; a.logits_sel = k.d_sel;
+        DecodeState st;
+        st.feed = c->feed; st.out_tokens = c->out_tokens; st.n_out = c->n_out; st.done = c->done;
+        st.forced = c->forced; st.n_forced = k.n_forced; st.n_prompt = k.n_prompt; st.eot = k.eot; st.tok_ld = c->tok_ld;
+        st.logprob = c->sm_lp;
+        NextEmbed ne;
+        ne.tok_emb = m->tok_emb; ne.pos_emb = m->dec_pos; ne.x = c->dx; ne.xslab = c->dxs; ne.stats = c->lnpart;
+        ne.xgamma = f8 ? m->dec[0].ln1_w : nullptr; ne.d = (int)d; ne.mpad = mpad; ne.shift = c->dshift; ne.off = d_off;
+        const bool tm = c->sm_timing && !c->capturing;   // (measurement runs only: positions launched eagerly)
+        std::array<hipEvent_t, 2> te = {nullptr, nullptr};
+        if (tm) { for (auto& e : te) hipEventCreate(&e); hipEventRecord(te[0], s); }
+        wh_launch_sample_select(s, prec, a, st, ne, nb, c->pos, c->step_ticket);
+        if (tm) { hipEventRecord(te[1], s); c->sm_events.push_back(te); }
     }
 
     // the listed ids' unfiltered logits of this prompt position -> each row's language token in column tok_col of the next one; the
@@ -984,7 +1054,7 @@ int read_back(wh_ctx* c, const DecodePlan& pl, int64_t* tokens_out, size_t tok_s
     hipStream_t s = c->stream;
     const int nb = pl.key.nb, ld = c->tok_ld, Nmax = pl.Nmax, PP = pl.key.n_prompt, vocab = c->m->dims.vocab;
     const size_t logits_rows = pl.key.logits_rows;
-    const bool lp = c->lp_on;
+    const bool lp = c->lp_on || pl.key.sample_buf;   // (a sampling call records log-probabilities itself, in its own buffer)
     const size_t n_lang = c->lang_ids.size();
     std::vector<int> toks, nout, lch, afr, asb;
     std::vector<float> lps, nsp, lpr;
@@ -995,7 +1065,7 @@ int read_back(wh_ctx* c, const DecodePlan& pl, int64_t* tokens_out, size_t tok_s
     };
     CTX_HIP(c, fetch(toks, c->out_tokens, (size_t)nb * ld));
     CTX_HIP(c, fetch(nout, c->n_out, nb));
-    if (lp) CTX_HIP(c, fetch(lps, c->lp_tok, (size_t)nb * ld));
+    if (lp) CTX_HIP(c, fetch(lps, pl.key.sample_buf ? c->sm_lp : c->lp_tok, (size_t)nb * ld));
     if (pl.lp_probe) CTX_HIP(c, fetch(nsp, c->lp_ns, nb));
     if (pl.lang_det) {
         CTX_HIP(c, fetch(lch, c->lang_chosen, nb));
@@ -1007,6 +1077,15 @@ int read_back(wh_ctx* c, const DecodePlan& pl, int64_t* tokens_out, size_t tok_s
     }
     CTX_HIP(c, hipStreamSynchronize(s));
     CTX_HIP(c, hipGetLastError());
+    c->sm_ms = 0;
+    c->sm_timed = (long)c->sm_events.size();
+    for (auto& te : c->sm_events) {
+        float ms = 0;
+        hipEventElapsedTime(&ms, te[0], te[1]);
+        c->sm_ms += ms;
+        for (auto& e : te) hipEventDestroy(e);
+    }
+    c->sm_events.clear();
     if (c->al_on) {   // kept for wh_get_token_frames / wh_get_alignment_debug
         const int tc = c->m->dims.n_text_ctx, nh = (int)(c->al_heads.size() / 2), Sp = (c->m->dims.n_audio_ctx + 3) / 4 * 4, NEW = pl.NEW;
         for (int b = 0; b < nb; b++) {
@@ -1297,6 +1376,9 @@ int check_params(wh_ctx* c, const wh_decode_params* p) {
     for (auto& te : c->bm_events)   // (timing events of a call that failed before its read-back)
         for (auto& e : te) hipEventDestroy(e);
     c->bm_events.clear();
+    for (auto& te : c->sm_events)
+        for (auto& e : te) hipEventDestroy(e);
+    c->sm_events.clear();
     if (!p) return fail(c, WH_ERR_ARG, "decode params are NULL");
     if ((p->n_suppress && !p->suppress) || (p->n_begin_suppress && !p->begin_suppress) || (p->n_forced && !p->forced))
         return fail(c, WH_ERR_ARG, "decode params: NULL list with non-zero length");
@@ -1435,6 +1517,7 @@ static int ctx_create_impl(wh_model* m, const wh_ctx_opts* opts, wh_ctx** out) {
     c->sync_every_pos = getenv("WH_SYNC_EVERY_POS") != nullptr;
     c->al_timing = getenv("WH_ALIGN_TIMING") != nullptr;
     c->bm_timing = getenv("WH_BEAM_TIMING") != nullptr;
+    c->sm_timing = getenv("WH_SAMPLE_TIMING") != nullptr;
     const wh_dims& D = m->dims;
     const size_t B = max_batch, d = D.d_model, S = D.n_audio_ctx, F = D.ffn, C = D.n_mels, esz = m->esz;
     const size_t Ld = D.dec_layers, H = D.n_heads, TC = D.n_text_ctx;
@@ -1961,6 +2044,58 @@ int wh_ctx_set_beam_search(wh_ctx* c, const wh_beam_opts* o) {
     return WH_OK;
 }
 
+// Temperature sampling on every decode entry of the ctx.  The logits scratch and the per-row buffers are allocated when the option
+// is turned on and freed when it is cleared; the captured decode step is keyed on the buffers' identity and dropped before they are freed.  The
+// per-row values reach the kernel through those buffers (upload_token_state), so another rung of a ladder replays the same captured step.
+static void sample_release(wh_ctx* c) {
+    if (c->sm_logits || c->sm_buf) drop_step_graph(c);   // (a captured step may hold the buffers' addresses)
+    if (c->sm_logits) hipFree(c->sm_logits);
+    if (c->sm_buf) hipFree(c->sm_buf);
+    c->sm_logits = nullptr; c->sm_buf = nullptr;
+    c->sm_on = false;
+    c->sm_temp.clear(); c->sm_active.clear(); c->sm_ids.clear();
+}
+int wh_ctx_set_sampling(wh_ctx* c, const wh_sampling_opts* o) {
+    if (!c) return WH_ERR_ARG;
+    if (!o) {
+        hipSetDevice(c->m->device);
+        sample_release(c);
+        return WH_OK;
+    }
+    if (o->struct_size != sizeof(wh_sampling_opts)) return fail(c, WH_ERR_ARG, "wh_ctx_set_sampling: struct_size %zu, expected %zu", o->struct_size, sizeof(wh_sampling_opts));
+    if (o->n_rows < 1 || o->n_rows > (size_t)c->max_batch || !o->temperature)
+        return fail(c, WH_ERR_ARG, "wh_ctx_set_sampling: n_rows %zu outside 1 .. max_batch (%d) (or a NULL temperature list)", o->n_rows, c->max_batch);
+    for (size_t i = 0; i < o->n_rows; i++)
+        if (!std::isfinite(o->temperature[i]) || o->temperature[i] < 0.0f)
+            return fail(c, WH_ERR_ARG, "wh_ctx_set_sampling: temperature[%zu] = %g is negative or not finite", i, (double)o->temperature[i]);
+    if (!c->sm_logits) {
+        auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+        const size_t B = (size_t)c->max_batch, vocab = (size_t)c->m->dims.vocab, TL = (size_t)c->tok_ld;
+        const size_t b_t = up(B * 4), b_id = up(B * 8), b_seed = up(8), b_state = up(B * 16), b_lp = up(B * TL * 4);
+        float* lg = (float*)setter_alloc(c, "wh_ctx_set_sampling", B * vocab * 4);
+        char* buf = (char*)(lg ? setter_alloc(c, "wh_ctx_set_sampling", b_t + b_id + b_seed + b_state + b_lp) : nullptr);
+        if (!buf) {
+            if (lg) hipFree(lg);
+            return WH_ERR_NOMEM;
+        }
+        c->sm_logits = lg; c->sm_buf = buf;
+        char* q = buf;
+        c->sm_d_ids = (unsigned long long*)q; q += b_id;
+        c->sm_d_seed = (unsigned long long*)q; q += b_seed;
+        c->sm_d_temp = (float*)q; q += b_t;
+        c->sm_state = (int*)q; q += b_state;
+        c->sm_lp = (float*)q;
+    }
+    c->sm_on = true;
+    c->sm_seed = o->seed;
+    c->sm_temp.assign(o->temperature, o->temperature + o->n_rows);
+    c->sm_active.assign(o->n_rows, 1);
+    if (o->active) c->sm_active.assign(o->active, o->active + o->n_rows);
+    c->sm_ids.resize(o->n_rows);
+    for (size_t i = 0; i < o->n_rows; i++) c->sm_ids[i] = o->row_ids ? o->row_ids[i] : (uint64_t)i;
+    return WH_OK;
+}
+
 int wh_get_beams(const wh_ctx* c, int64_t* tokens, size_t cap_tokens, size_t* n_tokens, float* sum_logprob, float* rank_score, int32_t* finished,
                  size_t cap_hyp, size_t* n_hyp, size_t cap_clips, size_t* n_clips_out) {
     if (!c) return WH_ERR_ARG;
@@ -2111,6 +2246,10 @@ void wh_ctx_free(wh_ctx* c) {
     if (c->bm_buf) hipFree(c->bm_buf);
     for (auto& te : c->bm_events)
         for (auto& e : te) hipEventDestroy(e);
+    if (c->sm_logits) hipFree(c->sm_logits);
+    if (c->sm_buf) hipFree(c->sm_buf);
+    for (auto& te : c->sm_events)
+        for (auto& e : te) hipEventDestroy(e);
     if (c->s_copy) { hipStreamSynchronize(c->s_copy); hipStreamDestroy(c->s_copy); }
     if (c->ev_h2d) hipEventDestroy(c->ev_h2d);
     if (c->pcm2) hipFree(c->pcm2);
@@ -2142,6 +2281,15 @@ extern "C" int wh_debug_beam_times(const wh_ctx* c, double* ms2, long* positions
     if (!c || !ms2 || !positions || !c->bm_timing) return WH_ERR_ARG;
     ms2[0] = c->bm_ms[0]; ms2[1] = c->bm_ms[1];
     *positions = c->bm_timed;
+    return WH_OK;
+}
+
+// measurement hook (tools/sample_bench.py; not in the public header): milliseconds of k_sample_select of the last call, summed over the positions
+// that were launched eagerly (their count in *positions) — filled when the context was created under WH_SAMPLE_TIMING=1
+extern "C" int wh_debug_sample_times(const wh_ctx* c, double* ms, long* positions) {
+    if (!c || !ms || !positions || !c->sm_timing) return WH_ERR_ARG;
+    *ms = c->sm_ms;
+    *positions = c->sm_timed;
     return WH_OK;
 }
 
@@ -2301,7 +2449,7 @@ int wh_decode_greedy(wh_ctx* c, const wh_decode_params* p, int64_t* tokens_out, 
         return fail(c, WH_ERR_ARG, "wh_decode_greedy: logits_out holds one row's logits, beam search has %d rows per clip; use wh_decode_greedy_rows", c->bm_k);
     rc = prefix_check(c, p, 1, false);
     if (rc) return rc;
-    if ((rc = align_check(c, 1)) || (rc = beam_check(c, p, 1))) return rc;
+    if ((rc = align_check(c, 1)) || (rc = beam_check(c, p, 1)) || (rc = sample_check(c, 1, false))) return rc;
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -2328,7 +2476,7 @@ int wh_decode_greedy_batch(wh_ctx* c, const wh_decode_params* p, int64_t* tokens
         return fail(c, WH_ERR_ARG, "wh_decode_greedy_batch: with beam search logits_out holds %d clips x %d beams: cap_clips must be at least %d", nb, c->bm_k, nb * c->bm_k);
     rc = prefix_check(c, p, nb, false);
     if (rc) return rc;
-    if ((rc = align_check(c, nb)) || (rc = beam_check(c, p, nb))) return rc;
+    if ((rc = align_check(c, nb)) || (rc = beam_check(c, p, nb)) || (rc = sample_check(c, nb, false))) return rc;
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -2354,7 +2502,7 @@ int wh_decode_greedy_rows(wh_ctx* c, const wh_decode_params* p, const int32_t* r
     if (cap_logits_rows < p->max_new_tokens) return fail(c, WH_ERR_ARG, "logits_out needs max_new_tokens rows per selected clip");
     rc = prefix_check(c, p, nb, false);
     if (rc) return rc;
-    if ((rc = align_check(c, nb)) || (rc = beam_check(c, p, nb))) return rc;
+    if ((rc = align_check(c, nb)) || (rc = beam_check(c, p, nb)) || (rc = sample_check(c, nb, false))) return rc;
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -2416,7 +2564,7 @@ int wh_transcribe_batch(wh_ctx* c, const wh_clip* clips, size_t n_clips, const w
     if (n_clips == 0 || n_clips > (size_t)c->max_batch) return fail(c, WH_ERR_ARG, "n_clips must be 1..max_batch (%d)", c->max_batch);
     rc = prefix_check(c, p, (int)n_clips, false);
     if (rc) return rc;
-    if ((rc = align_check(c, (int)n_clips)) || (rc = beam_check(c, p, (int)n_clips))) return rc;
+    if ((rc = align_check(c, (int)n_clips)) || (rc = beam_check(c, p, (int)n_clips)) || (rc = sample_check(c, (int)n_clips, false))) return rc;
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
@@ -2464,7 +2612,7 @@ int wh_transcribe_batch_next(wh_ctx* c, const wh_clip* clips, size_t n_clips, co
     if (n_clips == 0 || n_clips > (size_t)c->max_batch) return fail(c, WH_ERR_ARG, "n_clips must be 1..max_batch (%d)", c->max_batch);
     rc = prefix_check(c, p, (int)n_clips, false);
     if (rc) return rc;
-    if ((rc = align_check(c, (int)n_clips)) || (rc = beam_check(c, p, (int)n_clips))) return rc;
+    if ((rc = align_check(c, (int)n_clips)) || (rc = beam_check(c, p, (int)n_clips)) || (rc = sample_check(c, (int)n_clips, false))) return rc;
     if (next_clips && (n_next == 0 || n_next > (size_t)c->max_batch)) return fail(c, WH_ERR_ARG, "n_next must be 1..max_batch (%d)", c->max_batch);
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
@@ -2529,7 +2677,7 @@ int wh_transcribe_batch_device_next(wh_ctx* c, const float* d_pcm, size_t n_clip
     if (n_clips == 0 || n_clips > (size_t)c->max_batch) return fail(c, WH_ERR_ARG, "n_clips must be 1..max_batch (%d)", c->max_batch);
     rc = prefix_check(c, p, (int)n_clips, false);
     if (rc) return rc;
-    if ((rc = align_check(c, (int)n_clips)) || (rc = beam_check(c, p, (int)n_clips))) return rc;
+    if ((rc = align_check(c, (int)n_clips)) || (rc = beam_check(c, p, (int)n_clips)) || (rc = sample_check(c, (int)n_clips, false))) return rc;
     if (d_pcm_next && (n_clips_next == 0 || n_clips_next > (size_t)c->max_batch))
         return fail(c, WH_ERR_ARG, "n_clips_next must be 1..max_batch (%d)", c->max_batch);
     CTX_HIP(c, hipSetDevice(c->m->device));
@@ -2588,7 +2736,7 @@ int wh_transcribe_longform(wh_ctx* c, const float* pcm, size_t n_samples, double
         wh_longform_plan(n_samples, chunk_length_s, overlap_s, nullptr, 0, &nw);
         if ((rc = align_check(c, nw ? (int)(nw - (nw - 1) / c->max_batch * c->max_batch) : 1))) return rc;
     }
-    if ((rc = beam_check(c, p, 1))) return rc;
+    if ((rc = beam_check(c, p, 1)) || (rc = sample_check(c, 1, true))) return rc;
     const size_t win_batch = (size_t)(c->bm_on ? c->max_batch / c->bm_k : c->max_batch);   // windows per device batch (beam search: K rows each)
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);

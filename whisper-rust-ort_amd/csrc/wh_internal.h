@@ -221,7 +221,8 @@ struct wh_ctx {
         unsigned al_gen = 0;
         int beam_k = 0, beam_c = 0;            // beam search: beam_k 0 = off; nb then counts rows = clips x beam_k.  beam_buf: the identity of the
         const void* beam_buf = nullptr;        // setter's buffers (logits scratch and search state: one allocation each, freed together)
-        auto members() const { return std::tie(nb, n_prompt, eot, n_forced, logits_rows, d_logits, d_sel, ts_begin, ts_max_init, lp_sum, pfx, rep, rep_p, rep_n, al_q, al_cap, al_gen, beam_k, beam_c, beam_buf); }
+        const void* sample_buf = nullptr;      // temperature sampling: nullptr = off; the identity of the setter's buffers (the per-row values are read through them)
+        auto members() const { return std::tie(nb, n_prompt, eot, n_forced, logits_rows, d_logits, d_sel, ts_begin, ts_max_init, lp_sum, pfx, rep, rep_p, rep_n, al_q, al_cap, al_gen, beam_k, beam_c, beam_buf, sample_buf); }
         bool operator==(const StepKey& o) const { return members() == o.members(); }
     } step_key;
     // Whisper's timestamp rules (wh_ctx_set_timestamp_rules): off unless ts_on.  The timestamp logits and the per-row state
@@ -335,6 +336,25 @@ struct wh_ctx {
     bool bm_have = false;
     std::vector<std::vector<BeamHyp>> bm_hyps;
     std::vector<BeamTrace> bm_traces;
+    // Temperature sampling (wh_ctx_set_sampling): off unless sm_on.  The logits scratch and the per-row values are allocated by
+    // the setter (not part of the workspace carve) and freed when the option is cleared and in wh_ctx_free; the captured step is dropped before
+    // that.  The setter keeps the caller's lists; upload_token_state writes each call's rows to the device.
+    bool sm_on = false;
+    uint64_t sm_seed = 0;
+    std::vector<float> sm_temp;            // [n_rows]
+    std::vector<uint8_t> sm_active;        // [n_rows]
+    std::vector<uint64_t> sm_ids;          // [n_rows]
+    float* sm_logits = nullptr;            // [max_batch][vocab] raw logits of the current position
+    char* sm_buf = nullptr;                // carved into:
+    float* sm_d_temp = nullptr;            // [max_batch]
+    unsigned long long* sm_d_ids = nullptr;    // [max_batch]
+    unsigned long long* sm_d_seed = nullptr;   // [1]
+    int* sm_state = nullptr;               // [max_batch][4] rule state of each row
+    float* sm_lp = nullptr;                // [max_batch][tok_ld] DecodeState::logprob of a sampling call
+    bool sm_timing = false;                // WH_SAMPLE_TIMING=1: events around k_sample_select of every eagerly launched position (tools/sample_bench.py)
+    std::vector<std::array<hipEvent_t, 2>> sm_events;
+    double sm_ms = 0;                      // k_sample_select of the last call, milliseconds, over sm_timed positions
+    long sm_timed = 0;
     hipGraph_t step_graph = nullptr;
     hipGraphExec_t step_exec = nullptr;
 };

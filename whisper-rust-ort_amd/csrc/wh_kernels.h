@@ -405,6 +405,25 @@ void wh_launch_beam_select(hipStream_t s, int prec, const BeamArgs& a, const Nex
 void wh_launch_beam_reorder(hipStream_t s, int esz, void* kc, void* vc, const int* parent, const int* done, int K, int n_clips, int layers, int n_heads, int tc,
                             int* pos_p, int* ticket);
 
+// Temperature sampling (wh_sample.hip): k_sample_select, one workgroup per batch row, chooses the row's token from the
+// current position's raw logits and does what k_argmax_finish does after its reduce.  The per-call values are read through pointers, so a
+// captured step serves every rung of a temperature ladder.
+struct SampleArgs {
+    const float* logits = nullptr;      // [rows][vocab] raw logits of the current position (SkinnyArgs::logits with logits_cur)
+    int vocab = 0;
+    const unsigned* mask_first = nullptr;
+    const unsigned* mask_base = nullptr;
+    int ts_begin = -1, ts_max_init = -1;   // timestamp rules: ts_begin < 0 = off
+    int* ts_state = nullptr;            // [rows][4] {text_lo, ts_lo, ts_hi, last timestamp}, as TsFinish::state
+    const float* temperature = nullptr; // [rows]
+    const unsigned long long* row_ids = nullptr;   // [rows]
+    const unsigned long long* seed = nullptr;      // [1]
+    float* logits_out = nullptr;        // parity harness: SkinnyArgs::logits / logits_rows / logits_sel of a greedy call, filled by this kernel
+    int logits_rows = 0;
+    const int* logits_sel = nullptr;
+};
+void wh_launch_sample_select(hipStream_t s, int prec, const SampleArgs& a, const DecodeState& st, const NextEmbed& ne, int rows, int* pos_p, int* ticket);
+
 extern int wh_dbg_cross_unroll;
 extern int wh_dbg_lm_blocks_per_cu;
 extern int wh_dbg_mt;

@@ -3,6 +3,8 @@
 // serde_json / the csv crate, WAV reader + linear resampler, prompt ids, token → text fallback and
 // byte-level BPE decode, long-form stitcher.  Citations: /root/reference/src/main.rs.
 #pragma once
+#include <dlfcn.h>
+
 #include <algorithm>
 #include <cctype>
 #include <cmath>
@@ -164,6 +166,8 @@ struct RowOut {
     std::string language;
     double language_probability = 0;
     std::string hypotheses;   // --beam-size N >= 2: JSON array of the n best {text, sum_logprob, rank_score, finished}; empty: no key
+    bool has_ladder = false;  // --temperature with a ladder other than the single rung 0: the rung that produced the row and its compression ratio
+    double temperature = 0, compression_ratio = 0;
     bool has_prompt = false;  // --prompt-ids / --prompt-ids-dir: the length of the file's text context (<|startofprev|> included; 0: none)
     long long prompt_tokens = 0;
 };
@@ -174,6 +178,17 @@ inline std::string fmt_conf(double v) {
     if (!std::isfinite(v)) return "null";
     char b[48];
     snprintf(b, sizeof b, "%.9g", v);
+    return b;
+}
+
+// a float as the shortest decimal text that reads back as the same float (0.2f -> "0.2")
+inline std::string fmt_f32(float v) {
+    if (!std::isfinite(v)) return "null";
+    char b[48];
+    for (int p = 1; p <= 9; p++) {
+        snprintf(b, sizeof b, "%.*g", p, (double)v);
+        if (strtof(b, nullptr) == v) break;
+    }
     return b;
 }
 
@@ -228,6 +243,7 @@ inline std::string per_file_json(const std::vector<RowOut>& rows) {  // :1232 to
         if (rows[i].has_lang) { JVal v; v.raw = fmt_conf(rows[i].language_probability); r.set("language", JVal::str(rows[i].language)).set("language_probability", v); }
         if (rows[i].has_prompt) r.set("prompt_tokens", JVal::integer(rows[i].prompt_tokens));
         if (rows[i].has_conf) { JVal v; v.raw = fmt_conf(rows[i].avg_logprob); r.set("avg_logprob", v); v.raw = fmt_conf(rows[i].no_speech_prob); r.set("no_speech_prob", v); }
+        if (rows[i].has_ladder) { JVal v; v.raw = fmt_f32((float)rows[i].temperature); r.set("temperature", v); v.raw = fmt_conf(rows[i].compression_ratio); r.set("compression_ratio", v); }
         if (!rows[i].segments.empty()) { JVal sg; sg.raw = rows[i].segments; r.set("segments", sg); }
         if (!rows[i].hypotheses.empty()) { JVal h; h.raw = rows[i].hypotheses; r.set("hypotheses", h); }
         if (!rows[i].words.empty()) { JVal w; w.raw = rows[i].words; r.set("words", w); w.raw = rows[i].token_times; r.set("token_times", w); }
@@ -243,6 +259,7 @@ struct OrtCfg {  // :91-100 — CPU-EP knobs: accepted and echoed only, they hav
     std::string execution_mode = "SEQUENTIAL", graph_opt = "ENABLE_ALL";
     bool cpu_mem_arena = true, mem_pattern = true, allow_spinning = true;
     long long beam_size = 1;   // additive (no reference counterpart: the reference is greedy): echoed only when >= 2, so a greedy run's config_used keeps the reference's keys
+    std::vector<float> temperature;   // additive: the temperature ladder, echoed only when it is not the single rung 0 (left empty then)
     JVal json(bool sorted) const {
         JVal j = JVal::obj(sorted);
         j.set("intra_op", JVal::integer(intra_op)).set("inter_op", JVal::integer(inter_op))
@@ -250,6 +267,13 @@ struct OrtCfg {  // :91-100 — CPU-EP knobs: accepted and echoed only, they hav
             .set("cpu_mem_arena", JVal::boolean(cpu_mem_arena)).set("mem_pattern", JVal::boolean(mem_pattern))
             .set("allow_spinning", JVal::boolean(allow_spinning));
         if (beam_size >= 2) j.set("beam_size", JVal::integer(beam_size));
+        if (!temperature.empty()) {
+            JVal t;
+            t.raw = "[";
+            for (size_t i = 0; i < temperature.size(); i++) t.raw += (i ? ", " : "") + fmt_f32(temperature[i]);
+            t.raw += "]";
+            j.set("temperature", t);
+        }
         return j;
     }
 };
@@ -527,6 +551,90 @@ inline bool skip_window(double no_speech_prob, double avg_lp, double no_speech_t
     if (std::isnan(no_speech_threshold) || !(no_speech_prob > no_speech_threshold)) return false;
     return std::isnan(logprob_threshold) || avg_lp < logprob_threshold;
 }
+// ---- the temperature ladder (openai-whisper's decode_with_fallback; --temperature) ----------------------------------------------------------
+// zlib, loaded by its soname at the first use (the development symlink libz.so is not needed): compress2, compressBound, zlibVersion
+struct Zlib {
+    typedef int (*compress2_t)(unsigned char*, unsigned long*, const unsigned char*, unsigned long, int);
+    typedef unsigned long (*bound_t)(unsigned long);
+    typedef const char* (*version_t)();
+    compress2_t compress2 = nullptr;
+    bound_t bound = nullptr;
+    version_t version = nullptr;
+    static const Zlib& get() {
+        static const Zlib z = [] {
+            Zlib r;
+            void* h = dlopen("libz.so.1", RTLD_NOW | RTLD_GLOBAL);
+            if (!h) throw std::runtime_error(std::string("compression_ratio needs zlib: dlopen(\"libz.so.1\") failed: ") + dlerror());
+            r.compress2 = (compress2_t)dlsym(h, "compress2");
+            r.bound = (bound_t)dlsym(h, "compressBound");
+            r.version = (version_t)dlsym(h, "zlibVersion");
+            if (!r.compress2 || !r.bound || !r.version) throw std::runtime_error("compression_ratio needs zlib: libz.so.1 lacks compress2 / compressBound / zlibVersion");
+            return r;
+        }();
+        return z;
+    }
+};
+// bytes of zlib's compress2 of `text` at the default level (Python's zlib.compress(text))
+inline size_t zlib_compressed_size(const std::string& text) {
+    const Zlib& z = Zlib::get();
+    unsigned long n = z.bound((unsigned long)text.size());
+    std::vector<unsigned char> out(n);
+    const int rc = z.compress2(out.data(), &n, (const unsigned char*)text.data(), (unsigned long)text.size(), -1);   // Z_DEFAULT_COMPRESSION
+    if (rc != 0) throw std::runtime_error("zlib compress2 failed: " + std::to_string(rc));
+    return (size_t)n;
+}
+// openai-whisper's compression_ratio: byte length / compressed byte length
+inline double compression_ratio(const std::string& text) { return (double)text.size() / (double)zlib_compressed_size(text); }
+// openai-whisper's fallback decision for one window: too repetitive (compression ratio above its threshold) or too unlikely (avg_logprob
+// below its threshold) — unless the window counts as silence (no_speech_prob above its threshold).  A NaN threshold is off, as in skip_window.
+inline bool needs_fallback(double cr, double avg_lp, double no_speech_prob, double cr_thr, double lp_thr, double ns_thr) {
+    bool need = (!std::isnan(cr_thr) && cr > cr_thr) || (!std::isnan(lp_thr) && avg_lp < lp_thr);
+    if (!std::isnan(ns_thr) && no_speech_prob > ns_thr) need = false;
+    return need;
+}
+// The ladder over the n windows of one device batch.  decode(rung, active, scores) decodes the windows with active[w] != 0 at temperatures[rung]
+// (rung 0: every window) and fills their scores; a window that needs a fallback is decoded again at the next rung, the others keep their
+// result; after the last rung the last result stands.  rung_of[w] = the rung that produced window w's result.
+struct WindowScore { double compression_ratio = 0, avg_logprob = 0, no_speech_prob = 0; };
+template <typename Decode>
+inline void run_ladder(size_t n, size_t n_rungs, double cr_thr, double lp_thr, double ns_thr, Decode&& decode, std::vector<int>& rung_of, std::vector<WindowScore>& scores) {
+    rung_of.assign(n, 0);
+    scores.assign(n, WindowScore());
+    std::vector<unsigned char> active(n, 1);
+    for (size_t r = 0; r < n_rungs; r++) {
+        bool any = false;
+        for (size_t w = 0; w < n; w++) any = any || active[w];
+        if (!any) break;
+        decode(r, active, scores);
+        for (size_t w = 0; w < n; w++) {
+            if (!active[w]) continue;
+            rung_of[w] = (int)r;
+            active[w] = needs_fallback(scores[w].compression_ratio, scores[w].avg_logprob, scores[w].no_speech_prob, cr_thr, lp_thr, ns_thr) ? 1 : 0;
+        }
+    }
+}
+inline std::string trim_ascii(const std::string& s) {
+    size_t a = 0, b = s.size();
+    while (a < b && isspace((unsigned char)s[a])) a++;
+    while (b > a && isspace((unsigned char)s[b - 1])) b--;
+    return s.substr(a, b - a);
+}
+// "0,0.2,0.4": the rungs of --temperature; each finite and >= 0, at least one
+inline std::vector<float> parse_temperatures(const std::string& txt) {
+    std::vector<float> out;
+    size_t i = 0;
+    while (i <= txt.size()) {
+        const size_t j = std::min(txt.find(',', i), txt.size());
+        const std::string w = trim_ascii(txt.substr(i, j - i));
+        char* e = nullptr;
+        const float f = strtof(w.c_str(), &e);
+        if (w.empty() || *e || !std::isfinite(f) || f < 0.0f) throw std::runtime_error("--temperature: '" + w + "' is not a finite value >= 0");
+        out.push_back(f);
+        i = j + 1;
+    }
+    return out;
+}
+
 inline void set_conf(std::vector<Segment>& segs, double avg_lp, double no_speech_prob) {
     for (Segment& s : segs) { s.has_conf = true; s.avg_logprob = avg_lp; s.no_speech_prob = no_speech_prob; }
 }

@@ -251,4 +251,64 @@ int whh_pipeline_selftest(size_t nfiles, int n_loaders, size_t n_workers, size_t
         if (seen[i] != 1) { put("file " + std::to_string(i) + " processed " + std::to_string(seen[i]) + " times", err, cap); return 2; }
     return 0;
 }
+
+// ---- the temperature ladder (tests/test_sample_cpu.py) ----
+// compression_ratio of n bytes; *compressed (optional) = the compressed length.  Returns NaN with the message in err when zlib is missing.
+double whh_compression_ratio(const char* text, size_t n, size_t* compressed, char* err, size_t cap) {
+    try {
+        const std::string s(text, n);
+        if (compressed) *compressed = zlib_compressed_size(s);
+        return compression_ratio(s);
+    } catch (const std::exception& e) {
+        put(e.what(), err, cap);
+        return std::nan("");
+    }
+}
+size_t whh_zlib_version(char* out, size_t cap) {
+    try { return put(Zlib::get().version(), out, cap); } catch (const std::exception&) { return 0; }
+}
+int whh_needs_fallback(double cr, double avg_lp, double no_speech_prob, double cr_thr, double lp_thr, double ns_thr) {
+    return needs_fallback(cr, avg_lp, no_speech_prob, cr_thr, lp_thr, ns_thr) ? 1 : 0;
+}
+// run_ladder over a scripted decoder: script [n_rungs][n][3] = {compression_ratio, avg_logprob, no_speech_prob} a window would score at a rung.
+// rung_of [n]; decoded [n_rungs][n]: 1 where the window was decoded at that rung.
+void whh_run_ladder(size_t n, size_t n_rungs, const double* script, double cr_thr, double lp_thr, double ns_thr, int* rung_of, unsigned char* decoded) {
+    std::vector<int> ro;
+    std::vector<WindowScore> sc;
+    memset(decoded, 0, n * n_rungs);
+    run_ladder(n, n_rungs, cr_thr, lp_thr, ns_thr,
+               [&](size_t r, const std::vector<unsigned char>& active, std::vector<WindowScore>& scores) {
+                   for (size_t w = 0; w < n; w++) {
+                       if (!active[w]) continue;
+                       decoded[r * n + w] = 1;
+                       const double* s = script + (r * n + w) * 3;
+                       scores[w] = WindowScore{s[0], s[1], s[2]};
+                   }
+               },
+               ro, sc);
+    for (size_t w = 0; w < n; w++) rung_of[w] = ro[w];
+}
+// parse_temperatures: the count (out: up to cap values), or -1 with the message in err
+long whh_parse_temperatures(const char* txt, float* out, size_t cap, char* err, size_t ecap) {
+    try {
+        const std::vector<float> t = parse_temperatures(txt);
+        for (size_t i = 0; i < t.size() && i < cap; i++) out[i] = t[i];
+        return (long)t.size();
+    } catch (const std::exception& e) {
+        put(e.what(), err, ecap);
+        return -1;
+    }
+}
+// per_file_json of one row, with (ladder != 0) or without the ladder's keys
+size_t whh_ladder_row_json(const char* file, const char* text, double temperature, double cr, int ladder, char* out, size_t cap) {
+    RowOut r = make_row(file, 1.0, 1.0, text);
+    r.has_ladder = ladder != 0; r.temperature = temperature; r.compression_ratio = cr;
+    return put(per_file_json({r}), out, cap);
+}
+// config_used of a ladder (n == 0: none)
+size_t whh_ladder_config_json(const float* temps, size_t n, char* out, size_t cap) {
+    OrtCfg c;
+    c.temperature.assign(temps, temps + n);
+    return put(c.json(true).pretty(), out, cap);
+}
 }

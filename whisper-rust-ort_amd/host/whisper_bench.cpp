@@ -61,6 +61,11 @@ struct Args {
     // additive: beam search (wh_ctx_set_beam_search).  --beam-size 1 is the greedy path with the option not set
     int beam_size = 1, n_best = 1;
     float patience = 1.0f, length_penalty = -1.0f;
+    // additive: the temperature ladder (wh_ctx_set_sampling; openai-whisper's decode_with_fallback).  The single rung 0 is the greedy path with the
+    // option not set; --seed also seeds the sampler
+    std::vector<float> temperature = {0.0f};
+    double compression_ratio_threshold = std::nan("");
+    bool ladder() const { return temperature.size() > 1 || temperature[0] != 0.0f; }
     bool beam() const { return beam_size >= 2; }
     bool prompts() const { return !prompt_ids.empty() || !prompt_ids_dir.empty(); }
 };
@@ -132,7 +137,16 @@ static bool parse_args(int argc, char** argv, Args& a) {
                    "[--device 0] [--devices 0-7] [--streams-per-gpu 1] [--load-threads N] [--precision bf16|f32|fp8|f16x3] [--max-batch 16] "
                    "[--synthetic-clips N] [--seed 1000] [--print-plan] [--timestamp-rules] [--write-srt] [--write-vtt] "
                    "[--logprobs] [--no-speech-threshold X] [--logprob-threshold Y] [--prompt-ids a,b,c] [--prompt-ids-dir DIR] [--prompt-all-windows] "
-                   "[--repetition-penalty F] [--no-repeat-ngram-size N] [--beam-size N] [--patience F] [--length-penalty F] [--n-best M]\n"
+                   "[--repetition-penalty F] [--no-repeat-ngram-size N] [--beam-size N] [--patience F] [--length-penalty F] [--n-best M] "
+                   "[--temperature 0,0.2,...] [--compression-ratio-threshold X]\n"
+                   "  --temperature a,b,c      the temperature ladder (openai-whisper's decode_with_fallback; default 0 = greedy, today's outputs byte for byte): every\n"
+                   "                           window is decoded at the first rung; a window whose compression ratio exceeds --compression-ratio-threshold or whose\n"
+                   "                           avg_logprob lies below --logprob-threshold — and whose no_speech_prob does not exceed --no-speech-threshold — is decoded\n"
+                   "                           again at the next rung (sampled at that temperature, seeded by --seed and the file's index), the others keep their result;\n"
+                   "                           after the last rung the last result stands.  The per-file JSON gains temperature and compression_ratio, config_used the\n"
+                   "                           ladder.  With a ladder the batches go through the unpipelined transcribe entry (the re-decode reads the batch's resident\n"
+                   "                           encoder states, which a prefetched next batch would replace), and every file must fit one 30 s window\n"
+                   "  --compression-ratio-threshold X   openai-whisper's default is 2.4 (off unless given)\n"
                    "  --beam-size N            beam search with N beams per window (1 .. 8; 1 = greedy, the default); a device batch then holds max-batch / N files\n"
                    "  --patience F             round(N * F) finished hypotheses end a window's search (openai-whisper's patience; default 1)\n"
                    "  --length-penalty F       rank by score / ((5 + len) / 6)^F; below 0 (the default): by score / len\n"
@@ -187,6 +201,13 @@ static bool parse_args(int argc, char** argv, Args& a) {
             else if (k == "--no-speech-threshold") { a.no_speech_threshold = strtod(v.c_str(), nullptr); a.logprobs = true; }
             else if (k == "--logprob-threshold") { a.logprob_threshold = strtod(v.c_str(), nullptr); a.logprobs = true; }
             else if (k == "--seed") a.seed = strtoull(v.c_str(), nullptr, 10);
+            else if (k == "--temperature") {   // what wh_ctx_set_sampling refuses is refused here, before any device is touched
+                try { a.temperature = parse_temperatures(v); } catch (const std::exception& e) { fprintf(stderr, "error: %s\n", e.what()); return false; }
+            } else if (k == "--compression-ratio-threshold") {
+                char* end = nullptr;
+                a.compression_ratio_threshold = strtod(v.c_str(), &end);
+                if (v.empty() || *end || std::isnan(a.compression_ratio_threshold)) { fprintf(stderr, "error: --compression-ratio-threshold '%s' is not a number\n", v.c_str()); return false; }
+            }
             else if (k == "--prompt-ids") a.prompt_ids = v;
             else if (k == "--alignment-heads") a.alignment_heads = v;
             else if (k == "--prompt-ids-dir") a.prompt_ids_dir = v;
@@ -242,6 +263,15 @@ static bool parse_args(int argc, char** argv, Args& a) {
         if (clash) { fprintf(stderr, "error: --beam-size %d cannot be combined with %s\n", a.beam_size, clash); return false; }
     } else if (a.n_best > 1) {
         fprintf(stderr, "error: --n-best %d needs --beam-size 2 or more\n", a.n_best);
+        return false;
+    }
+    if (a.ladder()) {   // the combinations every sampling call would refuse; the fallback decision reads avg_logprob and no_speech_prob
+        const char* clash = a.beam() ? "--beam-size" : a.have_rep_penalty || a.have_rep_ngram ? "--repetition-penalty / --no-repeat-ngram-size"
+                            : a.word_timestamps ? "--word-timestamps" : nullptr;
+        if (clash) { fprintf(stderr, "error: --temperature %s cannot be combined with %s\n", "above 0 or with several rungs", clash); return false; }
+        a.logprobs = true;
+    } else if (!std::isnan(a.compression_ratio_threshold)) {
+        fprintf(stderr, "error: --compression-ratio-threshold needs a --temperature ladder\n");
         return false;
     }
     return true;
@@ -605,6 +635,7 @@ int main(int argc, char** argv) {
         if (a.intra_op > 0) cfg.intra_op = a.intra_op;
         if (a.inter_op > 0) cfg.inter_op = a.inter_op;
         if (a.beam()) cfg.beam_size = a.beam_size;   // (config_used gains beam_size only then: the greedy summaries keep their bytes)
+        if (a.ladder()) cfg.temperature = a.temperature;   // (the same for the ladder)
 
         Tokenizer tok;  // resolve_tokenizer, src/main.rs:574-635: explicit path, model directories, then the Hugging Face cache
         if (!trim(a.tokenizer_json).empty()) {
@@ -643,6 +674,14 @@ int main(int argc, char** argv) {
             if (a.beam())
                 plan.set("beam_size", JVal::integer(a.beam_size)).set("patience", JVal::num(a.patience)).set("length_penalty", JVal::num(a.length_penalty))
                     .set("n_best", JVal::integer(a.n_best)).set("files_per_batch", JVal::integer(a.max_batch / a.beam_size));
+            if (a.ladder()) {
+                JVal t, thr;
+                t.raw = "[";
+                for (size_t i = 0; i < a.temperature.size(); i++) t.raw += (i ? ", " : "") + fmt_f32(a.temperature[i]);
+                t.raw += "]";
+                thr.raw = fmt_conf(a.compression_ratio_threshold);
+                plan.set("temperature", t).set("compression_ratio_threshold", thr).set("seed", JVal::integer((long long)a.seed)).set("pipelined", JVal::boolean(false));
+            }
             printf("%s\n", plan.pretty().c_str());
             return 0;
         }
@@ -766,7 +805,8 @@ int main(int argc, char** argv) {
                             return hipHostMalloc((void**)&p, (size_t)WH_CLIP_SAMPLES * sizeof(float), hipHostMallocDefault) == hipSuccess ? p : nullptr;
                         },
                         [](float* p) { (void)hipHostFree(p); });
-        struct Result { std::string text; double dur = 0, load_s = 0; Timing t; bool ok = false; std::vector<Cue> cues; Conf conf; Lang lang; WordOut words; std::string hyps; };
+        struct Result { std::string text; double dur = 0, load_s = 0; Timing t; bool ok = false; std::vector<Cue> cues; Conf conf; Lang lang; WordOut words; std::string hyps;
+                        bool has_ladder = false; double temperature = 0, compression_ratio = 0; };
         const size_t nfiles = files.size();
         std::vector<Result> results(nfiles);
         const unsigned hc = std::thread::hardware_concurrency();
@@ -782,6 +822,8 @@ int main(int argc, char** argv) {
             if (batch.size() == 1 && batch[0].n() > (size_t)WH_CLIP_SAMPLES) {
                 // a file longer than one window goes alone through the long-form entry (which batches its windows)
                 Result& r = results[batch[0].idx];
+                if (a.ladder())   // (the re-decode needs the windows' encoder states resident: the long-form entry keeps its last device batch's only)
+                    throw std::runtime_error("--temperature: " + files[batch[0].idx] + " is longer than one 30 s window; the ladder is built for one-window files");
                 r.text = transcribe(ctx, batch[0].audio, a, &tok, gen, r.t, &r.cues, &r.conf, lang_auto ? &lang_table : nullptr, &r.lang, &file_prefix[batch[0].idx], &r.words, &r.hyps);
                 r.dur = batch[0].dur; r.load_s = batch[0].load_s; r.ok = true;
             } else {
@@ -806,14 +848,63 @@ int main(int argc, char** argv) {
                     if (int rc = wh_ctx_set_prefixes(ctx, &po)) throw std::runtime_error(std::string("wh_ctx_set_prefixes: ") + std::to_string(rc) + ": " + wh_last_error(ctx));
                 }
                 const double t0 = now_s();
-                // the next batch of this worker, if it is loaded already, is copied to the device beside this batch's work
-                int rc = wh_transcribe_batch_next(ctx, clips.data(), clips.size(), nclips.empty() ? nullptr : nclips.data(), nclips.size(), &p, toks.data(), ntok.data());
-                if (rc) throw std::runtime_error(std::string("libwhisper_hip error ") + std::to_string(rc) + ": " + wh_last_error(ctx));
-                const double batch_s = now_s() - t0;
                 wh_timing wt{};
-                wh_get_timings(ctx, &wt);
                 std::vector<float> lps, nss;
-                if (a.logprobs) fetch_logprobs(ctx, batch.size(), a.max_new_tokens, lps, nss);
+                std::vector<int> rung_of;
+                std::vector<WindowScore> scores;
+                if (!a.ladder()) {
+                    // the next batch of this worker, if it is loaded already, is copied to the device beside this batch's work
+                    int rc = wh_transcribe_batch_next(ctx, clips.data(), clips.size(), nclips.empty() ? nullptr : nclips.data(), nclips.size(), &p, toks.data(), ntok.data());
+                    if (rc) throw std::runtime_error(std::string("libwhisper_hip error ") + std::to_string(rc) + ": " + wh_last_error(ctx));
+                    wh_get_timings(ctx, &wt);
+                    if (a.logprobs) fetch_logprobs(ctx, batch.size(), a.max_new_tokens, lps, nss);
+                } else {
+                    // The temperature ladder over this device batch (wh_host.h run_ladder).  Rung 0 is the ordinary, unpipelined transcribe call
+                    // (every temperature 0: the plain kernels); a later rung decodes the resident encoder states again with the failing rows
+                    // sampled at its temperature and the others inactive, and replaces the failing rows' results only.  A row's random stream
+                    // is named by its file's index, so a result does not depend on --max-batch.
+                    const size_t n = batch.size();
+                    lps.assign(n * a.max_new_tokens, 0.0f);
+                    nss.assign(n, 0.0f);
+                    run_ladder(n, a.temperature.size(), a.compression_ratio_threshold, a.logprob_threshold, a.no_speech_threshold,
+                               [&](size_t rung, const std::vector<unsigned char>& active, std::vector<WindowScore>& sc) {
+                                   std::vector<float> temps(n);
+                                   std::vector<uint8_t> act(active.begin(), active.end());
+                                   std::vector<uint64_t> ids(n);
+                                   for (size_t k = 0; k < n; k++) { temps[k] = active[k] ? a.temperature[rung] : 0.0f; ids[k] = (uint64_t)batch[k].idx; }
+                                   wh_sampling_opts so{sizeof(wh_sampling_opts), a.seed, temps.data(), act.data(), ids.data(), n};
+                                   if (int rc = wh_ctx_set_sampling(ctx, &so)) throw std::runtime_error(std::string("wh_ctx_set_sampling: ") + std::to_string(rc) + ": " + wh_last_error(ctx));
+                                   std::vector<int64_t> toks2(n * stride);
+                                   std::vector<size_t> ntok2(n);
+                                   size_t got = 0;
+                                   const int rc = rung == 0 ? wh_transcribe_batch(ctx, clips.data(), n, &p, toks2.data(), ntok2.data())
+                                                            : wh_decode_greedy_batch(ctx, &p, toks2.data(), stride, ntok2.data(), n, &got, nullptr, 0);
+                                   if (rc) throw std::runtime_error(std::string("libwhisper_hip error ") + std::to_string(rc) + ": " + wh_last_error(ctx));
+                                   if (rung == 0) wh_get_timings(ctx, &wt);
+                                   std::vector<float> lps2, nss2;
+                                   fetch_logprobs(ctx, n, a.max_new_tokens, lps2, nss2);
+                                   for (size_t k = 0; k < n; k++) {
+                                       if (!active[k]) continue;
+                                       std::copy_n(toks2.begin() + k * stride, stride, toks.begin() + k * stride);
+                                       ntok[k] = ntok2[k];
+                                       std::copy_n(lps2.begin() + k * a.max_new_tokens, a.max_new_tokens, lps.begin() + k * a.max_new_tokens);
+                                       nss[k] = nss2[k];
+                                       std::vector<int64_t> g;
+                                       if (ntok[k] > prompt.size()) g.assign(toks.begin() + k * stride + prompt.size(), toks.begin() + k * stride + ntok[k]);
+                                       sc[k].avg_logprob = avg_logprob(std::vector<float>(lps.begin() + k * a.max_new_tokens, lps.begin() + k * a.max_new_tokens + g.size()), g, sp.eot);
+                                       sc[k].no_speech_prob = nss[k];
+                                       if (!g.empty() && g.back() == sp.eot) g.pop_back();
+                                       if (a.timestamp_rules) g = text_ids(g, sp.timestamp_begin);
+                                       sc[k].compression_ratio = compression_ratio(trim(decode_tokens(g, &tok)));
+                                   }
+                               },
+                               rung_of, scores);
+                    for (size_t k = 0; k < n; k++) {
+                        Result& r = results[batch[k].idx];
+                        r.has_ladder = true; r.temperature = a.temperature[rung_of[k]]; r.compression_ratio = scores[k].compression_ratio;
+                    }
+                }
+                const double batch_s = now_s() - t0;
                 std::vector<Lang> langs;
                 if (lang_auto) langs = fetch_languages(ctx, batch.size(), lang_table);
                 std::vector<int32_t> frames;
@@ -883,6 +974,7 @@ int main(int argc, char** argv) {
             if (a.prompts()) { rows.back().has_prompt = true; rows.back().prompt_tokens = (long long)file_prefix[i].size(); }
             if (r.lang.has) { rows.back().has_lang = true; rows.back().language = r.lang.code; rows.back().language_probability = r.lang.prob; }
             if (r.conf.has) { rows.back().has_conf = true; rows.back().avg_logprob = r.conf.avg_logprob(); rows.back().no_speech_prob = r.conf.no_speech_prob(); }
+            if (r.has_ladder) { rows.back().has_ladder = true; rows.back().temperature = r.temperature; rows.back().compression_ratio = r.compression_ratio; }
             loadl.push_back(r.load_s); pre.push_back(r.t.preprocess_s); model_only.push_back(r.t.model_only_s);
             dec.push_back(r.t.decode_s); e2e.push_back(end_to_end); rtfl.push_back(end_to_end / std::max(r.dur, 1e-9));
             audio_total += r.dur;
@@ -921,6 +1013,10 @@ int main(int argc, char** argv) {
         if (a.logprobs) summary.set("logprobs", JVal::boolean(true));
         if (a.have_rep_penalty) summary.set("repetition_penalty", JVal::num(a.rep_penalty));
         if (a.have_rep_ngram) summary.set("no_repeat_ngram_size", JVal::integer(a.rep_ngram));
+        if (a.ladder()) {
+            summary.set("seed", JVal::integer((long long)a.seed));
+            if (!std::isnan(a.compression_ratio_threshold)) summary.set("compression_ratio_threshold", JVal::num(a.compression_ratio_threshold));
+        }
         if (a.beam()) summary.set("patience", JVal::num(a.patience)).set("length_penalty", JVal::num(a.length_penalty)).set("n_best", JVal::integer(a.n_best));
         write_file(a.out_summary_json, summary.pretty());
         printf("DONE\n");  // :1261-1268
