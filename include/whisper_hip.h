@@ -487,6 +487,50 @@ int wh_transcribe_batch_device_next(wh_ctx* c, const float* d_pcm, size_t n_clip
                                     size_t n_clips_next, const wh_decode_params* p, int64_t* tokens_out,
                                     size_t* n_tokens_out);
 
+/* ---- raw audio in (src/main.rs:207-316: load_audio_16k_mono + resample_linear, run on the GPU) ----
+ * The caller hands over what the file holds: interleaved samples with their format, channel count and sample rate.  One kernel in front of
+ * log-mel converts each sample (S16: (float)s / 32768.0f, U8: ((float)u - 128.0f) / 128.0f, F32: as is), takes the
+ * channel mean of every frame (f32 additions in channel order, one division) and, for rates other than 16000, interpolates linearly with the
+ * reference's f64 position arithmetic (:211-223) — the same operations in the same order as the reference's loader, so the 16 kHz mono f32
+ * samples, and everything computed from them, are bit-identical to the host-converted path. */
+#define WH_PCM_S16 0
+#define WH_PCM_U8  1
+#define WH_PCM_F32 2
+#define WH_MAX_CHANNELS 64
+typedef struct {
+    const void* data;      /* n_frames * channels interleaved samples of `format`, any alignment */
+    size_t n_frames;
+    uint32_t sample_rate;  /* 1 .. 768000 */
+    uint16_t channels;     /* 1 .. WH_MAX_CHANNELS */
+    uint16_t format;       /* WH_PCM_* */
+} wh_raw_clip;
+/* Host only, like wh_mel_frames: the 16 kHz length of n_frames at sample_rate — n_frames itself at 16000, else
+ * llround(n_frames * (16000.0 / sample_rate)), half away from zero (src/main.rs:211-212).  0 for sample_rate 0. */
+size_t wh_resampled_samples(size_t n_frames, uint32_t sample_rate);
+/* Parity entry (as wh_log_mel is for the mel; not a production path): copies the clips' raw bytes, converts them on the device and reads the
+ * rows back.  pcm_out: [n_clips][cap_samples]; n_samples_out: [n_clips].  One clip may have any length (it is converted where the long-form
+ * entry converts a file); the clips of a larger batch at most WH_CLIP_SAMPLES resampled samples each.
+ * WH_ERR_ARG: NULL data, unknown format, channels outside 1 .. 64, rate outside 1 .. 768000, n_clips outside 1 .. max_batch, cap_samples
+ * smaller than a clip's resampled length.  WH_ERR_EMPTY_AUDIO: n_frames == 0 or a resampled length of 0.  Nothing is launched on a refusal. */
+int wh_ingest_raw(wh_ctx* c, const wh_raw_clip* clips, size_t n_clips, float* pcm_out, size_t cap_samples, size_t* n_samples_out);
+/* wh_transcribe_batch on raw clips (src/main.rs:207-316 + 870-915): returns exactly what wh_transcribe_batch returns for the host-converted
+ * clips, with every per-ctx option and every wh_get_* as after that call.  Refusals as wh_ingest_raw; a clip whose resampled length exceeds
+ * WH_CLIP_SAMPLES -> WH_ERR_ARG (use wh_transcribe_longform_raw).  The raw bytes are staged in device memory the ctx owns (grown on demand,
+ * allocated only by contexts that call a raw entry; WH_ERR_NOMEM if it cannot be allocated, the ctx stays usable). */
+int wh_transcribe_batch_raw(wh_ctx* c, const wh_raw_clip* clips, size_t n_clips, const wh_decode_params* p, int64_t* tokens_out,
+                            size_t* n_tokens_out);
+/* wh_transcribe_batch_next on raw clips (src/main.rs:207-316, 1164-1213): the NEXT batch's raw bytes are copied to a second staging buffer on
+ * the copy stream beside this batch's work.  A following call whose clips equal `next` in every field of every clip (pointer, frames, rate,
+ * channels, format) finds its bytes resident; any other call copies as wh_transcribe_batch_raw does.  next's memory must stay valid and
+ * unchanged until that call.  Results are identical to wh_transcribe_batch_raw.  The raw and the f32 entries may be mixed on one ctx: an
+ * entry of one family waits for and drops a pending prefetch of the other. */
+int wh_transcribe_batch_raw_next(wh_ctx* c, const wh_raw_clip* clips, size_t n_clips, const wh_raw_clip* next, size_t n_next,
+                                 const wh_decode_params* p, int64_t* tokens_out, size_t* n_tokens_out);
+/* wh_transcribe_longform on a raw file (src/main.rs:207-316 + 834-1008): the whole file is converted on the device, then as
+ * wh_transcribe_longform on the converted samples (declared below). */
+int wh_transcribe_longform_raw(wh_ctx* c, const wh_raw_clip* file, double chunk_length_s, double overlap_s, const wh_decode_params* p,
+                               int64_t* tokens_out, size_t* n_tokens_out, size_t cap_chunks, size_t* n_chunks_out);
+
 /* ---- long-form (src/main.rs:834-1008): whole-file mel once, 30 s windows every
  * (chunk_len - overlap) samples, all windows decoded as batches; returns per-window tokens ------ */
 int wh_longform_plan(size_t n_samples, double chunk_length_s, double overlap_s, size_t* offsets, size_t cap,

@@ -23,6 +23,9 @@ LIB_PATH = os.path.join(HERE, "libwhisper_hip.so")
 WH_PREC_F32, WH_PREC_BF16, WH_PREC_FP8, WH_PREC_F16X3 = 0, 1, 2, 3
 PRECISIONS = {"f32": WH_PREC_F32, "bf16": WH_PREC_BF16, "fp8": WH_PREC_FP8, "f16x3": WH_PREC_F16X3}
 WH_N_FRAMES, WH_CLIP_SAMPLES = 3000, 480000
+WH_PCM_S16, WH_PCM_U8, WH_PCM_F32 = 0, 1, 2
+WH_MAX_CHANNELS = 64
+PCM_FORMATS = {np.dtype(np.int16): WH_PCM_S16, np.dtype(np.uint8): WH_PCM_U8, np.dtype(np.float32): WH_PCM_F32}
 KG_NAMES = ("mel", "enc_gemm", "enc_attn", "dec_cross_attn", "dec_gemm", "dec_other")
 
 STATUS = {0: "WH_OK", 1: "WH_ERR_EMPTY_AUDIO", 2: "WH_ERR_BAD_SHAPE", 3: "WH_ERR_STATE", 4: "WH_ERR_ARG",
@@ -37,7 +40,8 @@ EXPORTS = ("wh_model_load", "wh_model_create", "wh_model_free", "wh_model_get_di
            "wh_device_count", "wh_ctx_set_timestamp_rules", "wh_ctx_set_logprobs", "wh_get_logprobs",
            "wh_ctx_set_language_detection", "wh_get_languages", "wh_ctx_set_prefixes", "wh_ctx_set_repetition",
            "wh_ctx_set_alignment", "wh_get_token_frames", "wh_get_alignment_debug", "wh_ctx_set_beam_search", "wh_get_beams", "wh_get_beam_trace",
-           "wh_ctx_set_sampling")
+           "wh_ctx_set_sampling", "wh_resampled_samples", "wh_ingest_raw", "wh_transcribe_batch_raw", "wh_transcribe_batch_raw_next",
+           "wh_transcribe_longform_raw")
 
 
 class WhisperHipError(RuntimeError):
@@ -64,6 +68,31 @@ class WhDecodeParams(C.Structure):
 
 class WhClip(C.Structure):
     _fields_ = [("pcm", C.POINTER(C.c_float)), ("n_samples", C.c_size_t)]
+
+
+class WhRawClip(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("n_frames", C.c_size_t), ("sample_rate", C.c_uint32), ("channels", C.c_uint16), ("format", C.c_uint16)]
+
+
+def raw_clips(clips: Sequence[Tuple[np.ndarray, int]]):
+    """wh_raw_clip array from (samples, sample_rate) pairs: samples of dtype int16 / uint8 / float32 and shape [frames, channels] (or [frames]
+    for mono), interleaved as a file holds them.  A C-contiguous array is passed as it lies in memory, whatever its alignment.  Returns the
+    ctypes array and the arrays it points into (keep them alive while the library may read them)."""
+    arrs = []
+    out = (WhRawClip * len(clips))()
+    for i, (a, rate) in enumerate(clips):
+        a = np.asarray(a)
+        if a.dtype not in PCM_FORMATS:
+            raise TypeError(f"raw clip {i}: dtype {a.dtype} (int16, uint8 or float32 expected)")
+        if a.ndim == 1:
+            a = a.reshape(-1, 1)
+        if a.ndim != 2:
+            raise ValueError(f"raw clip {i}: shape {a.shape} ([frames, channels] expected)")
+        if not a.flags.c_contiguous:
+            a = np.ascontiguousarray(a)
+        arrs.append(a)
+        out[i] = WhRawClip(a.ctypes.data, a.shape[0], int(rate), a.shape[1], PCM_FORMATS[a.dtype])
+    return out, arrs
 
 
 class WhCtxOpts(C.Structure):
@@ -192,6 +221,13 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.wh_longform_plan.argtypes = [C.c_size_t, C.c_double, C.c_double, szp, C.c_size_t, szp]
     L.wh_transcribe_longform.argtypes = [vp, f32p, C.c_size_t, C.c_double, C.c_double, C.POINTER(WhDecodeParams), i64p,
                                          szp, C.c_size_t, szp]
+    rawp = C.POINTER(WhRawClip)
+    L.wh_resampled_samples.argtypes = [C.c_size_t, C.c_uint32]
+    L.wh_resampled_samples.restype = C.c_size_t
+    L.wh_ingest_raw.argtypes = [vp, rawp, C.c_size_t, f32p, C.c_size_t, szp]
+    L.wh_transcribe_batch_raw.argtypes = [vp, rawp, C.c_size_t, C.POINTER(WhDecodeParams), i64p, szp]
+    L.wh_transcribe_batch_raw_next.argtypes = [vp, rawp, C.c_size_t, rawp, C.c_size_t, C.POINTER(WhDecodeParams), i64p, szp]
+    L.wh_transcribe_longform_raw.argtypes = [vp, rawp, C.c_double, C.c_double, C.POINTER(WhDecodeParams), i64p, szp, C.c_size_t, szp]
     L.wh_profile_enable.argtypes = [vp, C.c_int]
     L.wh_profile_get.argtypes = [vp, C.POINTER(C.c_double), i64p]
     L.wh_synthetic_weights.argtypes = [C.c_char_p, C.c_uint64, f32p, C.c_size_t, szp]
@@ -666,6 +702,48 @@ class Context:
         got = C.c_size_t(0)
         self._check(self.lib.wh_transcribe_longform(self.h, _f32(pcm), pcm.size, chunk_length_s, overlap_s, C.byref(p),
                                                     _i64(toks), n, k, C.byref(got)))
+        return self._took([toks[i, : n[i]].copy() for i in range(int(got.value))], params)
+
+    # --- raw audio in (src/main.rs:207-316 on the GPU): clips are (samples [frames, channels] int16 / uint8 / float32, sample_rate) pairs ---
+    def ingest_raw(self, clips: Sequence[Tuple[np.ndarray, int]]) -> List[np.ndarray]:
+        """wh_ingest_raw (parity entry): the clips' 16 kHz mono f32 samples as the device converted them."""
+        cl, keep = raw_clips(clips)
+        lens = [int(self.lib.wh_resampled_samples(a.shape[0], int(r))) for a, (_, r) in zip(keep, clips)]
+        cap = max(1, max(lens))
+        out = np.zeros((len(keep), cap), np.float32)
+        n = (C.c_size_t * len(keep))()
+        self._check(self.lib.wh_ingest_raw(self.h, cl, len(keep), _f32(out), cap, n))
+        return [out[i, : n[i]].copy() for i in range(len(keep))]
+
+    def transcribe_batch_raw(self, clips: Sequence[Tuple[np.ndarray, int]], params: DecodeParams,
+                             next_clips: Optional[Sequence[Tuple[np.ndarray, int]]] = None, prefetch: bool = False) -> List[np.ndarray]:
+        """wh_transcribe_batch_raw, or (prefetch=True or next_clips given) wh_transcribe_batch_raw_next.  The prefetch is recognised by the
+        samples' addresses: pass the same arrays again in the call that transcribes them."""
+        cl, keep = raw_clips(clips)
+        ncl, nkeep = raw_clips(next_clips) if next_clips is not None else (None, None)
+        p, pkeep = params.to_c()
+        stride = len(params.prompt) + params.max_new_tokens
+        toks = np.zeros((len(keep), stride), np.int64)
+        n = (C.c_size_t * len(keep))()
+        if next_clips is None and not prefetch:
+            self._check(self.lib.wh_transcribe_batch_raw(self.h, cl, len(keep), C.byref(p), _i64(toks), n))
+        else:
+            self._check(self.lib.wh_transcribe_batch_raw_next(self.h, cl, len(keep), ncl, len(nkeep) if nkeep else 0, C.byref(p), _i64(toks), n))
+        self._keep_next_raw = nkeep   # (the arrays the asynchronous copy reads)
+        return self._took([toks[i, : n[i]].copy() for i in range(len(keep))], params)
+
+    def transcribe_longform_raw(self, samples: np.ndarray, sample_rate: int, params: DecodeParams, chunk_length_s: float = 30.0,
+                                overlap_s: float = 5.0) -> List[np.ndarray]:
+        cl, keep = raw_clips([(samples, sample_rate)])
+        nch = C.c_size_t(0)
+        self.lib.wh_longform_plan(int(self.lib.wh_resampled_samples(keep[0].shape[0], int(sample_rate))), chunk_length_s, overlap_s, None, 0, C.byref(nch))
+        k = max(1, int(nch.value))
+        p, pkeep = params.to_c()
+        stride = len(params.prompt) + params.max_new_tokens
+        toks = np.zeros((k, stride), np.int64)
+        n = (C.c_size_t * k)()
+        got = C.c_size_t(0)
+        self._check(self.lib.wh_transcribe_longform_raw(self.h, cl, chunk_length_s, overlap_s, C.byref(p), _i64(toks), n, k, C.byref(got)))
         return self._took([toks[i, : n[i]].copy() for i in range(int(got.value))], params)
 
     # --- measurement -------------------------------------------------------------------------------

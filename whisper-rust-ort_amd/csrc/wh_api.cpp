@@ -17,6 +17,7 @@
 #include <functional>
 
 #include "wh_common.h"
+#include "wh_ingest_desc.h"
 #include "wh_internal.h"
 
 const std::string& wh_global_error();
@@ -1335,6 +1336,13 @@ int run_encoder_pass(wh_ctx* c, const float* pcm, int nb, int set) {
     if (rc) return rc;
     hipStream_t s = c->s_enc;
     CTX_HIP(c, hipEventRecord(c->enc_ev[set][0], s));
+    if (c->ing_n) {   // a raw entry: the clips' bytes in ing_raw[ing_buf] become the PCM rows first (part of the pass's preprocess time)
+        c->cur = s;
+        Prof p(c, WH_KG_MEL);
+        wh_launch_ingest(s, c->ing_raw[c->ing_buf], c->ing_desc, c->ing_n, c->ing_max_out, c->pcm);
+        c->ing_last_n = c->ing_n; c->ing_last_buf = c->ing_buf; c->ing_last_max_out = c->ing_max_out;
+        c->ing_n = 0;
+    }
     rc = run_mel_batch(c, pcm, nb);
     if (rc) return rc;
     CTX_HIP(c, hipEventRecord(c->enc_ev[set][1], s));
@@ -2253,6 +2261,9 @@ void wh_ctx_free(wh_ctx* c) {
     if (c->s_copy) { hipStreamSynchronize(c->s_copy); hipStreamDestroy(c->s_copy); }
     if (c->ev_h2d) hipEventDestroy(c->ev_h2d);
     if (c->pcm2) hipFree(c->pcm2);
+    for (void* r : c->ing_raw)
+        if (r) hipFree(r);
+    if (c->ing_desc) hipFree(c->ing_desc);
     delete c;
 }
 
@@ -2265,6 +2276,29 @@ extern "C" int wh_debug_set_es_pad(wh_ctx* c, int pad_rows) {
     c->es_rows = c->m->dims.n_audio_ctx + pad_rows;
     c->have_enc = false;
     return WH_OK;
+}
+
+// measurement hook (tools/ingest_bench.py; not in the public header): the conversion of the last wh_transcribe_batch_raw* batch (its raw bytes and
+// descriptors are still resident) launched `reps` more times, each between two events on the encoder stream: microseconds per launch in us[reps].
+// The rows it writes are the rows it wrote before.
+extern "C" int wh_debug_ingest_times(wh_ctx* c, int reps, float* us) {
+    if (!c || !us || reps < 1 || c->ing_last_n == 0 || c->h2d_valid) return WH_ERR_ARG;
+    CTX_HIP(c, hipSetDevice(c->m->device));
+    hipEvent_t a, b;
+    CTX_HIP(c, hipEventCreate(&a));
+    CTX_HIP(c, hipEventCreate(&b));
+    int rc = WH_OK;
+    for (int i = 0; i < reps && rc == WH_OK; i++) {
+        hipEventRecord(a, c->s_enc);
+        wh_launch_ingest(c->s_enc, c->ing_raw[c->ing_last_buf], c->ing_desc, c->ing_last_n, c->ing_last_max_out, c->pcm);
+        hipEventRecord(b, c->s_enc);
+        float ms = 0;
+        if (hipEventSynchronize(b) != hipSuccess || hipEventElapsedTime(&ms, a, b) != hipSuccess) rc = fail(c, WH_ERR_HIP, "wh_debug_ingest_times: %s", hipGetErrorString(hipGetLastError()));
+        us[i] = ms * 1e3f;
+    }
+    hipEventDestroy(a);
+    hipEventDestroy(b);
+    return rc;
 }
 
 // measurement hook (tools/align_bench.py; not in the public header): milliseconds of the three post-pass kernels of the last call, summed over
@@ -2335,10 +2369,57 @@ static int ensure_long(wh_ctx* c, size_t n, size_t nf) {
     return WH_OK;
 }
 
+// grow raw staging buffer `k` to `bytes`.  A failed allocation leaves the ctx as it was, with no sticky HIP error.
+static int ensure_ingest(wh_ctx* c, int k, size_t bytes) {
+    if (!c->ing_desc) {
+        void* d = nullptr;
+        const hipError_t e = hipMalloc(&d, (size_t)c->max_batch * sizeof(WhIngestDesc));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, WH_ERR_NOMEM, "raw audio descriptors: hipMalloc: %s", hipGetErrorString(e));
+        }
+        c->ing_desc = (WhIngestDesc*)d;
+    }
+    if (bytes <= c->ing_raw_cap[k]) return WH_OK;
+    void* nb = nullptr;
+    const hipError_t e = hipMalloc(&nb, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();   // (the old, smaller buffer is kept)
+        return fail(c, WH_ERR_NOMEM, "raw audio staging (%zu bytes): hipMalloc: %s", bytes, hipGetErrorString(e));
+    }
+    if (c->ing_raw[k]) hipFree(c->ing_raw[k]);
+    c->ing_raw[k] = nb;
+    c->ing_raw_cap[k] = bytes;
+    return WH_OK;
+}
+
+// the refusals of the raw entries (include/whisper_hip.h), before anything is launched; max_out: the longest resampled clip allowed
+static int check_raw_clips(wh_ctx* c, const wh_raw_clip* clips, size_t n, size_t max_out, const char* too_long) {
+    for (size_t i = 0; i < n; i++) {
+        if (const char* why = wh_raw_clip_problem(clips[i])) return fail(c, WH_ERR_ARG, "clip %zu: %s", i, why);
+        if (clips[i].n_frames > ((size_t)1 << 40)) return fail(c, WH_ERR_ARG, "clip %zu: more than 2^40 frames", i);
+    }
+    for (size_t i = 0; i < n; i++) {
+        const size_t no = wh_resampled_len(clips[i].n_frames, clips[i].sample_rate);
+        if (clips[i].n_frames == 0 || no == 0) return fail(c, WH_ERR_EMPTY_AUDIO, "Empty audio");   // src/main.rs:414-416
+        if (no > max_out) return fail(c, WH_ERR_ARG, "clip %zu %s", i, too_long);
+    }
+    return WH_OK;
+}
+
+// the batch's raw bytes -> staging buffer k on stream s
+static int copy_raw_clips(wh_ctx* c, const wh_raw_clip* clips, const WhIngestPlan& plan, int k, hipStream_t s) {
+    for (size_t i = 0; i < plan.desc.size(); i++)
+        CTX_HIP(c, hipMemcpyAsync((char*)c->ing_raw[k] + plan.desc[i].raw_off, clips[i].data, plan.bytes[i], hipMemcpyHostToDevice, s));
+    return WH_OK;
+}
+
 // whole-file raw log-mel into c->raw_long (row stride = align16(frames)); returns frames
-static int whole_file_mel(wh_ctx* c, const float* pcm, size_t n, size_t* nf_out, size_t* ld_out) {
+// `raw` (optional): the file as it was read; it is converted into c->pcm_long on the device instead of copying `pcm`
+static int whole_file_mel(wh_ctx* c, const float* pcm, size_t n, size_t* nf_out, size_t* ld_out, const wh_raw_clip* raw = nullptr,
+                          double* h2d_s_out = nullptr) {
     if (n == 0) return fail(c, WH_ERR_EMPTY_AUDIO, "Empty audio");  // src/main.rs:414-416
-    if (!pcm) return fail(c, WH_ERR_ARG, "pcm is NULL");
+    if (!pcm && !raw) return fail(c, WH_ERR_ARG, "pcm is NULL");
     if (n > 0x7fffffffu) return fail(c, WH_ERR_ARG, "audio longer than 2^31 samples");
     const size_t nf = wh_mel_frames(n), ld = align_up(nf, 16);
     int rc = ensure_long(c, n, nf);
@@ -2347,11 +2428,24 @@ static int whole_file_mel(wh_ctx* c, const float* pcm, size_t n, size_t* nf_out,
     if (rc) return rc;
     hipStream_t s = c->s_enc;
     const int ni = (int)n, nfi = (int)nf;
-    CTX_HIP(c, hipMemcpyAsync(c->pcm_long, pcm, n * 4, hipMemcpyHostToDevice, s));
+    const double t_copy = now_s();
+    WhIngestPlan plan;
+    if (raw) {
+        wh_ingest_pack(raw, 1, 0, plan);
+        CTX_HIP(c, hipMemcpyAsync(c->ing_raw[0], raw->data, plan.bytes[0], hipMemcpyHostToDevice, s));
+        CTX_HIP(c, hipMemcpyAsync(c->ing_desc, plan.desc.data(), sizeof(WhIngestDesc), hipMemcpyHostToDevice, s));
+    } else {
+        CTX_HIP(c, hipMemcpyAsync(c->pcm_long, pcm, n * 4, hipMemcpyHostToDevice, s));
+    }
     CTX_HIP(c, hipMemcpyAsync(c->d_nsamp, &ni, 4, hipMemcpyHostToDevice, s));
     CTX_HIP(c, hipMemcpyAsync(c->d_nframes, &nfi, 4, hipMemcpyHostToDevice, s));
     CTX_HIP(c, hipMemsetAsync(c->d_gmax, 0, 4, s));
     CTX_HIP(c, hipStreamSynchronize(s));
+    if (h2d_s_out) *h2d_s_out = now_s() - t_copy;
+    if (raw) {
+        Prof p(c, WH_KG_MEL);
+        wh_launch_ingest(s, c->ing_raw[0], c->ing_desc, 1, plan.max_out, c->pcm_long);
+    }
     {
         Prof p(c, WH_KG_MEL);
         wh_launch_mel_stft(s, c->pcm_long, 0, c->d_nsamp, 1, (long)nf, c->m->mel_tw, c->m->mel_win, c->m->mel_fbT,
@@ -2555,6 +2649,14 @@ static int transcribe_resident(wh_ctx* c, const float* pcm, int nb, bool prefetc
     return rc;
 }
 
+// A prefetch of wh_transcribe_batch_next / wh_transcribe_batch_raw_next that the call now starting does not take over: wait for its copies
+// (they write c->pcm, c->pcm2 or a raw staging buffer this call may reuse) and forget it.
+static int drop_pending_h2d(wh_ctx* c) {
+    if (c->h2d_valid) CTX_HIP(c, hipStreamSynchronize(c->s_copy));
+    c->h2d_valid = false;
+    return WH_OK;
+}
+
 int wh_transcribe_batch(wh_ctx* c, const wh_clip* clips, size_t n_clips, const wh_decode_params* p, int64_t* tokens_out,
                         size_t* n_tokens_out) {
     if (!c) return WH_ERR_ARG;
@@ -2568,6 +2670,8 @@ int wh_transcribe_batch(wh_ctx* c, const wh_clip* clips, size_t n_clips, const w
     CTX_HIP(c, hipSetDevice(c->m->device));
     prof_reset(c);
     const double t0 = now_s();
+    rc = drop_pending_h2d(c);   // (a prefetch of wh_transcribe_batch*_next may be on its way into c->pcm)
+    if (rc) return rc;
     rc = enc_begin(c);
     if (rc) return rc;
     hipStream_t s = c->s_enc;
@@ -2587,6 +2691,13 @@ int wh_transcribe_batch(wh_ctx* c, const wh_clip* clips, size_t n_clips, const w
     c->timing.h2d_s = now_s() - t0;
     c->enc_nframes = nf;
     return transcribe_resident(c, c->pcm, (int)n_clips, false, nullptr, 0, p, tokens_out, n_tokens_out, t0);
+}
+
+// the copy stream and its event (shared by the f32 and the raw prefetch)
+static int ensure_copy_stream(wh_ctx* c) {
+    if (!c->s_copy) CTX_HIP(c, hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking));
+    if (!c->ev_h2d) CTX_HIP(c, hipEventCreateWithFlags(&c->ev_h2d, hipEventDisableTiming));
+    return WH_OK;
 }
 
 // per-clip checks + counts of a host batch (wh_transcribe_batch*)
@@ -2619,8 +2730,7 @@ int wh_transcribe_batch_next(wh_ctx* c, const wh_clip* clips, size_t n_clips, co
     const double t0 = now_s();
     if (!c->pcm2) {   // second PCM buffer, copy stream and its event: only contexts that use this entry pay for them
         CTX_HIP(c, hipMalloc((void**)&c->pcm2, (size_t)c->max_batch * WH_CLIP_SAMPLES * 4));
-        CTX_HIP(c, hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking));
-        CTX_HIP(c, hipEventCreateWithFlags(&c->ev_h2d, hipEventDisableTiming));
+        if ((rc = ensure_copy_stream(c))) return rc;
     }
     std::vector<int> ns, nf;
     rc = host_batch_counts(c, clips, n_clips, ns, nf);
@@ -2630,7 +2740,7 @@ int wh_transcribe_batch_next(wh_ctx* c, const wh_clip* clips, size_t n_clips, co
     hipStream_t s = c->s_enc;
     c->pre_valid = false;
     // this batch's PCM: already on its way (copied beside the previous call's work), or copied now
-    const bool hit = c->h2d_valid && c->h2d_src == clips[0].pcm && c->h2d_n == (int)n_clips && c->h2d_ns == ns;
+    const bool hit = c->h2d_valid && !c->h2d_is_raw && c->h2d_src == clips[0].pcm && c->h2d_n == (int)n_clips && c->h2d_ns == ns;
     int buf = hit ? c->h2d_buf : 0;
     float* d_pcm = buf ? c->pcm2 : c->pcm;
     c->timing = wh_timing{};
@@ -2660,6 +2770,7 @@ int wh_transcribe_batch_next(wh_ctx* c, const wh_clip* clips, size_t n_clips, co
             for (size_t i = 0; i < n_next; i++)
                 CTX_HIP(c, hipMemcpyAsync(d_next + i * WH_CLIP_SAMPLES, next_clips[i].pcm, next_clips[i].n_samples * 4, hipMemcpyHostToDevice, c->s_copy));
             CTX_HIP(c, hipEventRecord(c->ev_h2d, c->s_copy));
+            c->h2d_is_raw = false;
             c->h2d_buf = nbuf; c->h2d_src = next_clips[0].pcm; c->h2d_n = (int)n_next; c->h2d_ns = ns2; c->h2d_nf = nf2; c->h2d_valid = true;
             return WH_OK;
         };
@@ -2722,13 +2833,10 @@ int wh_longform_plan(size_t n_samples, double chunk_length_s, double overlap_s, 
     return (offsets && n > cap) ? WH_ERR_ARG : WH_OK;
 }
 
-int wh_transcribe_longform(wh_ctx* c, const float* pcm, size_t n_samples, double chunk_length_s, double overlap_s,
-                           const wh_decode_params* p, int64_t* tokens_out, size_t* n_tokens_out, size_t cap_chunks,
-                           size_t* n_chunks_out) {
-    if (!c) return WH_ERR_ARG;
-    int rc = check_params(c, p);
-    if (rc) return rc;
-    if (!tokens_out || !n_tokens_out || !n_chunks_out) return fail(c, WH_ERR_ARG, "NULL argument");
+// wh_transcribe_longform on `pcm`, or (raw != NULL) on the file `raw` converted on the device: n_samples is then its resampled length
+static int longform_impl(wh_ctx* c, const float* pcm, const wh_raw_clip* raw, size_t n_samples, double chunk_length_s, double overlap_s,
+                         const wh_decode_params* p, int64_t* tokens_out, size_t* n_tokens_out, size_t cap_chunks, size_t* n_chunks_out) {
+    int rc;
     rc = prefix_check(c, p, 1, true);
     if (rc) return rc;
     {   // (alignment debug rows are rows of a device batch: they must exist in every batch of the call, so in its last, smallest one)
@@ -2753,7 +2861,8 @@ int wh_transcribe_longform(wh_ctx* c, const float* pcm, size_t n_samples, double
     // whole-file mel once: the normalisation max is global over the FILE (src/main.rs:870-872)
     CTX_HIP(c, hipEventRecord(c->ev[0], s));
     size_t nf = 0, ld = 0;
-    rc = whole_file_mel(c, pcm, n_samples, &nf, &ld);
+    double h2d_s = 0;
+    rc = whole_file_mel(c, pcm, n_samples, &nf, &ld, raw, &h2d_s);
     if (rc) return rc;
     CTX_HIP(c, hipEventRecord(c->ev[1], s));
     const size_t stride = p->n_prompt + p->max_new_tokens;
@@ -2801,12 +2910,184 @@ int wh_transcribe_longform(wh_ctx* c, const float* pcm, size_t n_samples, double
     float a = 0;
     hipEventElapsedTime(&a, c->ev[0], c->ev[1]);
     c->timing = wh_timing{};
+    if (raw) c->timing.h2d_s = h2d_s;
     c->timing.preprocess_s = a * 1e-3;
     c->timing.encode_s = enc_s;
     c->timing.decode_s = dec_s;
     c->timing.total_s = now_s() - t0;
     prof_collect(c);
     return WH_OK;
+}
+
+int wh_transcribe_longform(wh_ctx* c, const float* pcm, size_t n_samples, double chunk_length_s, double overlap_s,
+                           const wh_decode_params* p, int64_t* tokens_out, size_t* n_tokens_out, size_t cap_chunks,
+                           size_t* n_chunks_out) {
+    if (!c) return WH_ERR_ARG;
+    int rc = check_params(c, p);
+    if (rc) return rc;
+    if (!tokens_out || !n_tokens_out || !n_chunks_out) return fail(c, WH_ERR_ARG, "NULL argument");
+    return longform_impl(c, pcm, nullptr, n_samples, chunk_length_s, overlap_s, p, tokens_out, n_tokens_out, cap_chunks, n_chunks_out);
+}
+
+// ---- raw audio in (src/main.rs:207-316 run on the device) ----
+
+size_t wh_resampled_samples(size_t n_frames, uint32_t sample_rate) { return wh_resampled_len(n_frames, sample_rate); }
+
+// the common front of the raw entries that write rows of c->pcm: stage `clips` in buffer k (copied on the encoder stream unless `resident`),
+// upload descriptors and per-clip counts, and arm the conversion for the next encoder pass
+static int stage_raw_batch(wh_ctx* c, const wh_raw_clip* clips, size_t n_clips, int k, bool resident, std::vector<int>& nf) {
+    WhIngestPlan plan;
+    wh_ingest_pack(clips, n_clips, WH_CLIP_SAMPLES, plan);
+    hipStream_t s = c->s_enc;
+    if (!resident) {
+        int rc = ensure_ingest(c, k, plan.total_bytes);
+        if (rc) return rc;
+        if ((rc = copy_raw_clips(c, clips, plan, k, s))) return rc;
+    }
+    std::vector<int> ns(n_clips);
+    nf.resize(n_clips);
+    for (size_t i = 0; i < n_clips; i++) {
+        ns[i] = (int)plan.desc[i].n_out;
+        nf[i] = (int)wh_mel_frames(plan.desc[i].n_out);
+    }
+    CTX_HIP(c, hipMemcpyAsync(c->ing_desc, plan.desc.data(), n_clips * sizeof(WhIngestDesc), hipMemcpyHostToDevice, s));
+    CTX_HIP(c, hipMemcpyAsync(c->d_nsamp, ns.data(), n_clips * 4, hipMemcpyHostToDevice, s));
+    CTX_HIP(c, hipMemcpyAsync(c->d_nframes, nf.data(), n_clips * 4, hipMemcpyHostToDevice, s));
+    CTX_HIP(c, hipStreamSynchronize(s));
+    c->ing_n = (int)n_clips;
+    c->ing_buf = k;
+    c->ing_max_out = plan.max_out;
+    return WH_OK;
+}
+
+static const char* const RAW_TOO_LONG = "longer than one 30 s window; use wh_transcribe_longform_raw";
+
+int wh_ingest_raw(wh_ctx* c, const wh_raw_clip* clips, size_t n_clips, float* pcm_out, size_t cap_samples, size_t* n_samples_out) {
+    if (!c) return WH_ERR_ARG;
+    if (!clips || !pcm_out || !n_samples_out) return fail(c, WH_ERR_ARG, "NULL argument");
+    if (n_clips == 0 || n_clips > (size_t)c->max_batch) return fail(c, WH_ERR_ARG, "n_clips must be 1..max_batch (%d)", c->max_batch);
+    int rc = check_raw_clips(c, clips, n_clips, n_clips == 1 ? (size_t)0x7fffffffu : (size_t)WH_CLIP_SAMPLES, RAW_TOO_LONG);
+    if (rc) return rc;
+    for (size_t i = 0; i < n_clips; i++)
+        if (wh_resampled_len(clips[i].n_frames, clips[i].sample_rate) > cap_samples)
+            return fail(c, WH_ERR_ARG, "pcm_out too small: clip %zu needs %zu samples", i, wh_resampled_len(clips[i].n_frames, clips[i].sample_rate));
+    CTX_HIP(c, hipSetDevice(c->m->device));
+    prof_reset(c);
+    const double t0 = now_s();
+    if ((rc = drop_pending_h2d(c)) || (rc = enc_begin(c))) return rc;
+    hipStream_t s = c->s_enc;
+    c->timing = wh_timing{};
+    if (n_clips == 1) {   // one clip of any length: converted where wh_transcribe_longform_raw converts a file
+        const size_t n = wh_resampled_len(clips[0].n_frames, clips[0].sample_rate);
+        WhIngestPlan plan;
+        wh_ingest_pack(clips, 1, 0, plan);
+        if ((rc = ensure_ingest(c, 0, plan.total_bytes)) || (rc = ensure_long(c, n, wh_mel_frames(n)))) return rc;
+        if ((rc = copy_raw_clips(c, clips, plan, 0, s))) return rc;
+        CTX_HIP(c, hipMemcpyAsync(c->ing_desc, plan.desc.data(), sizeof(WhIngestDesc), hipMemcpyHostToDevice, s));
+        CTX_HIP(c, hipStreamSynchronize(s));
+        c->timing.h2d_s = now_s() - t0;
+        {
+            Prof p(c, WH_KG_MEL);
+            wh_launch_ingest(s, c->ing_raw[0], c->ing_desc, 1, plan.max_out, c->pcm_long);
+        }
+        CTX_HIP(c, hipMemcpyAsync(pcm_out, c->pcm_long, n * 4, hipMemcpyDeviceToHost, s));
+        n_samples_out[0] = n;
+    } else {
+        std::vector<int> nf;
+        if ((rc = stage_raw_batch(c, clips, n_clips, 0, false, nf))) return rc;
+        c->timing.h2d_s = now_s() - t0;
+        {
+            Prof p(c, WH_KG_MEL);
+            wh_launch_ingest(s, c->ing_raw[0], c->ing_desc, (int)n_clips, c->ing_max_out, c->pcm);
+        }
+        c->ing_n = 0;
+        for (size_t i = 0; i < n_clips; i++) {
+            n_samples_out[i] = wh_resampled_len(clips[i].n_frames, clips[i].sample_rate);
+            CTX_HIP(c, hipMemcpyAsync(pcm_out + i * cap_samples, c->pcm + i * WH_CLIP_SAMPLES, n_samples_out[i] * 4, hipMemcpyDeviceToHost, s));
+        }
+    }
+    CTX_HIP(c, hipStreamSynchronize(s));
+    CTX_HIP(c, hipGetLastError());
+    c->timing.preprocess_s = c->timing.total_s = now_s() - t0;
+    prof_collect(c);
+    return WH_OK;
+}
+
+int wh_transcribe_batch_raw_next(wh_ctx* c, const wh_raw_clip* clips, size_t n_clips, const wh_raw_clip* next, size_t n_next,
+                                 const wh_decode_params* p, int64_t* tokens_out, size_t* n_tokens_out) {
+    if (!c) return WH_ERR_ARG;
+    int rc = check_params(c, p);
+    if (rc) return rc;
+    if (!clips || !tokens_out || !n_tokens_out) return fail(c, WH_ERR_ARG, "NULL argument");
+    if (n_clips == 0 || n_clips > (size_t)c->max_batch) return fail(c, WH_ERR_ARG, "n_clips must be 1..max_batch (%d)", c->max_batch);
+    rc = prefix_check(c, p, (int)n_clips, false);
+    if (rc) return rc;
+    if ((rc = align_check(c, (int)n_clips)) || (rc = beam_check(c, p, (int)n_clips)) || (rc = sample_check(c, (int)n_clips, false))) return rc;
+    if (next && (n_next == 0 || n_next > (size_t)c->max_batch)) return fail(c, WH_ERR_ARG, "n_next must be 1..max_batch (%d)", c->max_batch);
+    if ((rc = check_raw_clips(c, clips, n_clips, WH_CLIP_SAMPLES, RAW_TOO_LONG))) return rc;
+    if (next && (rc = check_raw_clips(c, next, n_next, WH_CLIP_SAMPLES, RAW_TOO_LONG))) return rc;
+    CTX_HIP(c, hipSetDevice(c->m->device));
+    prof_reset(c);
+    const double t0 = now_s();
+    auto same = [](const wh_raw_clip& a, const wh_raw_clip& b) {
+        return a.data == b.data && a.n_frames == b.n_frames && a.sample_rate == b.sample_rate && a.channels == b.channels && a.format == b.format;
+    };
+    // this batch's raw bytes: already on their way (copied beside the previous call's work), or copied now
+    bool hit = c->h2d_valid && c->h2d_is_raw && c->h2d_raw_clips.size() == n_clips;
+    for (size_t i = 0; hit && i < n_clips; i++) hit = same(c->h2d_raw_clips[i], clips[i]);
+    if (!hit && (rc = drop_pending_h2d(c))) return rc;   // (an f32 prefetch may be on its way into c->pcm, a raw one into the buffer reused now)
+    const int k = hit ? c->h2d_buf : 0;
+    WhIngestPlan plan_next;
+    if (next) {   // both staging buffers exist before anything is launched: a refusal for memory leaves no work behind
+        wh_ingest_pack(next, n_next, WH_CLIP_SAMPLES, plan_next);
+        if ((rc = ensure_copy_stream(c)) || (rc = ensure_ingest(c, k ^ 1, plan_next.total_bytes))) return rc;
+    }
+    if ((rc = enc_begin(c))) return rc;
+    c->pre_valid = false;
+    c->timing = wh_timing{};
+    if (hit) CTX_HIP(c, hipStreamWaitEvent(c->s_enc, c->ev_h2d, 0));
+    c->h2d_valid = false;
+    std::vector<int> nf;
+    if ((rc = stage_raw_batch(c, clips, n_clips, k, hit, nf))) { c->ing_n = 0; return rc; }
+    c->timing.h2d_s = now_s() - t0;   // (a prefetched batch: what was left of its copy)
+    std::function<int()> copy_next;
+    if (next) {
+        // issued once this batch's conversion, log-mel, encoder and cross-K/V step are enqueued, as wh_transcribe_batch_next does
+        copy_next = [c, next, n_next, k, plan_next]() -> int {
+            int rc2 = copy_raw_clips(c, next, plan_next, k ^ 1, c->s_copy);
+            if (rc2) return rc2;
+            CTX_HIP(c, hipEventRecord(c->ev_h2d, c->s_copy));
+            c->h2d_is_raw = true;
+            c->h2d_buf = k ^ 1;
+            c->h2d_raw_clips.assign(next, next + n_next);
+            c->h2d_n = (int)n_next;
+            c->h2d_valid = true;
+            return WH_OK;
+        };
+    }
+    c->enc_nframes = nf;
+    rc = transcribe_resident(c, c->pcm, (int)n_clips, false, nullptr, 0, p, tokens_out, n_tokens_out, t0, copy_next);
+    c->ing_n = 0;
+    return rc;
+}
+
+int wh_transcribe_batch_raw(wh_ctx* c, const wh_raw_clip* clips, size_t n_clips, const wh_decode_params* p, int64_t* tokens_out,
+                            size_t* n_tokens_out) {
+    return wh_transcribe_batch_raw_next(c, clips, n_clips, nullptr, 0, p, tokens_out, n_tokens_out);
+}
+
+int wh_transcribe_longform_raw(wh_ctx* c, const wh_raw_clip* file, double chunk_length_s, double overlap_s, const wh_decode_params* p,
+                               int64_t* tokens_out, size_t* n_tokens_out, size_t cap_chunks, size_t* n_chunks_out) {
+    if (!c) return WH_ERR_ARG;
+    int rc = check_params(c, p);
+    if (rc) return rc;
+    if (!file || !tokens_out || !n_tokens_out || !n_chunks_out) return fail(c, WH_ERR_ARG, "NULL argument");
+    if ((rc = check_raw_clips(c, file, 1, 0x7fffffffu, "longer than 2^31 samples"))) return rc;
+    const size_t n = wh_resampled_len(file->n_frames, file->sample_rate);
+    CTX_HIP(c, hipSetDevice(c->m->device));
+    if ((rc = drop_pending_h2d(c))) return rc;   // (staging buffer 0 may hold a prefetched raw batch)
+    if ((rc = ensure_ingest(c, 0, file->n_frames * file->channels * wh_pcm_sample_bytes(file->format)))) return rc;
+    return longform_impl(c, nullptr, file, n, chunk_length_s, overlap_s, p, tokens_out, n_tokens_out, cap_chunks, n_chunks_out);
 }
 
 }  // extern "C"

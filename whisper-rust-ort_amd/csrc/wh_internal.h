@@ -194,6 +194,18 @@ struct wh_ctx {
     int h2d_n = 0;
     bool h2d_valid = false;
     std::vector<int> h2d_ns, h2d_nf;  // its per-clip sample / frame counts
+    // raw audio ingest: two grow-only staging buffers for the clips' raw bytes (the batch being converted, and the next batch's
+    // prefetch on the copy stream) and the descriptors' device copy; allocated by the first raw entry that needs them
+    void* ing_raw[2] = {nullptr, nullptr};
+    size_t ing_raw_cap[2] = {0, 0};
+    struct WhIngestDesc* ing_desc = nullptr;   // [max_batch]
+    // the conversion the next encoder pass runs before its log-mel (inside the pass's preprocess events); n == 0: none
+    int ing_n = 0, ing_buf = 0;
+    size_t ing_max_out = 0;
+    int ing_last_n = 0, ing_last_buf = 0;      // the last conversion into c->pcm (measurement hook wh_debug_ingest_times)
+    size_t ing_last_max_out = 0;
+    bool h2d_is_raw = false;                   // the pending prefetch is a raw batch in ing_raw[h2d_buf] (else f32 PCM in pcm / pcm2)
+    std::vector<wh_raw_clip> h2d_raw_clips;    // its clips, every field
     int tok_ld = 0;
     int mpad = 16;              // row pitch of the k-slab-major decode activations (multiple of 16)
     int cross_splits = 1;

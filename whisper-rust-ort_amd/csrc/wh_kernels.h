@@ -209,6 +209,10 @@ struct DecodeState {
     float* logprob = nullptr;   // [B][tok_ld], indexed like out_tokens: the log-probability of each recorded token (k_argmax_finish<T, RULES, true>)
 };
 
+// raw audio ingest (wh_ingest.hip): n_clips descriptors (wh_ingest_desc.h, device memory) -> n_out 16 kHz mono f32 samples in
+// row dst_row of `out` each, from the interleaved samples at raw + raw_off; max_out = the longest n_out of the batch
+struct WhIngestDesc;
+void wh_launch_ingest(hipStream_t s, const void* raw, const WhIngestDesc* descs, int n_clips, size_t max_out, float* out);
 void wh_build_mel_tables(int n_mels, std::vector<double>& tw, std::vector<float>& win, std::vector<float>& fbT);
 void wh_launch_mel_stft(hipStream_t s, const float* pcm, long pcm_stride, const int* n_samples, int n_clips,
                         long max_frames, const double* tw, const float* win, const float* fbT, int n_mels, float* raw,

@@ -323,11 +323,14 @@ inline std::vector<float> resample_linear(const std::vector<float>& x, uint32_t 
     return y;
 }
 
-// Decodes PCM WAV (U8 / S16 / IEEE F32), channel-mean downmix (:266-302), resample to 16 kHz.
-inline void load_audio_16k_mono(const std::string& path, std::vector<float>& out, double* dur_s) {
+// The RIFF walk of the loader: the whole file in `d`, the fmt chunk's fields and the data chunk's place in it.
+struct WavLayout {
+    uint32_t fmt = 0, ch = 0, sr = 0, bits = 0;
+    size_t data_off = 0, data_len = 0;
+};
+inline WavLayout read_wav_layout(const std::string& path, std::vector<unsigned char>& d) {
     FILE* f = fopen(path.c_str(), "rb");
     if (!f) throw std::runtime_error("Failed to open audio: " + path);
-    std::vector<unsigned char> d;
     unsigned char buf[1 << 16];
     size_t n;
     while ((n = fread(buf, 1, sizeof buf, f)) > 0) d.insert(d.end(), buf, buf + n);
@@ -336,22 +339,58 @@ inline void load_audio_16k_mono(const std::string& path, std::vector<float>& out
     auto u32 = [&](size_t o) { return u16(o) | (u16(o + 2) << 16); };
     if (d.size() < 12 || memcmp(d.data(), "RIFF", 4) || memcmp(d.data() + 8, "WAVE", 4))
         throw std::runtime_error("Unsupported container (only RIFF/WAVE is decoded here): " + path);
-    uint32_t fmt = 0, ch = 0, sr = 0, bits = 0;
-    size_t data_off = 0, data_len = 0, p = 12;
+    WavLayout w;
+    size_t p = 12;
     while (p + 8 <= d.size()) {
         uint32_t len = u32(p + 4);
         if (!memcmp(d.data() + p, "fmt ", 4) && p + 8 + 16 <= d.size()) {
-            fmt = u16(p + 8); ch = u16(p + 10); sr = u32(p + 12); bits = u16(p + 22);
-            if (fmt == 0xFFFE && len >= 26) fmt = u16(p + 8 + 24);  // WAVE_FORMAT_EXTENSIBLE sub-format
+            w.fmt = u16(p + 8); w.ch = u16(p + 10); w.sr = u32(p + 12); w.bits = u16(p + 22);
+            if (w.fmt == 0xFFFE && len >= 26) w.fmt = u16(p + 8 + 24);  // WAVE_FORMAT_EXTENSIBLE sub-format
         } else if (!memcmp(d.data() + p, "data", 4)) {
-            data_off = p + 8;
-            data_len = std::min<size_t>(len, d.size() - data_off);
+            w.data_off = p + 8;
+            w.data_len = std::min<size_t>(len, d.size() - w.data_off);
             break;
         }
         p += 8 + len + (len & 1);
     }
-    if (!sr) throw std::runtime_error("Unknown sample rate");
-    if (!ch) throw std::runtime_error("Unknown channels");
+    if (!w.sr) throw std::runtime_error("Unknown sample rate");
+    if (!w.ch) throw std::runtime_error("Unknown channels");
+    return w;
+}
+
+// The file's samples as it holds them (whisper_bench --gpu-ingest, wh_transcribe_batch_raw*): the same walk, the same refusals with the same
+// texts as load_audio_16k_mono, and no conversion.  `format` is the C ABI's WH_PCM_* (S16 0, U8 1, F32 2).
+struct RawWav {
+    std::vector<unsigned char> file;   // the whole file; the payload is file[data_off .. data_off + n_bytes)
+    size_t data_off = 0, n_bytes = 0, n_frames = 0;
+    uint32_t sample_rate = 0, channels = 0;
+    int format = -1;
+    const unsigned char* payload() const { return file.data() + data_off; }
+};
+inline RawWav read_wav_raw(const std::string& path) {
+    RawWav r;
+    const WavLayout w = read_wav_layout(path, r.file);
+    const size_t bps = w.bits / 8;
+    r.n_frames = bps ? w.data_len / (bps * w.ch) : 0;
+    if (w.fmt == 1 && w.bits == 8) r.format = 1;
+    else if (w.fmt == 1 && w.bits == 16) r.format = 0;
+    else if (w.fmt == 3 && w.bits == 32) r.format = 2;
+    else if (r.n_frames) throw std::runtime_error("Unsupported decoded sample format");  // :303 (the loader meets it at the first sample)
+    r.data_off = w.data_off;
+    r.n_bytes = r.n_frames * bps * w.ch;
+    r.sample_rate = w.sr;
+    r.channels = w.ch;
+    return r;
+}
+
+// Decodes PCM WAV (U8 / S16 / IEEE F32), channel-mean downmix (:266-302), resample to 16 kHz.
+inline void load_audio_16k_mono(const std::string& path, std::vector<float>& out, double* dur_s) {
+    std::vector<unsigned char> d;
+    const WavLayout w = read_wav_layout(path, d);
+    auto u16 = [&](size_t o) { return (uint32_t)d[o] | ((uint32_t)d[o + 1] << 8); };
+    auto u32 = [&](size_t o) { return u16(o) | (u16(o + 2) << 16); };
+    const uint32_t fmt = w.fmt, ch = w.ch, sr = w.sr, bits = w.bits;
+    const size_t data_off = w.data_off, data_len = w.data_len;
     std::vector<float> s;
     const size_t bps = bits / 8, frames = (bps && ch) ? data_len / (bps * ch) : 0;
     s.reserve(frames);
@@ -1030,8 +1069,14 @@ struct PipeItem {
     double dur = 0, load_s = 0;
     float* pin = nullptr;   // samples in a pool buffer instead of `audio`
     size_t n_pin = 0;
-    size_t n() const { return pin ? n_pin : audio.size(); }
+    // a raw payload beside `audio` (whisper_bench --gpu-ingest): the file's samples as it holds them, in `raw.file` or, when they fit, in the
+    // pool buffer `pin`; n_16k = their length once resampled, which is what decides between a batch of one-window files and the long-form entry
+    RawWav raw;
+    bool is_raw = false;
+    size_t n_16k = 0;
+    size_t n() const { return is_raw ? n_16k : pin ? n_pin : audio.size(); }
     const float* data() const { return pin ? pin : audio.data(); }
+    const void* raw_data() const { return pin ? (const void*)pin : (const void*)raw.payload(); }
 };
 
 // Fixed-size staging buffers from caller-supplied alloc / free (page-locked memory in the CLI).  Allocated on first use
@@ -1101,10 +1146,12 @@ inline size_t file_pipeline_pool_size(size_t max_batch, size_t n_workers, int n_
 // them, only what is already loaded) or ONE multi-window file; `next` (may be null) is the batch of one-window files this worker
 // will be given next, already loaded — the place to start its host-to-device copy (wh_transcribe_batch_next); both may throw.
 // Returns the first error ("" = none).  `pool` (optional) stages one-window files; a batch's buffers go back to the pool after
-// the process() call that transcribed it returns.
+// the process() call that transcribed it returns.  `load_raw` (optional) replaces `load`: it fills the item's raw payload, n_16k and dur
+// (it.raw, it.is_raw); a payload of a one-window file that fits a pool buffer (window_samples floats) is staged there like converted samples.
 inline std::string run_file_pipeline(size_t nfiles, int n_loaders, size_t n_workers, size_t max_batch, size_t window_samples, BufferPool* pool,
                                      const std::function<void(size_t, std::vector<float>&, double&)>& load,
-                                     const std::function<void(size_t, std::vector<PipeItem>&, std::vector<PipeItem>*)>& process) {
+                                     const std::function<void(size_t, std::vector<PipeItem>&, std::vector<PipeItem>*)>& process,
+                                     const std::function<void(size_t, PipeItem&)>& load_raw = nullptr) {
     std::mutex mu;
     std::condition_variable cv_items, cv_space;
     std::deque<PipeItem> ready;               // loaded files, in index order
@@ -1134,8 +1181,17 @@ inline std::string run_file_pipeline(size_t nfiles, int n_loaders, size_t n_work
             it.idx = i;
             try {
                 const double tl0 = now();
-                load(i, it.audio, it.dur);
+                if (load_raw) load_raw(i, it);
+                else load(i, it.audio, it.dur);
                 it.load_s = now() - tl0;
+                if (it.is_raw) {
+                    if (pool && it.n_16k <= window_samples && it.raw.n_bytes <= window_samples * sizeof(float) && pool->ensure(pool_size)) {
+                        it.pin = pool->acquire();
+                        if (!it.pin) return;   // aborted: another thread has failed
+                        memcpy(it.pin, it.raw.payload(), it.raw.n_bytes);
+                        std::vector<unsigned char>().swap(it.raw.file);
+                    }
+                } else
                 // one-window files move into a staging buffer of the pool (page-locked in the CLI: the library's host-to-device
                 // copy is then one DMA at link speed; a pageable source goes through the runtime's staging buffers)
                 if (pool && it.audio.size() <= window_samples && pool->ensure(pool_size)) {

@@ -197,6 +197,20 @@ int whh_load_wav(const char* path, float* out, size_t cap, size_t* n, double* du
         return 0;
     } catch (...) { return 1; }
 }
+// read_wav_raw: the payload bytes (up to cap) and info = {format (WH_PCM_*), channels, sample_rate}; 0, or 1 with the refusal's text in err
+int whh_read_wav_raw(const char* path, unsigned char* out, size_t cap, size_t* n_bytes, size_t* n_frames, unsigned* info3, char* err, size_t cap_err) {
+    try {
+        const RawWav r = read_wav_raw(path);
+        *n_bytes = r.n_bytes;
+        *n_frames = r.n_frames;
+        info3[0] = (unsigned)r.format; info3[1] = r.channels; info3[2] = r.sample_rate;
+        if (out) memcpy(out, r.payload(), std::min(cap, r.n_bytes));
+        return 0;
+    } catch (const std::exception& e) {
+        put(e.what(), err, cap_err);
+        return 1;
+    }
+}
 // The CLI's loader / worker pipeline (run_file_pipeline) with stand-in load and process callbacks: file `bad_load` fails to
 // load, the batch holding file `bad_process` fails in the worker (either may be >= nfiles: none), `pool_buffers` staging
 // buffers can be allocated before the allocator runs dry (0 = no pool).  Returns 0 and the number of processed files, or 1

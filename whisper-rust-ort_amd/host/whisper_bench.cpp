@@ -48,6 +48,9 @@ struct Args {
     bool print_plan = false;   // --print-plan: print the device -> context plan of this command line and exit before any device is touched
     size_t synthetic_clips = 0;
     uint64_t seed = 1000;
+    // additive: the loaders only read and parse; sample conversion, downmix and resampling run on the GPU (wh_transcribe_batch_raw_next /
+    // wh_transcribe_longform_raw).  --synthetic-clips ignores it
+    bool gpu_ingest = false;
     // additive: text context (wh_ctx_set_prefixes): ids for every file, or DIR/<audio stem>.txt per file; the prefix on every window of a long file
     std::string prompt_ids, prompt_ids_dir;
     bool prompt_all_windows = false;
@@ -126,6 +129,7 @@ static bool parse_args(int argc, char** argv, Args& a) {
         else if (k == "--write-srt") a.write_srt = a.timestamp_rules = true;
         else if (k == "--write-vtt") a.write_vtt = a.timestamp_rules = true;
         else if (k == "--logprobs") a.logprobs = true;
+        else if (k == "--gpu-ingest") a.gpu_ingest = true;
         else if (k == "--word-timestamps") a.word_timestamps = true;
         else if (k == "--print-plan") a.print_plan = true;
         else if (k == "--prompt-all-windows") a.prompt_all_windows = true;
@@ -135,7 +139,7 @@ static bool parse_args(int argc, char** argv, Args& a) {
                    "[--out-csv F] [--out-json F] [--out-summary-json F] [--intra-op N] [--inter-op N] [--write-txt] "
                    "[--tokenizer-json F] [--timestamps] [--chunk-parallelism N] [--chunk-length-s 30] [--overlap-s 5] "
                    "[--device 0] [--devices 0-7] [--streams-per-gpu 1] [--load-threads N] [--precision bf16|f32|fp8|f16x3] [--max-batch 16] "
-                   "[--synthetic-clips N] [--seed 1000] [--print-plan] [--timestamp-rules] [--write-srt] [--write-vtt] "
+                   "[--synthetic-clips N] [--seed 1000] [--print-plan] [--gpu-ingest] [--timestamp-rules] [--write-srt] [--write-vtt] "
                    "[--logprobs] [--no-speech-threshold X] [--logprob-threshold Y] [--prompt-ids a,b,c] [--prompt-ids-dir DIR] [--prompt-all-windows] "
                    "[--repetition-penalty F] [--no-repeat-ngram-size N] [--beam-size N] [--patience F] [--length-penalty F] [--n-best M] "
                    "[--temperature 0,0.2,...] [--compression-ratio-threshold X]\n"
@@ -543,11 +547,23 @@ static std::vector<std::string> fetch_hypotheses(wh_ctx* ctx, size_t n, const Ar
     return out;
 }
 
+// a pipeline item's raw payload as the C ABI takes it
+static wh_raw_clip raw_clip_of(const PipeItem& it) {
+    wh_raw_clip r{};
+    r.data = it.raw_data();
+    r.n_frames = it.raw.n_frames;
+    r.sample_rate = it.raw.sample_rate;
+    r.channels = (uint16_t)std::min<uint32_t>(it.raw.channels, 0xFFFF);   // (more than WH_MAX_CHANNELS: the library refuses the clip)
+    r.format = (uint16_t)it.raw.format;
+    return r;
+}
+
 static std::string transcribe(wh_ctx* ctx, const std::vector<float>& audio, const Args& a, const Tokenizer* tok,
                               const GenCfg& gen, Timing& t, std::vector<Cue>* cues = nullptr, Conf* conf = nullptr,
                               const LanguageTable* lt = nullptr, Lang* lang = nullptr, const std::vector<int64_t>* prefix = nullptr, WordOut* words = nullptr,
-                              std::string* hyps = nullptr) {
+                              std::string* hyps = nullptr, const wh_raw_clip* raw = nullptr) {
     const double t0 = now_s();
+    const size_t n_audio = raw ? wh_resampled_samples(raw->n_frames, raw->sample_rate) : audio.size();   // (raw: the file is converted on the device)
     if (a.prompts()) {   // the file's text context, on its first window or on every one (no context: an empty prefix)
         const size_t offs[2] = {0, prefix ? prefix->size() : 0};
         wh_prefix_opts po{sizeof(wh_prefix_opts), prefix ? prefix->data() : nullptr, offs, 1, a.prompt_all_windows ? WH_PREFIX_ALL_WINDOWS : WH_PREFIX_FIRST_WINDOW};
@@ -561,13 +577,14 @@ static std::string transcribe(wh_ctx* ctx, const std::vector<float>& audio, cons
     p.suppress = gen.suppress.data(); p.n_suppress = gen.suppress.size();
     p.begin_suppress = gen.begin_suppress.data(); p.n_begin_suppress = gen.begin_suppress.size();
     size_t nch = 0;
-    wh_longform_plan(audio.size(), a.chunk_length_s, a.overlap_s, nullptr, 0, &nch);
+    wh_longform_plan(n_audio, a.chunk_length_s, a.overlap_s, nullptr, 0, &nch);
     const size_t stride = prompt.size() + a.max_new_tokens;
     std::vector<int64_t> toks(std::max<size_t>(1, nch) * stride);
     std::vector<size_t> ntok(std::max<size_t>(1, nch));
     size_t got = 0;
-    int rc = wh_transcribe_longform(ctx, audio.data(), audio.size(), a.chunk_length_s, a.overlap_s, &p, toks.data(),
-                                    ntok.data(), ntok.size(), &got);
+    int rc = raw ? wh_transcribe_longform_raw(ctx, raw, a.chunk_length_s, a.overlap_s, &p, toks.data(), ntok.data(), ntok.size(), &got)
+                 : wh_transcribe_longform(ctx, audio.data(), audio.size(), a.chunk_length_s, a.overlap_s, &p, toks.data(),
+                                          ntok.data(), ntok.size(), &got);
     if (rc) throw std::runtime_error(std::string("libwhisper_hip error ") + std::to_string(rc) + ": " + wh_last_error(ctx));
     wh_timing wt{};
     wh_get_timings(ctx, &wt);
@@ -587,7 +604,7 @@ static std::string transcribe(wh_ctx* ctx, const std::vector<float>& audio, cons
     const double td0 = now_s();
     std::vector<std::string> texts;
     std::vector<size_t> offs(std::max<size_t>(1, got));
-    if (a.timestamp_rules || a.word_timestamps) wh_longform_plan(audio.size(), a.chunk_length_s, a.overlap_s, offs.data(), offs.size(), &nch);
+    if (a.timestamp_rules || a.word_timestamps) wh_longform_plan(n_audio, a.chunk_length_s, a.overlap_s, offs.data(), offs.size(), &nch);
     std::vector<std::vector<Segment>> wsegs;
     std::vector<double> wstart;
     for (size_t c = 0; c < got; c++) {  // :926-943
@@ -598,12 +615,12 @@ static std::string transcribe(wh_ctx* ctx, const std::vector<float>& audio, cons
         const bool skip = a.logprobs && window_conf(a, g, lps.data() + c * a.max_new_tokens, nss[c], sp.eot, conf ? *conf : unused, avg_lp);
         if (skip) g.clear();   // the silence rule: empty text, no segments
         if (a.word_timestamps && words) {
-            const size_t wlen = std::min<size_t>(audio.size() - offs[c], (size_t)std::llround(a.chunk_length_s * 16000.0));
+            const size_t wlen = std::min<size_t>(n_audio - offs[c], (size_t)std::llround(a.chunk_length_s * 16000.0));
             window_words(a, g, frames.data() + c * a.max_new_tokens, sp, (double)wlen / 16000.0, (double)offs[c] / 16000.0, tok, *words);
         }
         if (!g.empty() && g.back() == sp.eot) g.pop_back();
         if (a.timestamp_rules) {
-            const size_t len = std::min<size_t>(audio.size() - offs[c], (size_t)std::llround(a.chunk_length_s * 16000.0));
+            const size_t len = std::min<size_t>(n_audio - offs[c], (size_t)std::llround(a.chunk_length_s * 16000.0));
             wsegs.push_back(skip ? std::vector<Segment>() : window_segments(g, sp, (double)len / 16000.0));
             if (a.logprobs) set_conf(wsegs.back(), avg_lp, nss[c]);
             wstart.push_back((double)offs[c] / 16000.0);
@@ -790,6 +807,14 @@ int main(int argc, char** argv) {
             if (a.synthetic_clips) { audio = synthetic_clip(a.seed + idx); dur = (double)audio.size() / 16000.0; }
             else load_audio_16k_mono(a.audio_dir + "/" + files[idx], audio, &dur);
         };
+        // --gpu-ingest: the loader reads and parses only (wh_host.h read_wav_raw); duration_s is the resampled length over 16000, as above
+        auto load_raw = [&](size_t idx, PipeItem& it) {
+            it.raw = read_wav_raw(a.audio_dir + "/" + files[idx]);
+            it.is_raw = true;
+            it.n_16k = wh_resampled_samples(it.raw.n_frames, it.raw.sample_rate);
+            it.dur = (double)it.n_16k / 16000.0;
+        };
+        const bool gpu_ingest = a.gpu_ingest && !a.synthetic_clips;
         if (a.warmup > 0) {  // :1131-1152
             std::vector<float> a0; double d0;
             load(0, a0, d0);
@@ -824,7 +849,10 @@ int main(int argc, char** argv) {
                 Result& r = results[batch[0].idx];
                 if (a.ladder())   // (the re-decode needs the windows' encoder states resident: the long-form entry keeps its last device batch's only)
                     throw std::runtime_error("--temperature: " + files[batch[0].idx] + " is longer than one 30 s window; the ladder is built for one-window files");
-                r.text = transcribe(ctx, batch[0].audio, a, &tok, gen, r.t, &r.cues, &r.conf, lang_auto ? &lang_table : nullptr, &r.lang, &file_prefix[batch[0].idx], &r.words, &r.hyps);
+                wh_raw_clip rc0{};
+                if (batch[0].is_raw) rc0 = raw_clip_of(batch[0]);
+                r.text = transcribe(ctx, batch[0].audio, a, &tok, gen, r.t, &r.cues, &r.conf, lang_auto ? &lang_table : nullptr, &r.lang, &file_prefix[batch[0].idx], &r.words, &r.hyps,
+                                    batch[0].is_raw ? &rc0 : nullptr);
                 r.dur = batch[0].dur; r.load_s = batch[0].load_s; r.ok = true;
             } else {
                 // the per-window body of transcribe_longform_chunked (:870-915) for a batch of one-window files
@@ -835,8 +863,15 @@ int main(int argc, char** argv) {
                 p.suppress = gen.suppress.data(); p.n_suppress = gen.suppress.size();
                 p.begin_suppress = gen.begin_suppress.data(); p.n_begin_suppress = gen.begin_suppress.size();
                 std::vector<wh_clip> clips(batch.size()), nclips(next ? next->size() : 0);
-                for (size_t k = 0; k < batch.size(); k++) { clips[k].pcm = batch[k].data(); clips[k].n_samples = batch[k].n(); }
-                for (size_t k = 0; k < nclips.size(); k++) { nclips[k].pcm = (*next)[k].data(); nclips[k].n_samples = (*next)[k].n(); }
+                const bool raw = batch[0].is_raw;   // --gpu-ingest: every item of the run carries the file's own samples
+                std::vector<wh_raw_clip> rclips(raw ? batch.size() : 0), rnext(raw && next ? next->size() : 0);
+                if (raw) {
+                    for (size_t k = 0; k < batch.size(); k++) rclips[k] = raw_clip_of(batch[k]);
+                    for (size_t k = 0; k < rnext.size(); k++) rnext[k] = raw_clip_of((*next)[k]);
+                } else {
+                    for (size_t k = 0; k < batch.size(); k++) { clips[k].pcm = batch[k].data(); clips[k].n_samples = batch[k].n(); }
+                    for (size_t k = 0; k < nclips.size(); k++) { nclips[k].pcm = (*next)[k].data(); nclips[k].n_samples = (*next)[k].n(); }
+                }
                 if (a.prompts()) {   // every file of the batch with its own text context
                     std::vector<int64_t> ids;
                     std::vector<size_t> offs(1, 0);
@@ -854,7 +889,8 @@ int main(int argc, char** argv) {
                 std::vector<WindowScore> scores;
                 if (!a.ladder()) {
                     // the next batch of this worker, if it is loaded already, is copied to the device beside this batch's work
-                    int rc = wh_transcribe_batch_next(ctx, clips.data(), clips.size(), nclips.empty() ? nullptr : nclips.data(), nclips.size(), &p, toks.data(), ntok.data());
+                    int rc = raw ? wh_transcribe_batch_raw_next(ctx, rclips.data(), rclips.size(), rnext.empty() ? nullptr : rnext.data(), rnext.size(), &p, toks.data(), ntok.data())
+                                 : wh_transcribe_batch_next(ctx, clips.data(), clips.size(), nclips.empty() ? nullptr : nclips.data(), nclips.size(), &p, toks.data(), ntok.data());
                     if (rc) throw std::runtime_error(std::string("libwhisper_hip error ") + std::to_string(rc) + ": " + wh_last_error(ctx));
                     wh_get_timings(ctx, &wt);
                     if (a.logprobs) fetch_logprobs(ctx, batch.size(), a.max_new_tokens, lps, nss);
@@ -877,7 +913,8 @@ int main(int argc, char** argv) {
                                    std::vector<int64_t> toks2(n * stride);
                                    std::vector<size_t> ntok2(n);
                                    size_t got = 0;
-                                   const int rc = rung == 0 ? wh_transcribe_batch(ctx, clips.data(), n, &p, toks2.data(), ntok2.data())
+                                   const int rc = rung == 0 ? (raw ? wh_transcribe_batch_raw(ctx, rclips.data(), n, &p, toks2.data(), ntok2.data())
+                                                                   : wh_transcribe_batch(ctx, clips.data(), n, &p, toks2.data(), ntok2.data()))
                                                             : wh_decode_greedy_batch(ctx, &p, toks2.data(), stride, ntok2.data(), n, &got, nullptr, 0);
                                    if (rc) throw std::runtime_error(std::string("libwhisper_hip error ") + std::to_string(rc) + ": " + wh_last_error(ctx));
                                    if (rung == 0) wh_get_timings(ctx, &wt);
@@ -955,7 +992,8 @@ int main(int argc, char** argv) {
         const size_t files_per_batch = (size_t)(a.max_batch / std::max(1, a.beam() ? a.beam_size : 1));   // beam search: a file takes beam_size rows
         if (a.synthetic_clips) pool.ensure(file_pipeline_pool_size(files_per_batch, ctxs.size(), n_loaders));
         const double loop0 = now_s();
-        const std::string first_error = run_file_pipeline(nfiles, n_loaders, ctxs.size(), files_per_batch, (size_t)WH_CLIP_SAMPLES, &pool, load, process);
+        const std::string first_error = run_file_pipeline(nfiles, n_loaders, ctxs.size(), files_per_batch, (size_t)WH_CLIP_SAMPLES, &pool, load, process,
+                                                          gpu_ingest ? std::function<void(size_t, PipeItem&)>(load_raw) : nullptr);
         const double loop_s = now_s() - loop0;
         if (!first_error.empty()) throw std::runtime_error(first_error);
 
@@ -1009,6 +1047,7 @@ int main(int argc, char** argv) {
                             // second the busiest context spent inside the library (what bench.py measures with PCM resident)
                             .set("wall_s", JVal::num(loop_s)).set("throughput_rtfx", JVal::num(audio_total / std::max(loop_s, 1e-12)))
                             .set("gpu_busy_s", JVal::num(busy_max)).set("gpu_throughput_rtfx", JVal::num(audio_total / std::max(busy_max, 1e-12))));
+        if (gpu_ingest) summary.set("gpu_ingest", JVal::boolean(true));
         if (a.timestamp_rules) summary.set("timestamp_rules", JVal::boolean(true));
         if (a.logprobs) summary.set("logprobs", JVal::boolean(true));
         if (a.have_rep_penalty) summary.set("repetition_penalty", JVal::num(a.rep_penalty));
