@@ -60,7 +60,7 @@ constexpr int ES_ROWB = ES_D * 2;                      // bytes per key row
 constexpr Format ES_F = {32, 32 * ES_ROWB, 4, true, 36};
 
 // qe : [B][8][512] f32 expanded queries (natural-log score units)        E: [B][e_rows][512] bf16 encoder states (final LayerNorm applied),
-// e_rows >= S: the clips' states sit e_rows rows apart (20 rows of padding take the lock-step streams off a common 4 KiB phase, wh_api.cpp)
+// e_rows >= S: the clips' states sit e_rows rows apart (20 rows of padding take the lock-step streams off a common 4 KiB phase, wh_ctx.cpp)
 // out: ctx as the decode GEMM's operand, slab layout [8 * 512 / 32][mpad][32] bf16, column h * 512 + dim
 //
 // Roles.  Waves 0-3 compute; waves 4 .. 3 + NL only load: every LDS-DMA piece of the ring and of the query prefetch is issued by

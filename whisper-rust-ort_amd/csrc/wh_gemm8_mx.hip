@@ -408,7 +408,7 @@ int wh_launch_gemm8_mx(hipStream_t s, int out, const GemmArgs& g) {
 int wh_launch_layernorm_mx(hipStream_t s, const float* x, const float* w, const float* b, void* codes, void* exps, long rows, int d) {
     dim3 grid((unsigned)((rows + 3) / 4));
     unsigned char *cp = (unsigned char*)codes, *ep = (unsigned char*)exps;
-    switch (d) {   // the MX path exists for these widths only (wh_api.cpp: mx_ok)
+    switch (d) {   // the MX path exists for these widths only (wh_ctx.cpp: mx_ok)
         case 256: hipLaunchKernelGGL(k_layernorm_mx<1>, grid, dim3(256), 0, s, x, w, b, cp, ep, rows); break;
         case 512: hipLaunchKernelGGL(k_layernorm_mx<2>, grid, dim3(256), 0, s, x, w, b, cp, ep, rows); break;
         case 1024: hipLaunchKernelGGL(k_layernorm_mx<4>, grid, dim3(256), 0, s, x, w, b, cp, ep, rows); break;

@@ -69,6 +69,30 @@ struct wh_model {
     float *mel_win = nullptr, *mel_fbT = nullptr;
 };
 
+// A hipMalloc'ed block and its size in bytes: move-only, freed by reset() and by the destructor.  A context's buffers are members of wh_ctx, so
+// `delete c` at the end of wh_ctx_free frees them — after the streams have drained and the step graph is gone.  Converts to its T*.
+template <typename T = char>
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; } return *this; }
+    ~DevBuf() { reset(); }
+    void reset() { if (p) hipFree(p); p = nullptr; bytes = 0; }
+    operator T*() const { return (T*)p; }
+};
+
+// the events of a timing hook, N per timed position: adds the N - 1 intervals to ms (nullptr: the call failed before its read-back) and destroys them
+template <size_t N>
+void wh_drain_events(std::vector<std::array<hipEvent_t, N>>& events, double* ms) {
+    for (auto& te : events) {
+        for (size_t i = 0; ms && i + 1 < N; i++) { float t = 0; hipEventElapsedTime(&t, te[i], te[i + 1]); ms[i] += t; }
+        for (auto& e : te) hipEventDestroy(e);
+    }
+    events.clear();
+}
+
 struct wh_ctx {
     wh_model* m = nullptr;
     int max_batch = 1;
@@ -109,14 +133,11 @@ struct wh_ctx {
     hipEvent_t ev[8] = {nullptr};
 
     // ---- device workspace (sized for max_batch clips) ----
-    char* ws = nullptr;
-    size_t ws_bytes = 0;
+    DevBuf<> ws;
     float* pcm = nullptr;       // [B][480000]
-    size_t pcm_cap = 0;         // samples allocated behind `pcm_long` for whole-file mel
-    float* pcm_long = nullptr;  // staged-API / long-form whole file (grown on demand)
-    float* raw_long = nullptr;  // [n_mels][frames] raw log-mel of a whole file (grown on demand)
-    size_t raw_long_cap = 0;    // frames
-    float* mel_out_long = nullptr;
+    DevBuf<float> pcm_long;     // staged-API / long-form whole file (grown on demand)
+    DevBuf<float> raw_long;     // [n_mels][frames] raw log-mel of a whole file (grown on demand)
+    DevBuf<float> mel_out_long;
     int* d_nsamp = nullptr;     // [B]
     int* d_nframes = nullptr;   // [B]
     int* d_src_index = nullptr; // [B]
@@ -182,11 +203,10 @@ struct wh_ctx {
     int *feed = nullptr, *out_tokens = nullptr, *n_out = nullptr, *done = nullptr, *forced = nullptr, *pos = nullptr;
     int* step_ticket = nullptr;  // zeroed at creation, re-armed by its last arriver
     unsigned *mask_first = nullptr, *mask_base = nullptr;
-    float* logits = nullptr;    // optional parity buffer (grown on demand)
-    size_t logits_cap = 0;
+    DevBuf<float> logits;       // optional parity buffer (grown on demand)
     int* logits_sel = nullptr;  // [B]: slot of a batch row in `logits` or -1 (wh_decode_greedy_rows)
     // wh_transcribe_batch_next: the next batch's PCM copied to a second device buffer on a copy stream beside this batch's work
-    float* pcm2 = nullptr;      // [B][480000], allocated at the first call of that entry
+    DevBuf<float> pcm2;         // [B][480000], allocated at the first call of that entry
     hipStream_t s_copy = nullptr;
     hipEvent_t ev_h2d = nullptr;
     int h2d_buf = 0;            // buffer (0: pcm, 1: pcm2) that holds / will hold the prefetched batch
@@ -196,9 +216,8 @@ struct wh_ctx {
     std::vector<int> h2d_ns, h2d_nf;  // its per-clip sample / frame counts
     // raw audio ingest: two grow-only staging buffers for the clips' raw bytes (the batch being converted, and the next batch's
     // prefetch on the copy stream) and the descriptors' device copy; allocated by the first raw entry that needs them
-    void* ing_raw[2] = {nullptr, nullptr};
-    size_t ing_raw_cap[2] = {0, 0};
-    struct WhIngestDesc* ing_desc = nullptr;   // [max_batch]
+    DevBuf<> ing_raw[2];
+    DevBuf<WhIngestDesc> ing_desc;      // [max_batch]
     // the conversion the next encoder pass runs before its log-mel (inside the pass's preprocess events); n == 0: none
     int ing_n = 0, ing_buf = 0;
     size_t ing_max_out = 0;
@@ -211,7 +230,7 @@ struct wh_ctx {
     int cross_splits = 1;
     // the decode GEMMs as LDS-DMA tile GEMMs (wh_dec_tile.hip): decided at creation from the model and the context's capacity
     bool dec_tile = false;
-    // The decode step's key: every call-dependent value an emitting decoder position bakes into kernel arguments.  launch_step (wh_api.cpp)
+    // The decode step's key: every call-dependent value an emitting decoder position bakes into kernel arguments.  launch_step (wh_decode_host.cpp)
     // sees the context and this struct and nothing else of the call, so a value that is not listed here cannot reach the captured step; the
     // context supplies only fixed workspace addresses and the option buffers.  A call with the same key replays the instantiated graph as it
     // is; the graph is destroyed in wh_ctx_free (after the stream has drained) or when the key changes.
@@ -237,136 +256,167 @@ struct wh_ctx {
         auto members() const { return std::tie(nb, n_prompt, eot, n_forced, logits_rows, d_logits, d_sel, ts_begin, ts_max_init, lp_sum, pfx, rep, rep_p, rep_n, al_q, al_cap, al_gen, beam_k, beam_c, beam_buf, sample_buf); }
         bool operator==(const StepKey& o) const { return members() == o.members(); }
     } step_key;
-    // Whisper's timestamp rules (wh_ctx_set_timestamp_rules): off unless ts_on.  The timestamp logits and the per-row state
-    // are allocated when rules are set (not part of the workspace carve; the logits again when timestamp_begin changes) and freed in wh_ctx_free.
-    bool ts_on = false;
-    int64_t ts_begin = 0, ts_no_ts = -1;
-    int ts_max_init = 50;
-    float* ts_logits = nullptr; // [mpad][ts_ld] allowed timestamp logits of the current position (-inf: not allowed)
-    int ts_ld = 0;              // vocab - timestamp_begin
-    int* ts_state = nullptr;    // [mpad][4] {text_lo, ts_lo, ts_hi, last timestamp}
-    // Token log-probabilities and the no-speech probe (wh_ctx_set_logprobs): off unless lp_on.  One allocation made by the setter
-    // (not part of the workspace carve), freed in wh_ctx_free: the (max, sum) partials' sums, the tokens' log-probabilities, an all-zero
+    // ---- the decode options: one struct each, laid out alike — `on` and the settings, the device buffers (DevBuf: freed with the context or
+    // when the struct is reset), what the getter returns for the last call, and the timing hook's fields where the option has one.
+    // reset_results() forgets the last call (check_params, first thing in every decode entry).  DESIGN.md §5g, "An option's state".
+    // Whisper's timestamp rules (wh_ctx_set_timestamp_rules): off unless on.  The timestamp logits and the per-row state
+    // are allocated when rules are set (not part of the workspace carve; the logits again when timestamp_begin changes) and freed with the context.
+    struct TimestampRules {
+        bool on = false;
+        int64_t begin = 0, no_ts = -1;
+        int max_init = 50;
+        int ld = 0;                 // vocab - timestamp_begin
+        DevBuf<float> logits;       // [mpad][ld] allowed timestamp logits of the current position (-inf: not allowed)
+        DevBuf<int> state;          // [mpad][4] {text_lo, ts_lo, ts_hi, last timestamp}
+        void reset_results() {}
+    } ts;
+    // Token log-probabilities and the no-speech probe (wh_ctx_set_logprobs): off unless on.  One allocation made by the setter
+    // (not part of the workspace carve), freed with the context: the (max, sum) partials' sums, the tokens' log-probabilities, an all-zero
     // suppress mask, the probe's logit and its result.
-    bool lp_on = false;
-    int64_t lp_no_speech = -1;
-    int lp_sot_index = 0;
-    char* lp_buf = nullptr;
-    float* lp_part_sum = nullptr;   // [part][mpad], beside part_val / part_idx
-    float* lp_tok = nullptr;        // [max_batch][tok_ld], DecodeState::logprob
-    unsigned* lp_mask_zero = nullptr;
-    float* lp_probe_v = nullptr;    // [mpad] logit of no_speech at the probed position
-    float* lp_ns = nullptr;         // [max_batch] no-speech probability
-    // what wh_get_logprobs returns: the last decode call's clips in the order their tokens were returned (a long-form call: every device batch)
-    bool lp_have = false, lp_have_ns = false;
-    std::vector<std::vector<float>> lp_rows;
-    std::vector<float> lp_ns_rows;
-    // Language detection (wh_ctx_set_language_detection): off unless lang_on.  One allocation made by the setter (not part of the
-    // workspace carve), freed in wh_ctx_free: the id list, the listed ids' logits, the probabilities and the chosen ids.  Lives in the eagerly
+    struct Logprobs {
+        bool on = false;
+        int64_t no_speech = -1;
+        int sot_index = 0;
+        DevBuf<> buf;
+        float* part_sum = nullptr;   // [part][mpad], beside part_val / part_idx
+        float* tok = nullptr;        // [max_batch][tok_ld], DecodeState::logprob
+        unsigned* mask_zero = nullptr;
+        float* probe_v = nullptr;    // [mpad] logit of no_speech at the probed position
+        float* ns = nullptr;         // [max_batch] no-speech probability
+        // what wh_get_logprobs returns: the last decode call's clips in the order their tokens were returned (a long-form call: every device batch)
+        bool have = false, have_ns = false;
+        std::vector<std::vector<float>> rows;
+        std::vector<float> ns_rows;
+        void reset_results() { have = have_ns = false; rows.clear(); ns_rows.clear(); }
+    } lp;
+    // Language detection (wh_ctx_set_language_detection): off unless on.  One allocation made by the setter (not part of the
+    // workspace carve), freed with the context: the id list, the listed ids' logits, the probabilities and the chosen ids.  Lives in the eagerly
     // launched prompt positions only (launch_step's PromptStep): the captured step and its key know nothing of it.
-    bool lang_on = false;
-    int lang_sot_index = 0;
-    std::vector<int64_t> lang_ids;  // the caller's list, in the caller's order
-    char* lang_buf = nullptr;
-    int* lang_d_ids = nullptr;      // [WH_LANG_LD], padded with the first listed id
-    float* lang_logits = nullptr;   // [mpad][WH_LANG_LD]
-    float* lang_probs = nullptr;    // [max_batch][n_lang]
-    int* lang_chosen = nullptr;     // [max_batch]
-    // long-form: the first device batch detects on its row 0 for every row (lang_bcast); later batches of the same call decode with that id
-    // in the prompt (lang_fixed >= 0) and report window 0's probabilities
-    bool lang_bcast = false;
-    int64_t lang_fixed = -1;
-    // what wh_get_languages returns: the last decode call's clips in the order their tokens were returned
-    bool lang_have = false;
-    size_t lang_have_n = 0;         // n_lang of that call
-    std::vector<int64_t> lang_rows;
-    std::vector<float> lang_prob_rows;   // [clips][lang_have_n]
-    // Per-clip prompt prefixes (wh_ctx_set_prefixes): off unless pfx_on.  pfx_off is allocated by the first setter call (not part
-    // of the workspace carve) and freed in wh_ctx_free; upload_token_state fills it per call.  A call whose rows all have empty prefixes passes no
+    struct LanguageDetection {
+        bool on = false;
+        int sot_index = 0;
+        std::vector<int64_t> ids;   // the caller's list, in the caller's order
+        DevBuf<> buf;
+        int* d_ids = nullptr;       // [WH_LANG_LD], padded with the first listed id
+        float* logits = nullptr;    // [mpad][WH_LANG_LD]
+        float* probs = nullptr;     // [max_batch][n_lang]
+        int* chosen = nullptr;      // [max_batch]
+        // long-form: the first device batch detects on its row 0 for every row (bcast); later batches of the same call decode with that id
+        // in the prompt (fixed >= 0) and report window 0's probabilities
+        bool bcast = false;
+        int64_t fixed = -1;
+        // what wh_get_languages returns: the last decode call's clips in the order their tokens were returned
+        bool have = false;
+        size_t have_n = 0;          // n_lang of that call
+        std::vector<int64_t> rows;
+        std::vector<float> prob_rows;   // [clips][have_n]
+        void reset_results() { have = false; rows.clear(); prob_rows.clear(); }
+    } lang;
+    // Per-clip prompt prefixes (wh_ctx_set_prefixes): off unless on.  `off` is allocated by the first setter call (not part
+    // of the workspace carve) and freed with the context; upload_token_state fills it per call.  A call whose rows all have empty prefixes passes no
     // offsets to the kernels and launches what a context without prefixes launches.
-    bool pfx_on = false;
-    std::vector<int64_t> pfx_ids;      // the clips' prefixes back to back (the setter's copy)
-    std::vector<size_t> pfx_offsets;   // [n_clips + 1]
-    int pfx_scope = 0;                 // WH_PREFIX_*
-    int* pfx_off = nullptr;            // [max_batch] device: first live global position of each row (Nmax - n_b)
-    long pfx_win_base = -1;            // long-form: index of the device batch's first window (row b is window pfx_win_base + b); -1: rows are clips
-    // Repetition penalty / no-repeat n-grams (wh_ctx_set_repetition): off unless rep_on.  The bitmap and the side buffer are
-    // allocated by the setter (not part of the workspace carve) and freed when the option is cleared and in wh_ctx_free; upload_token_state clears
-    // the bitmap at the start of a call.
-    bool rep_on = false;
-    float rep_p = 1.0f;
-    int rep_n = 0;
-    int rep_words = 0;                 // ceil(vocab / 32)
-    unsigned* rep_bits = nullptr;      // [max_batch][rep_words] touched ids of each row's current position
-    float* rep_side = nullptr;         // [max_batch][vocab] raw logits of the touched ids (only those entries are written)
-    // Word-level timestamps (wh_ctx_set_alignment): off unless al_on.  The captured step copies the listed heads' queries into
-    // al_q (grown on demand by a call; the step graph is dropped when its address changes); the post-pass of a call works in al_ws, a chunk of
-    // clips at a time.  al_d (frames + per-clip frame counts) is allocated by the setter and freed in wh_ctx_free with the rest.
-    bool al_on = false;
-    unsigned al_gen = 0;                       // counts the setter's calls: the identity of the head list in the step's key
-    std::vector<int> al_heads;                 // [n][2] (layer, head), the caller's order
-    std::vector<int> al_debug;                 // batch rows whose P and M are kept
-    std::vector<AlignLayerHeads> al_layer;     // [dec_layers] the listed heads of each layer
-    float* al_q = nullptr;                     // [n_heads][nb][max_new_tokens][dk] f32
-    size_t al_q_cap = 0;                       // floats
-    char* al_ws = nullptr;                     // post-pass workspace: P, M, the DTW steps of one chunk of clips
-    size_t al_ws_cap = 0;                      // bytes
-    int* al_frames = nullptr;                  // [max_batch][n_text_ctx] frame of each generated token
-    int* al_sb = nullptr;                      // [max_batch] S_b of each row
-    bool al_timing = false;                    // WH_ALIGN_TIMING=1: events around the three post-pass kernels (tools/align_bench.py)
-    double al_ms[3] = {0, 0, 0};               // scores, filter, DTW of the last call, milliseconds
-    std::vector<int> enc_nframes;              // mel frames of each clip whose encoder states are resident (what S_b derives from)
-    // what wh_get_token_frames / wh_get_alignment_debug return: the last decode call's clips in the order their tokens were returned
-    bool al_have = false;
-    std::vector<std::vector<int>> al_rows;
-    std::vector<int> al_nframes;
+    struct Prefixes {
+        bool on = false;
+        std::vector<int64_t> ids;      // the clips' prefixes back to back (the setter's copy)
+        std::vector<size_t> offsets;   // [n_clips + 1]
+        int scope = 0;                 // WH_PREFIX_*
+        long win_base = -1;            // long-form: index of the device batch's first window (row b is window win_base + b); -1: rows are clips
+        DevBuf<int> off;               // [max_batch] device: first live global position of each row (Nmax - n_b)
+        void reset_results() {}
+    } pfx;
+    // Repetition penalty / no-repeat n-grams (wh_ctx_set_repetition): off unless on.  The bitmap and the side buffer are
+    // allocated by the setter (not part of the workspace carve) and freed when the option is cleared and with the context; upload_token_state
+    // clears the bitmap at the start of a call.
+    struct Repetition {
+        bool on = false;
+        float p = 1.0f;
+        int n = 0;
+        int words = 0;                 // ceil(vocab / 32)
+        DevBuf<unsigned> bits;         // [max_batch][words] touched ids of each row's current position
+        DevBuf<float> side;            // [max_batch][vocab] raw logits of the touched ids (only those entries are written)
+        bool held() const { return bits || side; }   // buffers the captured step may hold
+        void reset_results() {}
+    } rep;
+    // Word-level timestamps (wh_ctx_set_alignment): off unless on.  The captured step copies the listed heads' queries into
+    // q (grown on demand by a call; the step graph is dropped when its address changes); the post-pass of a call works in ws, a chunk of
+    // clips at a time.  frames and sb (per-clip frame counts) are allocated by the setter and freed with the context like the rest.
     struct AlignDebug { int n_heads = 0, n_gen = 0, sb = 0; std::vector<float> probs, matrix; };
-    std::vector<AlignDebug> al_dbg;
-    // Beam search (wh_ctx_set_beam_search): off unless bm_on.  The logits scratch and the search state are allocated by the setter
-    // (not part of the workspace carve) and freed when the option is cleared and in wh_ctx_free; the captured step is dropped before that.
-    bool bm_on = false;
-    int bm_k = 0, bm_c = 0;
-    float bm_length_penalty = -1.0f;
-    std::vector<int> bm_trace_clips;
-    float* bm_logits = nullptr;       // [max_batch][vocab] raw logits of the current position
-    char* bm_buf = nullptr;           // the search state, carved into:
-    float* bm_scores = nullptr;       // [max_batch]
-    int* bm_parent = nullptr;         // [max_batch]
-    int* bm_state = nullptr;          // [max_batch][WH_BEAM_STATE]
-    int* bm_pool_n = nullptr;         // [max_batch] per clip
-    int* bm_n_steps = nullptr;        // [max_batch] per clip
-    int* bm_pool = nullptr;           // [max_batch][WH_MAX_BEAM_CANDIDATES][4] per clip
-    int *bm_tr_parent = nullptr, *bm_tr_token = nullptr, *bm_tr_pool = nullptr;   // [tok_ld][max_batch]
-    float *bm_tr_score = nullptr, *bm_tr_lp = nullptr;
-    // what wh_get_beams / wh_get_beam_trace return: the last decode call's clips in the order their tokens were returned
+    struct Alignment {
+        bool on = false;
+        unsigned gen = 0;                       // counts the setter's calls: the identity of the head list in the step's key
+        std::vector<int> heads;                 // [n][2] (layer, head), the caller's order
+        std::vector<int> debug;                 // batch rows whose P and M are kept
+        std::vector<AlignLayerHeads> layer;     // [dec_layers] the listed heads of each layer
+        DevBuf<float> q;                        // [n_heads][nb][max_new_tokens][dk] f32
+        DevBuf<> ws;                            // post-pass workspace: P, M, the DTW steps of one chunk of clips
+        DevBuf<int> frames;                     // [max_batch][n_text_ctx] frame of each generated token
+        DevBuf<int> sb;                         // [max_batch] S_b of each row
+        // what wh_get_token_frames / wh_get_alignment_debug return: the last decode call's clips in the order their tokens were returned
+        bool have = false;
+        std::vector<std::vector<int>> rows;
+        std::vector<int> nframes;
+        std::vector<AlignDebug> dbg;
+        bool timing = false;                    // WH_ALIGN_TIMING=1: events around the three post-pass kernels (tools/align_bench.py)
+        double ms[3] = {0, 0, 0};               // scores, filter, DTW of the last call, milliseconds
+        void reset_results() { have = false; rows.clear(); nframes.clear(); dbg.clear(); }
+    } al;
+    std::vector<int> enc_nframes;              // mel frames of each clip whose encoder states are resident (what alignment's S_b derives from)
+    // Beam search (wh_ctx_set_beam_search): off unless on.  The logits scratch and the search state are allocated by the setter
+    // (not part of the workspace carve) and freed when the option is cleared and with the context; the captured step is dropped before that.
     struct BeamHyp { std::vector<int> tokens; std::vector<float> lps; float sum = 0.0f, rank = 0.0f; bool finished = false; };
     struct BeamTrace { int K = 0, n_steps = 0; std::vector<int> parents, tokens, pool; std::vector<float> scores; };
-    bool bm_timing = false;                    // WH_BEAM_TIMING=1: events around the two kernels of every eagerly launched position (tools/beam_bench.py)
-    std::vector<std::array<hipEvent_t, 3>> bm_events;
-    double bm_ms[2] = {0, 0};                  // k_beam_select, k_beam_reorder of the last call, milliseconds, over bm_timed positions
-    long bm_timed = 0;
-    bool bm_have = false;
-    std::vector<std::vector<BeamHyp>> bm_hyps;
-    std::vector<BeamTrace> bm_traces;
-    // Temperature sampling (wh_ctx_set_sampling): off unless sm_on.  The logits scratch and the per-row values are allocated by
-    // the setter (not part of the workspace carve) and freed when the option is cleared and in wh_ctx_free; the captured step is dropped before
+    struct BeamSearch {
+        bool on = false;
+        int k = 0, c = 0;
+        float length_penalty = -1.0f;
+        std::vector<int> trace_clips;
+        DevBuf<float> logits;          // [max_batch][vocab] raw logits of the current position
+        DevBuf<> buf;                  // the search state, carved into:
+        float* scores = nullptr;       // [max_batch]
+        int* parent = nullptr;         // [max_batch]
+        int* state = nullptr;          // [max_batch][WH_BEAM_STATE]
+        int* pool_n = nullptr;         // [max_batch] per clip
+        int* n_steps = nullptr;        // [max_batch] per clip
+        int* pool = nullptr;           // [max_batch][WH_MAX_BEAM_CANDIDATES][4] per clip
+        int *tr_parent = nullptr, *tr_token = nullptr, *tr_pool = nullptr;   // [tok_ld][max_batch]
+        float *tr_score = nullptr, *tr_lp = nullptr;
+        bool held() const { return logits || buf; }   // buffers the captured step may hold
+        // what wh_get_beams / wh_get_beam_trace return: the last decode call's clips in the order their tokens were returned
+        bool have = false;
+        std::vector<std::vector<BeamHyp>> hyps;
+        std::vector<BeamTrace> traces;
+        bool timing = false;                    // WH_BEAM_TIMING=1: events around the two kernels of every eagerly launched position (tools/beam_bench.py)
+        std::vector<std::array<hipEvent_t, 3>> events;
+        double ms[2] = {0, 0};                  // k_beam_select, k_beam_reorder of the last call, milliseconds, over `timed` positions
+        long timed = 0;
+        void collect_timing() { ms[0] = ms[1] = 0; timed = (long)events.size(); wh_drain_events(events, ms); }
+        void reset_results() { have = false; hyps.clear(); traces.clear(); wh_drain_events(events, nullptr); }   // (events of a call that failed before its read-back)
+    } bm;
+    // Temperature sampling (wh_ctx_set_sampling): off unless on.  The logits scratch and the per-row values are allocated by
+    // the setter (not part of the workspace carve) and freed when the option is cleared and with the context; the captured step is dropped before
     // that.  The setter keeps the caller's lists; upload_token_state writes each call's rows to the device.
-    bool sm_on = false;
-    uint64_t sm_seed = 0;
-    std::vector<float> sm_temp;            // [n_rows]
-    std::vector<uint8_t> sm_active;        // [n_rows]
-    std::vector<uint64_t> sm_ids;          // [n_rows]
-    float* sm_logits = nullptr;            // [max_batch][vocab] raw logits of the current position
-    char* sm_buf = nullptr;                // carved into:
-    float* sm_d_temp = nullptr;            // [max_batch]
-    unsigned long long* sm_d_ids = nullptr;    // [max_batch]
-    unsigned long long* sm_d_seed = nullptr;   // [1]
-    int* sm_state = nullptr;               // [max_batch][4] rule state of each row
-    float* sm_lp = nullptr;                // [max_batch][tok_ld] DecodeState::logprob of a sampling call
-    bool sm_timing = false;                // WH_SAMPLE_TIMING=1: events around k_sample_select of every eagerly launched position (tools/sample_bench.py)
-    std::vector<std::array<hipEvent_t, 2>> sm_events;
-    double sm_ms = 0;                      // k_sample_select of the last call, milliseconds, over sm_timed positions
-    long sm_timed = 0;
+    struct Sampling {
+        bool on = false;
+        uint64_t seed = 0;
+        std::vector<float> temp;            // [n_rows]
+        std::vector<uint8_t> active;        // [n_rows]
+        std::vector<uint64_t> ids;          // [n_rows]
+        DevBuf<float> logits;               // [max_batch][vocab] raw logits of the current position
+        DevBuf<> buf;                       // carved into:
+        float* d_temp = nullptr;            // [max_batch]
+        unsigned long long* d_ids = nullptr;    // [max_batch]
+        unsigned long long* d_seed = nullptr;   // [1]
+        int* state = nullptr;               // [max_batch][4] rule state of each row
+        float* lp = nullptr;                // [max_batch][tok_ld] DecodeState::logprob of a sampling call
+        bool held() const { return logits || buf; }   // buffers the captured step may hold
+        bool timing = false;                // WH_SAMPLE_TIMING=1: events around k_sample_select of every eagerly launched position (tools/sample_bench.py)
+        std::vector<std::array<hipEvent_t, 2>> events;
+        double ms = 0;                      // k_sample_select of the last call, milliseconds, over `timed` positions
+        long timed = 0;
+        void collect_timing() { ms = 0; timed = (long)events.size(); wh_drain_events(events, &ms); }
+        void reset_results() { wh_drain_events(events, nullptr); }
+    } sm;
+    void reset_option_results() { ts.reset_results(); lp.reset_results(); lang.reset_results(); pfx.reset_results(); rep.reset_results(); al.reset_results(); bm.reset_results(); sm.reset_results(); }
     hipGraph_t step_graph = nullptr;
     hipGraphExec_t step_exec = nullptr;
 };

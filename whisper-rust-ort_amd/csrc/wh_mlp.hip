@@ -3,7 +3,7 @@
 //   x[m][:] += W2 · gelu( LN(x[m][:]) · W1^T + b1 ) + b2          and, for the next LayerNorm: bf16 copy of the new row + its partial sums
 //
 // It stands in for the MatMul / Gelu / MatMul / Add nodes of an encoder layer behind run_encoder (reference src/main.rs:698-707,
-// encoder_model.onnx) and replaces two k_gemm8 launches (fc1 + GELU, fc2 + residual) wherever the LayerNorm fold is on (wh_api.cpp).
+// encoder_model.onnx) and replaces two k_gemm8 launches (fc1 + GELU, fc2 + residual) wherever the LayerNorm fold is on (wh_ctx.cpp).
 // Why one kernel: the two GEMMs on their own are bound by the L2 -> LDS stream of 256 x 256 tiles (64 flop per streamed byte), by an
 // epilogue that stores while nothing else runs on the CU (tools/gemm8_stamps.hip: 31-53 % of a workgroup's life), and they move the
 // 2048-wide hidden activations through HBM twice (12.6 GB written + read per layer at 2048 clips).  Here a workgroup owns 128 rows and
