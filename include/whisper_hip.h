@@ -539,6 +539,39 @@ int wh_transcribe_longform(wh_ctx* c, const float* pcm, size_t n_samples, double
                            const wh_decode_params* p, int64_t* tokens_out /* [n_chunks][n_prompt+max_new] */,
                            size_t* n_tokens_out /* [n_chunks] */, size_t cap_chunks, size_t* n_chunks_out);
 
+/* ---- sequential long-form: a resident set of files, and windows cut from it by (file, start frame) ----
+ * What openai-whisper's transcribe(), faster-whisper and HF generate(return_timestamps=True) long-form need from the device: each step decodes
+ * one 30 s window per unfinished file, and where a file's next window starts follows from the timestamps of the one before.  No reference
+ * entry corresponds (the reference cuts fixed windows, src/main.rs:875-882).  The seek rule and the loop are host code
+ * (whisper-rust-ort_amd/host/wh_host.h: seek_advance, run_sequential); the library keeps the files' log-mels and decodes
+ * the rows a step names.
+ * wh_files_load computes every file's whole-file raw log-power mel (any length from 1 sample; the normalisation maximum is global over the
+ * FILE, src/main.rs:870-872, exactly as wh_log_mel) into one ragged device buffer the ctx owns: n_mels * 4 bytes per frame rounded up to 16
+ * frames per file (whisper-base: 115 MB per hour of audio).  n_frames_out[f] = wh_mel_frames(n_samples of file f).  The set stays until the
+ * next load, wh_files_load(c, NULL, 0, ...) (which frees it) or wh_ctx_free; no other entry reads or writes it.  wh_files_load_raw takes the
+ * files as they were read and converts them on the device (as wh_transcribe_longform_raw does); the mels are bit-identical.
+ * Refusals launch nothing and leave the ctx and a loaded set as they were: WH_ERR_ARG for NULL data, n_files > WH_MAX_FILES, a NULL
+ * n_frames_out, a file beyond 2^31 samples or a bad raw descriptor (the cases of wh_ingest_raw); WH_ERR_EMPTY_AUDIO for a file of 0 samples;
+ * WH_ERR_NOMEM if a buffer cannot be grown (the ctx stays usable).  Both wait for and drop a pending prefetch of the _next entries. */
+#define WH_MAX_FILES 4096
+int wh_files_load(wh_ctx* c, const wh_clip* files, size_t n_files, int64_t* n_frames_out /* [n_files] */);
+int wh_files_load_raw(wh_ctx* c, const wh_raw_clip* files, size_t n_files, int64_t* n_frames_out /* [n_files] */);
+/* Row i = the 3000 mel frames of file file[i] of the loaded set from frame seek_frame[i] on (0 <= seek < that file's frames; 100 frames per
+ * second), normalised with that file's maximum and zero-filled in normalised space past the file's last frame (src/main.rs:895-905) — the window
+ * wh_transcribe_longform cuts at sample seek * 160.  The n_rows rows run as ONE batch (window cut, encoder, token loop) exactly as
+ * wh_transcribe_batch runs n_rows clips: tokens_out [n_rows][n_prompt + max_new_tokens], n_tokens_out [n_rows], every per-ctx option (prefixes
+ * and sampling take n_rows entries, beam search allows n_rows * K <= max_batch, alignment's S_b comes from min(3000, frames - seek)), every
+ * wh_get_* and wh_get_timings as after that call.  A file may appear in several rows.  The rows' encoder states stay resident:
+ * wh_decode_greedy_batch decodes the same rows again (the later rungs of a temperature ladder).
+ * Refused before anything is launched: WH_ERR_STATE without a loaded set; WH_ERR_ARG for a file index or seek out of range or n_rows outside
+ * 1 .. max_batch; and whatever the options refuse for a batch of n_rows clips. */
+int wh_transcribe_windows(wh_ctx* c, const int32_t* file, const int64_t* seek_frame, size_t n_rows, const wh_decode_params* p,
+                          int64_t* tokens_out, size_t* n_tokens_out);
+/* Parity entry (as wh_log_mel is for the mel): the window of (file, seek_frame) as the encoder receives it, in wh_encode's input layout
+ * mel_out [n_mels][3000] f32 — cut by the same kernel into the same operand; in the modes whose operand is bf16 (WH_PREC_BF16, WH_PREC_FP8) the
+ * values are the bf16-rounded ones, widened.  Refusals as wh_transcribe_windows. */
+int wh_files_window_mel(wh_ctx* c, int32_t file, int64_t seek_frame, float* mel_out);
+
 /* ---- measurement hooks (bench.py): time named kernel groups with HIP events on the ctx stream -- */
 #define WH_KG_MEL 0
 #define WH_KG_ENC_GEMM 1

@@ -41,7 +41,7 @@ EXPORTS = ("wh_model_load", "wh_model_create", "wh_model_free", "wh_model_get_di
            "wh_ctx_set_language_detection", "wh_get_languages", "wh_ctx_set_prefixes", "wh_ctx_set_repetition",
            "wh_ctx_set_alignment", "wh_get_token_frames", "wh_get_alignment_debug", "wh_ctx_set_beam_search", "wh_get_beams", "wh_get_beam_trace",
            "wh_ctx_set_sampling", "wh_resampled_samples", "wh_ingest_raw", "wh_transcribe_batch_raw", "wh_transcribe_batch_raw_next",
-           "wh_transcribe_longform_raw")
+           "wh_transcribe_longform_raw", "wh_files_load", "wh_files_load_raw", "wh_transcribe_windows", "wh_files_window_mel")
 
 
 class WhisperHipError(RuntimeError):
@@ -250,6 +250,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.wh_ctx_set_sampling.argtypes = [vp, C.POINTER(WhSamplingOpts)]
     L.wh_get_beams.argtypes =[vp, i64p, C.c_size_t, szp, f32p, f32p, i32p, C.c_size_t, szp, C.c_size_t, szp]
     L.wh_get_beam_trace.argtypes = [vp, C.c_size_t, i32p, i32p, f32p, i32p, C.c_size_t, szp]
+    L.wh_files_load.argtypes = [vp, C.POINTER(WhClip), C.c_size_t, i64p]
+    L.wh_files_load_raw.argtypes = [vp, rawp, C.c_size_t, i64p]
+    L.wh_transcribe_windows.argtypes = [vp, i32p, i64p, C.c_size_t, C.POINTER(WhDecodeParams), i64p, szp]
+    L.wh_files_window_mel.argtypes = [vp, C.c_int32, C.c_int64, f32p]
     _lib = L
     return L
 
@@ -746,6 +750,46 @@ class Context:
         self._check(self.lib.wh_transcribe_longform_raw(self.h, cl, chunk_length_s, overlap_s, C.byref(p), _i64(toks), n, k, C.byref(got)))
         return self._took([toks[i, : n[i]].copy() for i in range(int(got.value))], params)
 
+    # --- sequential long-form: a resident file set and windows cut from it -----------------------------------------------
+    def files_load(self, files: Sequence[np.ndarray]) -> List[int]:
+        """wh_files_load: the whole-file log-mels of `files` (16 kHz mono f32, any lengths) become the context's file set; returns each
+        file's frame count.  An empty list frees the set."""
+        arrs = [np.ascontiguousarray(f, np.float32) for f in files]
+        if not arrs:
+            self._check(self.lib.wh_files_load(self.h, None, 0, None))
+            return []
+        cl = (WhClip * len(arrs))(*[WhClip(_f32(a), a.size) for a in arrs])
+        nf = (C.c_int64 * len(arrs))()
+        self._check(self.lib.wh_files_load(self.h, cl, len(arrs), nf))
+        return [int(v) for v in nf]
+
+    def files_load_raw(self, files: Sequence[Tuple[np.ndarray, int]]) -> List[int]:
+        """wh_files_load_raw: the same from files as they were read, (samples [frames, channels], sample_rate) pairs."""
+        if not files:
+            self._check(self.lib.wh_files_load_raw(self.h, None, 0, None))
+            return []
+        cl, keep = raw_clips(files)
+        nf = (C.c_int64 * len(keep))()
+        self._check(self.lib.wh_files_load_raw(self.h, cl, len(keep), nf))
+        return [int(v) for v in nf]
+
+    def transcribe_windows(self, rows: Sequence[Tuple[int, int]], params: DecodeParams) -> List[np.ndarray]:
+        """wh_transcribe_windows: `rows` are (file, seek_frame) pairs of the loaded file set, decoded as one batch."""
+        fi = np.ascontiguousarray([r[0] for r in rows], np.int32)
+        sk = np.ascontiguousarray([r[1] for r in rows], np.int64)
+        p, keep = params.to_c()
+        stride = len(params.prompt) + params.max_new_tokens
+        toks = np.zeros((max(1, len(fi)), stride), np.int64)
+        n = (C.c_size_t * max(1, len(fi)))()
+        self._check(self.lib.wh_transcribe_windows(self.h, fi.ctypes.data_as(C.POINTER(C.c_int32)), _i64(sk), len(fi), C.byref(p), _i64(toks), n))
+        return self._took([toks[i, : n[i]].copy() for i in range(len(fi))], params)
+
+    def files_window_mel(self, file: int, seek_frame: int) -> np.ndarray:
+        """wh_files_window_mel (parity entry): the window as the encoder receives it, [n_mels, 3000] f32."""
+        out = np.empty((self.model.dims.n_mels, WH_N_FRAMES), np.float32)
+        self._check(self.lib.wh_files_window_mel(self.h, file, seek_frame, _f32(out)))
+        return out
+
     # --- measurement -------------------------------------------------------------------------------
     def timings(self) -> dict:
         t = WhTiming()
@@ -907,8 +951,49 @@ def load_host_library(path: str = HOST_LIB_PATH) -> C.CDLL:
         L.whh_language_table.restype = C.c_longlong
         L.whh_words_json.argtypes = [ll, C.POINTER(C.c_int), C.c_size_t, C.c_longlong, C.c_longlong, C.c_double, C.c_double, C.c_char_p, C.c_char_p, C.c_size_t]
         L.whh_words_json.restype = C.c_size_t
+        szp, dp = C.POINTER(C.c_size_t), C.POINTER(C.c_double)
+        L.whh_seek_advance.argtypes = [ll, C.c_size_t, C.c_longlong, C.c_longlong, C.c_longlong, C.c_char_p, C.c_size_t]
+        L.whh_seek_advance.restype = C.c_size_t
+        L.whh_run_sequential.argtypes = [ll, C.c_size_t, ll, dp, ll, C.c_size_t, szp, szp, ll, szp, dp, C.c_size_t, C.c_char_p, C.c_size_t]
+        L.whh_run_sequential.restype = C.c_size_t
         _host = L
     return _host
+
+
+def _ll(values) -> np.ndarray:
+    return np.ascontiguousarray(list(values) or [0], np.int64)
+
+
+def seek_advance(generated: Sequence[int], tb: int, eot: int, seg_frames: int) -> dict:
+    """wh_host.h seek_advance: {"advance": frames, "segments": [{"start", "end", "ids"}]} of one window's generated tokens."""
+    import json
+    t = _ll(generated)
+    L = load_host_library()
+    return json.loads(_host_string(lambda o, c: L.whh_seek_advance(t.ctypes.data_as(C.POINTER(C.c_longlong)), len(generated), tb, eot, seg_frames, o, c)))
+
+
+def run_sequential_scripted(frames: Sequence[int], script: Sequence[Sequence[dict]], tb: int, eot: int, sot_prev: int, n_text_ctx: int, n_prompt: int,
+                            max_new_tokens: int, condition_on_previous_text: bool = True, no_speech_threshold: Optional[float] = None,
+                            logprob_threshold: Optional[float] = None, initial_prompt: Sequence[int] = ()) -> dict:
+    """wh_host.h run_sequential over a scripted step: script[f][k] = {"tokens", "avg_logprob", "no_speech_prob", "temperature"} is what file f's
+    window k decodes to (the file's last entry repeats).  Returns {"steps": [[files]], "files": [{"windows", "segments"}]}."""
+    import json
+    nan = float("nan")
+    ll = C.POINTER(C.c_longlong)
+    entries = [e for f in script for e in f]
+    first = np.ascontiguousarray(np.cumsum([0] + [len(f) for f in script])[:-1], np.uintp)
+    count = np.ascontiguousarray([len(f) for f in script], np.uintp)
+    toks = _ll([t for e in entries for t in e["tokens"]])
+    lens = np.ascontiguousarray([len(e["tokens"]) for e in entries], np.uintp)
+    scores = np.ascontiguousarray([[e.get("avg_logprob", 0.0), e.get("no_speech_prob", 0.0), e.get("temperature", 0.0)] for e in entries], np.float64)
+    fr, ini = _ll(frames), _ll(initial_prompt)
+    cfg_i = _ll([tb, eot, sot_prev, n_text_ctx, n_prompt, max_new_tokens, int(condition_on_previous_text)])
+    cfg_d = np.ascontiguousarray([nan if no_speech_threshold is None else no_speech_threshold, nan if logprob_threshold is None else logprob_threshold], np.float64)
+    szp, dp = C.POINTER(C.c_size_t), C.POINTER(C.c_double)
+    L = load_host_library()
+    return json.loads(_host_string(lambda o, c: L.whh_run_sequential(
+        fr.ctypes.data_as(ll), len(frames), cfg_i.ctypes.data_as(ll), cfg_d.ctypes.data_as(dp), ini.ctypes.data_as(ll), len(initial_prompt),
+        first.ctypes.data_as(szp), count.ctypes.data_as(szp), toks.ctypes.data_as(ll), lens.ctypes.data_as(szp), scores.ctypes.data_as(dp), len(entries), o, c)))
 
 
 def _host_string(call) -> str:

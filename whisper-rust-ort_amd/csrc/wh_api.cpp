@@ -664,4 +664,142 @@ int wh_transcribe_longform_raw(wh_ctx* c, const wh_raw_clip* file, double chunk_
     return longform_impl(c, nullptr, file, n, chunk_length_s, overlap_s, p, tokens_out, n_tokens_out, cap_chunks, n_chunks_out);
 }
 
+// ---- the resident file set and windows cut from it ----
+
+// the common body of the two loads, after their refusals
+static int files_load_impl(wh_ctx* c, const wh_clip* files, const wh_raw_clip* raws, size_t n, int64_t* n_frames_out) {
+    CTX_HIP(c, hipSetDevice(c->m->device));
+    prof_reset(c);
+    const double t0 = now_s();
+    int rc = drop_pending_h2d(c);   // (staging buffer 0 may hold a prefetched raw batch)
+    if (rc) return rc;
+    if ((rc = load_file_set(c, files, raws, n))) return rc;
+    for (size_t f = 0; f < n; f++) n_frames_out[f] = c->fs.host[f].frames;
+    c->timing = wh_timing{};
+    c->timing.preprocess_s = c->timing.total_s = now_s() - t0;
+    prof_collect(c);
+    return WH_OK;
+}
+
+static int files_free(wh_ctx* c) {
+    CTX_HIP(c, hipSetDevice(c->m->device));
+    int rc = drop_pending_h2d(c);
+    if (rc) return rc;
+    c->fs.n = 0;
+    c->fs.host.clear();
+    c->fs.mel.reset();
+    return WH_OK;
+}
+
+int wh_files_load(wh_ctx* c, const wh_clip* files, size_t n_files, int64_t* n_frames_out) {
+    if (!c) return WH_ERR_ARG;
+    if (!files || n_files == 0) return files_free(c);
+    if (n_files > WH_MAX_FILES) return fail(c, WH_ERR_ARG, "n_files must be 1..%d", WH_MAX_FILES);
+    if (!n_frames_out) return fail(c, WH_ERR_ARG, "NULL argument");
+    for (size_t f = 0; f < n_files; f++) {
+        if (files[f].n_samples && !files[f].pcm) return fail(c, WH_ERR_ARG, "file %zu: pcm is NULL", f);
+        if (files[f].n_samples > 0x7fffffffu) return fail(c, WH_ERR_ARG, "file %zu: audio longer than 2^31 samples", f);
+    }
+    for (size_t f = 0; f < n_files; f++)
+        if (files[f].n_samples == 0) return fail(c, WH_ERR_EMPTY_AUDIO, "Empty audio");   // src/main.rs:414-416
+    return files_load_impl(c, files, nullptr, n_files, n_frames_out);
+}
+
+int wh_files_load_raw(wh_ctx* c, const wh_raw_clip* files, size_t n_files, int64_t* n_frames_out) {
+    if (!c) return WH_ERR_ARG;
+    if (!files || n_files == 0) return files_free(c);
+    if (n_files > WH_MAX_FILES) return fail(c, WH_ERR_ARG, "n_files must be 1..%d", WH_MAX_FILES);
+    if (!n_frames_out) return fail(c, WH_ERR_ARG, "NULL argument");
+    if (int rc = check_raw_clips(c, files, n_files, 0x7fffffffu, "longer than 2^31 samples")) return rc;
+    return files_load_impl(c, nullptr, files, n_files, n_frames_out);
+}
+
+// the refusals of a window row, before anything is launched
+static int check_window(wh_ctx* c, int64_t file, int64_t seek, size_t i) {
+    if (file < 0 || (size_t)file >= c->fs.n) return fail(c, WH_ERR_ARG, "row %zu: file %lld outside the set of %zu files", i, (long long)file, c->fs.n);
+    if (seek < 0 || seek >= c->fs.host[file].frames)
+        return fail(c, WH_ERR_ARG, "row %zu: seek %lld outside file %lld's %d frames", i, (long long)seek, (long long)file, c->fs.host[file].frames);
+    return WH_OK;
+}
+
+static int upload_window_rows(wh_ctx* c, const std::vector<int>& rf, const std::vector<int>& rs) {
+    CTX_HIP(c, hipMemcpyAsync(c->fs.rows, rf.data(), rf.size() * 4, hipMemcpyHostToDevice, c->s_enc));
+    CTX_HIP(c, hipMemcpyAsync((int*)c->fs.rows + c->max_batch, rs.data(), rs.size() * 4, hipMemcpyHostToDevice, c->s_enc));
+    CTX_HIP(c, hipStreamSynchronize(c->s_enc));
+    return WH_OK;
+}
+
+int wh_transcribe_windows(wh_ctx* c, const int32_t* file, const int64_t* seek_frame, size_t n_rows, const wh_decode_params* p, int64_t* tokens_out,
+                          size_t* n_tokens_out) {
+    if (!c) return WH_ERR_ARG;
+    int rc = check_params(c, p);
+    if (rc) return rc;
+    if (!file || !seek_frame || !tokens_out || !n_tokens_out) return fail(c, WH_ERR_ARG, "NULL argument");
+    if (c->fs.n == 0) return fail(c, WH_ERR_STATE, "wh_transcribe_windows: no file set is loaded (call wh_files_load first)");
+    if (n_rows == 0 || n_rows > (size_t)c->max_batch) return fail(c, WH_ERR_ARG, "n_rows must be 1..max_batch (%d)", c->max_batch);
+    for (size_t i = 0; i < n_rows; i++)
+        if ((rc = check_window(c, file[i], seek_frame[i], i))) return rc;
+    if ((rc = options_check(c, p, (int)n_rows, false))) return rc;
+    CTX_HIP(c, hipSetDevice(c->m->device));
+    prof_reset(c);
+    const double t0 = now_s();
+    if ((rc = drop_pending_h2d(c)) || (rc = enc_begin(c))) return rc;
+    hipStream_t s = c->s_enc;
+    c->pre_valid = false;   // the resident encoder states are replaced
+    std::vector<int> rf(file, file + n_rows), rs(n_rows), nf(n_rows);
+    for (size_t i = 0; i < n_rows; i++) {
+        rs[i] = (int)seek_frame[i];
+        nf[i] = std::min<int>(WH_N_FRAMES, c->fs.host[rf[i]].frames - rs[i]);   // each window's valid mel frames
+    }
+    if ((rc = upload_window_rows(c, rf, rs))) return rc;
+    c->timing = wh_timing{};
+    c->timing.h2d_s = now_s() - t0;
+    CTX_HIP(c, hipEventRecord(c->enc_ev[c->enc_set][0], s));
+    launch_window_cut(c, (int)n_rows);
+    CTX_HIP(c, hipEventRecord(c->enc_ev[c->enc_set][1], s));
+    if ((rc = run_encoder(c, (int)n_rows, false))) return rc;
+    CTX_HIP(c, hipEventRecord(c->enc_ev[c->enc_set][2], s));
+    c->enc_nframes = nf;
+    if ((rc = run_decode(c, (int)n_rows, p, tokens_out, p->n_prompt + p->max_new_tokens, n_tokens_out, nullptr, 0))) return rc;
+    return finish_timing(c, t0);
+}
+
+int wh_files_window_mel(wh_ctx* c, int32_t file, int64_t seek_frame, float* mel_out) {
+    if (!c) return WH_ERR_ARG;
+    if (!mel_out) return fail(c, WH_ERR_ARG, "NULL argument");
+    if (c->fs.n == 0) return fail(c, WH_ERR_STATE, "wh_files_window_mel: no file set is loaded (call wh_files_load first)");
+    int rc = check_window(c, file, seek_frame, 0);
+    if (rc) return rc;
+    CTX_HIP(c, hipSetDevice(c->m->device));
+    prof_reset(c);
+    const double t0 = now_s();
+    if ((rc = drop_pending_h2d(c)) || (rc = enc_begin(c))) return rc;
+    hipStream_t s = c->s_enc;
+    if ((rc = upload_window_rows(c, std::vector<int>(1, file), std::vector<int>(1, (int)seek_frame)))) return rc;
+    launch_window_cut(c, 1);
+    // the conv1 operand's rows 1 .. 3000 of batch row 0, token-major in the compute dtype -> [n_mels][3000] f32
+    const size_t C = (size_t)c->m->dims.n_mels, esz = c->m->esz;
+    std::vector<char> tok((size_t)WH_N_FRAMES * C * esz);
+    CTX_HIP(c, hipMemcpyAsync(tok.data(), (char*)c->melT + C * esz, tok.size(), hipMemcpyDeviceToHost, s));
+    CTX_HIP(c, hipStreamSynchronize(s));
+    CTX_HIP(c, hipGetLastError());
+    for (size_t t = 0; t < WH_N_FRAMES; t++)
+        for (size_t m = 0; m < C; m++) {
+            float v;
+            if (esz == 4) {
+                memcpy(&v, tok.data() + (t * C + m) * 4, 4);
+            } else {   // bf16: the upper half of the f32
+                uint16_t h;
+                memcpy(&h, tok.data() + (t * C + m) * 2, 2);
+                const uint32_t w = (uint32_t)h << 16;
+                memcpy(&v, &w, 4);
+            }
+            mel_out[m * WH_N_FRAMES + t] = v;
+        }
+    c->timing = wh_timing{};
+    c->timing.preprocess_s = c->timing.total_s = now_s() - t0;
+    prof_collect(c);
+    return WH_OK;
+}
+
 }  // extern "C"

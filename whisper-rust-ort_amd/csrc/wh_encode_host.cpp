@@ -264,6 +264,85 @@ int whole_file_mel(wh_ctx* c, const float* pcm, size_t n, size_t* nf_out, size_t
     return WH_OK;
 }
 
+// ---- the resident file set (wh_files_load) ----------------------------------------------------------------------------
+// Whole-file raw log-mels of n validated files (f32 `files`, or `raws` converted on the device), back to back in c->fs.mel: file f is
+// [n_mels][ld_f] floats at desc[f].base, computed by its own k_mel_stft launch with the arguments whole_file_mel uses — so it is
+// wh_log_mel's result bit for bit.  Every buffer exists before anything is launched or the loaded set is touched: a refusal for memory
+// (WH_ERR_NOMEM) leaves the old set usable.  The files pass through c->pcm_long one at a time, in stream order.
+int load_file_set(wh_ctx* c, const wh_clip* files, const wh_raw_clip* raws, size_t n) {
+    const size_t C = (size_t)c->m->dims.n_mels;
+    std::vector<WhFileDesc> desc(n);
+    std::vector<WhIngestDesc> ing(raws ? n : 0);
+    size_t total = 0, max_n = 0, max_raw = 0;
+    for (size_t f = 0; f < n; f++) {
+        const size_t ns = raws ? wh_resampled_len(raws[f].n_frames, raws[f].sample_rate) : files[f].n_samples;
+        const size_t nf = wh_mel_frames(ns), ld = align_up(nf, 16);
+        desc[f] = WhFileDesc{(long long)total, (int)ld, (int)nf, 0u, (int)ns};
+        total += C * ld;
+        max_n = std::max(max_n, ns);
+        if (raws) {
+            WhIngestPlan one;
+            wh_ingest_pack(raws + f, 1, 0, one);
+            ing[f] = one.desc[0];
+            max_raw = std::max(max_raw, one.total_bytes);
+        }
+    }
+    int rc;
+    if ((rc = grow(c, c->pcm_long, max_n * 4, false, GROW_KEEP_OLD, "the whole-file PCM")) ||
+        (rc = grow(c, c->fs.desc, (size_t)WH_MAX_FILES * sizeof(WhFileDesc), false, GROW_KEEP_OLD, "the file set's descriptors")) ||
+        (rc = grow(c, c->fs.rows, (size_t)2 * c->max_batch * sizeof(int), false, GROW_KEEP_OLD, "the window rows")))
+        return rc;
+    if (raws && ((rc = grow(c, c->ing_raw[0], max_raw, false, GROW_KEEP_OLD, "raw audio staging")) ||
+                 (rc = grow(c, c->fs.ing, (size_t)WH_MAX_FILES * sizeof(WhIngestDesc), false, GROW_KEEP_OLD, "the file set's raw descriptors"))))
+        return rc;
+    DevBuf<float> store;
+    if (total * 4 > c->fs.mel.bytes) {
+        const hipError_t e = hipMalloc(&store.p, total * 4);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, WH_ERR_NOMEM, "the file set's log-mel store (%zu bytes): hipMalloc: %s", total * 4, hipGetErrorString(e));
+        }
+        store.bytes = total * 4;
+    }
+    if ((rc = enc_begin(c))) return rc;
+    hipStream_t s = c->s_enc;
+    c->fs.n = 0;   // from here on the old set is gone
+    c->fs.host.clear();
+    if (store.p) c->fs.mel = std::move(store);
+    CTX_HIP(c, hipMemcpyAsync(c->fs.desc, desc.data(), n * sizeof(WhFileDesc), hipMemcpyHostToDevice, s));
+    if (raws) CTX_HIP(c, hipMemcpyAsync(c->fs.ing, ing.data(), n * sizeof(WhIngestDesc), hipMemcpyHostToDevice, s));
+    for (size_t f = 0; f < n; f++) {
+        char* d = (char*)c->fs.desc.p + f * sizeof(WhFileDesc);
+        if (raws) {
+            CTX_HIP(c, hipMemcpyAsync(c->ing_raw[0], raws[f].data, raws[f].n_frames * raws[f].channels * wh_pcm_sample_bytes(raws[f].format), hipMemcpyHostToDevice, s));
+            Prof p(c, WH_KG_MEL);
+            wh_launch_ingest(s, c->ing_raw[0], (WhIngestDesc*)c->fs.ing + f, 1, ing[f].n_out, c->pcm_long);
+        } else {
+            CTX_HIP(c, hipMemcpyAsync(c->pcm_long, files[f].pcm, files[f].n_samples * 4, hipMemcpyHostToDevice, s));
+        }
+        Prof p(c, WH_KG_MEL);
+        wh_launch_mel_stft(s, c->pcm_long, 0, (const int*)(d + offsetof(WhFileDesc, n_samples)), 1, (long)desc[f].frames, c->m->mel_tw, c->m->mel_win,
+                           c->m->mel_fbT, (int)C, (float*)c->fs.mel + desc[f].base, 0, (long)desc[f].ld, (unsigned*)(d + offsetof(WhFileDesc, gmax)));
+    }
+    CTX_HIP(c, hipStreamSynchronize(s));   // (the host copies of the descriptors, and the caller's files, are read until here)
+    CTX_HIP(c, hipGetLastError());
+    c->fs.host = std::move(desc);
+    c->fs.n = n;
+    return WH_OK;
+}
+
+// the conv1 operand of nb windows of the file set (rows already in c->fs.rows: [0] the files, [1] the seeks) into c->melT
+void launch_window_cut(wh_ctx* c, int nb) {
+    const wh_dims& D = c->m->dims;
+    hipStream_t s = c->s_enc;
+    c->cur = s;
+    Prof p(c, WH_KG_MEL);
+    const int* rf = c->fs.rows;
+    const int* rs = rf + c->max_batch;
+    if (c->m->esz == 4) wh_launch_mel_window<float>(s, c->fs.mel, c->fs.desc, rf, rs, D.n_mels, nb, (float*)c->melT, (long)TOK_ROWS * D.n_mels);
+    else wh_launch_mel_window<bf16>(s, c->fs.mel, c->fs.desc, rf, rs, D.n_mels, nb, (bf16*)c->melT, (long)TOK_ROWS * D.n_mels);
+}
+
 }  // namespace wh
 
 extern "C" {

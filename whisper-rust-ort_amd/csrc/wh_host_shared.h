@@ -130,6 +130,8 @@ int run_encoder(wh_ctx* c, int nb, bool want_f32);
 int run_encoder_pass(wh_ctx* c, const float* pcm, int nb, int set);
 int ensure_long(wh_ctx* c, size_t n, size_t nf);
 int whole_file_mel(wh_ctx* c, const float* pcm, size_t n, size_t* nf_out, size_t* ld_out, const wh_raw_clip* raw = nullptr, double* h2d_s_out = nullptr);
+int load_file_set(wh_ctx* c, const wh_clip* files, const wh_raw_clip* raws, size_t n);
+void launch_window_cut(wh_ctx* c, int nb);
 
 // ---- wh_decode_host.cpp ----
 int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out, size_t tok_stride, size_t* n_tokens_out, float* logits_out,

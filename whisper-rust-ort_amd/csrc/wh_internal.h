@@ -225,6 +225,17 @@ struct wh_ctx {
     size_t ing_last_max_out = 0;
     bool h2d_is_raw = false;                   // the pending prefetch is a raw batch in ing_raw[h2d_buf] (else f32 PCM in pcm / pcm2)
     std::vector<wh_raw_clip> h2d_raw_clips;    // its clips, every field
+    // The resident file set (wh_files_load / wh_files_load_raw): the whole-file raw log-mels of many files in one ragged store,
+    // which wh_transcribe_windows cuts its rows from.  Its own buffers, like an option's: no other entry reads or writes them (raw_long stays
+    // the one-file entries').  Allocated by the first load, grown by a later one that needs more, freed by wh_files_load(NULL, 0) and with the context.
+    struct FileSet {
+        size_t n = 0;                     // files loaded; 0: no set
+        DevBuf<float> mel;                // file f: [n_mels][ld_f] raw log-power at host[f].base
+        DevBuf<WhFileDesc> desc;          // [WH_MAX_FILES] what k_mel_window looks up per row (gmax written by the file's k_mel_stft)
+        DevBuf<WhIngestDesc> ing;         // [WH_MAX_FILES] the raw load's conversion descriptors
+        DevBuf<int> rows;                 // [2][max_batch] the file and the seek of each row of a window call
+        std::vector<WhFileDesc> host;     // the descriptors' host copy (gmax not filled)
+    } fs;
     int tok_ld = 0;
     int mpad = 16;              // row pitch of the k-slab-major decode activations (multiple of 16)
     int cross_splits = 1;

@@ -223,6 +223,20 @@ template <typename T>
 void wh_launch_mel_tokens(hipStream_t s, const float* src, long src_clip_stride, long src_row_stride,
                           const int* src_index, const int* frame_start, const int* n_frames_src, const unsigned* gmax,
                           int mode, int n_mels, int n_out, T* tok, long tok_clip_stride);
+// One file of the resident file set (wh_files_load): its raw log-power mel is [n_mels][ld] floats at store + base.  gmax and
+// n_samples are the operands of that file's k_mel_stft launch (its normalisation maximum, order-encoded, and its sample count).
+struct WhFileDesc {
+    long long base;   // in floats; a multiple of 16
+    int ld;           // row stride: frames rounded up to 16
+    int frames;
+    unsigned gmax;
+    int n_samples;
+};
+static_assert(sizeof(WhFileDesc) == 24, "descriptor layout is shared with the kernel");
+// the conv1 operand of n_rows windows cut out of the file set: row b = 3000 frames of file row_file[b] from frame row_seek[b] on
+template <typename T>
+void wh_launch_mel_window(hipStream_t s, const float* store, const WhFileDesc* files, const int* row_file, const int* row_seek,
+                          int n_mels, int n_rows, T* tok, long tok_clip_stride);
 
 // The GEMM launchers return WH_OK or an error code with the reason in wh_set_error: a launch that cannot run as asked is
 // reported to the caller, never skipped silently (run_encoder / run_decode propagate it).

@@ -308,6 +308,45 @@ __global__ __launch_bounds__(256) void k_mel_tokens(const float* __restrict__ sr
     }
 }
 
+// The same window, cut out of the resident file set (wh_files_load): batch row b is the 3000 frames of file
+// row_file[b] from frame row_seek[b] on.  The source is looked up per row — the file's base offset in the ragged store, its row
+// stride, its frame count and its normalisation maximum —, so the rows of one launch may come from files of any lengths and one
+// file may feed several rows.  One workgroup = one (64-frame tile, row); the transpose through LDS, the zero fill past the file's
+// last frame (in normalised space) and the untouched rows 0 and 3001 are k_mel_tokens's.
+template <typename T>
+__global__ __launch_bounds__(256) void k_mel_window(const float* __restrict__ store, const WhFileDesc* __restrict__ files,
+                                                    const int* __restrict__ row_file, const int* __restrict__ row_seek,
+                                                    int n_mels, T* __restrict__ tok, long tok_clip_stride) {
+    __shared__ float tile[64][65];
+    const int b = blockIdx.y;
+    const WhFileDesc fd = files[row_file[b]];
+    const long fs = row_seek[b];
+    const long nf = fd.frames, ld = fd.ld;
+    const float mx = ord2f(fd.gmax);
+    const int t0 = blockIdx.x * 64;
+    const float* sp = store + fd.base;
+    T* tp = tok + (long)b * tok_clip_stride;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    for (int m0 = 0; m0 < n_mels; m0 += 64) {
+        for (int r = ty; r < 64; r += 4) {
+            int m = m0 + r;
+            long f = fs + t0 + tx;
+            float v = 0.0f;
+            if (m < n_mels && t0 + tx < WH_N_FRAMES && f < nf) {
+                float lv = sp[(long)m * ld + f];
+                v = (fmaxf(lv, mx - 8.0f) + 4.0f) * 0.25f;
+            }
+            tile[r][tx] = v;
+        }
+        __syncthreads();
+        for (int r = ty; r < 64; r += 4) {
+            int t = t0 + r, m = m0 + tx;
+            if (t < WH_N_FRAMES && m < n_mels) tp[(long)(1 + t) * n_mels + m] = cvt_out<T>(tile[tx][r]);
+        }
+        __syncthreads();
+    }
+}
+
 // ---- host-side tables ---------------------------------------------------------------------------
 float hz_to_mel(float hz) {  // src/main.rs:332-341
     const float logstep = 27.0f / logf(6.4f);
@@ -375,6 +414,14 @@ void wh_launch_mel_tokens(hipStream_t s, const float* src, long src_clip_stride,
     hipLaunchKernelGGL(k_mel_tokens<T>, grid, dim3(256), 0, s, src, src_clip_stride, src_row_stride, src_index,
                        frame_start, n_frames_src, gmax, mode, n_mels, tok, tok_clip_stride);
 }
+template <typename T>
+void wh_launch_mel_window(hipStream_t s, const float* store, const WhFileDesc* files, const int* row_file, const int* row_seek,
+                          int n_mels, int n_rows, T* tok, long tok_clip_stride) {
+    dim3 grid((WH_N_FRAMES + 63) / 64, (unsigned)n_rows);
+    hipLaunchKernelGGL(k_mel_window<T>, grid, dim3(256), 0, s, store, files, row_file, row_seek, n_mels, tok, tok_clip_stride);
+}
+template void wh_launch_mel_window<float>(hipStream_t, const float*, const WhFileDesc*, const int*, const int*, int, int, float*, long);
+template void wh_launch_mel_window<bf16>(hipStream_t, const float*, const WhFileDesc*, const int*, const int*, int, int, bf16*, long);
 template void wh_launch_mel_tokens<float>(hipStream_t, const float*, long, long, const int*, const int*, const int*,
                                           const unsigned*, int, int, int, float*, long);
 template void wh_launch_mel_tokens<bf16>(hipStream_t, const float*, long, long, const int*, const int*, const int*,

@@ -170,6 +170,7 @@ struct RowOut {
     double temperature = 0, compression_ratio = 0;
     bool has_prompt = false;  // --prompt-ids / --prompt-ids-dir: the length of the file's text context (<|startofprev|> included; 0: none)
     long long prompt_tokens = 0;
+    std::string windows;      // --sequential: JSON array of the file's windows {seek_s, frames, advance_s, skipped, temperature, tokens}; empty: no key
 };
 
 // avg_logprob / no_speech_prob in JSON: shortest text that reads back as the same float (the library's values are floats); a window in which
@@ -244,6 +245,7 @@ inline std::string per_file_json(const std::vector<RowOut>& rows) {  // :1232 to
         if (rows[i].has_prompt) r.set("prompt_tokens", JVal::integer(rows[i].prompt_tokens));
         if (rows[i].has_conf) { JVal v; v.raw = fmt_conf(rows[i].avg_logprob); r.set("avg_logprob", v); v.raw = fmt_conf(rows[i].no_speech_prob); r.set("no_speech_prob", v); }
         if (rows[i].has_ladder) { JVal v; v.raw = fmt_f32((float)rows[i].temperature); r.set("temperature", v); v.raw = fmt_conf(rows[i].compression_ratio); r.set("compression_ratio", v); }
+        if (!rows[i].windows.empty()) { JVal w; w.raw = rows[i].windows; r.set("windows", w); }
         if (!rows[i].segments.empty()) { JVal sg; sg.raw = rows[i].segments; r.set("segments", sg); }
         if (!rows[i].hypotheses.empty()) { JVal h; h.raw = rows[i].hypotheses; r.set("hypotheses", h); }
         if (!rows[i].words.empty()) { JVal w; w.raw = rows[i].words; r.set("words", w); w.raw = rows[i].token_times; r.set("token_times", w); }
@@ -748,6 +750,171 @@ inline std::vector<Segment> merge_window_segments(const std::vector<std::vector<
         }
     }
     return out;
+}
+
+// ---- sequential long-form (whisper_bench --sequential) --------------------------------------------------------------------
+// openai-whisper's transcribe() without word_timestamps, stated on tokens: where a window's segments end and how far the file advances.
+// `generated` are one window's generated ids (the prompt left out); g = those before the first EOT, ts(i) = g[i] >= tb;
+// cuts = { i >= 1 : ts(i-1) && ts(i) }; single_end = len >= 2 && !ts(len-2) && ts(len-1).
+//   - cuts non-empty: with single_end, len joins the cuts.  One segment per slice [last, c): from (g[last] - tb) * 0.02 s (0 if the slice opens
+//     with text, which the timestamp rules never produce) to (g[c-1] - tb) * 0.02 s.  Text after the last cut is NOT a segment: the next window
+//     decodes it again.  advance = seg_frames if single_end, else (g[c_last - 1] - tb) * 2 frames, c_last the last pair's cut;
+//   - no cuts: one segment from 0 to seg_frames * 0.01 s, or to (t - tb) * 0.02 s where t, the last timestamp among g, lies above tb;
+//     advance = seg_frames;
+//   - a segment with start == end, or without a text id, is dropped.  A kept segment's ids are its slice, timestamps included.
+// Deviation from openai-whisper: an advance of 0 (a closing pair at <|0.00|>) becomes seg_frames — openai-whisper would decode the same
+// window for ever there, and flat synthetic logits do produce it.  The advance may exceed seg_frames at a file's end; the loop ends there.
+struct SeqSegment {
+    double start = 0, end = 0;
+    std::vector<int64_t> ids;   // the slice: text ids and timestamps
+    size_t window = 0;          // run_sequential: the ordinal of its window in the file
+};
+// *consumed (optional): how many of the generated ids the slices cover — what --word-timestamps takes its words from.
+inline int64_t seek_advance(const std::vector<int64_t>& generated, int64_t tb, int64_t eot, int64_t seg_frames, std::vector<SeqSegment>& segs, size_t* consumed = nullptr) {
+    segs.clear();
+    std::vector<int64_t> g;
+    for (int64_t x : generated) {
+        if (x == eot) break;
+        g.push_back(x);
+    }
+    const size_t len = g.size();
+    auto ts = [&](size_t i) { return g[i] >= tb; };
+    auto keep = [&](SeqSegment&& s) {
+        bool text = false;
+        for (int64_t x : s.ids) text = text || x < tb;
+        if (text && s.start != s.end) segs.push_back(std::move(s));
+    };
+    std::vector<size_t> cuts;
+    for (size_t i = 1; i < len; i++)
+        if (ts(i - 1) && ts(i)) cuts.push_back(i);
+    int64_t advance = seg_frames;
+    if (!cuts.empty()) {
+        const bool single_end = len >= 2 && !ts(len - 2) && ts(len - 1);
+        if (!single_end) advance = (g[cuts.back() - 1] - tb) * 2;
+        if (single_end) cuts.push_back(len);
+        size_t last = 0;
+        for (size_t c : cuts) {
+            SeqSegment s;
+            s.start = ts(last) ? (double)(g[last] - tb) * kTimePrecision : 0.0;
+            s.end = (double)(g[c - 1] - tb) * kTimePrecision;
+            s.ids.assign(g.begin() + (long)last, g.begin() + (long)c);
+            keep(std::move(s));
+            last = c;
+        }
+    } else {
+        SeqSegment s;
+        s.end = (double)seg_frames * 0.01;
+        for (size_t i = len; i-- > 0;)
+            if (ts(i)) { if (g[i] > tb) s.end = (double)(g[i] - tb) * kTimePrecision; break; }
+        s.ids = g;
+        keep(std::move(s));
+    }
+    if (consumed) *consumed = cuts.empty() ? len : cuts.back();
+    return advance == 0 ? seg_frames : advance;
+}
+
+// The loop over many files in lockstep: step t decodes, as ONE device batch, the current window of every file that is not finished.
+struct SeqConfig {
+    int64_t tb = 0, eot = 0, sot_prev = 0;
+    int n_text_ctx = 448;
+    size_t n_prompt = 0, max_new_tokens = 0;
+    bool condition_on_previous_text = true;
+    double no_speech_threshold = std::nan(""), logprob_threshold = std::nan("");   // skip_window's; NaN: off
+    std::vector<int64_t> initial_prompt;   // every file's history starts with these ids ...
+    std::vector<std::vector<int64_t>> file_prompts;   // ... or, where this holds an entry for the file, with its own
+};
+struct SeqRow {          // one row of a step
+    size_t file = 0, window = 0;   // the file, and the ordinal of this window in it
+    int64_t seek = 0;
+    int seg_frames = 0;            // min(3000, frames - seek)
+    std::vector<int64_t> prefix;   // [sot_prev] ++ history, or empty
+};
+struct SeqStepResult {   // what step() returns per row
+    std::vector<int64_t> tokens;   // the generated ids
+    double avg_logprob = 0, no_speech_prob = 0, temperature = 0;
+};
+struct SeqWindow {
+    int64_t seek = 0, advance = 0;
+    int seg_frames = 0;
+    bool skipped = false;
+    size_t consumed = 0;           // generated ids its segments cover (seek_advance)
+    std::vector<int64_t> tokens, prefix;
+    double temperature = 0, avg_logprob = 0, no_speech_prob = 0;
+};
+struct SeqFile {
+    std::vector<SeqWindow> windows;
+    std::vector<SeqSegment> segments;   // times in the file
+};
+constexpr int kSeqWindowFrames = 3000;
+constexpr double kSeqPromptResetTemperature = 0.5;   // openai-whisper's constant: a window decoded above it does not condition the next one
+// the row's prefix: build_prev_prefix of the live history, trimmed from the front (the oldest ids go; <|startofprev|> stays) so that
+// prefix + n_prompt + max_new_tokens <= n_text_ctx; no room for a single id: no prefix
+inline std::vector<int64_t> seq_prefix(const std::vector<int64_t>& history, size_t reset_since, const SeqConfig& cfg) {
+    std::vector<int64_t> pre = build_prev_prefix(std::vector<int64_t>(history.begin() + (long)std::min(reset_since, history.size()), history.end()), cfg.sot_prev, cfg.n_text_ctx);
+    const long room = (long)cfg.n_text_ctx - (long)cfg.n_prompt - (long)cfg.max_new_tokens;
+    if ((long)pre.size() <= room) return pre;
+    if (room < 2) return {};
+    std::vector<int64_t> out(1, cfg.sot_prev);
+    out.insert(out.end(), pre.end() - (room - 1), pre.end());
+    return out;
+}
+// frames[f]: mel frames of file f.  step(rows, results) decodes the rows (in file order) and fills one SeqStepResult per row.  Per file:
+// seek = 0, history = the initial prompt, reset_since = 0; per window: a skipped one (skip_window) yields no segments, advances the whole
+// window and leaves the history and reset_since alone (openai-whisper `continue`s there); any other goes through seek_advance, its segments
+// shifted by seek * 0.01 s, their ids appended to the history; then, without conditioning or above the reset temperature, reset_since = the
+// history's length.
+template <typename Step>
+inline void run_sequential(const std::vector<int64_t>& frames, const SeqConfig& cfg, Step&& step, std::vector<SeqFile>& out) {
+    const size_t n = frames.size();
+    out.assign(n, SeqFile());
+    std::vector<int64_t> seek(n, 0);
+    std::vector<std::vector<int64_t>> history(n, cfg.initial_prompt);
+    for (size_t f = 0; f < n && f < cfg.file_prompts.size(); f++) history[f] = cfg.file_prompts[f];
+    std::vector<size_t> reset_since(n, 0);
+    for (;;) {
+        std::vector<SeqRow> rows;
+        for (size_t f = 0; f < n; f++) {
+            if (seek[f] >= frames[f]) continue;
+            SeqRow r;
+            r.file = f;
+            r.window = out[f].windows.size();
+            r.seek = seek[f];
+            r.seg_frames = (int)std::min<int64_t>(kSeqWindowFrames, frames[f] - seek[f]);
+            r.prefix = seq_prefix(history[f], reset_since[f], cfg);
+            rows.push_back(std::move(r));
+        }
+        if (rows.empty()) break;
+        std::vector<SeqStepResult> res(rows.size());
+        step(rows, res);
+        for (size_t i = 0; i < rows.size(); i++) {
+            const size_t f = rows[i].file;
+            SeqWindow w;
+            w.seek = rows[i].seek;
+            w.seg_frames = rows[i].seg_frames;
+            w.prefix = rows[i].prefix;
+            w.tokens = res[i].tokens;
+            w.temperature = res[i].temperature;
+            w.avg_logprob = res[i].avg_logprob;
+            w.no_speech_prob = res[i].no_speech_prob;
+            if (skip_window(res[i].no_speech_prob, res[i].avg_logprob, cfg.no_speech_threshold, cfg.logprob_threshold)) {
+                w.skipped = true;
+                w.advance = w.seg_frames;
+            } else {
+                std::vector<SeqSegment> segs;
+                w.advance = seek_advance(res[i].tokens, cfg.tb, cfg.eot, w.seg_frames, segs, &w.consumed);
+                for (SeqSegment& s : segs) {
+                    s.start += (double)w.seek * 0.01;
+                    s.end += (double)w.seek * 0.01;
+                    s.window = rows[i].window;
+                    history[f].insert(history[f].end(), s.ids.begin(), s.ids.end());
+                    out[f].segments.push_back(std::move(s));
+                }
+                if (!cfg.condition_on_previous_text || res[i].temperature > kSeqPromptResetTemperature) reset_since[f] = history[f].size();
+            }
+            seek[f] += w.advance;
+            out[f].windows.push_back(std::move(w));
+        }
+    }
 }
 
 // "HH:MM:SS,mmm" (SRT) / "HH:MM:SS.mmm" (VTT), rounded to the millisecond

@@ -302,6 +302,70 @@ void whh_run_ladder(size_t n, size_t n_rungs, const double* script, double cr_th
                ro, sc);
     for (size_t w = 0; w < n; w++) rung_of[w] = ro[w];
 }
+// ---- sequential long-form (tests/test_sequential_cpu.py) ----
+static std::string ids_json(const std::vector<int64_t>& v) {
+    std::string o = "[";
+    for (size_t j = 0; j < v.size(); j++) o += (j ? ", " : "") + std::to_string(v[j]);
+    return o + "]";
+}
+static std::string f64_json(double v) {   // round-trips exactly
+    char b[40];
+    snprintf(b, sizeof b, "%.17g", v);
+    return b;
+}
+static std::string seq_segments_json(const std::vector<SeqSegment>& segs) {
+    std::string o = "[";
+    for (size_t i = 0; i < segs.size(); i++)
+        o += std::string(i ? ", " : "") + "{\"start\": " + f64_json(segs[i].start) + ", \"end\": " + f64_json(segs[i].end) + ", \"ids\": " + ids_json(segs[i].ids) + "}";
+    return o + "]";
+}
+// seek_advance: {"advance": frames, "segments": [{"start", "end", "ids"}]}
+size_t whh_seek_advance(const long long* toks, size_t n, long long tb, long long eot, long long seg_frames, char* out, size_t cap) {
+    std::vector<SeqSegment> segs;
+    const int64_t adv = seek_advance(std::vector<int64_t>(toks, toks + n), tb, eot, seg_frames, segs);
+    return put("{\"advance\": " + std::to_string(adv) + ", \"segments\": " + seq_segments_json(segs) + "}", out, cap);
+}
+// run_sequential over a scripted step.  cfg_i = {tb, eot, sot_prev, n_text_ctx, n_prompt, max_new_tokens, condition_on_previous_text}; cfg_d =
+// {no_speech_threshold, logprob_threshold} (NaN: off).  The script is a table of windows: file f's window k is entry first[f] + min(k, count[f] - 1)
+// (the last entry repeats), entry e = lens[e] generated ids of `toks` (back to back) and scores[e] = {avg_logprob, no_speech_prob, temperature}.
+// JSON out: {"steps": [[files of step 0], ...], "files": [{"windows": [...], "segments": [...]}]}.
+size_t whh_run_sequential(const long long* frames, size_t n_files, const long long* cfg_i, const double* cfg_d, const long long* initial_prompt, size_t n_initial,
+                          const size_t* first, const size_t* count, const long long* toks, const size_t* lens, const double* scores, size_t n_entries, char* out,
+                          size_t cap) {
+    SeqConfig cfg;
+    cfg.tb = cfg_i[0]; cfg.eot = cfg_i[1]; cfg.sot_prev = cfg_i[2]; cfg.n_text_ctx = (int)cfg_i[3]; cfg.n_prompt = (size_t)cfg_i[4]; cfg.max_new_tokens = (size_t)cfg_i[5];
+    cfg.condition_on_previous_text = cfg_i[6] != 0;
+    cfg.no_speech_threshold = cfg_d[0]; cfg.logprob_threshold = cfg_d[1];
+    cfg.initial_prompt.assign(initial_prompt, initial_prompt + n_initial);
+    std::vector<size_t> tok_off(n_entries + 1, 0);
+    for (size_t e = 0; e < n_entries; e++) tok_off[e + 1] = tok_off[e] + lens[e];
+    std::string steps = "[";
+    std::vector<SeqFile> files;
+    run_sequential(std::vector<int64_t>(frames, frames + n_files), cfg,
+                   [&](const std::vector<SeqRow>& rows, std::vector<SeqStepResult>& res) {
+                       std::vector<int64_t> fs;
+                       for (size_t i = 0; i < rows.size(); i++) {
+                           const size_t f = rows[i].file, e = first[f] + std::min(rows[i].window, count[f] - 1);
+                           fs.push_back((int64_t)f);
+                           res[i].tokens.assign(toks + tok_off[e], toks + tok_off[e + 1]);
+                           res[i].avg_logprob = scores[e * 3]; res[i].no_speech_prob = scores[e * 3 + 1]; res[i].temperature = scores[e * 3 + 2];
+                       }
+                       steps += (steps.size() > 1 ? ", " : "") + ids_json(fs);
+                   },
+                   files);
+    std::string o = "{\"steps\": " + steps + "], \"files\": [";
+    for (size_t f = 0; f < files.size(); f++) {
+        o += std::string(f ? ", " : "") + "{\"windows\": [";
+        for (size_t k = 0; k < files[f].windows.size(); k++) {
+            const SeqWindow& w = files[f].windows[k];
+            o += std::string(k ? ", " : "") + "{\"seek\": " + std::to_string(w.seek) + ", \"seg_frames\": " + std::to_string(w.seg_frames) + ", \"advance\": " + std::to_string(w.advance) +
+                 ", \"skipped\": " + (w.skipped ? "true" : "false") + ", \"temperature\": " + f64_json(w.temperature) + ", \"tokens\": " + ids_json(w.tokens) +
+                 ", \"prefix\": " + ids_json(w.prefix) + "}";
+        }
+        o += "], \"segments\": " + seq_segments_json(files[f].segments) + "}";
+    }
+    return put(o + "]}", out, cap);
+}
 // parse_temperatures: the count (out: up to cap values), or -1 with the message in err
 long whh_parse_temperatures(const char* txt, float* out, size_t cap, char* err, size_t ecap) {
     try {

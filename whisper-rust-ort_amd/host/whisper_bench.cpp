@@ -68,6 +68,11 @@ struct Args {
     // option not set; --seed also seeds the sampler
     std::vector<float> temperature = {0.0f};
     double compression_ratio_threshold = std::nan("");
+    // additive: sequential long-form (wh_files_load / wh_transcribe_windows; wh_host.h run_sequential): a worker's files advance in lockstep, each
+    // window starting where the timestamps of the one before say; implies --timestamp-rules.  A worker loads at most this much audio into one
+    // file set: n_mels * 400 bytes per second of audio = 115 MB per hour at 80 mel bins, 184 MB at 128 (4 h: 461 / 737 MB)
+    bool sequential = false, condition_on_previous_text = true, overlap_given = false;
+    double sequential_max_audio_s = 14400.0;
     bool ladder() const { return temperature.size() > 1 || temperature[0] != 0.0f; }
     bool beam() const { return beam_size >= 2; }
     bool prompts() const { return !prompt_ids.empty() || !prompt_ids_dir.empty(); }
@@ -133,6 +138,7 @@ static bool parse_args(int argc, char** argv, Args& a) {
         else if (k == "--word-timestamps") a.word_timestamps = true;
         else if (k == "--print-plan") a.print_plan = true;
         else if (k == "--prompt-all-windows") a.prompt_all_windows = true;
+        else if (k == "--sequential") a.sequential = a.timestamp_rules = true;
         else if (k == "--help" || k == "-h") {
             printf("Usage: whisper_bench [--audio-dir DIR] [--model-id ID] [--onnx-dir DIR|synthetic:<preset>:<seed>] [--language en|auto] "
                    "[--task transcribe] [--max-new-tokens 128] [--warmup 0] [--limit-files 0] [--discovery-best-json F] "
@@ -142,14 +148,24 @@ static bool parse_args(int argc, char** argv, Args& a) {
                    "[--synthetic-clips N] [--seed 1000] [--print-plan] [--gpu-ingest] [--timestamp-rules] [--write-srt] [--write-vtt] "
                    "[--logprobs] [--no-speech-threshold X] [--logprob-threshold Y] [--prompt-ids a,b,c] [--prompt-ids-dir DIR] [--prompt-all-windows] "
                    "[--repetition-penalty F] [--no-repeat-ngram-size N] [--beam-size N] [--patience F] [--length-penalty F] [--n-best M] "
-                   "[--temperature 0,0.2,...] [--compression-ratio-threshold X]\n"
+                   "[--temperature 0,0.2,...] [--compression-ratio-threshold X] [--sequential] [--condition-on-previous-text 0|1] [--sequential-max-audio-s S]\n"
+                   "  --sequential             openai-whisper's sequential long-form instead of fixed overlapping windows: a worker takes up to --max-batch files of any\n"
+                   "                           length, keeps their log-mels on the device and decodes one window of every unfinished file per step as one batch; a file's\n"
+                   "                           next window starts where the last complete timestamp pair of this one ends (else a whole window on), the previous text is\n"
+                   "                           its prompt, silent windows (--no-speech-threshold / --logprob-threshold) are skipped, and with a --temperature ladder a\n"
+                   "                           failing window is decoded again at the next rung.  Implies --timestamp-rules; the text is the segments' text one after the\n"
+                   "                           other (no stitcher); the per-file JSON gains windows.  Not with --language auto, --overlap-s or --beam-size\n"
+                   "  --condition-on-previous-text 0|1   1 (the default): a window's prompt is the file's text so far (reset after a window decoded above temperature 0.5);\n"
+                   "                           0: only the first window sees --prompt-ids\n"
+                   "  --sequential-max-audio-s S   audio a worker loads into one file set (default 14400: n_mels x 400 bytes per second, 115 MB per hour at 80 mel bins,\n"
+                   "                           184 MB at 128); a batch holding more is run as several sets, a single longer file alone\n"
                    "  --temperature a,b,c      the temperature ladder (openai-whisper's decode_with_fallback; default 0 = greedy, today's outputs byte for byte): every\n"
                    "                           window is decoded at the first rung; a window whose compression ratio exceeds --compression-ratio-threshold or whose\n"
                    "                           avg_logprob lies below --logprob-threshold — and whose no_speech_prob does not exceed --no-speech-threshold — is decoded\n"
                    "                           again at the next rung (sampled at that temperature, seeded by --seed and the file's index), the others keep their result;\n"
                    "                           after the last rung the last result stands.  The per-file JSON gains temperature and compression_ratio, config_used the\n"
                    "                           ladder.  With a ladder the batches go through the unpipelined transcribe entry (the re-decode reads the batch's resident\n"
-                   "                           encoder states, which a prefetched next batch would replace), and every file must fit one 30 s window\n"
+                   "                           encoder states, which a prefetched next batch would replace), and every file must fit one 30 s window unless --sequential is given\n"
                    "  --compression-ratio-threshold X   openai-whisper's default is 2.4 (off unless given)\n"
                    "  --beam-size N            beam search with N beams per window (1 .. 8; 1 = greedy, the default); a device batch then holds max-batch / N files\n"
                    "  --patience F             round(N * F) finished hypotheses end a window's search (openai-whisper's patience; default 1)\n"
@@ -194,7 +210,15 @@ static bool parse_args(int argc, char** argv, Args& a) {
             else if (k == "--tokenizer-json") a.tokenizer_json = v;
             else if (k == "--chunk-parallelism") a.chunk_parallelism = strtoull(v.c_str(), nullptr, 10);
             else if (k == "--chunk-length-s") a.chunk_length_s = strtof(v.c_str(), nullptr);
-            else if (k == "--overlap-s") a.overlap_s = strtof(v.c_str(), nullptr);
+            else if (k == "--overlap-s") { a.overlap_s = strtof(v.c_str(), nullptr); a.overlap_given = true; }
+            else if (k == "--condition-on-previous-text") {
+                if (v != "0" && v != "1") { fprintf(stderr, "error: --condition-on-previous-text '%s' is not 0 or 1\n", v.c_str()); return false; }
+                a.condition_on_previous_text = v == "1";
+            } else if (k == "--sequential-max-audio-s") {
+                char* end = nullptr;
+                a.sequential_max_audio_s = strtod(v.c_str(), &end);
+                if (v.empty() || *end || !(a.sequential_max_audio_s > 0.0)) { fprintf(stderr, "error: --sequential-max-audio-s '%s' is not a value above 0\n", v.c_str()); return false; }
+            }
             else if (k == "--device") a.device = atoi(v.c_str());
             else if (k == "--devices") a.devices = v;
             else if (k == "--streams-per-gpu") a.streams_per_gpu = std::max(1, atoi(v.c_str()));
@@ -268,6 +292,15 @@ static bool parse_args(int argc, char** argv, Args& a) {
     } else if (a.n_best > 1) {
         fprintf(stderr, "error: --n-best %d needs --beam-size 2 or more\n", a.n_best);
         return false;
+    }
+    if (a.sequential) {
+        if (a.language == "auto") {
+            fprintf(stderr, "error: --sequential cannot be combined with --language auto: one prompt serves all rows of a device batch and its files may differ in "
+                            "language; detect the languages with a run without --sequential first\n");
+            return false;
+        }
+        if (a.overlap_given) { fprintf(stderr, "error: --sequential cannot be combined with --overlap-s: its windows start where the timestamps say, they do not overlap\n"); return false; }
+        if (a.beam()) { fprintf(stderr, "error: --sequential cannot be combined with --beam-size: beam search refuses the per-row text context\n"); return false; }
     }
     if (a.ladder()) {   // the combinations every sampling call would refuse; the fallback decision reads avg_logprob and no_speech_prob
         const char* clash = a.beam() ? "--beam-size" : a.have_rep_penalty || a.have_rep_ngram ? "--repetition-penalty / --no-repeat-ngram-size"
@@ -780,7 +813,7 @@ int main(int argc, char** argv) {
         if (files.empty()) throw std::runtime_error("No audio files found in " + a.audio_dir);
 
         // text context: each file's prefix = <|startofprev|> ++ the tail of its ids (wh_host.h build_prev_prefix)
-        std::vector<std::vector<int64_t>> file_prefix(files.size());
+        std::vector<std::vector<int64_t>> file_prefix(files.size()), file_hist(files.size());   // (file_hist: the ids themselves, the head of --sequential's history)
         if (a.prompts()) {
             wh_dims dims{};
             wh_model_get_dims(models[0], &dims);
@@ -800,6 +833,7 @@ int main(int argc, char** argv) {
                 for (int64_t t : hist)
                     if (t >= dims.vocab) throw std::runtime_error("prompt id " + std::to_string(t) + " of " + files[i] + " is outside the vocabulary (" + std::to_string(dims.vocab) + ")");
                 file_prefix[i] = build_prev_prefix(hist, spp.sot_prev, dims.n_text_ctx);
+                file_hist[i] = hist;
             }
         }
 
@@ -831,7 +865,7 @@ int main(int argc, char** argv) {
                         },
                         [](float* p) { (void)hipHostFree(p); });
         struct Result { std::string text; double dur = 0, load_s = 0; Timing t; bool ok = false; std::vector<Cue> cues; Conf conf; Lang lang; WordOut words; std::string hyps;
-                        bool has_ladder = false; double temperature = 0, compression_ratio = 0; };
+                        bool has_ladder = false; double temperature = 0, compression_ratio = 0; std::string windows; };
         const size_t nfiles = files.size();
         std::vector<Result> results(nfiles);
         const unsigned hc = std::thread::hardware_concurrency();
@@ -840,15 +874,181 @@ int main(int argc, char** argv) {
         std::vector<int64_t> prompt = {sp.sot, sp.lang, sp.task};
         if (!a.timestamps && !a.timestamp_rules) prompt.push_back(sp.no_timestamps);
         std::vector<double> busy_s(ctxs.size(), 0.0);
+        // ---- --sequential: a worker's files as resident file sets, advanced in lockstep (wh_host.h run_sequential).  A step's rows go
+        // through wh_transcribe_windows with each row's text so far as its prefix; with a ladder, a step is run_ladder over its rows — rung 0 that call,
+        // later rungs wh_decode_greedy_batch on the resident states — and a row's random stream is (file index << 32 | window ordinal), so a result
+        // does not depend on --max-batch ----
+        wh_dims model_dims{};
+        wh_model_get_dims(models[0], &model_dims);
+        auto process_sequential = [&](wh_ctx* ctx, std::vector<Item>& batch) {
+            const size_t stride = prompt.size() + a.max_new_tokens, max_new = a.max_new_tokens;
+            wh_decode_params p{};
+            p.prompt = prompt.data(); p.n_prompt = prompt.size(); p.max_new_tokens = max_new; p.eot = sp.eot;
+            p.suppress = gen.suppress.data(); p.n_suppress = gen.suppress.size();
+            p.begin_suppress = gen.begin_suppress.data(); p.n_begin_suppress = gen.begin_suppress.size();
+            SeqConfig cfg;
+            cfg.tb = sp.timestamp_begin; cfg.eot = sp.eot; cfg.sot_prev = sp.sot_prev; cfg.n_text_ctx = model_dims.n_text_ctx;
+            cfg.n_prompt = prompt.size(); cfg.max_new_tokens = max_new; cfg.condition_on_previous_text = a.condition_on_previous_text;
+            cfg.no_speech_threshold = a.no_speech_threshold; cfg.logprob_threshold = a.logprob_threshold;
+            struct WinExtra { double avg_lp = 0, ns = 0; size_t n_tok = 0; std::vector<int32_t> frames; };
+            for (size_t at = 0; at < batch.size();) {
+                size_t end = at;   // the files of one set: as many as --sequential-max-audio-s holds, one at least
+                double audio_s = 0;
+                while (end < batch.size() && (end == at || audio_s + batch[end].dur <= a.sequential_max_audio_s)) audio_s += batch[end++].dur;
+                const size_t n = end - at;
+                const double t0 = now_s();
+                std::vector<int64_t> frames(n);
+                int rc;
+                if (batch[at].is_raw) {
+                    std::vector<wh_raw_clip> rcl(n);
+                    for (size_t k = 0; k < n; k++) rcl[k] = raw_clip_of(batch[at + k]);
+                    rc = wh_files_load_raw(ctx, rcl.data(), n, frames.data());
+                } else {
+                    std::vector<wh_clip> cl(n);
+                    for (size_t k = 0; k < n; k++) { cl[k].pcm = batch[at + k].data(); cl[k].n_samples = batch[at + k].n(); }
+                    rc = wh_files_load(ctx, cl.data(), n, frames.data());
+                }
+                if (rc) throw std::runtime_error(std::string("libwhisper_hip error ") + std::to_string(rc) + ": " + wh_last_error(ctx));
+                wh_timing wt{};
+                wh_get_timings(ctx, &wt);
+                const double mel_s = wt.preprocess_s;
+                double cut_s = 0, model_s = 0;
+                cfg.file_prompts.assign(n, std::vector<int64_t>());
+                for (size_t k = 0; k < n; k++) cfg.file_prompts[k] = file_hist[batch[at + k].idx];
+                std::vector<std::vector<WinExtra>> extra(n);
+                std::vector<double> done_s(n, 0.0);
+                std::vector<SeqFile> out;
+                run_sequential(frames, cfg, [&](const std::vector<SeqRow>& rows, std::vector<SeqStepResult>& res) {
+                    const size_t nr = rows.size();
+                    std::vector<int32_t> fi(nr);
+                    std::vector<int64_t> sk(nr), ids;
+                    std::vector<size_t> offs(1, 0);
+                    for (size_t i = 0; i < nr; i++) {
+                        fi[i] = (int32_t)rows[i].file; sk[i] = rows[i].seek;
+                        ids.insert(ids.end(), rows[i].prefix.begin(), rows[i].prefix.end());
+                        offs.push_back(ids.size());
+                    }
+                    wh_prefix_opts po{sizeof(wh_prefix_opts), ids.data(), offs.data(), nr, WH_PREFIX_FIRST_WINDOW};
+                    if (int rc2 = wh_ctx_set_prefixes(ctx, &po)) throw std::runtime_error(std::string("wh_ctx_set_prefixes: ") + std::to_string(rc2) + ": " + wh_last_error(ctx));
+                    std::vector<int64_t> toks(nr * stride);
+                    std::vector<size_t> ntok(nr);
+                    std::vector<float> lps(nr * max_new, 0.0f), nss(nr, 0.0f);
+                    std::vector<int> rung_of(nr, 0);
+                    std::vector<WindowScore> scores;
+                    auto timings = [&] { wh_timing w{}; wh_get_timings(ctx, &w); cut_s += w.preprocess_s; model_s += w.encode_s + w.decode_s; };
+                    if (!a.ladder()) {
+                        if (int rc2 = wh_transcribe_windows(ctx, fi.data(), sk.data(), nr, &p, toks.data(), ntok.data()))
+                            throw std::runtime_error(std::string("libwhisper_hip error ") + std::to_string(rc2) + ": " + wh_last_error(ctx));
+                        timings();
+                        if (a.logprobs) fetch_logprobs(ctx, nr, max_new, lps, nss);
+                    } else {
+                        run_ladder(nr, a.temperature.size(), a.compression_ratio_threshold, a.logprob_threshold, a.no_speech_threshold,
+                                   [&](size_t rung, const std::vector<unsigned char>& active, std::vector<WindowScore>& sc) {
+                                       std::vector<float> temps(nr);
+                                       std::vector<uint8_t> act(active.begin(), active.end());
+                                       std::vector<uint64_t> rid(nr);
+                                       for (size_t i = 0; i < nr; i++) {
+                                           temps[i] = active[i] ? a.temperature[rung] : 0.0f;
+                                           rid[i] = ((uint64_t)batch[at + rows[i].file].idx << 32) | (uint64_t)rows[i].window;
+                                       }
+                                       wh_sampling_opts so{sizeof(wh_sampling_opts), a.seed, temps.data(), act.data(), rid.data(), nr};
+                                       if (int rc2 = wh_ctx_set_sampling(ctx, &so)) throw std::runtime_error(std::string("wh_ctx_set_sampling: ") + std::to_string(rc2) + ": " + wh_last_error(ctx));
+                                       std::vector<int64_t> toks2(nr * stride);
+                                       std::vector<size_t> ntok2(nr);
+                                       size_t got = 0;
+                                       const int rc2 = rung == 0 ? wh_transcribe_windows(ctx, fi.data(), sk.data(), nr, &p, toks2.data(), ntok2.data())
+                                                                 : wh_decode_greedy_batch(ctx, &p, toks2.data(), stride, ntok2.data(), nr, &got, nullptr, 0);
+                                       if (rc2) throw std::runtime_error(std::string("libwhisper_hip error ") + std::to_string(rc2) + ": " + wh_last_error(ctx));
+                                       timings();
+                                       std::vector<float> lps2, nss2;
+                                       fetch_logprobs(ctx, nr, max_new, lps2, nss2);
+                                       for (size_t i = 0; i < nr; i++) {
+                                           if (!active[i]) continue;
+                                           std::copy_n(toks2.begin() + i * stride, stride, toks.begin() + i * stride);
+                                           ntok[i] = ntok2[i];
+                                           std::copy_n(lps2.begin() + i * max_new, max_new, lps.begin() + i * max_new);
+                                           nss[i] = nss2[i];
+                                           std::vector<int64_t> g;
+                                           if (ntok[i] > prompt.size()) g.assign(toks.begin() + i * stride + prompt.size(), toks.begin() + i * stride + ntok[i]);
+                                           sc[i].avg_logprob = avg_logprob(std::vector<float>(lps.begin() + i * max_new, lps.begin() + i * max_new + g.size()), g, sp.eot);
+                                           sc[i].no_speech_prob = nss[i];
+                                           if (!g.empty() && g.back() == sp.eot) g.pop_back();
+                                           sc[i].compression_ratio = compression_ratio(trim(decode_tokens(text_ids(g, sp.timestamp_begin), &tok)));
+                                       }
+                                   },
+                                   rung_of, scores);
+                    }
+                    std::vector<int32_t> fr;
+                    if (a.word_timestamps) fetch_frames(ctx, nr, max_new, fr);
+                    for (size_t i = 0; i < nr; i++) {
+                        std::vector<int64_t> g;
+                        if (ntok[i] > prompt.size()) g.assign(toks.begin() + i * stride + prompt.size(), toks.begin() + i * stride + ntok[i]);
+                        WinExtra x;
+                        if (a.logprobs) {
+                            x.avg_lp = avg_logprob(std::vector<float>(lps.begin() + i * max_new, lps.begin() + i * max_new + g.size()), g, sp.eot);
+                            x.ns = nss[i];
+                        }
+                        while (x.n_tok < g.size() && g[x.n_tok] != sp.eot) x.n_tok++;
+                        if (a.word_timestamps) x.frames.assign(fr.begin() + i * max_new, fr.begin() + i * max_new + g.size());
+                        res[i].tokens = g;
+                        res[i].avg_logprob = x.avg_lp;
+                        res[i].no_speech_prob = x.ns;
+                        res[i].temperature = a.ladder() ? (double)a.temperature[rung_of[i]] : 0.0;
+                        extra[rows[i].file].push_back(std::move(x));
+                        done_s[rows[i].file] = now_s() - t0;
+                    }
+                }, out);
+                for (size_t k = 0; k < n; k++) {
+                    Result& r = results[batch[at + k].idx];
+                    const double td0 = now_s();
+                    std::string text, wj = "[";
+                    for (const SeqSegment& s : out[k].segments) {
+                        const std::string piece = decode_tokens(text_ids(s.ids, sp.timestamp_begin), &tok);
+                        text += piece;
+                        const WinExtra& x = extra[k][s.window];
+                        if (!trim(piece).empty()) r.cues.push_back(Cue{s.start, s.end, trim(piece), a.logprobs, x.avg_lp, x.ns});
+                    }
+                    r.text = trim(text);
+                    double t_max = 0;
+                    for (size_t w = 0; w < out[k].windows.size(); w++) {
+                        const SeqWindow& sw = out[k].windows[w];
+                        const WinExtra& x = extra[k][w];
+                        if (a.logprobs) r.conf.add(x.avg_lp, x.n_tok, x.ns);
+                        t_max = std::max(t_max, sw.temperature);
+                        if (a.word_timestamps && !sw.skipped) {   // the words of what the window's segments cover, its frames offset by its seek
+                            const std::vector<int64_t> g(sw.tokens.begin(), sw.tokens.begin() + (long)std::min(sw.consumed, sw.tokens.size()));
+                            window_words(a, g, x.frames.data(), sp, sw.seg_frames * 0.01, (double)sw.seek * 0.01, &tok, r.words);
+                        }
+                        wj += std::string(w ? ", " : "") + "{\"seek_s\": " + fmt_f64((double)sw.seek * 0.01) + ", \"frames\": " + std::to_string(sw.seg_frames) + ", \"advance_s\": " +
+                              fmt_f64((double)sw.advance * 0.01) + ", \"skipped\": " + (sw.skipped ? "true" : "false") + ", \"temperature\": " + fmt_f32((float)sw.temperature) + ", \"tokens\": [";
+                        for (size_t j = 0; j < sw.tokens.size(); j++) wj += (j ? ", " : "") + std::to_string(sw.tokens[j]);
+                        wj += "]}";
+                    }
+                    r.windows = wj + "]";
+                    if (a.ladder()) { r.has_ladder = true; r.temperature = t_max; r.compression_ratio = r.text.empty() ? 0.0 : compression_ratio(r.text); }
+                    r.t.preprocess_s = mel_s + cut_s;
+                    r.t.model_only_s = model_s;
+                    r.t.decode_s = now_s() - td0;
+                    r.t.end_to_end_s = done_s[k] + r.t.decode_s;   // a file completes with the step that decodes its last window
+                    r.dur = batch[at + k].dur; r.load_s = batch[at + k].load_s; r.ok = true;
+                }
+                at = end;
+            }
+        };
         auto process = [&](size_t wi, std::vector<Item>& batch, std::vector<Item>* next) {
             wh_ctx* ctx = ctxs[wi];
             const size_t stride = prompt.size() + a.max_new_tokens;
             const double tb0 = now_s();
+            if (a.sequential) {
+                process_sequential(ctx, batch);
+                busy_s[wi] += now_s() - tb0;
+                return;
+            }
             if (batch.size() == 1 && batch[0].n() > (size_t)WH_CLIP_SAMPLES) {
                 // a file longer than one window goes alone through the long-form entry (which batches its windows)
                 Result& r = results[batch[0].idx];
                 if (a.ladder())   // (the re-decode needs the windows' encoder states resident: the long-form entry keeps its last device batch's only)
-                    throw std::runtime_error("--temperature: " + files[batch[0].idx] + " is longer than one 30 s window; the ladder is built for one-window files");
+                    throw std::runtime_error("--temperature: " + files[batch[0].idx] + " is longer than one 30 s window; the ladder is built for one-window files (--sequential runs it on files of any length)");
                 wh_raw_clip rc0{};
                 if (batch[0].is_raw) rc0 = raw_clip_of(batch[0]);
                 r.text = transcribe(ctx, batch[0].audio, a, &tok, gen, r.t, &r.cues, &r.conf, lang_auto ? &lang_table : nullptr, &r.lang, &file_prefix[batch[0].idx], &r.words, &r.hyps,
@@ -990,9 +1190,12 @@ int main(int argc, char** argv) {
         // synthetic clips are one-window files by construction: allocate the page-locked staging pool now, outside the timed loop
         // (5.9 GB at --max-batch 1024; a directory of audio files allocates it when the first one-window file shows up)
         const size_t files_per_batch = (size_t)(a.max_batch / std::max(1, a.beam() ? a.beam_size : 1));   // beam search: a file takes beam_size rows
-        if (a.synthetic_clips) pool.ensure(file_pipeline_pool_size(files_per_batch, ctxs.size(), n_loaders));
+        if (a.synthetic_clips && !a.sequential) pool.ensure(file_pipeline_pool_size(files_per_batch, ctxs.size(), n_loaders));
         const double loop0 = now_s();
-        const std::string first_error = run_file_pipeline(nfiles, n_loaders, ctxs.size(), files_per_batch, (size_t)WH_CLIP_SAMPLES, &pool, load, process,
+        // (--sequential: files of any length share a batch — to the pipeline every file is a "one-window" file — and stay in pageable memory: the
+        // pool's buffers hold one 30 s window)
+        const std::string first_error = run_file_pipeline(nfiles, n_loaders, ctxs.size(), files_per_batch, a.sequential ? (size_t)-1 : (size_t)WH_CLIP_SAMPLES,
+                                                          a.sequential ? nullptr : &pool, load, process,
                                                           gpu_ingest ? std::function<void(size_t, PipeItem&)>(load_raw) : nullptr);
         const double loop_s = now_s() - loop0;
         if (!first_error.empty()) throw std::runtime_error(first_error);
@@ -1009,6 +1212,7 @@ int main(int argc, char** argv) {
             if (a.timestamp_rules) rows.back().segments = cues_json(r.cues);
             if (a.word_timestamps) { rows.back().words = words_json(r.words.words); rows.back().token_times = times_json(r.words.token_times); }
             if (!r.hyps.empty()) rows.back().hypotheses = r.hyps;
+            if (a.sequential) rows.back().windows = r.windows;
             if (a.prompts()) { rows.back().has_prompt = true; rows.back().prompt_tokens = (long long)file_prefix[i].size(); }
             if (r.lang.has) { rows.back().has_lang = true; rows.back().language = r.lang.code; rows.back().language_probability = r.lang.prob; }
             if (r.conf.has) { rows.back().has_conf = true; rows.back().avg_logprob = r.conf.avg_logprob(); rows.back().no_speech_prob = r.conf.no_speech_prob(); }
@@ -1048,6 +1252,7 @@ int main(int argc, char** argv) {
                             .set("wall_s", JVal::num(loop_s)).set("throughput_rtfx", JVal::num(audio_total / std::max(loop_s, 1e-12)))
                             .set("gpu_busy_s", JVal::num(busy_max)).set("gpu_throughput_rtfx", JVal::num(audio_total / std::max(busy_max, 1e-12))));
         if (gpu_ingest) summary.set("gpu_ingest", JVal::boolean(true));
+        if (a.sequential) summary.set("sequential", JVal::boolean(true)).set("condition_on_previous_text", JVal::boolean(a.condition_on_previous_text));
         if (a.timestamp_rules) summary.set("timestamp_rules", JVal::boolean(true));
         if (a.logprobs) summary.set("logprobs", JVal::boolean(true));
         if (a.have_rep_penalty) summary.set("repetition_penalty", JVal::num(a.rep_penalty));
