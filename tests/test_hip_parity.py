@@ -471,6 +471,34 @@ def test_decode_gemm_kernels_alone(gpu):
     assert r.returncode == 0 and "MISMATCH" not in r.stdout, r.stdout + r.stderr
 
 
+@pytest.mark.parametrize("group", ["gemm8", "gemm8x", "gemm", "attn", "ln"])
+def test_encoder_kernels_alone(gpu, group):
+    """k_gemm8 and k_ln_stats, k_gemm8x, k_gemm, k_enc_attn, k_layernorm / k_layernorm_w8 alone against a float64 host restatement of their contracts
+    (tools/enc_check, one group per parameter): both k_gemm8 geometries, ring depths, cut row and column tiles (a last group of four columns), the
+    V^T shape's 220-column tail, conv-style overlapping rows across a block boundary, in-place residual, column planes, channel scale, tile counts
+    with and without an XCD remainder, the LayerNorm consumer modes, the producer outputs and the producer -> k_ln_stats -> consumer chain; the
+    attention at S from 64 to 1500 with small and peaked scores; every output buffer's guard regions.  The bounds are derived from the operands
+    (tests/test_enc_check_cpu.py shows that they bite).  The 4-wave bf16 attention is chosen by a switch read once per process: a second run."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = os.path.join(root, "tools", "enc_check")
+    assert os.path.exists(exe), f"{exe} missing: __graft_entry__.build() compiles it"
+    r = subprocess.run([exe, group], capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0 and "MISMATCH" not in r.stdout, r.stdout + r.stderr
+    assert "err/bound" in r.stdout, r.stdout
+    first = r.stdout
+    if group == "attn":
+        r = subprocess.run([exe, group], capture_output=True, text=True, timeout=300, env=dict(os.environ, WH_ENC_ATTN_W4="1"))
+        print(r.stdout)
+        assert r.returncode == 0 and "MISMATCH" not in r.stdout, r.stdout + r.stderr
+        assert "k_enc_attn<bf16, 4>" in r.stdout, r.stdout
+        # a query's result does not depend on how many queries share a workgroup: the two bf16 forms agree bit for bit
+        w8 = [ln.split(" out ")[1].split()[0] for ln in first.splitlines() if ln.startswith("k_enc_attn<bf16, 8>")]
+        w4 = [ln.split(" out ")[1].split()[0] for ln in r.stdout.splitlines() if ln.startswith("k_enc_attn<bf16, 4>")]
+        assert len(w8) == 13 and w8 == w4, (w8, w4)
+
+
 def test_bf16_batch_is_deterministic_and_permutation_invariant(gpu):
     b = bundle("micro", 11, wb.WH_PREC_BF16, max_batch=16)
     prompt, eot = small_prompt(b.dims)

@@ -76,13 +76,15 @@ def build_tools(verbose: bool = False, force: bool = False) -> None:
                 print(" ".join(cmd), flush=True)
             subprocess.check_call(cmd)
     # tools/dec_gemm_check (tests/test_hip_parity.py) calls the library's own launchers instead: it links libwhisper_hip.so, so it checks
-    # the kernels of whichever library it is built against
-    src, exe = os.path.join(TOOLS, "dec_gemm_check.cpp"), os.path.join(TOOLS, "dec_gemm_check")
-    if force or _stale(exe, [src, OUT, os.path.join(CSRC, "wh_kernels.h")]):
-        cmd = [hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-w", src, "-o", exe, "-L" + HERE, "-lwhisper_hip", "-Wl,-rpath,$ORIGIN/../whisper-rust-ort_amd"]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
+    # the kernels of whichever library it is built against; tools/enc_check (tests/test_hip_parity.py, tests/test_enc_check_cpu.py) does the same for
+    # the encoder side: k_gemm8 / k_ln_stats, k_gemm8x, k_gemm, k_enc_attn, k_layernorm
+    for name in ("dec_gemm_check", "enc_check"):
+        src, exe = os.path.join(TOOLS, name + ".cpp"), os.path.join(TOOLS, name)
+        if force or _stale(exe, [src, OUT, os.path.join(CSRC, "wh_kernels.h")]):
+            cmd = [hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-w", src, "-o", exe, "-L" + HERE, "-lwhisper_hip", "-Wl,-rpath,$ORIGIN/../whisper-rust-ort_amd"]
+            if verbose:
+                print(" ".join(cmd), flush=True)
+            subprocess.check_call(cmd)
 
 
 HOST = os.path.join(HERE, "host")
