@@ -499,6 +499,24 @@ def test_encoder_kernels_alone(gpu, group):
         assert len(w8) == 13 and w8 == w4, (w8, w4)
 
 
+@pytest.mark.parametrize("group", ["self", "cross", "cross8"])
+def test_decoder_attention_kernels_alone(gpu, group):
+    """k_dec_self_attn (cache append and prefix form included), k_dec_cross_attn in every instantiation, k_dec_cross_attn_cg, and k_kv_absmax /
+    k_kv_quant / k_dec_cross_attn8 alone against a float64 host restatement of their contracts (tools/dec_attn_check, one group per parameter):
+    positions around the self-attention's prefetch boundaries up to the last row of the plane, NaN-filled cache rows the contract must not use,
+    the append bit for bit, prefixed rows equal to un-prefixed launches, a chain on the kernel's own caches; the cross-attention at S from 1 to
+    1500 with idle waves, parities and empty key ranges, every unroll, beam rows, the LDS-reserved large launch; the e4m3 quantiser held to exact
+    maxima and codes.  The bounds are derived from the operands (tests/test_dec_attn_check_cpu.py shows that they bite)."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = os.path.join(root, "tools", "dec_attn_check")
+    assert os.path.exists(exe), f"{exe} missing: __graft_entry__.build() compiles it"
+    r = subprocess.run([exe, group], capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0 and "MISMATCH" not in r.stdout, r.stdout + r.stderr
+    assert "err/bound" in r.stdout, r.stdout
+
+
 def test_bf16_batch_is_deterministic_and_permutation_invariant(gpu):
     b = bundle("micro", 11, wb.WH_PREC_BF16, max_batch=16)
     prompt, eot = small_prompt(b.dims)
