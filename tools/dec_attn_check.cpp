@@ -7,8 +7,8 @@
 //              adv .. g - 1 of its own (clip, head) plane plus the current k / v taken from qkv; it writes k and v of qkv bit for bit into cache row g of
 //              that plane and out[slab_idx(b, 64 h + e, mpad)], slab_idx(m, k, mpad) = ((k >> 5) mpad + m) 32 + (k & 31).  Checked: the output within
 //              the bound; cache row g of every plane equal to the words of qkv; every other cache byte unchanged; the slab unchanged outside rows < B.
-//              Rows the contract reads hold valid data, every other cache row (rows >= g, rows < adv) a NaN pattern: the kernel's V prefetch does load
-//              masked rows (up to row tc - 1), a select must keep them out.
+//              Rows the contract reads hold valid data, every other cache row (rows >= g, rows < adv) a NaN pattern: the kernel's V prefetch loads
+//              rows again for its masked lanes (the last live row, never a row >= g), a select must keep them out.
 //   cross-attention  q [B][d] pre-scaled, ck / cv [B / rows_per_clip][S][d], row b reads clip b / rows_per_clip.  Key range sp is
 //              [sp per, min(S, sp per + per)), per = ceil(S / splits).  splits == 1: out[slab_idx(b, n, mpad)] = softmax(q_h . K) V, part and ml untouched.
 //              Otherwise, with m the range's maximum score of head h:  part[b][sp][n] = sum_j exp(s_j - m) v_j,  ml[b][sp][h] = m,
@@ -23,7 +23,10 @@
 //              one code step, only where the exact quotient lies within one f32 ulp of a rounding tie.  k_dec_cross_attn8 is then held to the
 //              cross-attention contract on the dequantised values code sc, K's scale riding on q and V's on the output (p is not rounded there).
 //
-// The program links libwhisper_hip.so and calls only wh_launch_dec_self_attn, wh_launch_dec_cross_attn, wh_launch_kv_quant and wh_launch_dec_cross_attn8
+//   reorder    wh_launch_beam_reorder (k_beam_reorder, wh_beam.hip) at position g - 1 on 2 clips x 3 beams (two rows sharing a parent; one clip done),
+//              then the self-attention at g: out, kc and vc must hash equal to the same launch on caches permuted on the host.  bf16 and f32, g 1, 64, 65, 130.
+//
+// The program links libwhisper_hip.so and calls only wh_launch_dec_self_attn, wh_launch_beam_reorder, wh_launch_dec_cross_attn, wh_launch_kv_quant and wh_launch_dec_cross_attn8
 // (and sets the exported wh_dbg_cross_unroll): the same source checks any revision of the library, and two builds that print the same hashes computed
 // the same bits.  Variants are chosen with the stream_nt argument and wh_dbg_cross_unroll, never with the WH_CROSS_NT / WH_CROSS_UNROLL environment
 // variables (read once per process).  The kernel name a case prints is the one the launchers' rules give for it (bf16: ceil(d / 8 / 64) == 1 ->
@@ -60,7 +63,7 @@
 //   all of these multiply sum_j w_j |v_j|;  then half an ulp of the stored type (2^-8 |v| bf16, U |v| f32, 2^-22 |v| + 2^-24 for a limb pair).
 //   m: d + U |m|.   den: den (exp(2 d) - 1 + sums) + sum_j p_j (4 U + 3 U (|s_j| + |m|)).
 //
-//   dec_attn_check [self | cross | cross8]   one group, or all of them
+//   dec_attn_check [self | reorder | cross | cross8]   one group, or all of them
 //   dec_attn_check --selftest   host only (no HIP call): for one case of each family the restatement carried out in the kernel's working precision (float
 //                          accumulation in the kernel's order of streams and merges, p rounded where the kernel rounds it, the output rounded to the
 //                          stored type) must stay within the bound, and the same with one defect at a time must exceed it, or fail an exact
@@ -407,6 +410,60 @@ static int group_self() {
     bad |= self_chain(BF16, 70);
     bad |= self_chain(F32, 36);
     printf("worst err/bound self %.3f\n", worst_self);
+    return bad;
+}
+
+// ===== beam reorder, then self-attention ===================================================================================================
+// After wh_launch_beam_reorder at position g - 1 (rows 0 .. g - 1 of a clip's beams become those of their parents, the position becomes g) a
+// self-attention launch must leave out, kc and vc equal, bit for bit, to the same launch on caches permuted on the host.  2 clips x 3 beams: clip 0
+// with two rows sharing a parent, clip 1 complete (done: its rows must not move).
+static void reorder_host(SData& s, const int* parent, const int* done, int K) {   // rows 0 .. g - 1 of dst row j = those of src row parent[j]
+    const SC& c = s.c;
+    const std::vector<double> K0 = s.K, V0 = s.V;
+    const std::vector<unsigned char> k0 = s.KC.h0, v0 = s.VC.h0;
+    for (int b = 0; b < c.B; b++) {
+        const int r0 = b / K * K, src = r0 + parent[b];
+        if (done[r0] || src == b) continue;
+        for (int h = 0; h < c.H; h++) for (int r = 0; r < c.g; r++) for (int e = 0; e < 64; e++) {
+            s.K[s.ci(b, h, r, e)] = K0[s.ci(src, h, r, e)]; s.V[s.ci(b, h, r, e)] = V0[s.ci(src, h, r, e)];
+            memcpy(&s.KC.h0[s.ci(b, h, r, e) * esz(s.T)], &k0[s.ci(src, h, r, e) * esz(s.T)], esz(s.T));
+            memcpy(&s.VC.h0[s.ci(b, h, r, e) * esz(s.T)], &v0[s.ci(src, h, r, e) * esz(s.T)], esz(s.T));
+        }
+    }
+}
+static int reorder_case(Mode md, int g) {
+    const int K = 3, clips = 2, parent[6] = {1, 1, 0, 2, 0, 1}, done[6] = {0, 0, 0, 1, 1, 1};
+    SC c; c.what = "permuted on the host"; c.mode = md; c.g = g; c.B = clips * K;
+    SData hs, dv;
+    self_prepare(hs, c);
+    c.what = "after k_beam_reorder";
+    self_prepare(dv, c);   // (the same seed: the same caches and qkv)
+    reorder_host(hs, parent, done, K);
+    self_launch(hs);
+    {   // the device's turn: the un-permuted caches, the reorder at position g - 1, then the self-attention at the position it left
+        std::vector<int> pos(1, g - 1), tick(1, 0), par(parent, parent + 6), dn(done, done + 6);
+        void *dq = to_dev(dv.hqkv), *dp = to_dev(pos), *dt = to_dev(tick), *dpar = to_dev(par), *ddn = to_dev(dn);
+        dv.KC.up(); dv.VC.up(); dv.O.up();
+        wh_launch_beam_reorder(0, (int)esz(dv.T), dv.KC.d, dv.VC.d, (const int*)dpar, (const int*)ddn, K, clips, 1, c.H, c.tc, (int*)dp, (int*)dt);
+        wh_launch_dec_self_attn(0, prec_of(md), dq, dv.KC.d, dv.VC.d, dv.O.d, (const int*)dp, c.d, c.H, c.tc, c.B, c.mpad, nullptr);
+        CK(hipGetLastError()); CK(hipDeviceSynchronize());
+        CK(hipMemcpy(pos.data(), dp, 4, hipMemcpyDeviceToHost));
+        dv.KC.down(); dv.VC.down(); dv.O.down(); dev_free({dq, dp, dt, dpar, ddn});
+        if (pos[0] != g) { printf("k_beam_reorder left position %d, not %d: MISMATCH\n", pos[0], g); return 1; }
+    }
+    // the reference history and the bytes that must come back unchanged are the permuted ones
+    dv.K = hs.K; dv.V = hs.V; dv.KC.h0 = hs.KC.h0; dv.VC.h0 = hs.VC.h0;
+    const SRes rh = self_verify(hs), rd = self_verify(dv);
+    const bool same = rh.h[0] == rd.h[0] && rh.h[1] == rd.h[1] && rh.h[2] == rd.h[2];
+    printf("reorder ");
+    int bad = self_report(hs, rh);
+    printf("reorder ");
+    bad |= self_report(dv, rd, same ? "  hashes equal" : "  hashes DIFFERENT: MISMATCH") | !same;
+    return bad;
+}
+static int group_reorder() {
+    int bad = 0;
+    for (Mode md : {BF16, F32}) for (int g : {1, 64, 65, 130}) bad |= reorder_case(md, g);
     return bad;
 }
 
@@ -901,12 +958,12 @@ int main(int argc, char** argv) {
     const std::string arg = argc > 1 ? argv[1] : "";
     if (arg == "--selftest") return selftest() ? 1 : 0;
     if (arg == "--time") return timing();
-    if (!arg.empty() && arg != "self" && arg != "cross" && arg != "cross8") { fprintf(stderr, "usage: dec_attn_check [self | cross | cross8 | --selftest | --time]\n"); return 2; }
+    if (!arg.empty() && arg != "self" && arg != "reorder" && arg != "cross" && arg != "cross8") { fprintf(stderr, "usage: dec_attn_check [self | reorder | cross | cross8 | --selftest | --time]\n"); return 2; }
     int bad = 0;
-    for (const char* grp : {"self", "cross", "cross8"}) {
+    for (const char* grp : {"self", "reorder", "cross", "cross8"}) {
         if (!arg.empty() && arg != grp) continue;
         const auto t0 = std::chrono::steady_clock::now();
-        bad |= !strcmp(grp, "self") ? group_self() : !strcmp(grp, "cross") ? group_cross() : group_cross8();
+        bad |= !strcmp(grp, "self") ? group_self() : !strcmp(grp, "reorder") ? group_reorder() : !strcmp(grp, "cross") ? group_cross() : group_cross8();
         printf("group %s: %.1f s wall\n", grp, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     }
     return bad ? 1 : 0;

@@ -1143,13 +1143,14 @@ __global__ __launch_bounds__(64) void k_lang_finish(const float* __restrict__ lo
 // The new k / v are appended (present.{i}.decoder.{key,value}) and used straight from registers.
 // PFX (per-clip prefixes): row b's history starts at cache row off[b] of its (clip, head) plane, not at row 0.  With
 // adv = min(off[b], g) at the global position g = *pos_p the kernel advances both plane pointers by adv rows and runs on the local
-// position g - adv with a local plane length tc - adv — so which lane scores which key, the prefetch groups and every summation order are
+// position g - adv — so which lane scores which key, the prefetch groups and every summation order are
 // those of an un-prefixed row at that model position (bit-identical results).  An idle row (g < off[b]) has adv = g: local position 0,
 // it attends to its current key only and appends its k / v at cache row g < off[b], which no later position of the row reads.
 // Invariants, for any row and any off[b] (clamped to >= 0 here; the host guarantees off[b] <= Nmax and g < tc):
 //   * 0 <= adv <= g, so the row appended is cache row adv + (g - adv) = g < tc of the row's own plane — nothing outside it is written;
-//   * every cached row read is adv + r with r < g - adv (live keys) or r <= (tc - adv) - 1 (the masked V prefetch is clamped with the
-//     LOCAL plane length tc - adv, i.e. to cache row tc - 1 of the same plane) — nothing outside the plane is read;
+//   * every cached row read is adv + r with r < g - adv, a live row below g: the V loads of masked lanes are clamped to the
+//     last live row, local row g - adv - 1, and at local position 0 no cache row is loaded at all — nothing outside the plane is read, nor
+//     the row this launch appends;
 //   * sc[] is indexed by local positions < tc <= 512.
 template <typename T, typename TO = T, bool PFX = false>   // TO: the attention output as the out-projection's operand (slab layout)
 __global__ __launch_bounds__(64) void k_dec_self_attn(const T* __restrict__ qkv, T* __restrict__ kc,
@@ -1163,7 +1164,7 @@ __global__ __launch_bounds__(64) void k_dec_self_attn(const T* __restrict__ qkv,
     const int h = blockIdx.x, b = blockIdx.y, lane = threadIdx.x, gpos = *pos_p;
     int adv = 0;   // cache rows of the plane below the row's first key
     if constexpr (PFX) adv = min(max(off[b], 0), gpos);
-    const int pos = gpos - adv, tc = tc_plane - adv;   // local position, local plane length
+    const int pos = gpos - adv;   // local position
     const T* row = qkv + (long)b * 3 * d;
     T* kcb = kc + (((long)b * n_heads + h) * tc_plane + adv) * HD;
     T* vcb = vc + (((long)b * n_heads + h) * tc_plane + adv) * HD;
@@ -1182,10 +1183,12 @@ __global__ __launch_bounds__(64) void k_dec_self_attn(const T* __restrict__ qkv,
     constexpr int EPC = 16 / (int)sizeof(T), CPR = HD / EPC, RPI = 64 / CPR, NPRE = 8;
     typedef __attribute__((ext_vector_type(EPC))) T vrow_t;
     const int rslot = lane / CPR, chunk = lane % CPR;
-    vrow_t vpre[NPRE];
+    vrow_t vpre[NPRE] = {};
+    if (pos > 0) {   // (wave-uniform) live rows only: a slot whose row is >= pos re-reads the last live row, pos - 1, and is masked below
 #pragma unroll
-    for (int u = 0; u < NPRE; u++)  // unconditional: rows >= pos are masked below
-        vpre[u] = *reinterpret_cast<const vrow_t*>(vcb + (long)min(u * RPI + rslot, tc - 1) * HD + chunk * EPC);
+        for (int u = 0; u < NPRE; u++)
+            vpre[u] = *reinterpret_cast<const vrow_t*>(vcb + (long)min(u * RPI + rslot, pos - 1) * HD + chunk * EPC);
+    }
     const vrow_t vcur_v = *reinterpret_cast<const vrow_t*>(row + 2 * d + h * HD + chunk * EPC);
     const T kcur = row[d + h * HD + lane], vcur = row[2 * d + h * HD + lane];
     qs[lane] = cvt_in<T>(row[h * HD + lane]);
@@ -1240,11 +1243,11 @@ __global__ __launch_bounds__(64) void k_dec_self_attn(const T* __restrict__ qkv,
 #pragma unroll
         for (int e = 0; e < EPC; e++) o[e] += (r < pos) ? pr * cvt_in<T>(vpre[u][e]) : 0.0f;
     }
-    for (int j = NPRE * RPI; j < pos; j += NPRE * RPI) {  // later rows: NPRE wide loads in flight, clamped and masked
+    for (int j = NPRE * RPI; j < pos; j += NPRE * RPI) {  // later rows: NPRE wide loads in flight, clamped to the last live row and masked
         vrow_t v[NPRE];
 #pragma unroll
         for (int u = 0; u < NPRE; u++)
-            v[u] = *reinterpret_cast<const vrow_t*>(vcb + (long)min(j + u * RPI + rslot, tc - 1) * HD + chunk * EPC);
+            v[u] = *reinterpret_cast<const vrow_t*>(vcb + (long)min(j + u * RPI + rslot, pos - 1) * HD + chunk * EPC);
 #pragma unroll
         for (int u = 0; u < NPRE; u++) {
             const int r = j + u * RPI + rslot;
