@@ -454,6 +454,47 @@ int wh_decode_greedy_batch(wh_ctx* c, const wh_decode_params* p, int64_t* tokens
 int wh_decode_greedy_rows(wh_ctx* c, const wh_decode_params* p, const int32_t* rows, size_t n_rows, int64_t* tokens_out, size_t cap_tokens,
                           size_t* n_tokens_out, size_t cap_clips, size_t* n_clips_out, float* logits_out, size_t cap_logits_rows);
 
+/* Scoring given transcripts: log p(tokens | audio) of many hypotheses in ONE decoder pass over all their positions (no reference entry
+ * corresponds; openai-whisper's rescoring, teacher-forced evaluation and subtitle verification need it).  Works on the clips whose encoder
+ * states are resident in the ctx — the set wh_decode_greedy_batch decodes — with H = hyps_per_clip hypotheses each: hypothesis j of clip b
+ * is entry b * H + j.  p->prompt, p->suppress and p->begin_suppress keep their meaning; p->max_new_tokens and p->eot are ignored (eot may
+ * serve as a filler id); p->n_forced must be 0.
+ * For hypothesis h with tokens t[0 .. n) and P = n_prompt the model sequence is prompt ++ t, and entry i refers to the logits v at model
+ * position P - 1 + i, whose input token is prompt[P - 1] for i == 0 and t[i - 1] otherwise (teacher forcing: an EOT inside t stops nothing).
+ *   - allowed set: an id that is not in `suppress`, not in `begin_suppress` when i == 0, and whose logit is neither NaN nor -inf — the set
+ *     wh_get_logprobs sums over with the rules off;
+ *   - logprob_out[h][i] = v[t[i]] - (m + logf(sum_allowed expf(v - m))), m the largest allowed logit; -inf if t[i] is not allowed;
+ *   - argmax_out[h][i] (may be NULL) = the allowed id with the largest logit, ties to the lowest id; nothing allowed: 0 (and logprob -inf);
+ *   - entries i >= n are 0;
+ *   - logits_out (may be NULL; parity): row i of listed hypothesis logit_hyps[k] holds the raw logits v of entry i,
+ *     [n_logit_hyps][cap_logits_rows][vocab].
+ * Like every decode entry, the call resets what the wh_get_* getters return for the previous decode call (they then report WH_ERR_STATE or
+ * empty results); wh_ctx_set_logprobs is irrelevant to this entry and ignored.  The resident encoder states and the self-attention caches are
+ * not modified: a decode call after a scoring call returns exactly what it returned before it.  wh_get_timings reports the call under decode_s.
+ * Let T = P + (longest hypothesis) - 1.  A hypothesis takes T rows of the ctx's max_batch; a pass holds floor(max_batch / (H * T)) whole clips,
+ * more clips run as further passes.  The raw logits of a pass live in a float [max_batch][vocab] scratch (425 MB at 2048 whisper-base rows)
+ * allocated by the first scoring call and freed with the ctx.
+ * Refused before anything is launched, the ctx unchanged:
+ *   WH_ERR_ARG: a wrong struct_size; offsets[0] != 0 or offsets not strictly increasing; an id outside [0, vocab); n_hyp != resident clips
+ *     * H; n_forced != 0; P + longest hypothesis > n_text_ctx; cap_tokens below the longest hypothesis; a logit_hyps entry out of range or
+ *     cap_logits_rows below a listed hypothesis's length; H * T > max_batch;
+ *   WH_ERR_STATE: no resident states, or states that belong to a prefetched batch;
+ *   WH_ERR_UNSUPPORTED: a WH_PREC_FP8 or WH_PREC_F16X3 model; timestamp rules, repetition controls, sampling, beam search, alignment,
+ *     language detection or a non-empty prefix set on the ctx. */
+typedef struct {
+    size_t struct_size;       /* sizeof(wh_score_input) */
+    const int64_t* ids;       /* the hypotheses' tokens back to back */
+    const size_t* offsets;    /* [n_hyp + 1], offsets[0] == 0, strictly increasing (every hypothesis has >= 1 token) */
+    size_t n_hyp;             /* == resident clips * hyps_per_clip */
+    size_t hyps_per_clip;     /* H >= 1: hypothesis j of resident clip b is entry b * H + j */
+} wh_score_input;
+int wh_score_tokens(wh_ctx* c, const wh_decode_params* p, const wh_score_input* in,
+                    float* logprob_out,      /* [n_hyp][cap_tokens] */
+                    int64_t* argmax_out,     /* [n_hyp][cap_tokens], may be NULL */
+                    size_t cap_tokens,
+                    const int32_t* logit_hyps, size_t n_logit_hyps,   /* parity only: hypotheses whose logits are read back */
+                    float* logits_out, size_t cap_logits_rows);       /* [n_logit_hyps][cap_logits_rows][vocab], may be NULL */
+
 /* ---- fused batch call: the body of transcribe_longform_chunked for ≤ max_batch single-window
  * clips (src/main.rs:870-915 / 946-967) run as one batch on the ctx stream -------------------- */
 typedef struct {

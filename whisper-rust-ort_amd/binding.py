@@ -41,7 +41,7 @@ EXPORTS = ("wh_model_load", "wh_model_create", "wh_model_free", "wh_model_get_di
            "wh_ctx_set_language_detection", "wh_get_languages", "wh_ctx_set_prefixes", "wh_ctx_set_repetition",
            "wh_ctx_set_alignment", "wh_get_token_frames", "wh_get_alignment_debug", "wh_ctx_set_beam_search", "wh_get_beams", "wh_get_beam_trace",
            "wh_ctx_set_sampling", "wh_resampled_samples", "wh_ingest_raw", "wh_transcribe_batch_raw", "wh_transcribe_batch_raw_next",
-           "wh_transcribe_longform_raw", "wh_files_load", "wh_files_load_raw", "wh_transcribe_windows", "wh_files_window_mel")
+           "wh_transcribe_longform_raw", "wh_files_load", "wh_files_load_raw", "wh_transcribe_windows", "wh_files_window_mel", "wh_score_tokens")
 
 
 class WhisperHipError(RuntimeError):
@@ -150,6 +150,16 @@ class WhSamplingOpts(C.Structure):
                 ("row_ids", C.POINTER(C.c_uint64)), ("n_rows", C.c_size_t)]
 
 
+class WhScoreInput(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("ids", C.POINTER(C.c_int64)), ("offsets", C.POINTER(C.c_size_t)), ("n_hyp", C.c_size_t),
+                ("hyps_per_clip", C.c_size_t)]
+
+
+def pack_hypotheses(hyps: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.ndarray]:
+    """wh_score_input's two arrays for a list of ragged hypotheses: (ids int64 back to back, offsets uint64 [n + 1]) — the layout of wh_prefix_opts."""
+    return pack_prefixes(hyps)
+
+
 def pack_prefixes(prefixes: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.ndarray]:
     """wh_prefix_opts' two arrays for a list of per-clip prefixes: (ids int64 back to back, offsets uint64 [n + 1])."""
     offsets = np.zeros(len(prefixes) + 1, np.uint64)
@@ -254,6 +264,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.wh_files_load_raw.argtypes = [vp, rawp, C.c_size_t, i64p]
     L.wh_transcribe_windows.argtypes = [vp, i32p, i64p, C.c_size_t, C.POINTER(WhDecodeParams), i64p, szp]
     L.wh_files_window_mel.argtypes = [vp, C.c_int32, C.c_int64, f32p]
+    L.wh_score_tokens.argtypes = [vp, C.POINTER(WhDecodeParams), C.POINTER(WhScoreInput), f32p, i64p, C.c_size_t, i32p, C.c_size_t, f32p, C.c_size_t]
     _lib = L
     return L
 
@@ -576,6 +587,25 @@ class Context:
                                                    C.byref(got), _f32(logits), params.max_new_tokens))
         k = int(got.value)
         return self._took([toks[i, : n[i]].copy() for i in range(k)], params), logits
+
+    def score_tokens(self, params: DecodeParams, hyps: Sequence[Sequence[int]], hyps_per_clip: int = 1, logit_hyps: Sequence[int] = ()):
+        """wh_score_tokens: log p(tokens | audio) of `hyps` (hypothesis j of resident clip b is hyps[b * hyps_per_clip + j]) in one decoder pass
+        over all their positions.  Returns per hypothesis (log-probabilities float32 [n], masked argmax int64 [n]) as two lists and, for the
+        hypotheses listed in logit_hyps, their raw logits [n][vocab] as a third (empty without logit_hyps)."""
+        p, keep = params.to_c()
+        ids, offsets = pack_hypotheses(hyps)
+        lens = [len(h) for h in hyps]
+        cap = max(lens, default=1) or 1
+        inp = WhScoreInput(C.sizeof(WhScoreInput), _i64(ids) if ids.size else None, offsets.ctypes.data_as(C.POINTER(C.c_size_t)), len(hyps), hyps_per_clip)
+        lp = np.zeros((len(hyps), cap), np.float32)
+        am = np.zeros((len(hyps), cap), np.int64)
+        sel = np.ascontiguousarray(list(logit_hyps), np.int32)
+        rows = max([lens[k] for k in sel if 0 <= k < len(lens)], default=1)
+        logits = np.zeros((len(sel), rows, self.model.dims.vocab), np.float32) if sel.size else None
+        self._check(self.lib.wh_score_tokens(self.h, C.byref(p), C.byref(inp), _f32(lp), _i64(am), cap, sel.ctypes.data_as(C.POINTER(C.c_int32)) if sel.size else None,
+                                             sel.size, _f32(logits) if sel.size else None, rows))
+        return ([lp[g, :n].copy() for g, n in enumerate(lens)], [am[g, :n].copy() for g, n in enumerate(lens)],
+                [logits[j, : lens[int(k)]] for j, k in enumerate(sel)])
 
     def _took(self, toks: List[np.ndarray], params: "DecodeParams") -> List[np.ndarray]:
         self._gen_lens = [len(t) - len(params.prompt) for t in toks]   # (what logprobs() cuts its rows to)

@@ -197,6 +197,24 @@ int wh_decode_greedy_rows(wh_ctx* c, const wh_decode_params* p, const int32_t* r
     return decode_resident(c, nb, p, tokens_out, cap_tokens, n_tokens_out, logits_out, cap_logits_rows, rows, n_rows);
 }
 
+// log p(given tokens | audio) of n_hyp hypotheses over the resident clips, one decoder pass over all their positions (wh_score_host.cpp)
+int wh_score_tokens(wh_ctx* c, const wh_decode_params* p, const wh_score_input* in, float* logprob_out, int64_t* argmax_out, size_t cap_tokens,
+                    const int32_t* logit_hyps, size_t n_logit_hyps, float* logits_out, size_t cap_logits_rows) {
+    if (!c) return WH_ERR_ARG;
+    int rc = check_params(c, p);
+    if (rc) return rc;
+    prof_reset(c);
+    const double t0 = now_s();
+    if ((rc = run_score(c, p, in, logprob_out, argmax_out, cap_tokens, logit_hyps, n_logit_hyps, logits_out, cap_logits_rows))) return rc;
+    float ms = 0;
+    hipEventElapsedTime(&ms, c->ev[5], c->ev[3]);
+    c->timing = wh_timing{};
+    c->timing.decode_s = ms * 1e-3;
+    c->timing.total_s = now_s() - t0;
+    prof_collect(c);
+    return WH_OK;
+}
+
 // Clips resident at `pcm` on the device → tokens.  The encoder pass of this batch runs now unless `prefetched`; if
 // `next_pcm` is given, the NEXT batch's log-mel + encoder are put on the encoder stream as soon as this batch's cross-K/V
 // projection has been enqueued, i.e. they run beside this batch's token loop.

@@ -168,6 +168,7 @@ static int ctx_create_impl(wh_model* m, const wh_ctx_opts* opts, wh_ctx** out) {
     c->al.timing = getenv("WH_ALIGN_TIMING") != nullptr;
     c->bm.timing = getenv("WH_BEAM_TIMING") != nullptr;
     c->sm.timing = getenv("WH_SAMPLE_TIMING") != nullptr;
+    c->sc.timing = getenv("WH_SCORE_TIMING") != nullptr;
     const wh_dims& D = m->dims;
     const size_t B = max_batch, d = D.d_model, S = D.n_audio_ctx, F = D.ffn, C = D.n_mels, esz = m->esz;
     const size_t Ld = D.dec_layers, H = D.n_heads, TC = D.n_text_ctx;

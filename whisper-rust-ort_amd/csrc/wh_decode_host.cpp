@@ -1,11 +1,11 @@
 // wh_decode_host.cpp — the host side of a decode call (greedy_decode_with_past, reference src/main.rs:753-829): run_decode and its stages — the
 // plan, the token state, the cross-K/V projection, one decoder position (Step), the captured step and the token loop, the alignment post-pass
 // and the two read-backs.
-#include "wh_host_shared.h"
+#include "wh_step.h"
 
 namespace wh {
 
-static void pack_mask(const int64_t* a, size_t na, const int64_t* b, size_t nb, int vocab, std::vector<unsigned>& out) {
+void pack_mask(const int64_t* a, size_t na, const int64_t* b, size_t nb, int vocab, std::vector<unsigned>& out) {
     out.assign((size_t)vocab / 32 + 1, 0u);
     for (size_t i = 0; i < na; i++)
         if (a[i] >= 0 && a[i] < vocab) out[a[i] >> 5] |= 1u << (a[i] & 31);
@@ -257,7 +257,7 @@ static int run_alignment(wh_ctx* c, const DecodePlan& pl) {
 // cross-attention K/V of every decoder layer, once per clip: present.{i}.encoder.{key,value} of the step-0 decoder run (src/main.rs:771-787).
 // `after_kv` (optional) runs on the host right after the projection has been enqueued and its completion event recorded: the place where
 // the NEXT batch's encoder pass is put on the encoder stream, before the host is tied up in the token loop.
-static int project_cross_kv(wh_ctx* c, int nb, const std::function<int()>& after_kv) {
+int project_cross_kv(wh_ctx* c, int nb, const std::function<int()>& after_kv) {
     wh_model* m = c->m;
     const wh_dims& D = m->dims;
     hipStream_t s = c->stream;
@@ -301,9 +301,7 @@ static int project_cross_kv(wh_ctx* c, int nb, const std::function<int()>& after
 }
 
 // ---- one decoder position (~50 kernel launches) ---------------------------------------------------
-// LayerNorm never runs as a kernel in the decoder: the kernel that produces a residual-stream row also emits its raw copy in the
-// compute dtype (c->dxs, slab layout) and per-column-tile partial sums (c->lnpart); the GEMM that consumes LN(x) has γ folded into
-// its weights and applies mean / rstd in its epilogue (wh_model.cpp fold_ln).
+// (the operands of the decode GEMMs and the layer's launch list: StepBase, wh_step.h)
 // What a prompt position does besides the layers.  It embeds its own input token (a generated position's input was embedded by the
 // previous position's argmax finish); only the last prompt position emits.
 struct PromptStep {
@@ -314,63 +312,10 @@ struct PromptStep {
 };
 
 // The launches of a position see the context (model, fixed workspace addresses, option buffers) and the step's key, nothing else.
-struct Step {
-    wh_ctx* c;
-    const wh_ctx::StepKey& k;
-    wh_model* m = c->m;
-    const wh_dims& D = m->dims;
-    hipStream_t s = c->stream;
-    const int prec = m->prec, nb = k.nb, mpad = c->mpad, ln_tiles_d = D.d_model / 16;
-    const long d = D.d_model, S = D.n_audio_ctx;
-    const bool f8 = prec == WH_PREC_FP8, rules = k.ts_begin >= 0;
-    // beam search: the nb rows are the beams of ncl = nb / rpc clips, and the cross-attention of row b reads clip b / rpc (rpc == 1: ncl == nb)
-    const int rpc = k.beam_k ? k.beam_k : 1, ncl = nb / rpc;
-    // the cross K/V of all layers are re-read at every position: below ~half the 256 MiB Infinity Cache they are served
-    // from it; above, their stream only evicts the decode weights and activations — then they are loaded non-temporally
-    const bool kv_nt = (c->cross_es ? 1.0 : (double)D.dec_layers * 2.0) * ncl * S * d * (f8 ? 1 : (double)m->esz) > 128.0 * 1024 * 1024;
+struct Step : StepBase {
+    using StepBase::StepBase;
     const int* d_off = k.pfx ? c->pfx.off : nullptr;
 
-    // the decode GEMMs: tile GEMMs on contexts of a thousand clips and more (a property of the context, never of the call)
-    void gemm(bool out_f32, const SkinnyArgs& a) const {
-        if (c->dec_tile && wh_dec_tile_applicable(prec, a)) wh_launch_dec_tile(s, prec, out_f32, a);
-        else wh_launch_dec_gemm(s, prec, out_f32, a);
-    }
-    // a GEMM that consumes LN(x) of the residual stream: out [nb][N], row-major or (slab_out) slab layout
-    SkinnyArgs ln_consumer(const void* W, const float* bias, const float* wscale, const float* ln_s, long N, void* out, int ln_tiles, bool slab_out = false) const {
-        SkinnyArgs a;
-        a.X = c->dxs; a.x_mpad = mpad; a.W = W; a.bias = bias; a.wscale = wscale; a.C = out;
-        if (slab_out) a.c_mpad = mpad; else a.ldc = N;
-        a.M = nb; a.N = (int)N; a.K = (int)d;
-        a.ln_part = c->lnpart; a.ln_tiles = ln_tiles; a.ln_s = ln_s; a.shift_io = c->dshift;
-        return a;
-    }
-    // a GEMM that adds to the residual stream: x += X W^T + bias, plus the raw slab copy and the partial sums of the next LayerNorm
-    // (next_gamma: that LayerNorm's γ, applied on the activation side in fp8 mode)
-    SkinnyArgs residual_producer(const void* W, const float* bias, const float* wscale, const void* X, long K, const float* next_gamma) const {
-        SkinnyArgs a;
-        a.X = X; a.x_mpad = mpad; a.W = W; a.bias = bias; a.wscale = wscale; a.R = c->dx; a.ldr = d; a.C = c->dx; a.ldc = d;
-        a.M = nb; a.N = (int)d; a.K = (int)K; a.xslab_out = c->dxs; a.stats_out = c->lnpart; a.row_shift = c->dshift;
-        if (f8) a.xgamma = next_gamma;
-        return a;
-    }
-    // final LN ∘ tied LM head: what the emitting step and the no-speech probe share (they differ in the masks and what they record)
-    SkinnyArgs lm_head_common() const {
-        SkinnyArgs a;
-        a.W = m->lm_w; a.bias = m->lm_c; a.ln_s = m->lm_s; a.ln_part = c->lnpart; a.ln_tiles = ln_tiles_d;
-        a.M = nb; a.N = D.vocab; a.K = (int)d;
-        a.X = c->dxs; a.x_mpad = mpad;
-        a.pos_p = c->pos; a.n_prompt = k.n_prompt;
-        a.part_val = c->part_val; a.part_idx = c->part_idx;
-        return a;
-    }
-    // ... with the call's two suppress masks: the LM head of an emitting step.  scratch: the rows' raw logits of this position go there instead of
-    // the argmax partials being read (beam search, sampling)
-    SkinnyArgs lm_head_masked(float* scratch = nullptr) const {
-        SkinnyArgs a = lm_head_common();
-        a.mask_first = c->mask_first; a.mask_base = c->mask_base;
-        if (scratch) { a.logits = scratch; a.logits_rows = 1; a.logits_cur = true; }
-        return a;
-    }
     // the token bookkeeping of the kernel that ends an emitting step; log-probabilities go to the sampling call's own buffer or, when they are on, to lp.tok
     DecodeState decode_state() const {
         DecodeState st;
@@ -388,87 +333,13 @@ struct Step {
         return ne;
     }
 
-    // `advance`: nothing follows the layers at this position (a prompt position without a head), so this fc2 advances the position
+    // one decoder layer at the current position: self-attention over the row's cache, with this position's k / v appended
     void layer(int l, bool advance) const {
-        const DecLayerDev& L = m->dec[l];
         const long cache_l = (long)nb * D.n_heads * D.n_text_ctx * WH_HEAD_DIM * m->esz;   // bytes per layer
-        const long kv_stride = (long)ncl * S * d;  // elements between consecutive [clips][S][d] planes
-        {   // LN1 ∘ Q|K|V projection
-            Prof pr(c, WH_KG_DEC_GEMM);
-            gemm(false, ln_consumer(L.qkv_w, L.qkv_b, L.qkv_sc, L.qkv_s, 3 * d, c->dqkv, (l == 0) ? 1 : ln_tiles_d));
-        }
-        {
-            Prof pr(c, WH_KG_DEC_OTHER);
+        layer_with(l, advance, [&] {
             wh_launch_dec_self_attn(s, prec, c->dqkv, (char*)c->self_k + l * cache_l, (char*)c->self_v + l * cache_l, c->datt, c->pos, (int)d, D.n_heads,
                                     D.n_text_ctx, nb, mpad, d_off);
-        }
-        {   // self-attention out-proj + residual → x, raw slab, LN2 partials
-            Prof pr(c, WH_KG_DEC_GEMM);
-            gemm(true, residual_producer(L.o_w, L.o_b, L.o_sc, c->datt, d, L.ln2_w));
-        }
-        if (c->cross_es) {
-            // the attention runs on the encoder states (wh_cross_es.hip): W_k moves to the query side, W_v behind the attention
-            {   // LN2 ∘ cross-attention query, kept in f32
-                Prof pr(c, WH_KG_DEC_GEMM);
-                gemm(true, ln_consumer(L.cq_w, L.cq_b, L.cq_sc, L.cq_s, d, c->dq32, ln_tiles_d));
-                // expanded queries qe[h] = W_k,h^T q_h: [nb][H][d] f32
-                wh_launch_dec_qexpand(s, prec, c->dq32, L.cqx_w, c->dqe, nb, (int)d, D.n_heads);
-            }
-            if (k.al_q && c->al.layer[l].n) {   // word-level timestamps: the listed heads' expanded queries of this position
-                Prof pr(c, WH_KG_DEC_OTHER);
-                wh_launch_align_copy(s, false, c->dqe, (long)D.n_heads * d, d, (int)d, c->al.layer[l], c->pos, k.n_prompt - 1, k.al_cap, nb, k.al_q);
-            }
-            {
-                Prof pr(c, WH_KG_DEC_CROSS_ATTN);
-                wh_launch_dec_cross_attn_es(s, prec, c->dqe, c->es_E, c->dctx, (int)S, c->es_rows, nb, mpad, kv_nt, c->dec_cus, rpc);
-            }
-            {   // per head: W_v,h ctx_h + b_v,h → the attention output the out-projection below expects (slab layout)
-                Prof pr(c, WH_KG_DEC_GEMM);
-                SkinnyArgs a;
-                a.X = c->dctx; a.x_mpad = mpad; a.W = L.cv_w; a.bias = L.cv_b; a.C = c->datt; a.c_mpad = mpad;
-                a.M = nb; a.N = WH_HEAD_DIM; a.K = (int)d;
-                a.zn = D.n_heads; a.x_zs = (long)(d / 32) * mpad * 32; a.w_zs = (long)WH_HEAD_DIM * d; a.c_zs = (long)(WH_HEAD_DIM / 32) * mpad * 32;
-                a.bias_zs = WH_HEAD_DIM;
-                if (f8) wh_launch_dec_gemm(s, WH_PREC_BF16, false, a);   // (fp8 mode: cv_w is the quantised model's W_v, code x row scale, as bf16 — wh_model.cpp)
-                else gemm(false, a);
-            }
-        } else {
-            {   // LN2 ∘ cross-attention query
-                Prof pr(c, WH_KG_DEC_GEMM);
-                gemm(false, ln_consumer(L.cq_w, L.cq_b, L.cq_sc, L.cq_s, d, c->dq, ln_tiles_d));
-            }
-            if (k.al_q && c->al.layer[l].n) {   // word-level timestamps: the listed heads' queries of this position
-                Prof pr(c, WH_KG_DEC_OTHER);
-                wh_launch_align_copy(s, m->esz == 2, c->dq, d, WH_HEAD_DIM, WH_HEAD_DIM, c->al.layer[l], c->pos, k.n_prompt - 1, k.al_cap, nb, k.al_q);
-            }
-            Prof pr(c, WH_KG_DEC_CROSS_ATTN);
-            if (f8)
-                wh_launch_dec_cross_attn8(s, c->dq, (char*)c->cross_kv8 + (2 * l) * kv_stride, (char*)c->cross_kv8 + (2 * l + 1) * kv_stride,
-                                          c->kv_amax + (long)(2 * l) * nb * D.n_heads, c->kv_amax + (long)(2 * l + 1) * nb * D.n_heads,
-                                          c->cpart, c->cml, (int)S, (int)d, D.n_heads, c->cross_splits, nb, c->datt, mpad, kv_nt);
-            else
-                wh_launch_dec_cross_attn(s, prec, c->dq, (char*)c->cross_kv + (2 * l) * kv_stride * m->esz, (char*)c->cross_kv + (2 * l + 1) * kv_stride * m->esz,
-                                         c->cpart, c->cml, (int)S, (int)d, D.n_heads, c->cross_splits, nb, c->datt, mpad, kv_nt, rpc);
-        }
-        {   // merge of the key ranges ∘ cross-attention out-proj + residual → x, raw slab, LN3 partials
-            Prof pr(c, WH_KG_DEC_GEMM);
-            const bool merged = c->cross_splits == 1 || c->cross_es;   // one key range per clip: the attention kernel wrote its output itself
-            SkinnyArgs a = residual_producer(L.co_w, L.co_b, L.co_sc, merged ? c->datt : nullptr, d, L.ln3_w);
-            if (!merged) { a.xpart = c->cpart; a.xml = c->cml; a.x_splits = c->cross_splits; a.x_heads = D.n_heads; }
-            gemm(true, a);
-        }
-        {   // LN3 ∘ fc1 + GELU (slab output)
-            Prof pr(c, WH_KG_DEC_GEMM);
-            SkinnyArgs a = ln_consumer(L.fc1_w, L.fc1_b, L.fc1_sc, L.fc1_s, D.ffn, c->dh, ln_tiles_d, true);
-            a.act = 1;
-            gemm(false, a);
-        }
-        {   // fc2 + residual → x, raw slab, partials for the next layer's LN1 / the final LN
-            Prof pr(c, WH_KG_DEC_GEMM);
-            SkinnyArgs a = residual_producer(L.fc2_w, L.fc2_b, L.fc2_sc, c->dh, D.ffn, (l + 1 < D.dec_layers) ? m->dec[l + 1].ln1_w : m->dec_ln_w);
-            if (advance) { a.ticket = c->step_ticket; a.pos_w = c->pos; }
-            gemm(true, a);
-        }
+        });
     }
 
     // final LN ∘ tied LM head + masked argmax; the finish kernel records the token, advances the position and embeds the next one

@@ -1,5 +1,5 @@
 // wh_host_shared.h — what the host files of libwhisper_hip.so share (wh_ctx.cpp, wh_options.cpp, wh_encode_host.cpp, wh_decode_host.cpp,
-// wh_api.cpp): error reporting, the profiling scope, the carve and growth helpers, and the functions one file defines for another.
+// wh_score_host.cpp, wh_api.cpp): error reporting, the profiling scope, the carve and growth helpers, and the functions one file defines for another.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -136,5 +136,10 @@ void launch_window_cut(wh_ctx* c, int nb);
 // ---- wh_decode_host.cpp ----
 int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out, size_t tok_stride, size_t* n_tokens_out, float* logits_out,
                size_t logits_rows, const std::function<int()>& after_kv = nullptr, const int32_t* sel = nullptr, size_t n_sel = 0);
+
+
+// ---- wh_score_host.cpp ----
+int run_score(wh_ctx* c, const wh_decode_params* p, const wh_score_input* in, float* logprob_out, int64_t* argmax_out, size_t cap_tokens,
+              const int32_t* logit_hyps, size_t n_logit_hyps, float* logits_out, size_t cap_logits_rows);
 
 }  // namespace wh

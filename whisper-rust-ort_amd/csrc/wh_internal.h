@@ -427,7 +427,24 @@ struct wh_ctx {
         void collect_timing() { ms = 0; timed = (long)events.size(); wh_drain_events(events, &ms); }
         void reset_results() { wh_drain_events(events, nullptr); }
     } sm;
-    void reset_option_results() { ts.reset_results(); lp.reset_results(); lang.reset_results(); pfx.reset_results(); rep.reset_results(); al.reset_results(); bm.reset_results(); sm.reset_results(); }
+    // Scoring given transcripts (wh_score_tokens): no setting, its own buffers only — allocated by the first scoring call, freed
+    // with the context.  No captured step holds them: the pass is launched eagerly.
+    struct Scoring {
+        DevBuf<float> logits;               // [max_batch][vocab] raw logits of a pass's rows (the LM head's scratch)
+        DevBuf<> buf;                       // carved into:
+        int* tok = nullptr;                 // [n_text_ctx + max_batch] the rows' input tokens from index T - 1 on (k_dec_embed reads feed[row + *pos])
+        int* off = nullptr;                 // [max_batch] T - 1 - t of each row: k_dec_embed<T, true> then embeds model position t
+        int* len = nullptr;                 // [max_batch] tokens of each hypothesis of the pass
+        int* target = nullptr;              // [max_batch] the given tokens, [hypothesis][Lmax]
+        float* lp = nullptr;                // [max_batch] log-probabilities, [hypothesis][Lmax]
+        int* am = nullptr;                  // [max_batch] argmax, [hypothesis][Lmax]
+        bool timing = false;                // WH_SCORE_TIMING=1: events around the two scoring kernels (tools/score_bench.py)
+        std::vector<std::array<hipEvent_t, 2>> ev_attn, ev_finish;
+        double ms[2] = {0, 0};              // k_score_self_attn (all layers), k_score_finish of the last call, milliseconds
+        void collect_timing() { ms[0] = ms[1] = 0; wh_drain_events(ev_attn, &ms[0]); wh_drain_events(ev_finish, &ms[1]); }
+        void reset_results() { wh_drain_events(ev_attn, nullptr); wh_drain_events(ev_finish, nullptr); }
+    } sc;
+    void reset_option_results() { sc.reset_results(); ts.reset_results(); lp.reset_results(); lang.reset_results(); pfx.reset_results(); rep.reset_results(); al.reset_results(); bm.reset_results(); sm.reset_results(); }
     hipGraph_t step_graph = nullptr;
     hipGraphExec_t step_exec = nullptr;
 };

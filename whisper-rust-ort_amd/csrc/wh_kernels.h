@@ -442,6 +442,15 @@ struct SampleArgs {
 };
 void wh_launch_sample_select(hipStream_t s, int prec, const SampleArgs& a, const DecodeState& st, const NextEmbed& ne, int rows, int* pos_p, int* ticket);
 
+// Scoring given transcripts (wh_score.hip).  The pass runs hypothesis g's T positions as the adjacent rows g * T .. g * T + T - 1.
+// Causal self-attention of those rows straight from the QKV buffer: qkv [n_hyp * T][3d] (q pre-scaled | k | v, compute dtype) -> out, the
+// out-projection's operand (slab layout, pitch mpad, compute dtype).  WH_PREC_F32 and WH_PREC_BF16 only.
+void wh_launch_score_self_attn(hipStream_t s, int prec, const void* qkv, void* out, int d, int n_heads, int T, int n_hyp, int mpad);
+// logits [rows][vocab] f32, rows = n_hyp * T.  Row (g, t) is entry i = t - (P - 1) of hypothesis g; for 0 <= i < len[g] its log-probability of
+// target[g * Lmax + i] and its masked argmax go to lp_out / am_out [g * Lmax + i].  Other rows are skipped.
+void wh_launch_score_finish(hipStream_t s, const float* logits, int vocab, const unsigned* mask_first, const unsigned* mask_base, int rows, int T, int P,
+                            int Lmax, const int* len, const int* target, float* lp_out, int* am_out);
+
 extern int wh_dbg_cross_unroll;
 extern int wh_dbg_lm_blocks_per_cu;
 extern int wh_dbg_mt;
