@@ -395,6 +395,16 @@ class Context:
         n = int(self.lib.wh_ctx_placement(self.h, C.byref(a), C.byref(b)))
         return {"workspaces_timed": n, "first_us_per_launch": float(a.value), "kept_us_per_launch": float(b.value)}
 
+    def debug_set_step_split(self, rows: int):
+        """Test hook (not in the public header): the generated positions of the following decode calls run rows [0, rows) and [rows, n) of the
+        batch as two branches wherever the call is eligible; 0: the context's own rule again."""
+        self._check(self.lib.wh_debug_set_step_split(self.h, C.c_int(rows)))
+
+    @property
+    def step_split(self) -> int:
+        """Rows of the first range the last decode call's generated positions ran with; 0: they ran one chain."""
+        return int(self.lib.wh_debug_get_step_split(self.h))
+
     def set_timestamp_rules(self, tb: int, no_timestamps: int = -1, max_initial_index: int = 50):
         """wh_ctx_set_timestamp_rules: Whisper's timestamp rules on every decode entry of this context (tb = id of <|0.00|>;
         no_timestamps = <|notimestamps|>, suppressed at every step, -1: none; max_initial_index < 0: no bound on the first timestamp)."""

@@ -35,6 +35,11 @@ void prof_collect(wh_ctx* c) {
 
 void drop_step_graph(wh_ctx* c) {
     if (c->step_exec && c->stream) hipStreamSynchronize(c->stream);  // an error path may have left replays in flight
+    // A two-branch step: measured, an executable graph with two branches that is destroyed after a wait for c->stream alone leaves
+    // the context's workspace allocated after hipFree (a 1024-clip context: 29 GB per context closed; every call returns success); with a wait
+    // for the device first, nothing stays.  The cause inside the runtime is not known — presumably the branch's replay on streams the runtime
+    // owns.  One-chain graphs never showed it and are destroyed as before: the device wait also stalls other contexts and the encoder stream
+    if (c->step_exec && c->step_key.split) hipDeviceSynchronize();
     if (c->step_exec) hipGraphExecDestroy(c->step_exec);
     if (c->step_graph) hipGraphDestroy(c->step_graph);
     c->step_exec = nullptr;
@@ -163,6 +168,10 @@ static int ctx_create_impl(wh_model* m, const wh_ctx_opts* opts, wh_ctx** out) {
     c->m = m;
     c->max_batch = max_batch;
     c->dec_cus = dec_masked ? (int)mask_bits(opts->dec_cu_mask, opts->dec_cu_mask_words) : n_cus;   // compute units the token-loop stream may use
+    if (dec_masked) c->dec_mask.assign(opts->dec_cu_mask, opts->dec_cu_mask + opts->dec_cu_mask_words);
+    if (const char* e = getenv("WH_DEC_SPLIT")) c->split_mode = atoi(e) != 0;                     // A/B runs: the split token loop off / on
+    if (const char* e = getenv("WH_DEC_SPLIT_ROWS")) c->split_rows = std::max(0, atoi(e));
+    if (const char* e = getenv("WH_DEC_SPLIT_CUS")) c->split_cus = std::max(1, atoi(e));
     c->no_graph = getenv("WH_NO_GRAPH") != nullptr;
     c->sync_every_pos = getenv("WH_SYNC_EVERY_POS") != nullptr;
     c->al.timing = getenv("WH_ALIGN_TIMING") != nullptr;
@@ -404,7 +413,10 @@ void wh_ctx_free(wh_ctx* c) {
     hipSetDevice(c->m->device);
     if (c->s_enc && c->s_enc != c->stream) hipStreamSynchronize(c->s_enc);   // a prefetched encoder pass may be in flight
     if (c->stream) hipStreamSynchronize(c->stream);
+    if (c->s_split) hipStreamSynchronize(c->s_split);
     drop_step_graph(c);
+    for (auto& e : c->split_ev) hipEventDestroy(e);
+    if (c->s_split) hipStreamDestroy(c->s_split);
     for (int g = 0; g < WH_KG_COUNT; g++)
         for (auto& e : c->prof_events[g]) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (auto& e : c->ev)
@@ -432,6 +444,16 @@ extern "C" int wh_debug_set_es_pad(wh_ctx* c, int pad_rows) {
     c->have_enc = false;
     return WH_OK;
 }
+
+// test hooks (tests/test_step_split_gpu.py; not in the public header).  rows > 0: the generated positions of the following decode calls run rows
+// [0, rows) and [rows, nb) as two branches wherever the call is eligible (choose_split, wh_decode_host.cpp); 0: the context's own rule again
+extern "C" int wh_debug_set_step_split(wh_ctx* c, int rows) {
+    if (!c || rows < 0) return WH_ERR_ARG;
+    c->dbg_split = rows;
+    return WH_OK;
+}
+// the first range's rows of the last decode call; 0 = it ran one chain
+extern "C" int wh_debug_get_step_split(const wh_ctx* c) { return c ? c->last_split : -1; }
 
 const char* wh_last_error(const wh_ctx* c) { return c ? c->err.c_str() : wh_global_error().c_str(); }
 

@@ -1586,6 +1586,7 @@ void set_max_smem(K kernel, size_t bytes) {
 template <typename T, typename TO, int NW, typename TW>
 void launch_dec_gemm_mt(hipStream_t s, const SkinnyArgs& a) {
     const int n_tiles = (a.N + 15) / 16;
+    const int Ms = a.m_sel ? a.m_sel : a.M;   // the rows the variant is chosen for: the whole batch's, also when the launch runs a row range of it
     auto launch = [&](auto kernel, dim3 grid, size_t smem) {
         set_max_smem(kernel, smem);
         hipLaunchKernelGGL(kernel, grid, dim3(NW * 64), smem, s, a);
@@ -1601,16 +1602,16 @@ void launch_dec_gemm_mt(hipStream_t s, const SkinnyArgs& a) {
     if (wh_dbg_mt > 0) mt_cap = wh_dbg_mt;  // microbench override
     // batches beyond 64 rows (measured at 256 clips): 64-row groups for the 4-way K split — the row groups already give
     // hundreds of workgroups, and each weight fragment then feeds four MFMAs instead of one or two (-0.7 % step time)
-    if (wh_dbg_mt <= 0 && a.M > 64 && NW == 4) mt_cap = n_tiles <= 32 ? 2 : 4;   // (narrow N at 256 rows: 4.1 vs 4.8 us)
-    if (wh_dbg_mt <= 0 && a.M > 64 && NW == 8 && !a.xpart) mt_cap = 2;  // fc2: 32-row groups (-0.5 %; 64 is slower again)
+    if (wh_dbg_mt <= 0 && Ms > 64 && NW == 4) mt_cap = n_tiles <= 32 ? 2 : 4;   // (narrow N at 256 rows: 4.1 vs 4.8 us)
+    if (wh_dbg_mt <= 0 && Ms > 64 && NW == 8 && !a.xpart) mt_cap = 2;  // fc2: 32-row groups (-0.5 %; 64 is slower again)
     // hundreds of rows (one key range per clip, so no merged X): NT column tiles per workgroup while >= 256 workgroups remain
     // (k_dec_gemm_wide; bit-identical results, so following the batch is allowed)
     if constexpr (!__is_same(T, float) && !__is_same(T, xf32))   // (f32 rows keep k_dec_gemm: the exact-f32 mode and the small-context form of the split-fp16 mode)
-    if (a.M > 64 && !a.xpart && wh_dbg_mt <= 0 && a.K % (NW * 4 * WTraits<T, TW>::KW) == 0) {
+    if (Ms > 64 && !a.xpart && wh_dbg_mt <= 0 && a.K % (NW * 4 * WTraits<T, TW>::KW) == 0) {
         constexpr int WMT = 4;
         int wide = wh_dbg_wide;
         if (const char* e = getenv("WH_DEC_WIDE")) wide = atoi(e);   // A/B switch for the parity test (0: k_dec_gemm only)
-        const int rg = (a.M + 16 * WMT - 1) / (16 * WMT);
+        const int rg = (Ms + 16 * WMT - 1) / (16 * WMT);   // (of the whole batch: decides nt; the grid below covers this launch's rows)
         // measured (tools/dec_gemm_sweep.cpp, profiles/r02_dec_gemm_sweep.txt): four column tiles while >= 512 workgroups
         // remain (fc1 at 1024 rows: 11.7 vs 13.2 us), else two while >= 128 remain (1280 x 1280 at 256 rows: 8.5 vs 11.3 us;
         // 512 x 512 at 256 rows would leave 64: 5.7 vs 4.1 us), else k_dec_gemm.  Eight waves x 16 tiles of partial sums
@@ -1621,12 +1622,12 @@ void launch_dec_gemm_mt(hipStream_t s, const SkinnyArgs& a) {
         if (wide == 2 || (wide == 4 && NW == 4)) nt = wide;
         if (wide != 0 && nt > 1 && n_tiles % nt == 0) {
             wh_with_pow2<2, 4>(nt, [&](auto NT) {
-                launch(k_dec_gemm_wide<T, TO, WMT, decltype(NT)::value, NW, TW>, dim3(n_tiles / nt, rg, a.zn), DecGemmLds<NW, WMT, WMT * decltype(NT)::value>::BYTES);
+                launch(k_dec_gemm_wide<T, TO, WMT, decltype(NT)::value, NW, TW>, dim3(n_tiles / nt, (a.M + 16 * WMT - 1) / (16 * WMT), a.zn), DecGemmLds<NW, WMT, WMT * decltype(NT)::value>::BYTES);
             });
             return;
         }
     }
-    const int mt = std::min(mt_cap, (a.M + 15) / 16);
+    const int mt = std::min(mt_cap, (Ms + 15) / 16);
     if (a.xpart) {  // X merged from attention partials: 16-row groups only (the merge is per-lane work)
         wh_with_pow2<4, 32>(a.x_splits, [&](auto XP) {   // + merged X tile
             launch(k_dec_gemm<T, TO, 1, NW, decltype(XP)::value, TW>, dim3(n_tiles, (a.M + 15) / 16), DecGemmLds<NW, 1, 1>::BYTES + (size_t)16 * a.K * sizeof(T));

@@ -40,6 +40,8 @@ struct DecodePlan {
     int K = 1, ncl = 0;
 };
 
+static int choose_split(const wh_ctx* c, const wh_ctx::StepKey& key);   // (the split token loop, below)
+
 // all validation; no HIP call
 static int plan_decode(wh_ctx* c, int ncl, const wh_decode_params* p, bool want_logits, size_t logits_rows, const int32_t* sel, size_t n_sel, DecodePlan& pl) {
     const wh_dims& D = c->m->dims;
@@ -95,6 +97,8 @@ static int plan_decode(wh_ctx* c, int ncl, const wh_decode_params* p, bool want_
     if (c->al.on) { key.al_cap = NEW; key.al_gen = c->al.gen; }   // (prepare_alignment completes it with the side buffer's address)
     if (c->bm.on) { key.beam_k = c->bm.k; key.beam_c = c->bm.c; key.beam_buf = c->bm.buf; }
     if (c->sm.on && !sample_trivial(c)) key.sample_buf = c->sm.buf;
+    key.split = choose_split(c, key);
+    key.split_cus = key.split ? std::min(c->split_cus, c->dec_cus) : 0;
     return WH_OK;
 }
 
@@ -335,10 +339,12 @@ struct Step : StepBase {
 
     // one decoder layer at the current position: self-attention over the row's cache, with this position's k / v appended
     void layer(int l, bool advance) const {
-        const long cache_l = (long)nb * D.n_heads * D.n_text_ctx * WH_HEAD_DIM * m->esz;   // bytes per layer
+        const long cache_row = (long)D.n_heads * D.n_text_ctx * WH_HEAD_DIM * m->esz;   // bytes per row
+        const long cache_l = (long)nb * cache_row;                                      // ... and per layer: the whole batch's, whatever the range
+        const long cache_0 = l * cache_l + row0 * cache_row;
         layer_with(l, advance, [&] {
-            wh_launch_dec_self_attn(s, prec, c->dqkv, (char*)c->self_k + l * cache_l, (char*)c->self_v + l * cache_l, c->datt, c->pos, (int)d, D.n_heads,
-                                    D.n_text_ctx, nb, mpad, d_off);
+            wh_launch_dec_self_attn(s, prec, rm(c->dqkv, 3 * d, prec == WH_PREC_F16X3 ? 4 : m->esz), (char*)c->self_k + cache_0, (char*)c->self_v + cache_0, slab(c->datt), c->pos,
+                                    (int)d, D.n_heads, D.n_text_ctx, nr, mpad, d_off);   // (a range with row0 > 0 has no prefixes: d_off == nullptr)
         });
     }
 
@@ -458,6 +464,69 @@ struct Step : StepBase {
     }
 };
 
+// ---- the split token loop ----------------------------------------------------------
+// Whether a call's generated positions run as two row ranges, and the first range's rows (0: one chain).  The rows of a greedy batch are
+// independent until the argmax finish, and no kernel of a layer mixes rows, so a range computes what it computes in the whole batch.
+//  * only the plain greedy key in bf16: no beam search (rows share clips and are permuted), no sampling, no alignment copies; what only acts in
+//    emit() — timestamp rules, log-probabilities, repetition controls — is allowed;
+//  * per-clip prefixes with a non-empty one in the batch fall back to one chain, and so do contexts whose decode GEMMs are k_dec_tile;
+//  * k_dec_gemm / k_dec_gemm_wide read whole row groups of G = min(64, nb rounded up to 16) rows whose tail is masked, not clamped: the second
+//    range's groups must end inside the slab pitch.
+constexpr bool WH_DEC_SPLIT_DEFAULT = true;    // (the rule below applies without WH_DEC_SPLIT=1)
+static int choose_split(const wh_ctx* c, const wh_ctx::StepKey& key) {
+    const int nb = key.nb;
+    if (c->split_mode == 0 || c->m->prec != WH_PREC_BF16 || c->dec_tile || nb < 2) return 0;   // (k_dec_tile takes no row range)
+    if (key.beam_k || key.sample_buf || c->al.on || key.pfx) return 0;
+    int r0 = 0;
+    if (c->dbg_split > 0) r0 = c->dbg_split;                                                       // the tests' hook: any context
+    else if ((c->split_mode == 1 || (c->split_mode < 0 && WH_DEC_SPLIT_DEFAULT)) && c->cross_es && nb >= 1024) {
+        r0 = c->split_rows > 0 ? c->split_rows : nb / 2 / 64 * 64;                                  // halves, on a row-group boundary of the decode GEMMs
+    }
+    if (r0 <= 0 || r0 >= nb) return 0;
+    const int G = std::min(64, (nb + 15) / 16 * 16);
+    if (r0 + (nb - r0 + G - 1) / G * G > c->mpad) return 0;
+    return r0;
+}
+
+// the second decode stream and the events of a split step: created outside any capture, at the first call that splits
+static int ensure_split_stream(wh_ctx* c) {
+    if (!c->s_split) {
+        hipError_t he = c->dec_mask.empty() ? hipStreamCreateWithFlags(&c->s_split, hipStreamNonBlocking)
+                                            : hipExtStreamCreateWithCUMask(&c->s_split, (uint32_t)c->dec_mask.size(), c->dec_mask.data());
+        if (he != hipSuccess) { c->s_split = nullptr; return fail(c, WH_ERR_HIP, "the second decode stream: %s", hipGetErrorString(he)); }
+    }
+    const size_t want = 3;   // fork, join, the first range's first cross-attention query
+    while (c->split_ev.size() < want) {
+        hipEvent_t e = nullptr;
+        CTX_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        c->split_ev.push_back(e);
+    }
+    return WH_OK;
+}
+
+// The decoder layers of a generated position as two branches: rows [0, split) on the decode stream, the rest on the second one, forked behind
+// the embedding (the previous position's finish) and joined before emit().  Captured, the events become the edges of a graph with two
+// parallel branches; launched eagerly they order the two streams.  The layers are issued alternately, so that the stagger's event is
+// recorded before the launch that waits for it is issued.
+static void launch_layers_split(wh_ctx* c, const Step& t) {
+    const int L = t.D.dec_layers, r0 = t.k.split;
+    hipEvent_t* ev = c->split_ev.data();
+    hipEvent_t e_fork = ev[0], e_join = ev[1];
+    Step a = t, b = t;
+    a.nr = r0; a.es_cus = t.k.split_cus;
+    b.row0 = r0; b.nr = t.nb - r0; b.es_cus = t.k.split_cus; b.s = c->s_split;
+    a.q_rec = ev[2];   // the stagger: B starts behind A's first cross-attention query (left alone, both reach their cross-attention together)
+    hipEventRecord(e_fork, t.s);
+    hipStreamWaitEvent(c->s_split, e_fork, 0);
+    for (int l = 0; l < L; l++) {
+        a.layer(l, false);
+        if (l == 0 && a.q_rec) hipStreamWaitEvent(c->s_split, a.q_rec, 0);
+        b.layer(l, false);
+    }
+    hipEventRecord(e_join, c->s_split);
+    hipStreamWaitEvent(t.s, e_join, 0);
+}
+
 // One decoder position.  prompt == nullptr: a generated position — the emitting step that is captured into the graph; it sees the
 // context and its key, nothing else (wh_ctx::StepKey).
 static void launch_step(wh_ctx* c, const wh_ctx::StepKey& k, const PromptStep* prompt = nullptr) {
@@ -468,7 +537,8 @@ static void launch_step(wh_ctx* c, const wh_ctx::StepKey& k, const PromptStep* p
         const NextEmbed ne = t.next_embed();
         wh_launch_dec_embed(t.s, t.prec, ne.tok_emb, ne.pos_emb, c->feed, c->tok_ld, c->pos, ne.x, ne.xslab, ne.stats, t.nb, ne.d, ne.mpad, ne.xgamma, ne.shift, ne.off);
     }
-    for (int l = 0; l < t.D.dec_layers; l++) t.layer(l, l == t.D.dec_layers - 1 && !emits && !lang && !probe);
+    if (!prompt && k.split) launch_layers_split(c, t);
+    else for (int l = 0; l < t.D.dec_layers; l++) t.layer(l, l == t.D.dec_layers - 1 && !emits && !lang && !probe);
     if (emits) t.emit();
     if (lang) t.lang(prompt->lang_col, !probe);   // (before the probe, if the probe sits at the same position)
     if (probe) t.probe();
@@ -517,6 +587,8 @@ static int run_token_loop(wh_ctx* c, const wh_ctx::StepKey& key, int remaining, 
         if (rc) return rc;
     }
     std::vector<int> done_h(key.nb);
+    wh_ctx::StepKey one_chain = key;   // event-timed positions run unsplit: their kernel-group brackets describe the one-chain form
+    one_chain.split = one_chain.split_cus = 0;
     for (int r = 0; r < remaining; r++) {
         const bool sampled = c->prof && stride > 1 && (r % stride) == stride / 2;
         if (use_graph && !sampled) {
@@ -527,8 +599,9 @@ static int run_token_loop(wh_ctx* c, const wh_ctx::StepKey& key, int remaining, 
                 return fail(c, WH_ERR_HIP, "hipGraphLaunch failed: %s", hipGetErrorString(ge));
             }
         } else {
-            launch_step(c, key);
+            launch_step(c, c->prof ? one_chain : key);
         }
+        if (!(c->prof && (!use_graph || sampled))) c->last_split = key.split;   // a position ran as two branches
         // diagnostic (profiles/README.md, rocprofv3 --pmc at whisper-large-v3 size): bound the number of dispatches in flight
         if (c->sync_every_pos) hipStreamSynchronize(s);
         // EOT early-out (src/main.rs:781-783, 820-822): poll the done flags every 16 generated tokens
@@ -762,6 +835,8 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
     int rc = plan_decode(c, nb, p, logits_out != nullptr, logits_rows, sel, n_sel, pl);
     if (rc) return rc;
     const wh_ctx::StepKey& key = pl.key;
+    c->last_split = 0;   // (run_token_loop sets it to what it launched)
+    if (key.split && (rc = ensure_split_stream(c))) return rc;
     // the encoder states come from the encoder stream
     if (c->s_enc != s) CTX_HIP(c, hipStreamWaitEvent(s, c->ev_enc_done, 0));
     CTX_HIP(c, hipEventRecord(c->ev[5], s));   // decode start (stage timing)

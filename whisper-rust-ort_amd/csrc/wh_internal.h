@@ -102,6 +102,15 @@ struct wh_ctx {
     // then the next batch's encoder runs beside this batch's token loop, each on its own part of the chip.
     hipStream_t s_enc = nullptr;
     hipStream_t cur = nullptr;      // stream of the phase being launched (event brackets of the profiling hooks)
+    // The split token loop: a generated position runs the decoder layers of two row ranges of the batch as two branches, the
+    // second on s_split (created with the token-loop stream's CU mask, at the first call that splits), forked and joined through split_ev.
+    // split_mode / split_rows / split_cus: WH_DEC_SPLIT (0 off, 1 on, unset: the rule of choose_split), WH_DEC_SPLIT_ROWS (rows of the first
+    // range, 0: half the batch) and WH_DEC_SPLIT_CUS (compute units of a range's cross-attention launch), read at creation for A/B runs.
+    // dbg_split: wh_debug_set_step_split's forced first-range rows (0: none); last_split: what the last decode call ran with (0: one chain)
+    hipStream_t s_split = nullptr;
+    std::vector<hipEvent_t> split_ev;
+    std::vector<uint32_t> dec_mask;
+    int split_mode = -1, split_rows = 0, split_cus = 160, dbg_split = 0, last_split = 0;
     // hand-offs between the two streams: encoder states ready (recorded on s_enc), encoder states consumed by the
     // cross-K/V projection (recorded on stream; the next encoder pass may overwrite them)
     hipEvent_t ev_enc_done = nullptr, ev_kv_done = nullptr;
@@ -264,7 +273,8 @@ struct wh_ctx {
         int beam_k = 0, beam_c = 0;            // beam search: beam_k 0 = off; nb then counts rows = clips x beam_k.  beam_buf: the identity of the
         const void* beam_buf = nullptr;        // setter's buffers (logits scratch and search state: one allocation each, freed together)
         const void* sample_buf = nullptr;      // temperature sampling: nullptr = off; the identity of the setter's buffers (the per-row values are read through them)
-        auto members() const { return std::tie(nb, n_prompt, eot, n_forced, logits_rows, d_logits, d_sel, ts_begin, ts_max_init, lp_sum, pfx, rep, rep_p, rep_n, al_q, al_cap, al_gen, beam_k, beam_c, beam_buf, sample_buf); }
+        int split = 0, split_cus = 0;          // the split token loop: rows of the first range (0 = one chain) and the compute units of a range's cross-attention launch
+        auto members() const { return std::tie(split, split_cus, nb, n_prompt, eot, n_forced, logits_rows, d_logits, d_sel, ts_begin, ts_max_init, lp_sum, pfx, rep, rep_p, rep_n, al_q, al_cap, al_gen, beam_k, beam_c, beam_buf, sample_buf); }
         bool operator==(const StepKey& o) const { return members() == o.members(); }
     } step_key;
     // ---- the decode options: one struct each, laid out alike — `on` and the settings, the device buffers (DevBuf: freed with the context or

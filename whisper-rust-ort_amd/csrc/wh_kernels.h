@@ -96,6 +96,11 @@ struct SkinnyArgs {
     long ldc = 0;
     int c_mpad = 0;
     int M = 0, N = 0, K = 0, act = 0;
+    // A launch on a row range of the batch (the split token loop): every row pointer above and below is already advanced to the
+    // range's first row, M counts the range's rows and the pitches (x_mpad, c_mpad) stay the workspace's.  m_sel: the rows of the whole batch — the
+    // launchers of k_dec_gemm / k_dec_gemm_wide choose the kernel variant from it, so a row runs the instructions it runs in the whole batch (0: M).
+    // (k_dec_tile takes no row range: it clamps padding rows to the slab's last row, which a range's pointers move — contexts with dec_tile do not split)
+    int m_sel = 0;
     // LayerNorm folded into this GEMM (consumer): y = rstd[m] * (acc - mean[m] * ln_s[n]) + bias[n], with
     // mean/rstd of row m reduced from ln_tiles per-tile partial sums {sum x, sum x^2} [ln_tiles][x_mpad][2]
     const float* ln_part = nullptr;

@@ -30,6 +30,19 @@ struct StepBase {
     // the cross K/V of all layers are re-read at every position: below ~half the 256 MiB Infinity Cache they are served
     // from it; above, their stream only evicts the decode weights and activations — then they are loaded non-temporally
     const bool kv_nt = (c->cross_es ? 1.0 : (double)D.dec_layers * 2.0) * ncl * S * d * (f8 ? 1 : (double)m->esz) > 128.0 * 1024 * 1024;
+    // The row range the launches run on: rows row0 .. row0 + nr - 1 of the nb, on the same workspace (the whole batch unless the split token loop
+    // sets a branch's range and stream).  Only the first row of every operand and the row count follow the range: pitches, the
+    // cache strides, the kernel variants (SkinnyArgs::m_sel) and kv_nt stay the whole batch's.  es_cus: compute units of the encoder-state
+    // cross-attention launch.  A range with row0 > 0 runs with rpc == 1 (no beam search), in bf16 (esz: the slabs' and the caches' element), without
+    // per-clip prefixes and on k_dec_gemm / k_dec_gemm_wide only (choose_split, wh_decode_host.cpp)
+    int row0 = 0, nr = nb, es_cus = c->dec_cus;
+    template <typename T> T* rm(T* p, long ld) const { return p + (long)row0 * ld; }                          // row-major rows of ld elements
+    void* rm(void* p, long ld, size_t esz) const { return (char*)p + (long)row0 * ld * (long)esz; }
+    void* slab(void* p) const { return (char*)p + (long)row0 * 32 * (long)m->esz; }                           // slab layout [K/32][mpad][32]: row r at r * 32
+    // the staggering of two branches (null in one chain): q_rec is recorded behind layer 0's cross-attention query — what the other branch's
+    // first launch waits for, so that one branch's cross-attention stream runs beside the other's GEMM chain
+    hipEvent_t q_rec = nullptr;
+    void after_query(int l) const { if (q_rec && l == 0) hipEventRecord(q_rec, s); }
 
     StepBase(wh_ctx* ctx, const wh_ctx::StepKey& key) : c(ctx), k(key), rpc(key.beam_k ? key.beam_k : 1), ncl(key.nb / rpc), clip0(0) {}
     StepBase(wh_ctx* ctx, const wh_ctx::StepKey& key, int rows_per_clip, int clips, int first_clip) : c(ctx), k(key), rpc(rows_per_clip), ncl(clips), clip0(first_clip) {}
@@ -39,21 +52,21 @@ struct StepBase {
         if (c->dec_tile && wh_dec_tile_applicable(prec, a)) wh_launch_dec_tile(s, prec, out_f32, a);
         else wh_launch_dec_gemm(s, prec, out_f32, a);
     }
-    // a GEMM that consumes LN(x) of the residual stream: out [nb][N], row-major or (slab_out) slab layout
+    // a GEMM that consumes LN(x) of the residual stream: out [nb][N], row-major or (slab_out) slab layout; `out` is the range's first row
     SkinnyArgs ln_consumer(const void* W, const float* bias, const float* wscale, const float* ln_s, long N, void* out, int ln_tiles, bool slab_out = false) const {
         SkinnyArgs a;
-        a.X = c->dxs; a.x_mpad = mpad; a.W = W; a.bias = bias; a.wscale = wscale; a.C = out;
+        a.X = slab(c->dxs); a.x_mpad = mpad; a.W = W; a.bias = bias; a.wscale = wscale; a.C = out;
         if (slab_out) a.c_mpad = mpad; else a.ldc = N;
-        a.M = nb; a.N = (int)N; a.K = (int)d;
-        a.ln_part = c->lnpart; a.ln_tiles = ln_tiles; a.ln_s = ln_s; a.shift_io = c->dshift;
+        a.M = nr; a.m_sel = nb; a.N = (int)N; a.K = (int)d;
+        a.ln_part = rm(c->lnpart, 2); a.ln_tiles = ln_tiles; a.ln_s = ln_s; a.shift_io = rm(c->dshift, 1);
         return a;
     }
     // a GEMM that adds to the residual stream: x += X W^T + bias, plus the raw slab copy and the partial sums of the next LayerNorm
-    // (next_gamma: that LayerNorm's γ, applied on the activation side in fp8 mode)
+    // (next_gamma: that LayerNorm's γ, applied on the activation side in fp8 mode; X: a slab, the range's first row)
     SkinnyArgs residual_producer(const void* W, const float* bias, const float* wscale, const void* X, long K, const float* next_gamma) const {
         SkinnyArgs a;
-        a.X = X; a.x_mpad = mpad; a.W = W; a.bias = bias; a.wscale = wscale; a.R = c->dx; a.ldr = d; a.C = c->dx; a.ldc = d;
-        a.M = nb; a.N = (int)d; a.K = (int)K; a.xslab_out = c->dxs; a.stats_out = c->lnpart; a.row_shift = c->dshift;
+        a.X = X; a.x_mpad = mpad; a.W = W; a.bias = bias; a.wscale = wscale; a.R = rm(c->dx, d); a.ldr = d; a.C = rm(c->dx, d); a.ldc = d;
+        a.M = nr; a.m_sel = nb; a.N = (int)d; a.K = (int)K; a.xslab_out = slab(c->dxs); a.stats_out = rm(c->lnpart, 2); a.row_shift = rm(c->dshift, 1);
         if (f8) a.xgamma = next_gamma;
         return a;
     }
@@ -76,17 +89,17 @@ struct StepBase {
         return a;
     }
 
-    // One decoder layer on the nb rows.  self_attn(): the launch that turns c->dqkv into c->datt (slab layout) — the cached single-position
+    // One decoder layer on the range's rows (the nb rows unless a range is set).  self_attn(): the launch that turns c->dqkv into c->datt (slab layout) — the cached single-position
     // kernel of the token loop, or the scoring pass's causal kernel over a hypothesis's rows.
     // `advance`: nothing follows the layers at this position (a prompt position without a head), so this fc2 advances the position
     template <typename SelfAttn>
     void layer_with(int l, bool advance, SelfAttn&& self_attn) const {
         const DecLayerDev& L = m->dec[l];
         const long kv_stride = (long)ncl * S * d;  // elements between consecutive [clips][S][d] planes
-        const long kv_clip0 = (long)clip0 * S * d; // ... and from the plane's first clip to this launch's first
+        const long kv_clip0 = (long)(clip0 + row0) * S * d; // ... and from the plane's first clip to this launch's first
         {   // LN1 ∘ Q|K|V projection
             Prof pr(c, WH_KG_DEC_GEMM);
-            gemm(false, ln_consumer(L.qkv_w, L.qkv_b, L.qkv_sc, L.qkv_s, 3 * d, c->dqkv, (l == 0) ? 1 : ln_tiles_d));
+            gemm(false, ln_consumer(L.qkv_w, L.qkv_b, L.qkv_sc, L.qkv_s, 3 * d, rm(c->dqkv, 3 * d, prec == WH_PREC_F16X3 ? 4 : m->esz), (l == 0) ? 1 : ln_tiles_d));
         }
         {
             Prof pr(c, WH_KG_DEC_OTHER);
@@ -94,15 +107,16 @@ struct StepBase {
         }
         {   // self-attention out-proj + residual → x, raw slab, LN2 partials
             Prof pr(c, WH_KG_DEC_GEMM);
-            gemm(true, residual_producer(L.o_w, L.o_b, L.o_sc, c->datt, d, L.ln2_w));
+            gemm(true, residual_producer(L.o_w, L.o_b, L.o_sc, slab(c->datt), d, L.ln2_w));
         }
         if (c->cross_es) {
             // the attention runs on the encoder states (wh_cross_es.hip): W_k moves to the query side, W_v behind the attention
             {   // LN2 ∘ cross-attention query, kept in f32
                 Prof pr(c, WH_KG_DEC_GEMM);
-                gemm(true, ln_consumer(L.cq_w, L.cq_b, L.cq_sc, L.cq_s, d, c->dq32, ln_tiles_d));
+                gemm(true, ln_consumer(L.cq_w, L.cq_b, L.cq_sc, L.cq_s, d, rm(c->dq32, d), ln_tiles_d));
                 // expanded queries qe[h] = W_k,h^T q_h: [nb][H][d] f32
-                wh_launch_dec_qexpand(s, prec, c->dq32, L.cqx_w, c->dqe, nb, (int)d, D.n_heads);
+                wh_launch_dec_qexpand(s, prec, rm(c->dq32, d), L.cqx_w, rm(c->dqe, D.n_heads * d), nr, (int)d, D.n_heads);
+                after_query(l);
             }
             if (k.al_q && c->al.layer[l].n) {   // word-level timestamps: the listed heads' expanded queries of this position
                 Prof pr(c, WH_KG_DEC_OTHER);
@@ -110,14 +124,14 @@ struct StepBase {
             }
             {
                 Prof pr(c, WH_KG_DEC_CROSS_ATTN);
-                wh_launch_dec_cross_attn_es(s, prec, c->dqe, (const char*)c->es_E + (long)clip0 * c->es_rows * d * m->esz, c->dctx, (int)S, c->es_rows, nb, mpad, kv_nt,
-                                            c->dec_cus, rpc);
+                wh_launch_dec_cross_attn_es(s, prec, rm(c->dqe, D.n_heads * d), (const char*)c->es_E + (long)(clip0 + row0) * c->es_rows * d * m->esz, slab(c->dctx), (int)S,
+                                            c->es_rows, nr, mpad, kv_nt, es_cus, rpc);
             }
             {   // per head: W_v,h ctx_h + b_v,h → the attention output the out-projection below expects (slab layout)
                 Prof pr(c, WH_KG_DEC_GEMM);
                 SkinnyArgs a;
-                a.X = c->dctx; a.x_mpad = mpad; a.W = L.cv_w; a.bias = L.cv_b; a.C = c->datt; a.c_mpad = mpad;
-                a.M = nb; a.N = WH_HEAD_DIM; a.K = (int)d;
+                a.X = slab(c->dctx); a.x_mpad = mpad; a.W = L.cv_w; a.bias = L.cv_b; a.C = slab(c->datt); a.c_mpad = mpad;
+                a.M = nr; a.m_sel = nb; a.N = WH_HEAD_DIM; a.K = (int)d;
                 a.zn = D.n_heads; a.x_zs = (long)(d / 32) * mpad * 32; a.w_zs = (long)WH_HEAD_DIM * d; a.c_zs = (long)(WH_HEAD_DIM / 32) * mpad * 32;
                 a.bias_zs = WH_HEAD_DIM;
                 if (f8) wh_launch_dec_gemm(s, WH_PREC_BF16, false, a);   // (fp8 mode: cv_w is the quantised model's W_v, code x row scale, as bf16 — wh_model.cpp)
@@ -126,7 +140,8 @@ struct StepBase {
         } else {
             {   // LN2 ∘ cross-attention query
                 Prof pr(c, WH_KG_DEC_GEMM);
-                gemm(false, ln_consumer(L.cq_w, L.cq_b, L.cq_sc, L.cq_s, d, c->dq, ln_tiles_d));
+                gemm(false, ln_consumer(L.cq_w, L.cq_b, L.cq_sc, L.cq_s, d, rm(c->dq, d, prec == WH_PREC_F16X3 ? 4 : m->esz), ln_tiles_d));
+                after_query(l);
             }
             if (k.al_q && c->al.layer[l].n) {   // word-level timestamps: the listed heads' queries of this position
                 Prof pr(c, WH_KG_DEC_OTHER);
@@ -138,26 +153,27 @@ struct StepBase {
                                           c->kv_amax + (long)(2 * l) * nb * D.n_heads, c->kv_amax + (long)(2 * l + 1) * nb * D.n_heads,
                                           c->cpart, c->cml, (int)S, (int)d, D.n_heads, c->cross_splits, nb, c->datt, mpad, kv_nt);
             else
-                wh_launch_dec_cross_attn(s, prec, c->dq, (char*)c->cross_kv + ((2 * l) * kv_stride + kv_clip0) * m->esz,
+                wh_launch_dec_cross_attn(s, prec, rm(c->dq, d, prec == WH_PREC_F16X3 ? 4 : m->esz), (char*)c->cross_kv + ((2 * l) * kv_stride + kv_clip0) * m->esz,
                                          (char*)c->cross_kv + ((2 * l + 1) * kv_stride + kv_clip0) * m->esz,
-                                         c->cpart, c->cml, (int)S, (int)d, D.n_heads, c->cross_splits, nb, c->datt, mpad, kv_nt, rpc);
+                                         rm(c->cpart, c->cross_splits * d), rm(c->cml, (long)c->cross_splits * D.n_heads * 2), (int)S, (int)d, D.n_heads, c->cross_splits, nr,
+                                         slab(c->datt), mpad, kv_nt, rpc);
         }
         {   // merge of the key ranges ∘ cross-attention out-proj + residual → x, raw slab, LN3 partials
             Prof pr(c, WH_KG_DEC_GEMM);
             const bool merged = c->cross_splits == 1 || c->cross_es;   // one key range per clip: the attention kernel wrote its output itself
-            SkinnyArgs a = residual_producer(L.co_w, L.co_b, L.co_sc, merged ? c->datt : nullptr, d, L.ln3_w);
-            if (!merged) { a.xpart = c->cpart; a.xml = c->cml; a.x_splits = c->cross_splits; a.x_heads = D.n_heads; }
+            SkinnyArgs a = residual_producer(L.co_w, L.co_b, L.co_sc, merged ? slab(c->datt) : nullptr, d, L.ln3_w);
+            if (!merged) { a.xpart = rm(c->cpart, c->cross_splits * d); a.xml = rm(c->cml, (long)c->cross_splits * D.n_heads * 2); a.x_splits = c->cross_splits; a.x_heads = D.n_heads; }
             gemm(true, a);
         }
         {   // LN3 ∘ fc1 + GELU (slab output)
             Prof pr(c, WH_KG_DEC_GEMM);
-            SkinnyArgs a = ln_consumer(L.fc1_w, L.fc1_b, L.fc1_sc, L.fc1_s, D.ffn, c->dh, ln_tiles_d, true);
+            SkinnyArgs a = ln_consumer(L.fc1_w, L.fc1_b, L.fc1_sc, L.fc1_s, D.ffn, slab(c->dh), ln_tiles_d, true);
             a.act = 1;
             gemm(false, a);
         }
         {   // fc2 + residual → x, raw slab, partials for the next layer's LN1 / the final LN
             Prof pr(c, WH_KG_DEC_GEMM);
-            SkinnyArgs a = residual_producer(L.fc2_w, L.fc2_b, L.fc2_sc, c->dh, D.ffn, (l + 1 < D.dec_layers) ? m->dec[l + 1].ln1_w : m->dec_ln_w);
+            SkinnyArgs a = residual_producer(L.fc2_w, L.fc2_b, L.fc2_sc, slab(c->dh), D.ffn, (l + 1 < D.dec_layers) ? m->dec[l + 1].ln1_w : m->dec_ln_w);
             if (advance) { a.ticket = c->step_ticket; a.pos_w = c->pos; }
             gemm(true, a);
         }
