@@ -517,6 +517,27 @@ def test_decoder_attention_kernels_alone(gpu, group):
     assert "err/bound" in r.stdout, r.stdout
 
 
+@pytest.mark.parametrize("group", ["head", "tile", "finish", "lang", "embed"])
+def test_lm_head_kernels_alone(gpu, group):
+    """The end of a decode step alone, through the library's launchers (tools/lm_check, one group per parameter): k_lm_head in every dtype, RULES x LP x
+    REP variant, row grouping and position; the LM-head tile kernels; k_argmax_finish with the fused next embedding and k_nospeech_finish; k_lang_head /
+    k_lang_finish; k_dec_embed.  Logits against a float64 product with bounds built from the operands; selection — masks, ranges, ties, timestamp and
+    side logits, tokens, state, bitmaps — exactly, from the kernels' own logits; sums of exp within a bound derived from the exponential's accuracy;
+    a chain of k_lm_head -> k_argmax_finish over six positions on the kernels' own row state, bitmap, tokens and position; guard words on both sides of every output (tests/test_lm_check_cpu.py shows that the bounds hold and bite)."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = os.path.join(root, "tools", "lm_check")
+    assert os.path.exists(exe), f"{exe} missing: __graft_entry__.build() compiles it"
+    r = subprocess.run([exe, group], capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0 and "MISMATCH" not in r.stdout, r.stdout + r.stderr
+    assert "err/bound" in r.stdout, r.stdout
+    if group == "tile":
+        assert any(ln.startswith("tile logits bit-identical to k_lm_head: ") and ln.endswith(" 0 differing  ok") for ln in r.stdout.splitlines()), r.stdout
+    if group == "lang":
+        assert any(ln.startswith("language logits bit-identical to k_lm_head: ") and ln.endswith(" 0 differing  ok") for ln in r.stdout.splitlines()), r.stdout
+
+
 def test_bf16_batch_is_deterministic_and_permutation_invariant(gpu):
     b = bundle("micro", 11, wb.WH_PREC_BF16, max_batch=16)
     prompt, eot = small_prompt(b.dims)

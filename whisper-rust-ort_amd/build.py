@@ -78,8 +78,10 @@ def build_tools(verbose: bool = False, force: bool = False) -> None:
     # tools/dec_gemm_check (tests/test_hip_parity.py) calls the library's own launchers instead: it links libwhisper_hip.so, so it checks
     # the kernels of whichever library it is built against; tools/enc_check (tests/test_hip_parity.py, tests/test_enc_check_cpu.py) does the same for
     # the encoder side: k_gemm8 / k_ln_stats, k_gemm8x, k_gemm, k_enc_attn, k_layernorm; tools/dec_attn_check (tests/test_hip_parity.py,
-    # tests/test_dec_attn_check_cpu.py) for the decoder's attention: k_dec_self_attn, k_dec_cross_attn, k_dec_cross_attn_cg, k_kv_quant, k_dec_cross_attn8
-    for name in ("dec_gemm_check", "enc_check", "dec_attn_check"):
+    # tests/test_dec_attn_check_cpu.py) for the decoder's attention: k_dec_self_attn, k_dec_cross_attn, k_dec_cross_attn_cg, k_kv_quant, k_dec_cross_attn8;
+    # tools/lm_check (tests/test_hip_parity.py, tests/test_lm_check_cpu.py) for the end of a decode step: k_lm_head, the LM-head tile kernels, k_argmax_finish,
+    # k_nospeech_finish, k_lang_head, k_lang_finish, k_dec_embed
+    for name in ("dec_gemm_check", "enc_check", "dec_attn_check", "lm_check"):
         src, exe = os.path.join(TOOLS, name + ".cpp"), os.path.join(TOOLS, name)
         if force or _stale(exe, [src, OUT, os.path.join(CSRC, "wh_kernels.h")]):
             cmd = [hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-w", src, "-o", exe, "-L" + HERE, "-lwhisper_hip", "-Wl,-rpath,$ORIGIN/../whisper-rust-ort_amd"]

@@ -64,28 +64,37 @@ __global__ __launch_bounds__(256) void k_dec_embed(const T* __restrict__ tok_emb
     if constexpr (PFX) mpos = max(pos - max(off[row], 0), 0);
     const float* pr = pos_emb + (long)mpos * d;
     // pass 1: the residual row and its mean; pass 2: the slab copy and the sums of the CENTRED row (SkinnyArgs::row_shift)
-    float s0 = 0.0f;
-    for (int c = lane * 4; c < d; c += 256) {
-        const f32x4 v = load4_f32(er + c) + *reinterpret_cast<const f32x4*>(pr + c);
-        *reinterpret_cast<f32x4*>(x + (long)row * d + c) = v;
-        s0 += (v[0] + v[1]) + (v[2] + v[3]);
-    }
-    const float mean = shift ? dpp_wave_sum(s0) / (float)d : 0.0f;
-    float s1 = 0.0f, s2 = 0.0f;
-    for (int c = lane * 4; c < d; c += 256) {
-        f32x4 v = load4_f32(er + c) + *reinterpret_cast<const f32x4*>(pr + c);
-        v -= mean;
-        f32x4 g = {1, 1, 1, 1};
-        if (xgamma) g = *reinterpret_cast<const f32x4*>(xgamma + c);  // fp8 mode: the first LayerNorm's γ rides on the slab copy
-        store4(xslab + slab_idx(row, c, mpad), v[0] * g[0], v[1] * g[1], v[2] * g[2], v[3] * g[3]);
-        s1 += (v[0] + v[1]) + (v[2] + v[3]);
-        s2 += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-    }
-    s1 = dpp_wave_sum(s1);
-    s2 = dpp_wave_sum(s2);
+    // The sums are taken in embed_next_row's order (wh_dec_epilogue.h: 256 threads, thread t the columns 4 t + 1024 i, one sum per wave, the four
+    // waves' sums added as (0 + 1) + (2 + 3)): lane l stands for the threads l, l + 64, l + 128, l + 192, so a token at a position gets the same
+    // mean, slab copy and row sums bit for bit whether it is embedded here (prompt positions, the scoring pass) or by the kernel that chose it
+    // (tools/lm_check.cpp, group finish).  Up to d = 256 the two orders coincide; above, one wave sum per row differed in the last bit.
+    float s0[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int w = 0; w < 4; w++)
+        for (int c = (lane + 64 * w) * 4; c < d; c += 1024) {
+            const f32x4 v = load4_f32(er + c) + *reinterpret_cast<const f32x4*>(pr + c);
+            *reinterpret_cast<f32x4*>(x + (long)row * d + c) = v;
+            s0[w] += (v[0] + v[1]) + (v[2] + v[3]);
+        }
+    float mean = 0.0f;
+    if (shift) mean = ((dpp_wave_sum(s0[0]) + dpp_wave_sum(s0[1])) + (dpp_wave_sum(s0[2]) + dpp_wave_sum(s0[3]))) / (float)d;
+    float s1[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s2[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int w = 0; w < 4; w++)
+        for (int c = (lane + 64 * w) * 4; c < d; c += 1024) {
+            f32x4 v = load4_f32(er + c) + *reinterpret_cast<const f32x4*>(pr + c);
+            v -= mean;
+            f32x4 g = {1, 1, 1, 1};
+            if (xgamma) g = *reinterpret_cast<const f32x4*>(xgamma + c);  // fp8 mode: the first LayerNorm's γ rides on the slab copy
+            store4(xslab + slab_idx(row, c, mpad), v[0] * g[0], v[1] * g[1], v[2] * g[2], v[3] * g[3]);
+            s1[w] += (v[0] + v[1]) + (v[2] + v[3]);
+            s2[w] += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+        }
+    const float t1 = (dpp_wave_sum(s1[0]) + dpp_wave_sum(s1[1])) + (dpp_wave_sum(s1[2]) + dpp_wave_sum(s1[3]));
+    const float t2 = (dpp_wave_sum(s2[0]) + dpp_wave_sum(s2[1])) + (dpp_wave_sum(s2[2]) + dpp_wave_sum(s2[3]));
     if (lane == 0) {
-        stats[2 * row] = s1;
-        stats[2 * row + 1] = s2;
+        stats[2 * row] = t1;
+        stats[2 * row + 1] = t2;
         if (shift) shift[row] = mean;
     }
 }

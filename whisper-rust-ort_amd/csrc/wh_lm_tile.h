@@ -257,10 +257,14 @@ struct WhLmTile {
 
     // ---- host side ------------------------------------------------------------------------------------------------------------------------
     // the conditions both kernels share: WH_LM_TILE_MIN_ROWS (default 256; 0 disables: A/B runs and the parity tests flip it between
-    // contexts) is read at every launch decision; whole k-steps; the decode slab layout as the activation operand; no per-channel scale
+    // contexts) is read at every launch decision; whole k-steps; the decode slab layout as the activation operand; no per-channel scale.
+    // A probe (probe_id >= 0) only without the rules and without the repetition bitmap, which is how the no-speech probe runs: the rules variants
+    // have no probe (lp_tile_row<TN, !RULES>), and with the bitmap a touched id's accumulator is NaN by the time the probe is read — k_lm_head,
+    // which hands the raw logit out in both, takes those calls (tools/lm_check.cpp holds the dispatch to that).
     static bool applicable(const SkinnyArgs& a, int bk) {
         const char* e = getenv("WH_LM_TILE_MIN_ROWS");
         const int min_rows = e ? atoi(e) : 256;
+        if (a.part_sum && a.probe_id >= 0 && (a.ts_logits || a.rep_bits)) return false;
         return min_rows > 0 && a.M >= min_rows && (a.K % bk) == 0 && a.X != nullptr && a.xpart == nullptr && a.wscale == nullptr;
     }
     static int parts(const SkinnyArgs& a) { return (a.N + BN - 1) / BN; }   // argmax partials per row, layout [part][x_mpad]
@@ -268,6 +272,10 @@ struct WhLmTile {
     // a.part_sum the log-probability variants, a.rep_bits the repetition variants
     template <typename Pick>
     static void launch(hipStream_t s, const SkinnyArgs& a, Pick pick) {
+        if (a.part_sum && a.probe_id >= 0 && (a.ts_logits || a.rep_bits)) {   // (see applicable: never launched with a probe it would not write)
+            wh_set_error("LM-head tile kernel: a probe needs a launch without timestamp rules and without the repetition bitmap");
+            return;
+        }
         const size_t sm = lds_bytes(a);
         dim3 grid(parts(a) * ((a.M + BM - 1) / BM));
         wh_with_flags([&](auto RULES, auto LP, auto REP) {
