@@ -405,6 +405,16 @@ class Context:
         """Rows of the first range the last decode call's generated positions ran with; 0: they ran one chain."""
         return int(self.lib.wh_debug_get_step_split(self.h))
 
+    def debug_set_step_free(self, on: bool):
+        """Test hook (not in the public header): where debug_set_step_split makes the following decode calls split, their two ranges run
+        whole positions on their own streams if the call is eligible; False: only where the context's own rule splits."""
+        self._check(self.lib.wh_debug_set_step_free(self.h, C.c_int(1 if on else 0)))
+
+    @property
+    def step_free(self) -> int:
+        """1: the generated positions of the last decode call ran as free halves; 0: joined, or one chain."""
+        return int(self.lib.wh_debug_get_step_free(self.h))
+
     def set_timestamp_rules(self, tb: int, no_timestamps: int = -1, max_initial_index: int = 50):
         """wh_ctx_set_timestamp_rules: Whisper's timestamp rules on every decode entry of this context (tb = id of <|0.00|>;
         no_timestamps = <|notimestamps|>, suppressed at every step, -1: none; max_initial_index < 0: no bound on the first timestamp)."""

@@ -34,16 +34,20 @@ void prof_collect(wh_ctx* c) {
 }
 
 void drop_step_graph(wh_ctx* c) {
-    if (c->step_exec && c->stream) hipStreamSynchronize(c->stream);  // an error path may have left replays in flight
+    if (c->step_exec[0] && c->stream) hipStreamSynchronize(c->stream);  // an error path may have left replays in flight
+    if (c->step_exec[0] && c->step_key.free && c->s_split) hipStreamSynchronize(c->s_split);   // (the second range's segments replay there)
     // A two-branch step: measured, an executable graph with two branches that is destroyed after a wait for c->stream alone leaves
     // the context's workspace allocated after hipFree (a 1024-clip context: 29 GB per context closed; every call returns success); with a wait
     // for the device first, nothing stays.  The cause inside the runtime is not known — presumably the branch's replay on streams the runtime
     // owns.  One-chain graphs never showed it and are destroyed as before: the device wait also stalls other contexts and the encoder stream
-    if (c->step_exec && c->step_key.split) hipDeviceSynchronize();
-    if (c->step_exec) hipGraphExecDestroy(c->step_exec);
-    if (c->step_graph) hipGraphDestroy(c->step_graph);
-    c->step_exec = nullptr;
-    c->step_graph = nullptr;
+    // The free-running halves (§5t) have no graph with branches: four single chains, destroyed like the one chain.
+    if (c->step_exec[0] && c->step_key.split && !c->step_key.free) hipDeviceSynchronize();
+    for (int i = 0; i < wh_ctx::STEP_GRAPHS; i++) {
+        if (c->step_exec[i]) hipGraphExecDestroy(c->step_exec[i]);
+        if (c->step_graph[i]) hipGraphDestroy(c->step_graph[i]);
+        c->step_exec[i] = nullptr;
+        c->step_graph[i] = nullptr;
+    }
     c->step_key = wh_ctx::StepKey();
 }
 
@@ -172,6 +176,8 @@ static int ctx_create_impl(wh_model* m, const wh_ctx_opts* opts, wh_ctx** out) {
     if (const char* e = getenv("WH_DEC_SPLIT")) c->split_mode = atoi(e) != 0;                     // A/B runs: the split token loop off / on
     if (const char* e = getenv("WH_DEC_SPLIT_ROWS")) c->split_rows = std::max(0, atoi(e));
     if (const char* e = getenv("WH_DEC_SPLIT_CUS")) c->split_cus = std::max(1, atoi(e));
+    if (const char* e = getenv("WH_DEC_FREE")) c->free_mode = atoi(e) != 0;                       // A/B runs: the free-running halves off / on
+    if (const char* e = getenv("WH_DEC_FREE_EB")) c->free_eb = atoi(e) != 0;                      // ... and without the edge that bounds the first range's lead
     c->no_graph = getenv("WH_NO_GRAPH") != nullptr;
     c->sync_every_pos = getenv("WH_SYNC_EVERY_POS") != nullptr;
     c->al.timing = getenv("WH_ALIGN_TIMING") != nullptr;
@@ -257,8 +263,8 @@ static int ctx_create_impl(wh_model* m, const wh_ctx_opts* opts, wh_ctx** out) {
     const size_t o_cpart = cv.take(B * c->cross_splits * d * 4), o_cml = cv.take(B * c->cross_splits * H * 2 * 4);
     const size_t o_pv = cv.take(MP * (n_tiles + 4) * 4), o_pi = cv.take(MP * (n_tiles + 4) * 4);  // [part][mpad]
     const size_t o_feed = cv.take(B * c->tok_ld * 4), o_out = cv.take(B * c->tok_ld * 4);
-    const size_t o_nout = cv.take(B * 4), o_done = cv.take(B * 4), o_forced = cv.take(TC * 4), o_pos = cv.take(4);
-    const size_t o_stk = cv.take(4);
+    const size_t o_nout = cv.take(B * 4), o_done = cv.take(B * 4), o_forced = cv.take(TC * 4), o_pos = cv.take(2 * 4);
+    const size_t o_stk = cv.take(2 * 4);   // (two each: the whole batch's, and the second range's while the halves run free)
     const size_t o_m1 = cv.take((D.vocab / 32 + 1) * 4), o_m2 = cv.take((D.vocab / 32 + 1) * 4);
     const size_t o_ns = cv.take(B * 4), o_nf = cv.take(B * 4), o_si = cv.take(B * 4), o_fs = cv.take(B * 4), o_gm = cv.take(B * 4);
     const size_t o_lsel = cv.take(B * 4);
@@ -416,6 +422,7 @@ void wh_ctx_free(wh_ctx* c) {
     if (c->s_split) hipStreamSynchronize(c->s_split);
     drop_step_graph(c);
     for (auto& e : c->split_ev) hipEventDestroy(e);
+    for (auto& e : c->free_ev) hipEventDestroy(e);
     if (c->s_split) hipStreamDestroy(c->s_split);
     for (int g = 0; g < WH_KG_COUNT; g++)
         for (auto& e : c->prof_events[g]) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
@@ -454,6 +461,15 @@ extern "C" int wh_debug_set_step_split(wh_ctx* c, int rows) {
 }
 // the first range's rows of the last decode call; 0 = it ran one chain
 extern "C" int wh_debug_get_step_split(const wh_ctx* c) { return c ? c->last_split : -1; }
+// test hooks (tests/test_free_halves_gpu.py; not in the public header).  on != 0: where wh_debug_set_step_split makes the following decode calls
+// split, their two ranges run free (choose_free, wh_decode_host.cpp); 0: only where the context's own rule splits
+extern "C" int wh_debug_set_step_free(wh_ctx* c, int on) {
+    if (!c) return WH_ERR_ARG;
+    c->dbg_free = on != 0;
+    return WH_OK;
+}
+// 1: the generated positions of the last decode call ran as free halves
+extern "C" int wh_debug_get_step_free(const wh_ctx* c) { return c ? c->last_free : -1; }
 
 const char* wh_last_error(const wh_ctx* c) { return c ? c->err.c_str() : wh_global_error().c_str(); }
 

@@ -41,6 +41,7 @@ struct DecodePlan {
 };
 
 static int choose_split(const wh_ctx* c, const wh_ctx::StepKey& key);   // (the split token loop, below)
+static bool choose_free(wh_ctx* c, const wh_ctx::StepKey& key, bool want_logits);   // (the free-running halves, below)
 
 // all validation; no HIP call
 static int plan_decode(wh_ctx* c, int ncl, const wh_decode_params* p, bool want_logits, size_t logits_rows, const int32_t* sel, size_t n_sel, DecodePlan& pl) {
@@ -99,6 +100,7 @@ static int plan_decode(wh_ctx* c, int ncl, const wh_decode_params* p, bool want_
     if (c->sm.on && !sample_trivial(c)) key.sample_buf = c->sm.buf;
     key.split = choose_split(c, key);
     key.split_cus = key.split ? std::min(c->split_cus, c->dec_cus) : 0;
+    key.free = choose_free(c, key, want_logits);
     return WH_OK;
 }
 
@@ -140,8 +142,8 @@ static int upload_token_state(wh_ctx* c, const wh_decode_params* p, const Decode
         CTX_HIP(c, hipMemcpyAsync(c->sm.d_seed, &seed, 8, hipMemcpyHostToDevice, s));
         CTX_HIP(c, hipStreamSynchronize(s));   // (`seed` goes out of scope)
     }
-    CTX_HIP(c, hipMemsetAsync(c->pos, 0, 4, s));
-    CTX_HIP(c, hipMemsetAsync(c->step_ticket, 0, 4, s));
+    CTX_HIP(c, hipMemsetAsync(c->pos, 0, 2 * 4, s));           // (both elements: the whole batch's and the second range's)
+    CTX_HIP(c, hipMemsetAsync(c->step_ticket, 0, 2 * 4, s));
     if (c->rep.on) CTX_HIP(c, hipMemsetAsync(c->rep.bits, 0, (size_t)nb * c->rep.words * 4, s));   // no history yet: nothing is touched
     if (pl.key.beam_k) {   // no position has run (the first one starts the scores and the pool itself)
         CTX_HIP(c, hipMemsetAsync(c->bm.n_steps, 0, (size_t)pl.ncl * 4, s));
@@ -320,10 +322,11 @@ struct Step : StepBase {
     using StepBase::StepBase;
     const int* d_off = k.pfx ? c->pfx.off : nullptr;
 
-    // the token bookkeeping of the kernel that ends an emitting step; log-probabilities go to the sampling call's own buffer or, when they are on, to lp.tok
+    // the token bookkeeping of the kernel that ends an emitting step, from the range's first row on; log-probabilities go to the sampling call's
+    // own buffer or, when they are on, to lp.tok (whole batch only: a range with row0 > 0 records none, choose_free)
     DecodeState decode_state() const {
         DecodeState st;
-        st.feed = c->feed; st.out_tokens = c->out_tokens; st.n_out = c->n_out; st.done = c->done;
+        st.feed = rm(c->feed, c->tok_ld); st.out_tokens = rm(c->out_tokens, c->tok_ld); st.n_out = rm(c->n_out, 1); st.done = rm(c->done, 1);
         st.forced = c->forced; st.n_forced = k.n_forced; st.n_prompt = k.n_prompt; st.eot = k.eot; st.tok_ld = c->tok_ld;
         st.logprob = k.sample_buf ? c->sm.lp : k.lp_sum ? c->lp.tok : nullptr;
         return st;
@@ -332,23 +335,30 @@ struct Step : StepBase {
     // hand without xgamma and off: it is refused in fp8 mode (f8 false: xgamma nullptr) and with a non-empty prefix (k.pfx false: d_off nullptr).
     NextEmbed next_embed() const {
         NextEmbed ne;
-        ne.tok_emb = m->tok_emb; ne.pos_emb = m->dec_pos; ne.x = c->dx; ne.xslab = c->dxs; ne.stats = c->lnpart;
-        ne.xgamma = f8 ? m->dec[0].ln1_w : nullptr; ne.d = (int)d; ne.mpad = mpad; ne.shift = c->dshift; ne.off = d_off;
+        ne.tok_emb = m->tok_emb; ne.pos_emb = m->dec_pos; ne.x = rm(c->dx, d); ne.xslab = slab(c->dxs); ne.stats = rm(c->lnpart, 2);
+        ne.xgamma = f8 ? m->dec[0].ln1_w : nullptr; ne.d = (int)d; ne.mpad = mpad; ne.shift = rm(c->dshift, 1); ne.off = d_off;
         return ne;
     }
 
     // one decoder layer at the current position: self-attention over the row's cache, with this position's k / v appended
     void layer(int l, bool advance) const {
+        layer_to_query(l);
+        layer_tail(l, advance);
+    }
+    // ... up to and including its cross-attention query: the first segment of a free-running range is layer 0's
+    void layer_to_query(int l) const {
         const long cache_row = (long)D.n_heads * D.n_text_ctx * WH_HEAD_DIM * m->esz;   // bytes per row
         const long cache_l = (long)nb * cache_row;                                      // ... and per layer: the whole batch's, whatever the range
         const long cache_0 = l * cache_l + row0 * cache_row;
-        layer_with(l, advance, [&] {
-            wh_launch_dec_self_attn(s, prec, rm(c->dqkv, 3 * d, prec == WH_PREC_F16X3 ? 4 : m->esz), (char*)c->self_k + cache_0, (char*)c->self_v + cache_0, slab(c->datt), c->pos,
+        layer_head(l, [&] {
+            wh_launch_dec_self_attn(s, prec, rm(c->dqkv, 3 * d, prec == WH_PREC_F16X3 ? 4 : m->esz), (char*)c->self_k + cache_0, (char*)c->self_v + cache_0, slab(c->datt), pos,
                                     (int)d, D.n_heads, D.n_text_ctx, nr, mpad, d_off);   // (a range with row0 > 0 has no prefixes: d_off == nullptr)
         });
     }
 
-    // final LN ∘ tied LM head + masked argmax; the finish kernel records the token, advances the position and embeds the next one
+    // final LN ∘ tied LM head + masked argmax; the finish kernel records the token, advances the position and embeds the next one.  The plain
+    // variant runs on the range's rows with the range's position and ticket (the partials' count is this launch's: two ranges may differ); the
+    // rules', the log-probabilities', the repetition bitmap's and the kept logits' per-row buffers are the whole batch's (row0 == 0)
     void emit() const {
         if (k.beam_k) return emit_beam();
         if (k.sample_buf) return emit_sample();
@@ -379,7 +389,7 @@ struct Step : StepBase {
             if (rules) rf.exempt_from = k.ts_begin;   // timestamps repeat in pairs and the rules own them
             rf.mask_first = c->mask_first; rf.mask_base = c->mask_base;
         }
-        wh_launch_argmax_finish(s, prec, c->part_val, c->part_idx, lm_parts, mpad, c->pos, c->step_ticket, decode_state(), nb, next_embed(), tf, k.lp_sum, rf);
+        wh_launch_argmax_finish(s, prec, c->part_val + row0, c->part_idx + row0, lm_parts, mpad, pos, ticket, decode_state(), nr, next_embed(), tf, k.lp_sum, rf);
     }
 
     // Beam search: the LM head leaves the rows' raw logits of this position in the scratch (its argmax partials are not read);
@@ -488,6 +498,8 @@ static int choose_split(const wh_ctx* c, const wh_ctx::StepKey& key) {
     return r0;
 }
 
+// the events of the free-running halves (below): A / B behind the first segment of a range's position, fork / join around a run of free positions
+enum { FREE_EV_A = 0, FREE_EV_B, FREE_EV_FORK, FREE_EV_JOIN, FREE_EVENTS };
 // the second decode stream and the events of a split step: created outside any capture, at the first call that splits
 static int ensure_split_stream(wh_ctx* c) {
     if (!c->s_split) {
@@ -501,7 +513,57 @@ static int ensure_split_stream(wh_ctx* c) {
         CTX_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         c->split_ev.push_back(e);
     }
+    while (c->free_ev.size() < FREE_EVENTS) {   // the free-running halves' own (never captured)
+        hipEvent_t e = nullptr;
+        CTX_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        c->free_ev.push_back(e);
+    }
     return WH_OK;
+}
+
+// ---- the free-running halves -------------------------------------------------------
+// The rows of a greedy batch are independent across positions too: clip b's position p + 1 needs nothing of another clip's position p.  So the
+// two ranges of a split call need not meet before the LM head: each runs whole positions — layers, LM head, finish — on its own stream, with its
+// own device-side position and ticket (element 1 of c->pos / c->step_ticket: the second range's), and the skew between them survives from one
+// position to the next: one range's LM head, finish and first GEMMs run beside the other's stream over the encoder side.
+// A range's position is two segments, each a single chain (captured: a graph without branches, replayed on the range's stream only):
+//   segment 0: layer 0 up to and including its cross-attention query;   segment 1: the rest of layer 0, the other layers, LM head, finish.
+// Applies where the call splits and its key is the plain one: timestamp rules, log-probabilities, the repetition bitmap and kept logits carry
+// per-row buffers that do not follow a range.  The LM head reads whole row groups past the range's last row (k_lm_head: masked; the tile
+// kernels: clamped to the slab pitch counted from the range's first row), so both ranges' groups must end inside the slab pitch.
+constexpr bool WH_DEC_FREE_DEFAULT = true;    // (where choose_split splits by its rule; WH_DEC_FREE=0 turns it off)
+// rows from a range's first one that its LM head launch may read
+static int lm_head_reach(const Step& r) {
+    const SkinnyArgs a = r.lm_head_masked();
+    if (wh_lm_head_tile_applicable(a)) return (r.nr + 255) / 256 * 256;
+    int reach = 0;   // k_lm_head: groups of 16 * mt rows, mt <= 4 as the launcher chooses it (any of them here)
+    for (int mt = 1; mt <= std::min(4, (r.nr + 15) / 16); mt++) reach = std::max(reach, (r.nr + 16 * mt - 1) / (16 * mt) * (16 * mt));
+    return reach;
+}
+// the two ranges of a free-running call: which = 0: rows [0, split) on the decode stream, position and ticket 0; 1: the rest on the second stream
+static Step free_range(wh_ctx* c, const wh_ctx::StepKey& k, int which) {
+    Step r{c, k};
+    r.es_cus = k.split_cus;
+    if (which == 0) { r.nr = k.split; return r; }
+    r.row0 = k.split; r.nr = k.nb - k.split; r.s = c->s_split;
+    r.pos = c->pos + 1; r.ticket = c->step_ticket + 1;
+    return r;
+}
+static bool choose_free(wh_ctx* c, const wh_ctx::StepKey& key, bool want_logits) {
+    if (!key.split || c->free_mode == 0) return false;
+    if (!(c->dbg_split > 0 ? c->dbg_free != 0 : (c->free_mode == 1 || WH_DEC_FREE_DEFAULT))) return false;
+    if (key.ts_begin >= 0 || key.lp_sum || key.rep || want_logits || key.d_logits) return false;
+    for (int which = 0; which < 2; which++) {
+        const Step r = free_range(c, key, which);
+        if (r.row0 + lm_head_reach(r) > c->mpad) return false;
+    }
+    return true;
+}
+static void launch_free_segment(const Step& r, int seg) {
+    if (seg == 0) return r.layer_to_query(0);
+    r.layer_tail(0, false);
+    for (int l = 1; l < r.D.dec_layers; l++) r.layer(l, false);
+    r.emit();
 }
 
 // The decoder layers of a generated position as two branches: rows [0, split) on the decode stream, the rest on the second one, forked behind
@@ -544,16 +606,14 @@ static void launch_step(wh_ctx* c, const wh_ctx::StepKey& k, const PromptStep* p
     if (probe) t.probe();
 }
 
-// the instantiated graph of launch_step(c, key): kept from the last call if the key is the same, else captured now
-static int ensure_step_graph(wh_ctx* c, const wh_ctx::StepKey& key) {
-    if (c->step_exec && c->step_key == key) return WH_OK;
-    hipStream_t s = c->stream;
-    drop_step_graph(c);   // nothing of it is in flight: every call ends with a stream synchronisation
+// captures what launches() puts on stream s into the step's graph `slot` and instantiates it
+template <typename F>
+static int capture_step_graph(wh_ctx* c, hipStream_t s, int slot, F&& launches) {
     c->capturing = true;  // no event records inside the captured step
     hipGraph_t graph = nullptr;
     hipError_t ce = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
     if (ce == hipSuccess) {
-        launch_step(c, key);
+        launches();
         ce = hipStreamEndCapture(s, &graph);
     }
     c->capturing = false;
@@ -567,8 +627,29 @@ static int ensure_step_graph(wh_ctx* c, const wh_ctx::StepKey& key) {
         hipGraphDestroy(graph);
         return fail(c, WH_ERR_HIP, "hipGraphInstantiate of the decode step failed: %s", hipGetErrorString(ce));
     }
-    c->step_graph = graph;
-    c->step_exec = gexec;
+    c->step_graph[slot] = graph;
+    c->step_exec[slot] = gexec;
+    return WH_OK;
+}
+
+// the instantiated graph of launch_step(c, key): kept from the last call if the key is the same, else captured now.  A free-running key
+// (DESIGN.md §5t): the four segments A1, A2, B1, B2 instead, each a single chain captured on the stream that replays it
+static int ensure_step_graph(wh_ctx* c, const wh_ctx::StepKey& key) {
+    if (c->step_exec[0] && c->step_key == key) return WH_OK;
+    drop_step_graph(c);   // nothing of it is in flight: every call ends with a stream synchronisation
+    int rc = WH_OK;
+    if (key.free) {
+        for (int i = 0; i < 4 && !rc; i++) {
+            const Step r = free_range(c, key, i / 2);
+            rc = capture_step_graph(c, r.s, i, [&] { launch_free_segment(r, i % 2); });
+        }
+    } else {
+        rc = capture_step_graph(c, c->stream, 0, [&] { launch_step(c, key); });
+    }
+    if (rc) {
+        drop_step_graph(c);   // (the segments captured before the one that failed)
+        return rc;
+    }
     c->step_key = key;
     return WH_OK;
 }
@@ -576,8 +657,10 @@ static int ensure_step_graph(wh_ctx* c, const wh_ctx::StepKey& key) {
 // The `remaining` generated positions after the prompt replay ONE captured hipGraph of an emitting step — every kernel reads the
 // position from device memory, so the graph is position-independent.  The host then pays one graph launch per token instead of ~50
 // kernel launches (src/main.rs:793-826 is one ORT Run per token in the reference).
+// A free-running key replays four single-chain graphs per position, two on each stream, ordered by two events; the halves
+// meet only where the host needs the whole batch: the done poll, an event-timed position, sync_every_pos and the end of the loop.
 static int run_token_loop(wh_ctx* c, const wh_ctx::StepKey& key, int remaining, bool poll_eot) {
-    hipStream_t s = c->stream;
+    hipStream_t s = c->stream, s2 = c->s_split;
     // with event timing on: every position is launched eagerly (stride 0/1), or only every stride-th one
     // (sampled live timing) while the others replay the graph
     const int stride = c->prof ? c->prof_stride : 0;
@@ -589,33 +672,78 @@ static int run_token_loop(wh_ctx* c, const wh_ctx::StepKey& key, int remaining, 
     std::vector<int> done_h(key.nb);
     wh_ctx::StepKey one_chain = key;   // event-timed positions run unsplit: their kernel-group brackets describe the one-chain form
     one_chain.split = one_chain.split_cus = 0;
+    one_chain.free = false;
+    const Step ra = free_range(c, key, 0), rb = free_range(c, key, key.free ? 1 : 0);   // (the ranges of a free-running key)
+    hipEvent_t* fe = c->free_ev.data();
+    bool forked = false, have_eb = false;   // forked: the second stream runs its range; have_eb: it has recorded FREE_EV_B since the fork
+    hipError_t he = hipSuccess;
+    auto note = [&](hipError_t e) { if (he == hipSuccess) he = e; };
+    // the halves meet: everything the second stream has been given is ordered before what the decode stream is given next
+    auto join = [&] {
+        if (!forked) return;
+        note(hipEventRecord(fe[FREE_EV_JOIN], s2));
+        note(hipStreamWaitEvent(s, fe[FREE_EV_JOIN], 0));
+        forked = false;
+    };
+    auto fail_loop = [&](const char* what) {
+        hipStreamSynchronize(s);
+        if (forked) hipStreamSynchronize(s2);
+        drop_step_graph(c);
+        return fail(c, WH_ERR_HIP, "%s failed: %s", what, hipGetErrorString(he));
+    };
     for (int r = 0; r < remaining; r++) {
         const bool sampled = c->prof && stride > 1 && (r % stride) == stride / 2;
-        if (use_graph && !sampled) {
-            hipError_t ge = hipGraphLaunch(c->step_exec, s);
-            if (ge != hipSuccess) {
-                hipStreamSynchronize(s);
-                drop_step_graph(c);
-                return fail(c, WH_ERR_HIP, "hipGraphLaunch failed: %s", hipGetErrorString(ge));
+        const bool timed = c->prof && (!use_graph || sampled);   // an event-timed position: eagerly, as the one chain on the whole batch
+        if (key.free && !timed) {
+            // One free-running position.  Issue order (every wait is issued after the record it refers to, in program order; the edges are
+            // ordered by (position, segment) and cannot form a cycle — a wait issued before its record is how this would hang):
+            //   [resume: copy pos[0] -> pos[1] on s, record FORK on s, s2 waits FORK]
+            //   1. s waits B(p-1)   2. A1(p) on s   3. record A on s   4. A2(p) on s
+            //   5. s2 waits A       6. B1(p) on s2  7. record B on s2  8. B2(p) on s2
+            // A: B starts behind A's first query expansion (the stagger of §5s).  B: A is never more than one position ahead.
+            if (!forked) {   // after whole-batch work (the prompt, a timed position, a poll): the second range's position is the batch's again
+                note(hipMemcpyAsync(c->pos + 1, c->pos, 4, hipMemcpyDeviceToDevice, s));
+                note(hipEventRecord(fe[FREE_EV_FORK], s));
+                note(hipStreamWaitEvent(s2, fe[FREE_EV_FORK], 0));
+                forked = true;
+                have_eb = false;
             }
+            if (have_eb && c->free_eb) note(hipStreamWaitEvent(s, fe[FREE_EV_B], 0));
+            if (use_graph) note(hipGraphLaunch(c->step_exec[0], s)); else launch_free_segment(ra, 0);
+            note(hipEventRecord(fe[FREE_EV_A], s));
+            if (use_graph) note(hipGraphLaunch(c->step_exec[1], s)); else launch_free_segment(ra, 1);
+            note(hipStreamWaitEvent(s2, fe[FREE_EV_A], 0));
+            if (use_graph) note(hipGraphLaunch(c->step_exec[2], s2)); else launch_free_segment(rb, 0);
+            note(hipEventRecord(fe[FREE_EV_B], s2));
+            have_eb = true;
+            if (use_graph) note(hipGraphLaunch(c->step_exec[3], s2)); else launch_free_segment(rb, 1);
+            if (he != hipSuccess) return fail_loop("a free-running decode position");
+            c->last_split = key.split;
+            c->last_free = 1;
         } else {
-            launch_step(c, c->prof ? one_chain : key);
+            join();
+            if (use_graph && !sampled) note(hipGraphLaunch(c->step_exec[0], s));
+            else launch_step(c, c->prof ? one_chain : key);
+            if (he != hipSuccess) return fail_loop("hipGraphLaunch");
+            if (!timed) c->last_split = key.split;   // a position ran as two branches
         }
-        if (!(c->prof && (!use_graph || sampled))) c->last_split = key.split;   // a position ran as two branches
         // diagnostic (profiles/README.md, rocprofv3 --pmc at whisper-large-v3 size): bound the number of dispatches in flight
-        if (c->sync_every_pos) hipStreamSynchronize(s);
+        if (c->sync_every_pos) { join(); hipStreamSynchronize(s); }
         // EOT early-out (src/main.rs:781-783, 820-822): poll the done flags every 16 generated tokens
         const int gen = r + 1;
         if ((gen & 15) == 15 && r + 1 < remaining && poll_eot) {
+            join();
             hipError_t e1 = hipMemcpyAsync(done_h.data(), c->done, key.nb * 4, hipMemcpyDeviceToHost, s);
             hipError_t e2 = hipStreamSynchronize(s);
-            if (e1 != hipSuccess || e2 != hipSuccess)
-                return fail(c, WH_ERR_HIP, "decode: polling the done flags failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+            if (e1 != hipSuccess || e2 != hipSuccess || he != hipSuccess)
+                return fail(c, WH_ERR_HIP, "decode: polling the done flags failed: %s", hipGetErrorString(he != hipSuccess ? he : e1 != hipSuccess ? e1 : e2));
             bool all = true;
             for (int b = 0; b < key.nb; b++) all = all && done_h[b];
             if (all) break;
         }
     }
+    join();   // what follows (alignment, the read-back) is the decode stream's
+    if (he != hipSuccess) return fail_loop("joining the free-running halves");
     return WH_OK;
 }
 
@@ -835,7 +963,7 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
     int rc = plan_decode(c, nb, p, logits_out != nullptr, logits_rows, sel, n_sel, pl);
     if (rc) return rc;
     const wh_ctx::StepKey& key = pl.key;
-    c->last_split = 0;   // (run_token_loop sets it to what it launched)
+    c->last_split = c->last_free = 0;   // (run_token_loop sets them to what it launched)
     if (key.split && (rc = ensure_split_stream(c))) return rc;
     // the encoder states come from the encoder stream
     if (c->s_enc != s) CTX_HIP(c, hipStreamWaitEvent(s, c->ev_enc_done, 0));

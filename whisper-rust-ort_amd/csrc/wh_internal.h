@@ -111,6 +111,13 @@ struct wh_ctx {
     std::vector<hipEvent_t> split_ev;
     std::vector<uint32_t> dec_mask;
     int split_mode = -1, split_rows = 0, split_cus = 160, dbg_split = 0, last_split = 0;
+    // The free-running halves: the two ranges of a split call run whole positions, LM head and finish included, each on its own
+    // stream with its own device-side position (pos[1], step_ticket[1]: the second range's), ordered by two events per position (free_ev).
+    // free_mode: WH_DEC_FREE (0 off, 1 on, unset: on wherever choose_split splits by its rule); free_eb: WH_DEC_FREE_EB=0 drops the edge that
+    // keeps the first range at most one position ahead (A/B runs); dbg_free: wh_debug_set_step_free; last_free: the last call's loop ran free
+    std::vector<hipEvent_t> free_ev;
+    int free_mode = -1, dbg_free = 0, last_free = 0;
+    bool free_eb = true;
     // hand-offs between the two streams: encoder states ready (recorded on s_enc), encoder states consumed by the
     // cross-K/V projection (recorded on stream; the next encoder pass may overwrite them)
     hipEvent_t ev_enc_done = nullptr, ev_kv_done = nullptr;
@@ -211,6 +218,8 @@ struct wh_ctx {
     int* part_idx = nullptr;
     int *feed = nullptr, *out_tokens = nullptr, *n_out = nullptr, *done = nullptr, *forced = nullptr, *pos = nullptr;
     int* step_ticket = nullptr;  // zeroed at creation, re-armed by its last arriver
+    // pos and step_ticket are two elements each: everything that runs on the whole batch uses element 0; element 1 is the second row range's
+    // own position and ticket while the halves of the token loop run free
     unsigned *mask_first = nullptr, *mask_base = nullptr;
     DevBuf<float> logits;       // optional parity buffer (grown on demand)
     int* logits_sel = nullptr;  // [B]: slot of a batch row in `logits` or -1 (wh_decode_greedy_rows)
@@ -274,7 +283,8 @@ struct wh_ctx {
         const void* beam_buf = nullptr;        // setter's buffers (logits scratch and search state: one allocation each, freed together)
         const void* sample_buf = nullptr;      // temperature sampling: nullptr = off; the identity of the setter's buffers (the per-row values are read through them)
         int split = 0, split_cus = 0;          // the split token loop: rows of the first range (0 = one chain) and the compute units of a range's cross-attention launch
-        auto members() const { return std::tie(split, split_cus, nb, n_prompt, eot, n_forced, logits_rows, d_logits, d_sel, ts_begin, ts_max_init, lp_sum, pfx, rep, rep_p, rep_n, al_q, al_cap, al_gen, beam_k, beam_c, beam_buf, sample_buf); }
+        bool free = false;                     // ... and its ranges run whole positions on their own streams, four single-chain graphs
+        auto members() const { return std::tie(split, split_cus, free, nb, n_prompt, eot, n_forced, logits_rows, d_logits, d_sel, ts_begin, ts_max_init, lp_sum, pfx, rep, rep_p, rep_n, al_q, al_cap, al_gen, beam_k, beam_c, beam_buf, sample_buf); }
         bool operator==(const StepKey& o) const { return members() == o.members(); }
     } step_key;
     // ---- the decode options: one struct each, laid out alike — `on` and the settings, the device buffers (DevBuf: freed with the context or
@@ -455,8 +465,10 @@ struct wh_ctx {
         void reset_results() { wh_drain_events(ev_attn, nullptr); wh_drain_events(ev_finish, nullptr); }
     } sc;
     void reset_option_results() { sc.reset_results(); ts.reset_results(); lp.reset_results(); lang.reset_results(); pfx.reset_results(); rep.reset_results(); al.reset_results(); bm.reset_results(); sm.reset_results(); }
-    hipGraph_t step_graph = nullptr;
-    hipGraphExec_t step_exec = nullptr;
+    // the captured step: one graph (element 0), or the four single-chain segments of the free-running halves (A1, A2, B1, B2)
+    static constexpr int STEP_GRAPHS = 4;
+    hipGraph_t step_graph[STEP_GRAPHS] = {nullptr, nullptr, nullptr, nullptr};
+    hipGraphExec_t step_exec[STEP_GRAPHS] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 // Linear weights that arrived already quantised (F8_E4M3 + "<name>_scale" in model.safetensors, written by

@@ -36,6 +36,9 @@ struct StepBase {
     // cross-attention launch.  A range with row0 > 0 runs with rpc == 1 (no beam search), in bf16 (esz: the slabs' and the caches' element), without
     // per-clip prefixes and on k_dec_gemm / k_dec_gemm_wide only (choose_split, wh_decode_host.cpp)
     int row0 = 0, nr = nb, es_cus = c->dec_cus;
+    // the device-side position the launches read and the ticket that advances it: the whole batch's (element 0) unless the range runs free
+    // with its own
+    int *pos = c->pos, *ticket = c->step_ticket;
     template <typename T> T* rm(T* p, long ld) const { return p + (long)row0 * ld; }                          // row-major rows of ld elements
     void* rm(void* p, long ld, size_t esz) const { return (char*)p + (long)row0 * ld * (long)esz; }
     void* slab(void* p) const { return (char*)p + (long)row0 * 32 * (long)m->esz; }                           // slab layout [K/32][mpad][32]: row r at r * 32
@@ -70,14 +73,16 @@ struct StepBase {
         if (f8) a.xgamma = next_gamma;
         return a;
     }
-    // final LN ∘ tied LM head: what the emitting step and the no-speech probe share (they differ in the masks and what they record)
+    // final LN ∘ tied LM head: what the emitting step and the no-speech probe share (they differ in the masks and what they record).  On the
+    // range's rows; only the plain emitting step runs on a range with row0 > 0 (choose_free, wh_decode_host.cpp: the other per-row buffers of
+    // the options do not follow the range)
     SkinnyArgs lm_head_common() const {
         SkinnyArgs a;
-        a.W = m->lm_w; a.bias = m->lm_c; a.ln_s = m->lm_s; a.ln_part = c->lnpart; a.ln_tiles = ln_tiles_d;
-        a.M = nb; a.N = D.vocab; a.K = (int)d;
-        a.X = c->dxs; a.x_mpad = mpad;
-        a.pos_p = c->pos; a.n_prompt = k.n_prompt;
-        a.part_val = c->part_val; a.part_idx = c->part_idx;
+        a.W = m->lm_w; a.bias = m->lm_c; a.ln_s = m->lm_s; a.ln_part = rm(c->lnpart, 2); a.ln_tiles = ln_tiles_d;
+        a.M = nr; a.N = D.vocab; a.K = (int)d;
+        a.X = slab(c->dxs); a.x_mpad = mpad;
+        a.pos_p = pos; a.n_prompt = k.n_prompt;
+        a.part_val = c->part_val + row0; a.part_idx = c->part_idx + row0;   // [part][mpad]: the range's first row of every partial
         return a;
     }
     // ... with the call's two suppress masks: the LM head of an emitting step.  scratch: the rows' raw logits of this position go there instead of
@@ -94,9 +99,13 @@ struct StepBase {
     // `advance`: nothing follows the layers at this position (a prompt position without a head), so this fc2 advances the position
     template <typename SelfAttn>
     void layer_with(int l, bool advance, SelfAttn&& self_attn) const {
+        layer_head(l, self_attn);
+        layer_tail(l, advance);
+    }
+    // ... its launches up to and including the cross-attention query (and after_query): what runs before the layer's stream over the encoder side
+    template <typename SelfAttn>
+    void layer_head(int l, SelfAttn&& self_attn) const {
         const DecLayerDev& L = m->dec[l];
-        const long kv_stride = (long)ncl * S * d;  // elements between consecutive [clips][S][d] planes
-        const long kv_clip0 = (long)(clip0 + row0) * S * d; // ... and from the plane's first clip to this launch's first
         {   // LN1 ∘ Q|K|V projection
             Prof pr(c, WH_KG_DEC_GEMM);
             gemm(false, ln_consumer(L.qkv_w, L.qkv_b, L.qkv_sc, L.qkv_s, 3 * d, rm(c->dqkv, 3 * d, prec == WH_PREC_F16X3 ? 4 : m->esz), (l == 0) ? 1 : ln_tiles_d));
@@ -116,8 +125,19 @@ struct StepBase {
                 gemm(true, ln_consumer(L.cq_w, L.cq_b, L.cq_sc, L.cq_s, d, rm(c->dq32, d), ln_tiles_d));
                 // expanded queries qe[h] = W_k,h^T q_h: [nb][H][d] f32
                 wh_launch_dec_qexpand(s, prec, rm(c->dq32, d), L.cqx_w, rm(c->dqe, D.n_heads * d), nr, (int)d, D.n_heads);
-                after_query(l);
             }
+        } else {   // LN2 ∘ cross-attention query
+            Prof pr(c, WH_KG_DEC_GEMM);
+            gemm(false, ln_consumer(L.cq_w, L.cq_b, L.cq_sc, L.cq_s, d, rm(c->dq, d, prec == WH_PREC_F16X3 ? 4 : m->esz), ln_tiles_d));
+        }
+        after_query(l);
+    }
+    // ... and the rest: cross-attention, its out-projection, the feed-forward block
+    void layer_tail(int l, bool advance) const {
+        const DecLayerDev& L = m->dec[l];
+        const long kv_stride = (long)ncl * S * d;  // elements between consecutive [clips][S][d] planes
+        const long kv_clip0 = (long)(clip0 + row0) * S * d; // ... and from the plane's first clip to this launch's first
+        if (c->cross_es) {
             if (k.al_q && c->al.layer[l].n) {   // word-level timestamps: the listed heads' expanded queries of this position
                 Prof pr(c, WH_KG_DEC_OTHER);
                 wh_launch_align_copy(s, false, c->dqe, (long)D.n_heads * d, d, (int)d, c->al.layer[l], c->pos, k.n_prompt - 1, k.al_cap, nb, k.al_q);
@@ -138,11 +158,6 @@ struct StepBase {
                 else gemm(false, a);
             }
         } else {
-            {   // LN2 ∘ cross-attention query
-                Prof pr(c, WH_KG_DEC_GEMM);
-                gemm(false, ln_consumer(L.cq_w, L.cq_b, L.cq_sc, L.cq_s, d, rm(c->dq, d, prec == WH_PREC_F16X3 ? 4 : m->esz), ln_tiles_d));
-                after_query(l);
-            }
             if (k.al_q && c->al.layer[l].n) {   // word-level timestamps: the listed heads' queries of this position
                 Prof pr(c, WH_KG_DEC_OTHER);
                 wh_launch_align_copy(s, m->esz == 2, c->dq, d, WH_HEAD_DIM, WH_HEAD_DIM, c->al.layer[l], c->pos, k.n_prompt - 1, k.al_cap, nb, k.al_q);
@@ -174,7 +189,7 @@ struct StepBase {
         {   // fc2 + residual → x, raw slab, partials for the next layer's LN1 / the final LN
             Prof pr(c, WH_KG_DEC_GEMM);
             SkinnyArgs a = residual_producer(L.fc2_w, L.fc2_b, L.fc2_sc, slab(c->dh), D.ffn, (l + 1 < D.dec_layers) ? m->dec[l + 1].ln1_w : m->dec_ln_w);
-            if (advance) { a.ticket = c->step_ticket; a.pos_w = c->pos; }
+            if (advance) { a.ticket = ticket; a.pos_w = pos; }
             gemm(true, a);
         }
     }
