@@ -1,6 +1,6 @@
 // dec_attn_check.cpp — the decoder's attention kernels, each alone against a double-precision host restatement of its contract, with an FNV-1a hash of
 // every raw output buffer:  k_dec_self_attn (cache append and the per-clip prefix form PFX included), k_dec_cross_attn in all its instantiations,
-// k_dec_cross_attn_cg (wh_decode.hip), k_kv_absmax, k_kv_quant and k_dec_cross_attn8 (wh_fp8.hip).  Built on tools/enc_check.cpp, whose idioms it copies.
+// k_dec_cross_attn_cg (wh_dec_attn.hip), k_kv_absmax, k_kv_quant and k_dec_cross_attn8 (wh_fp8.hip).  Built on tools/enc_check.cpp, whose idioms it copies.
 //
 //   self-attention   one position g = *pos_p.  prec bf16 (bf16 caches, bf16 slab out), f32 (f32 everything), f16x3 (f32 q/k/v and caches, h2 slab out).
 //              qkv [B][3d] (q pre-scaled | k | v), caches [B][H][tc][64].  With adv = off ? min(max(off[b], 0), g) : 0 the row attends over cache rows

@@ -1,4 +1,4 @@
-// dec_gemm_check.cpp — the decode GEMM family (k_dec_gemm, k_dec_gemm_wide: wh_decode.hip; k_dec_tile: wh_dec_tile.hip), each kernel alone
+// dec_gemm_check.cpp — the decode GEMM family (k_dec_gemm, k_dec_gemm_wide: wh_dec_gemm.hip; k_dec_tile: wh_dec_tile.hip), each kernel alone
 // against a double-precision host restatement of the SkinnyArgs contract, with an FNV-1a hash of every raw output.
 //
 //   C = act( LN-fold( sum_k X W ) wscale + bias ) (+ R);  producers also write xslab_out = (C - row_shift) xgamma and the per-16-column

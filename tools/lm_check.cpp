@@ -1,6 +1,6 @@
-// lm_check.cpp — the kernels that turn hidden rows into a token, each alone through the library's own launchers: k_lm_head (wh_decode.hip),
+// lm_check.cpp — the kernels that turn hidden rows into a token, each alone through the library's own launchers: k_lm_head (wh_lm_head.hip),
 // k_lm_head_tile (wh_gemm8.hip), k_lm_head_tile_x3 (wh_gemm8x.hip) with their shared epilogue (wh_lm_tile.h), k_argmax_finish with the fused
-// next-position embedding, k_nospeech_finish, k_lang_head / k_lang_finish and k_dec_embed (wh_decode.hip).  The program links libwhisper_hip.so and calls only launchers declared in wh_kernels.h, steered by wh_dbg_lm_mt,
+// next-position embedding, k_nospeech_finish, k_lang_head / k_lang_finish and k_dec_embed (wh_lm_head.hip).  The program links libwhisper_hip.so and calls only launchers declared in wh_kernels.h, steered by wh_dbg_lm_mt,
 // wh_dbg_lm_blocks_per_cu and WH_LM_TILE_MIN_ROWS (read at every launch decision), so the same source builds against any revision of the library.
 // Data come from the program's own LCG: no model, no Python.
 //
@@ -440,7 +440,7 @@ static Res run_head(const Ops& o, const Var& v, std::vector<float>* keep_logits 
         const int tiles = ((N + 15) / 16 + r.n_parts - 1) / r.n_parts;
         r.L = 4 * tiles + 2; r.A = 4 * tiles + 2;
     }
-    // the row groups lm_row_groups settles on (wh_decode.hip): the request, the rows, then 150 KB of LDS
+    // the row groups lm_row_groups settles on (wh_lm_head.hip): the request, the rows, then 150 KB of LDS
     int eff_mt = std::min(v.mt, (M + 15) / 16);
     { const size_t es = o.mode == BF16 ? 2 : 4; while (eff_mt > 1 && (size_t)eff_mt * 16 * o.K * es + (size_t)eff_mt * 16 * 2 * 4 * 5 > 150 * 1024) eff_mt--; }
     const long pw = (long)r.n_parts * o.mpad;

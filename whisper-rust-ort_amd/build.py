@@ -9,7 +9,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libwhisper_hip.so")
-SOURCES = ["wh_mel.hip", "wh_ingest.hip", "wh_gemm.hip", "wh_gemm8.hip", "wh_gemm8x.hip", "wh_gemm8_mx.hip", "wh_mlp.hip", "wh_attn.hip", "wh_decode.hip", "wh_dec_tile.hip", "wh_cross_es.hip", "wh_cross_es8.hip", "wh_cross_es3.hip", "wh_fp8.hip", "wh_align.hip", "wh_beam.hip", "wh_sample.hip", "wh_score.hip", "wh_model.cpp", "wh_ctx.cpp", "wh_options.cpp", "wh_encode_host.cpp", "wh_decode_host.cpp", "wh_score_host.cpp", "wh_api.cpp"]
+# the slowest first, so that the pool starts them first: wh_lm_head.hip (the 96 k_lm_head instantiations) bounds a clean build
+SOURCES = ["wh_lm_head.hip", "wh_dec_gemm.hip", "wh_mel.hip", "wh_ingest.hip", "wh_gemm.hip", "wh_gemm8.hip", "wh_gemm8x.hip", "wh_gemm8_mx.hip", "wh_mlp.hip", "wh_attn.hip", "wh_dec_attn.hip", "wh_dec_tile.hip", "wh_cross_es.hip", "wh_cross_es8.hip", "wh_cross_es3.hip", "wh_fp8.hip", "wh_align.hip", "wh_beam.hip", "wh_sample.hip", "wh_score.hip", "wh_model.cpp", "wh_ctx.cpp", "wh_options.cpp", "wh_encode_host.cpp", "wh_decode_host.cpp", "wh_score_host.cpp", "wh_api.cpp"]
 HEADERS = ["wh_common.h", "wh_es_common.h", "wh_dec_epilogue.h", "wh_kernels.h", "wh_lm_tile.h", "wh_internal.h", "wh_host_shared.h", "wh_step.h", "wh_ingest_desc.h", "wh_json.h", "../../include/whisper_hip.h"]
 # -amdgpu-mfma-vgpr-form: MFMA accumulators live in VGPRs (gfx950's register file is unified).  With the default
 # heuristic the attention kernel kept its score and output tiles in AGPRs and spent 160 of ~400 VALU instructions
@@ -75,12 +76,12 @@ def build_tools(verbose: bool = False, force: bool = False) -> None:
             if verbose:
                 print(" ".join(cmd), flush=True)
             subprocess.check_call(cmd)
-    # tools/dec_gemm_check (tests/test_hip_parity.py) calls the library's own launchers instead: it links libwhisper_hip.so, so it checks
-    # the kernels of whichever library it is built against; tools/enc_check (tests/test_hip_parity.py, tests/test_enc_check_cpu.py) does the same for
+    # tools/dec_gemm_check (tests/test_hip_parity.py) calls the library's own launchers instead (wh_dec_gemm.hip, wh_dec_tile.hip): it links
+    # libwhisper_hip.so, so it checks the kernels of whichever library it is built against; tools/enc_check (tests/test_hip_parity.py, tests/test_enc_check_cpu.py) does the same for
     # the encoder side: k_gemm8 / k_ln_stats, k_gemm8x, k_gemm, k_enc_attn, k_layernorm; tools/dec_attn_check (tests/test_hip_parity.py,
-    # tests/test_dec_attn_check_cpu.py) for the decoder's attention: k_dec_self_attn, k_dec_cross_attn, k_dec_cross_attn_cg, k_kv_quant, k_dec_cross_attn8;
-    # tools/lm_check (tests/test_hip_parity.py, tests/test_lm_check_cpu.py) for the end of a decode step: k_lm_head, the LM-head tile kernels, k_argmax_finish,
-    # k_nospeech_finish, k_lang_head, k_lang_finish, k_dec_embed
+    # tests/test_dec_attn_check_cpu.py) for the decoder's attention: k_dec_self_attn, k_dec_cross_attn, k_dec_cross_attn_cg (wh_dec_attn.hip), k_kv_quant,
+    # k_dec_cross_attn8 (wh_fp8.hip); tools/lm_check (tests/test_hip_parity.py, tests/test_lm_check_cpu.py) for the end of a decode step: k_lm_head,
+    # k_argmax_finish, k_nospeech_finish, k_lang_head, k_lang_finish, k_dec_embed (wh_lm_head.hip) and the LM-head tile kernels (wh_gemm8.hip, wh_gemm8x.hip)
     for name in ("dec_gemm_check", "enc_check", "dec_attn_check", "lm_check"):
         src, exe = os.path.join(TOOLS, name + ".cpp"), os.path.join(TOOLS, name)
         if force or _stale(exe, [src, OUT, os.path.join(CSRC, "wh_kernels.h")]):

@@ -486,6 +486,12 @@ int wh_fail_hip(hipError_t e, const char* what, const char* file, int line);
 // device that is current when it is called, so a process that opens several devices needs it on each.  A failure is
 // recorded through wh_set_error (the launch that follows then fails and surfaces at the call's hipGetLastError).
 bool wh_ensure_dyn_lds(const void* kernel, size_t bytes);
+// raise a kernel's dynamic-LDS limit once per (device, kernel, size)
+template <typename K>
+void set_max_smem(K kernel, size_t bytes) {
+    if (bytes <= 48 * 1024) return;
+    wh_ensure_dyn_lds((const void*)kernel, bytes);
+}
 void wh_set_error(const char* fmt, ...);
 
 // Runtime choices -> template arguments, for the launchers of kernels with variant flags.

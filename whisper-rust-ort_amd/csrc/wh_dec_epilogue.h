@@ -1,4 +1,4 @@
-// wh_dec_epilogue.h — what the decode GEMM kernels share around their epilogues: k_dec_gemm and k_dec_gemm_wide (wh_decode.hip; bit-identical
+// wh_dec_epilogue.h — what the decode GEMM kernels share around their epilogues: k_dec_gemm and k_dec_gemm_wide (wh_dec_gemm.hip; bit-identical
 // to each other) and k_dec_tile (wh_dec_tile.hip; its own accumulation order).  The contract of all three is
 //
 //   C[m][n] = act( LN-fold( sum_k X[m][k] W[n][k] ) * wscale[n] + bias[n] ) (+ R[m][n])

@@ -1,7 +1,7 @@
 // wh_dec_tile.hip — the decode GEMMs of contexts with a thousand clips and more as LDS-DMA tile GEMMs (gfx950; bf16 and
 // WH_PREC_F16X3 operands).
 //
-//   C[m][n] = act( LN-fold( sum_k X[m][k] W[n][k] ) + bias[n] ) (+ R[m][n])          (the contract of k_dec_gemm, wh_decode.hip)
+//   C[m][n] = act( LN-fold( sum_k X[m][k] W[n][k] ) + bias[n] ) (+ R[m][n])          (the contract of k_dec_gemm, wh_dec_gemm.hip)
 //
 // The with-past loop of greedy_decode_with_past (reference src/main.rs:793-826) runs seven such products per decoder layer and
 // position.  k_dec_gemm / k_dec_gemm_wide stream weights and activations straight from L2 into MFMA fragments: right for tens of

@@ -408,7 +408,7 @@ __global__ __launch_bounds__(512, Geo<BN>::WAVES_PER_SIMD) void k_gemm8(GemmArgs
 
 
 // ---- the LM head at hundreds of rows on the same tile structure ------------------------------------------------------------
-// logits = LN(x) · E^T over the whole vocabulary + masked argmax partials (k_lm_head's contract, wh_decode.hip; reference
+// logits = LN(x) · E^T over the whole vocabulary + masked argmax partials (k_lm_head's contract, wh_lm_head.hip; reference
 // argmax_last_dim_raw, src/main.rs:709-735).  k_lm_head stages a 64-row activation tile per workgroup and streams the 53 MB
 // tied embedding once per 64 rows: 850 MB through L2 per launch at 1024 rows.  Here a workgroup owns a 256 x 256 logit tile
 // (k_gemm8's BN = 256 geometry and LDS-DMA ring; the activation rows come from the decode slab layout [K/32][mpad][32], which

@@ -352,7 +352,7 @@ void wh_launch_dec_cross_attn_es8(hipStream_t s, const float* qe, const void* E,
 void wh_launch_layernorm_es8(hipStream_t s, const float* x, const float* gamma, const float* beta, void* out, long rows, int S, int e_rows);
 
 // dynamic LDS to request for a cross-attention launch of total_wgs workgroups whose kernel needs own_bytes: caps the resident
-// workgroups per CU at two for large launches (wh_decode.hip)
+// workgroups per CU at two for large launches (wh_dec_attn.hip)
 size_t wh_cross_lds_reserve(long total_wgs, size_t own_bytes);
 
 // WH_PREC_FP8 (wh_fp8.hip)
