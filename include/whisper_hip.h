@@ -495,6 +495,38 @@ int wh_score_tokens(wh_ctx* c, const wh_decode_params* p, const wh_score_input* 
                     const int32_t* logit_hyps, size_t n_logit_hyps,   /* parity only: hypotheses whose logits are read back */
                     float* logits_out, size_t cap_logits_rows);       /* [n_logit_hyps][cap_logits_rows][vocab], may be NULL */
 
+/* Forced alignment: the frame at which each token of a GIVEN transcript is spoken, in the one decoder pass of wh_score_tokens (openai-whisper's
+ * find_alignment, stable-ts, subtitle tools; no reference entry corresponds).  p and in mean exactly what they mean for
+ * wh_score_tokens: the resident clips, H = hyps_per_clip, hypothesis b * H + j, the model sequence prompt ++ t, T = P + longest - 1, passes of
+ * floor(max_batch / (H * T)) whole clips.  `heads` is a wh_alignment_opts given per call: the same (layer, head) list and checks as
+ * wh_ctx_set_alignment; its debug_rows are HYPOTHESIS indices.  What wh_ctx_set_alignment holds on the ctx is irrelevant to this entry and
+ * ignored, as wh_ctx_set_logprobs is.  Per hypothesis h with tokens t[0 .. n_h):
+ *   - row i (0 <= i < n_h) is model position P - 1 + i: the position whose logits predict t[i], the row the generating loop calls "the
+ *     position that emitted token i"; frames S_b = min(n_audio_ctx, max(8, (mel frames of the hypothesis's clip + 1) / 2));
+ *   - P[a][i][s] = softmax over s < S_b of q_i . k_s per listed head a;
+ *   - per head and frame the mean and population standard deviation over the hypothesis's own n_h rows, W = (P - mean) / std (0 where
+ *     std == 0), a median filter of width 7 along s with reflect padding, the mean over the heads: M[i][s], all in f32;
+ *   - openai-whisper's dtw on -M in f32 (ties go to the step along the frames), backtraced from (n_h, S_b);
+ *   - frames_out[h][i] = the smallest frame on the path within row i (its time: frame * 0.02 s from the window start); n_h == 1: frame 0,
+ *     nothing is launched for that hypothesis; entries i >= n_h are 0.  n_frames_out[h] (may be NULL) = S_b.
+ * With prompt = sot, lang, task, <|notimestamps|> and t = text ++ [eot] these rows are exactly the rows openai-whisper's find_alignment keeps.
+ * The one difference from find_alignment is the one wh_ctx_set_alignment has: the statistics run over the entry rows only, not over the prompt
+ * rows as well.
+ * logprob_out (may be NULL): what wh_score_tokens returns for the same p and in, bit for bit — it is the same pass.  NULL: the LM head and the
+ * log-probability kernel are not launched and the float [max_batch][vocab] logits scratch is neither needed nor allocated by this call.
+ * wh_get_alignment_debug(k) serves the call's debug hypotheses, shape {n_heads, n_h, S_b}; wh_get_token_frames and the other getters report
+ * WH_ERR_STATE or empty results after this call, as after a scoring call.  The resident encoder states, the self-attention caches, the
+ * captured decode step and every buffer it names are not modified (the call works in buffers of its own, grown on demand): a decode call after
+ * it — with wh_ctx_set_alignment on or off — returns exactly what it returned before it.  wh_get_timings reports the call under decode_s.
+ * Refused before anything is launched, the ctx unchanged: everything wh_score_tokens refuses, with the same codes (except alignment set on the
+ * ctx); WH_ERR_ARG: heads == NULL, every argument error of wh_ctx_set_alignment, a debug hypothesis >= n_hyp, cap_tokens below the longest
+ * hypothesis, frames_out == NULL; WH_ERR_UNSUPPORTED: a WH_PREC_FP8 or WH_PREC_F16X3 model. */
+int wh_align_tokens(wh_ctx* c, const wh_decode_params* p, const wh_score_input* in, const wh_alignment_opts* heads,
+                    int32_t* frames_out,     /* [n_hyp][cap_tokens] */
+                    int32_t* n_frames_out,   /* [n_hyp], may be NULL: S_b of the hypothesis's clip */
+                    float* logprob_out,      /* [n_hyp][cap_tokens], may be NULL */
+                    size_t cap_tokens);
+
 /* ---- fused batch call: the body of transcribe_longform_chunked for ≤ max_batch single-window
  * clips (src/main.rs:870-915 / 946-967) run as one batch on the ctx stream -------------------- */
 typedef struct {

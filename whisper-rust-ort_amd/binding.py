@@ -41,7 +41,7 @@ EXPORTS = ("wh_model_load", "wh_model_create", "wh_model_free", "wh_model_get_di
            "wh_ctx_set_language_detection", "wh_get_languages", "wh_ctx_set_prefixes", "wh_ctx_set_repetition",
            "wh_ctx_set_alignment", "wh_get_token_frames", "wh_get_alignment_debug", "wh_ctx_set_beam_search", "wh_get_beams", "wh_get_beam_trace",
            "wh_ctx_set_sampling", "wh_resampled_samples", "wh_ingest_raw", "wh_transcribe_batch_raw", "wh_transcribe_batch_raw_next",
-           "wh_transcribe_longform_raw", "wh_files_load", "wh_files_load_raw", "wh_transcribe_windows", "wh_files_window_mel", "wh_score_tokens")
+           "wh_transcribe_longform_raw", "wh_files_load", "wh_files_load_raw", "wh_transcribe_windows", "wh_files_window_mel", "wh_score_tokens", "wh_align_tokens")
 
 
 class WhisperHipError(RuntimeError):
@@ -160,6 +160,19 @@ def pack_hypotheses(hyps: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.ndarr
     return pack_prefixes(hyps)
 
 
+def align_pack(hyps: Sequence[Sequence[int]], heads: Sequence[Tuple[int, int]], hyps_per_clip: int = 1, debug_hyps: Sequence[int] = ()):
+    """The arguments of wh_align_tokens: (WhScoreInput, WhAlignmentOpts, the hypotheses' lengths, cap_tokens, the arrays the two structs point into)."""
+    ids, offsets = pack_hypotheses(hyps)
+    lens = [len(h) for h in hyps]
+    cap = max(lens, default=1) or 1
+    inp = WhScoreInput(C.sizeof(WhScoreInput), _i64(ids) if ids.size else None, offsets.ctypes.data_as(C.POINTER(C.c_size_t)), len(hyps), hyps_per_clip)
+    h = np.ascontiguousarray(list(heads), np.int32).reshape(-1, 2) if len(heads) else np.zeros((0, 2), np.int32)
+    d = np.ascontiguousarray(list(debug_hyps), np.int32)
+    i32p = C.POINTER(C.c_int32)
+    opts = WhAlignmentOpts(C.sizeof(WhAlignmentOpts), h.ctypes.data_as(i32p) if h.size else None, h.shape[0], d.ctypes.data_as(i32p) if d.size else None, d.size)
+    return inp, opts, lens, cap, (ids, offsets, h, d)
+
+
 def pack_prefixes(prefixes: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.ndarray]:
     """wh_prefix_opts' two arrays for a list of per-clip prefixes: (ids int64 back to back, offsets uint64 [n + 1])."""
     offsets = np.zeros(len(prefixes) + 1, np.uint64)
@@ -265,6 +278,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     L.wh_transcribe_windows.argtypes = [vp, i32p, i64p, C.c_size_t, C.POINTER(WhDecodeParams), i64p, szp]
     L.wh_files_window_mel.argtypes = [vp, C.c_int32, C.c_int64, f32p]
     L.wh_score_tokens.argtypes = [vp, C.POINTER(WhDecodeParams), C.POINTER(WhScoreInput), f32p, i64p, C.c_size_t, i32p, C.c_size_t, f32p, C.c_size_t]
+    L.wh_align_tokens.argtypes = [vp, C.POINTER(WhDecodeParams), C.POINTER(WhScoreInput), C.POINTER(WhAlignmentOpts), i32p, i32p, f32p, C.c_size_t]
     _lib = L
     return L
 
@@ -626,6 +640,24 @@ class Context:
                                              sel.size, _f32(logits) if sel.size else None, rows))
         return ([lp[g, :n].copy() for g, n in enumerate(lens)], [am[g, :n].copy() for g, n in enumerate(lens)],
                 [logits[j, : lens[int(k)]] for j, k in enumerate(sel)])
+
+    def align_tokens(self, params: DecodeParams, hyps: Sequence[Sequence[int]], heads: Sequence[Tuple[int, int]], hyps_per_clip: int = 1,
+                     debug_hyps: Sequence[int] = (), want_logprobs: bool = False):
+        """wh_align_tokens: the frame at which each token of the given `hyps` is spoken (hypothesis j of resident clip b is
+        hyps[b * hyps_per_clip + j]), from the listed (layer, head) pairs' cross-attention in one decoder pass over all positions.  Returns
+        (frames: one int32 array per hypothesis, 0.02 s apart; n_frames int32 [n_hyp], S_b of each hypothesis's clip; the log-probabilities of
+        score_tokens as a list of float32 arrays, or None without want_logprobs).  debug_hyps (parity harness): hypotheses whose
+        probabilities and alignment matrix are kept for alignment_debug()."""
+        p, keep = params.to_c()
+        inp, opts, lens, cap, keep2 = align_pack(hyps, heads, hyps_per_clip, debug_hyps)
+        fr = np.zeros((max(1, len(hyps)), cap), np.int32)
+        nf = np.zeros(max(1, len(hyps)), np.int32)
+        lp = np.zeros((max(1, len(hyps)), cap), np.float32) if want_logprobs else None
+        i32p = C.POINTER(C.c_int32)
+        self._check(self.lib.wh_align_tokens(self.h, C.byref(p), C.byref(inp), C.byref(opts), fr.ctypes.data_as(i32p), nf.ctypes.data_as(i32p),
+                                             _f32(lp) if want_logprobs else None, cap))
+        return ([fr[g, :n].copy() for g, n in enumerate(lens)], nf[: len(hyps)].copy(),
+                [lp[g, :n].copy() for g, n in enumerate(lens)] if want_logprobs else None)
 
     def _took(self, toks: List[np.ndarray], params: "DecodeParams") -> List[np.ndarray]:
         self._gen_lens = [len(t) - len(params.prompt) for t in toks]   # (what logprobs() cuts its rows to)

@@ -65,9 +65,9 @@ TOOLS = os.path.join(HERE, "..", "tools")
 
 def build_tools(verbose: bool = False, force: bool = False) -> None:
     """Device-side check binaries the GPU tests run (tests/test_fp8_gpu.py, tests/test_hip_parity.py): the MX MFMA layout probe, the MX GEMM /
-    LayerNorm kernels, the one-launch feed-forward block (k_enc_mlp) and the alignment score kernels (tests/test_align_gpu.py) against host restatements.  They include the library's kernel source directly."""
+    LayerNorm kernels, the one-launch feed-forward block (k_enc_mlp) the alignment score kernels (tests/test_align_gpu.py) and the forced pass's query gather (tests/test_forced_align_gpu.py) against host restatements.  They include the library's kernel source directly."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    for name, kernel_src in (("mx_mfma_check", "wh_gemm8_mx.hip"), ("mx_gemm_check", "wh_gemm8_mx.hip"), ("mlp_check", "wh_mlp.hip"), ("es16_check", "wh_cross_es.hip"), ("es8_check", "wh_cross_es8.hip"), ("es3_check", "wh_cross_es3.hip"), ("align_check", "wh_align.hip")):
+    for name, kernel_src in (("mx_mfma_check", "wh_gemm8_mx.hip"), ("mx_gemm_check", "wh_gemm8_mx.hip"), ("mlp_check", "wh_mlp.hip"), ("es16_check", "wh_cross_es.hip"), ("es8_check", "wh_cross_es8.hip"), ("es3_check", "wh_cross_es3.hip"), ("align_check", "wh_align.hip"), ("align_gather_check", "wh_align.hip")):
         src, exe = os.path.join(TOOLS, name + ".hip"), os.path.join(TOOLS, name)
         deps = [src, os.path.join(CSRC, kernel_src), os.path.join(CSRC, "wh_common.h"), os.path.join(CSRC, "wh_es_common.h"), os.path.join(CSRC, "wh_dec_epilogue.h"), os.path.join(CSRC, "wh_kernels.h")]
         if force or _stale(exe, deps):

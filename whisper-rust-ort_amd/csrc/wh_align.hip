@@ -1,5 +1,6 @@
 // wh_align.hip — word-level timestamps (wh_ctx_set_alignment): the per-position copy of the alignment heads' cross-attention
-// queries inside the token loop, and the post-pass of a decode call — scores + row softmax, column normalisation + median filter + head
+// queries inside the token loop (k_align_gather: the same for every position of a forced pass at once, wh_align_tokens), and the
+// post-pass of a decode call — scores + row softmax, column normalisation + median filter + head
 // average, dynamic time warping with its backtrace — for a chunk of clips per launch.
 //
 // Every kernel bounds a row by its own generated-token count n = clamp(n_out[b] - n_prompt, 0, cap), read on the device: rows that finished
@@ -24,6 +25,36 @@ __global__ __launch_bounds__(64) void k_align_copy(const T* __restrict__ src, lo
     const T* s = src + (long)b * row_pitch + (long)h * head_pitch;
     float* d = dst + (((long)a * nb + b) * cap + g) * dk;
     for (int k = threadIdx.x; k < dk; k += 64) d[k] = (float)s[k];
+}
+
+// ---- forced pass (wh_align_tokens): the same copy for all positions of all hypotheses of a pass at once -----------------------
+// grid (rows of the pass, listed heads of the layer).  Row r = g * T + t is entry i = t - (P - 1) of hypothesis g; a row outside 0 <= i < len[g]
+// (an earlier prompt position, the padding of a shorter hypothesis) or at or past `rows` returns before it reads anything.  VEC: every source
+// and destination address is 16-byte aligned (the launcher checks pitches, dk and the bases): a thread moves 16 source bytes per trip.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(64) void k_align_gather(const T* __restrict__ src, long row_pitch, long head_pitch, int dk, AlignLayerHeads hs, int rows, int Tn, int P,
+                                                     int Lmax, const int* __restrict__ len, int G, float* __restrict__ dst) {
+    const int r = blockIdx.x;
+    if (r >= rows) return;
+    const int g = r / Tn, i = r - g * Tn - (P - 1);
+    if (g >= G || i < 0 || i >= min(len[g], Lmax)) return;
+    const int a = hs.slot[blockIdx.y], h = hs.head[blockIdx.y];
+    const T* s = src + (long)r * row_pitch + (long)h * head_pitch;
+    float* d = dst + (((long)a * G + g) * Lmax + i) * dk;
+    if constexpr (VEC) {
+        constexpr int E = 16 / (int)sizeof(T);
+        for (int k = E * threadIdx.x; k < dk; k += E * 64) {
+            if constexpr (sizeof(T) == 2) {
+                const bf16x8 v = *reinterpret_cast<const bf16x8*>(s + k);
+                *reinterpret_cast<f32x4*>(d + k) = f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+                *reinterpret_cast<f32x4*>(d + k + 4) = f32x4{(float)v[4], (float)v[5], (float)v[6], (float)v[7]};
+            } else {
+                *reinterpret_cast<f32x4*>(d + k) = *reinterpret_cast<const f32x4*>(s + k);
+            }
+        }
+    } else {
+        for (int k = threadIdx.x; k < dk; k += 64) d[k] = (float)s[k];
+    }
 }
 
 // the row softmax both score kernels end with: wave `wave` of four normalises rows wave, wave + 4, ... of its workgroup's raw scores in place
@@ -52,7 +83,7 @@ __global__ __launch_bounds__(256) void k_align_scores_bf16(AlignArgs a) {
     if (n <= 1) return;
     const int Sb = a.sb[b];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fl = lane & 15, fg = lane >> 4;
-    const bf16* K = (const bf16*)a.k_base[hd] + (long)b * a.k_clip_pitch;
+    const bf16* K = (const bf16*)a.k_base[hd] + (long)(a.k_clip0 + b / a.k_div) * a.k_clip_pitch;
     const float* Q = a.q + ((long)hd * a.nb + b) * a.cap * DK;
     float* P = a.P + ((long)cl * a.n_heads + hd) * a.cap * a.Sp;
     const int n_st = (Sb + 15) >> 4, n_rt = (n + 15) >> 4;
@@ -98,7 +129,7 @@ __global__ __launch_bounds__(256) void k_align_scores_f32(AlignArgs a) {
     const int n = align_rows(a, b);
     if (n <= 1) return;
     const int Sb = a.sb[b], tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* K = (const float*)a.k_base[hd] + (long)b * a.k_clip_pitch;
+    const float* K = (const float*)a.k_base[hd] + (long)(a.k_clip0 + b / a.k_div) * a.k_clip_pitch;
     const float* Q = a.q + ((long)hd * a.nb + b) * a.cap * DK;
     float* P = a.P + ((long)cl * a.n_heads + hd) * a.cap * a.Sp;
     for (int s0 = 0; s0 < Sb; s0 += 256) {
@@ -269,6 +300,18 @@ void wh_launch_align_copy(hipStream_t s, bool src_bf16, const void* src, long ro
     if (hs.n <= 0) return;
     if (src_bf16) hipLaunchKernelGGL(k_align_copy<bf16>, dim3(nb, hs.n), dim3(64), 0, s, (const bf16*)src, row_pitch, head_pitch, dk, hs, pos_p, first_emit, cap, nb, dst);
     else hipLaunchKernelGGL(k_align_copy<float>, dim3(nb, hs.n), dim3(64), 0, s, (const float*)src, row_pitch, head_pitch, dk, hs, pos_p, first_emit, cap, nb, dst);
+}
+
+void wh_launch_align_gather(hipStream_t s, bool src_bf16, const void* src, long row_pitch, long head_pitch, int dk, const AlignLayerHeads& hs, int rows, int T,
+                            int P, int Lmax, const int* len, int G, float* dst) {
+    if (hs.n <= 0 || rows <= 0) return;
+    const long e = src_bf16 ? 8 : 4;   // elements in 16 source bytes
+    const bool vec = row_pitch % e == 0 && head_pitch % e == 0 && dk % 8 == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0;
+    const dim3 grid(rows, hs.n);
+#define GATHER(TY, V) hipLaunchKernelGGL((k_align_gather<TY, V>), grid, dim3(64), 0, s, (const TY*)src, row_pitch, head_pitch, dk, hs, rows, T, P, Lmax, len, G, dst)
+    if (src_bf16) { if (vec) GATHER(bf16, true); else GATHER(bf16, false); }
+    else { if (vec) GATHER(float, true); else GATHER(float, false); }
+#undef GATHER
 }
 
 bool wh_align_scores_supported(int form, int dk) { return form == WH_ALIGN_ES_BF16 ? dk == 512 : dk == WH_HEAD_DIM; }

@@ -215,6 +215,24 @@ int wh_score_tokens(wh_ctx* c, const wh_decode_params* p, const wh_score_input* 
     return WH_OK;
 }
 
+// forced alignment: the frame of every token of given transcripts over the resident clips, from the same pass (wh_score_host.cpp)
+int wh_align_tokens(wh_ctx* c, const wh_decode_params* p, const wh_score_input* in, const wh_alignment_opts* heads, int32_t* frames_out, int32_t* n_frames_out,
+                    float* logprob_out, size_t cap_tokens) {
+    if (!c) return WH_ERR_ARG;
+    int rc = check_params(c, p);
+    if (rc) return rc;
+    prof_reset(c);
+    const double t0 = now_s();
+    if ((rc = run_align_tokens(c, p, in, heads, frames_out, n_frames_out, logprob_out, cap_tokens))) return rc;
+    float ms = 0;
+    hipEventElapsedTime(&ms, c->ev[5], c->ev[3]);
+    c->timing = wh_timing{};
+    c->timing.decode_s = ms * 1e-3;
+    c->timing.total_s = now_s() - t0;
+    prof_collect(c);
+    return WH_OK;
+}
+
 // Clips resident at `pcm` on the device → tokens.  The encoder pass of this batch runs now unless `prefetched`; if
 // `next_pcm` is given, the NEXT batch's log-mel + encoder are put on the encoder stream as soon as this batch's cross-K/V
 // projection has been enqueued, i.e. they run beside this batch's token loop.

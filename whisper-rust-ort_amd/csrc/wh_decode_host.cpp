@@ -188,7 +188,7 @@ static int prepare_logits(wh_ctx* c, DecodePlan& pl) {
 
 // Word-level timestamps: the side buffer the captured step copies the alignment heads' queries into, [heads][nb][max_new_tokens][dk] f32 — sized
 // by the call, grown on demand; completes the key
-static int align_dk(const wh_ctx* c) { return c->cross_es ? c->m->dims.d_model : WH_HEAD_DIM; }
+int align_dk(const wh_ctx* c) { return c->cross_es ? c->m->dims.d_model : WH_HEAD_DIM; }
 static int prepare_alignment(wh_ctx* c, DecodePlan& pl) {
     if (!c->al.on) return WH_OK;
     if (int rc = grow(c, c->al.q, c->al.heads.size() / 2 * (size_t)pl.key.nb * pl.NEW * align_dk(c) * 4, true, GROW_FREE_FIRST, "the alignment queries")) return rc;
@@ -196,41 +196,36 @@ static int prepare_alignment(wh_ctx* c, DecodePlan& pl) {
     return WH_OK;
 }
 
-// The post-pass of a call with word-level timestamps, on the decode stream after the token loop: scores + softmax, filter, DTW for chunks of
-// clips sized so that the workspace (P, M and the DTW steps of a chunk) stays within WH_ALIGN_WS_BYTES; keeps the debug rows' P and M.
-constexpr size_t WH_ALIGN_WS_BYTES = (size_t)1 << 30;
-static int run_alignment(wh_ctx* c, const DecodePlan& pl) {
-    if (!c->al.on) return WH_OK;
-    hipStream_t s = c->stream;
+// the listed heads' key rows of clip 0 among ncl resident clips (wh_step.h)
+int align_keys(const wh_ctx* c, const std::vector<int>& heads, int ncl, AlignArgs& a) {
     const wh_dims& D = c->m->dims;
-    const int nb = pl.key.nb, NEW = pl.NEW, nh = (int)(c->al.heads.size() / 2), S = D.n_audio_ctx, Sp = (S + 3) / 4 * 4;
-    c->al.dbg.clear();
-    CTX_HIP(c, hipMemsetAsync(c->al.frames, 0, (size_t)nb * D.n_text_ctx * 4, s));
-    if (NEW == 1) return WH_OK;   // one row per clip: frame 0, nothing to launch
+    const int S = D.n_audio_ctx;
+    a.dk = align_dk(c);
+    const long kv_stride = (long)ncl * S * D.d_model;
+    for (size_t i = 0; i < heads.size() / 2; i++) {
+        const int l = heads[2 * i], h = heads[2 * i + 1];
+        a.k_base[i] = c->cross_es ? c->es_E : (const void*)((const char*)c->cross_kv + ((long)(2 * l) * kv_stride + (long)h * WH_HEAD_DIM) * c->m->esz);
+    }
+    a.k_clip_pitch = (long)(c->cross_es ? c->es_rows : S) * D.d_model; a.k_row_pitch = D.d_model;
+    return c->cross_es ? WH_ALIGN_ES_BF16 : c->m->prec == WH_PREC_F32 ? WH_ALIGN_KV_F32 : WH_ALIGN_KV_BF16;
+}
+
+// The post-pass over a.nb rows (wh_step.h): scores + softmax, filter, DTW for chunks of rows sized so that the workspace (P, M and the DTW steps
+// of a chunk) stays within WH_ALIGN_WS_BYTES; keeps the debug rows' P and M.
+constexpr size_t WH_ALIGN_WS_BYTES = (size_t)1 << 30;
+int align_post_pass(wh_ctx* c, AlignArgs a, int form, DevBuf<>& ws, const std::vector<int>& debug, std::vector<wh_ctx::AlignDebug>& dbg) {
+    hipStream_t s = c->stream;
+    const int nb = a.nb, NEW = a.cap, nh = a.n_heads, S = a.S, Sp = a.Sp;
     const size_t b_p = (size_t)nh * NEW * Sp * 4, b_m = (size_t)NEW * Sp * 4, b_t = (size_t)(NEW + 1) * (S + 1), per_clip = b_p + b_m + b_t;
     const int chunk = (int)std::min<size_t>((size_t)nb, std::max<size_t>(1, WH_ALIGN_WS_BYTES / per_clip));
     Carver cv;
     const size_t o_p = cv.take(chunk * b_p), o_m = cv.take(chunk * b_m), o_t = cv.take(chunk * b_t);
-    if (int rc = grow(c, c->al.ws, cv.off, false, GROW_FREE_FIRST, "the alignment workspace")) return rc;   // (only the post-pass reads it: no captured step to drop)
-    AlignArgs a;
-    a.q = c->al.q; a.dk = align_dk(c);
-    const long kv_stride = (long)nb * S * D.d_model;
-    for (int i = 0; i < nh; i++) {
-        const int l = c->al.heads[2 * i], h = c->al.heads[2 * i + 1];
-        a.k_base[i] = c->cross_es ? c->es_E : (const void*)((const char*)c->cross_kv + ((long)(2 * l) * kv_stride + (long)h * WH_HEAD_DIM) * c->m->esz);
-    }
-    a.k_clip_pitch = (long)(c->cross_es ? c->es_rows : S) * D.d_model; a.k_row_pitch = D.d_model;
-    a.n_out = c->n_out; a.n_prompt = pl.key.n_prompt; a.cap = NEW; a.sb = c->al.sb;
-    a.nb = nb; a.n_heads = nh; a.S = S; a.Sp = Sp;
-    a.P = at<float>(c->al.ws, o_p); a.M = at<float>(c->al.ws, o_m); a.trace = at<unsigned char>(c->al.ws, o_t);
-    a.frames = c->al.frames; a.frames_ld = D.n_text_ctx;
-    const int form = c->cross_es ? WH_ALIGN_ES_BF16 : c->m->prec == WH_PREC_F32 ? WH_ALIGN_KV_F32 : WH_ALIGN_KV_BF16;
-    c->al.dbg.resize(c->al.debug.size());
+    if (int rc = grow(c, ws, cv.off, false, GROW_FREE_FIRST, "the alignment workspace")) return rc;   // (only the post-pass reads it: no captured step to drop)
+    a.P = at<float>(ws, o_p); a.M = at<float>(ws, o_m); a.trace = at<unsigned char>(ws, o_t);
     const bool tm = c->al.timing && !c->capturing;
     hipEvent_t te[4] = {nullptr, nullptr, nullptr, nullptr};
     if (tm) for (auto& e : te) CTX_HIP(c, hipEventCreate(&e));
     struct TeGuard { hipEvent_t* te; ~TeGuard() { for (int i = 0; i < 4; i++) if (te[i]) hipEventDestroy(te[i]); } } te_guard{te};
-    c->al.ms[0] = c->al.ms[1] = c->al.ms[2] = 0;
     for (int c0 = 0; c0 < nb; c0 += chunk) {
         const int nc = std::min(chunk, nb - c0);
         a.clip0 = c0;
@@ -246,18 +241,38 @@ static int run_alignment(wh_ctx* c, const DecodePlan& pl) {
             CTX_HIP(c, hipEventSynchronize(te[3]));
             for (int i = 0; i < 3; i++) { float ms = 0; hipEventElapsedTime(&ms, te[i], te[i + 1]); c->al.ms[i] += ms; }
         }
-        for (size_t k = 0; k < c->al.debug.size(); k++) {   // parity harness: the whole slot; read_back cuts it to the row's n_gen and S_b
-            const int r = c->al.debug[k];
+        for (size_t k = 0; k < debug.size(); k++) {   // parity harness: the whole slot; the caller cuts it to the row's own rows and S_b
+            const int r = debug[k];
             if (r < c0 || r >= c0 + nc) continue;
-            wh_ctx::AlignDebug& dbg = c->al.dbg[k];
-            dbg.probs.resize((size_t)nh * NEW * Sp);
-            dbg.matrix.resize((size_t)NEW * Sp);
-            CTX_HIP(c, hipMemcpyAsync(dbg.probs.data(), a.P + (size_t)(r - c0) * nh * NEW * Sp, dbg.probs.size() * 4, hipMemcpyDeviceToHost, s));
-            CTX_HIP(c, hipMemcpyAsync(dbg.matrix.data(), a.M + (size_t)(r - c0) * NEW * Sp, dbg.matrix.size() * 4, hipMemcpyDeviceToHost, s));
+            wh_ctx::AlignDebug& d = dbg[k];
+            d.probs.resize((size_t)nh * NEW * Sp);
+            d.matrix.resize((size_t)NEW * Sp);
+            CTX_HIP(c, hipMemcpyAsync(d.probs.data(), a.P + (size_t)(r - c0) * nh * NEW * Sp, d.probs.size() * 4, hipMemcpyDeviceToHost, s));
+            CTX_HIP(c, hipMemcpyAsync(d.matrix.data(), a.M + (size_t)(r - c0) * NEW * Sp, d.matrix.size() * 4, hipMemcpyDeviceToHost, s));
             CTX_HIP(c, hipStreamSynchronize(s));
         }
     }
     return WH_OK;
+}
+
+// The post-pass of a call with word-level timestamps, on the decode stream after the token loop.
+static int run_alignment(wh_ctx* c, const DecodePlan& pl) {
+    if (!c->al.on) return WH_OK;
+    hipStream_t s = c->stream;
+    const wh_dims& D = c->m->dims;
+    const int nb = pl.key.nb, NEW = pl.NEW, nh = (int)(c->al.heads.size() / 2), S = D.n_audio_ctx, Sp = (S + 3) / 4 * 4;
+    c->al.dbg.clear();
+    CTX_HIP(c, hipMemsetAsync(c->al.frames, 0, (size_t)nb * D.n_text_ctx * 4, s));
+    if (NEW == 1) return WH_OK;   // one row per clip: frame 0, nothing to launch
+    AlignArgs a;
+    a.q = c->al.q;
+    const int form = align_keys(c, c->al.heads, nb, a);
+    a.n_out = c->n_out; a.n_prompt = pl.key.n_prompt; a.cap = NEW; a.sb = c->al.sb;
+    a.nb = nb; a.n_heads = nh; a.S = S; a.Sp = Sp;
+    a.frames = c->al.frames; a.frames_ld = D.n_text_ctx;
+    c->al.dbg.resize(c->al.debug.size());
+    c->al.ms[0] = c->al.ms[1] = c->al.ms[2] = 0;
+    return align_post_pass(c, a, form, c->al.ws, c->al.debug, c->al.dbg);
 }
 
 // cross-attention K/V of every decoder layer, once per clip: present.{i}.encoder.{key,value} of the step-0 decoder run (src/main.rs:771-787).

@@ -123,6 +123,8 @@ int grow(wh_ctx* c, DevBuf<T>& b, size_t bytes, bool step_holds, GrowPolicy poli
 const int64_t* prefix_of(const wh_ctx* c, long first_row, int b, int* len);
 int options_check(wh_ctx* c, const wh_decode_params* p, int n_clips, bool longform, int al_rows = -1);
 bool sample_trivial(const wh_ctx* c);
+int alignment_opts_check(wh_ctx* c, const wh_alignment_opts* o, const char* who);
+void alignment_layers(const wh_dims& D, const wh_alignment_opts* o, std::vector<AlignLayerHeads>& layer);
 
 // ---- wh_encode_host.cpp ----
 int enc_begin(wh_ctx* c);
@@ -141,5 +143,8 @@ int run_decode(wh_ctx* c, int nb, const wh_decode_params* p, int64_t* tokens_out
 // ---- wh_score_host.cpp ----
 int run_score(wh_ctx* c, const wh_decode_params* p, const wh_score_input* in, float* logprob_out, int64_t* argmax_out, size_t cap_tokens,
               const int32_t* logit_hyps, size_t n_logit_hyps, float* logits_out, size_t cap_logits_rows);
+// wh_align_tokens: the same pass with the listed heads' queries gathered, and the alignment post-pass over its hypotheses
+int run_align_tokens(wh_ctx* c, const wh_decode_params* p, const wh_score_input* in, const wh_alignment_opts* heads, int32_t* frames_out, int32_t* n_frames_out,
+                     float* logprob_out, size_t cap_tokens);
 
 }  // namespace wh

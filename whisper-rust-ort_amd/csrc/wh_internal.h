@@ -389,8 +389,19 @@ struct wh_ctx {
         std::vector<AlignDebug> dbg;
         bool timing = false;                    // WH_ALIGN_TIMING=1: events around the three post-pass kernels (tools/align_bench.py)
         double ms[3] = {0, 0, 0};               // scores, filter, DTW of the last call, milliseconds
-        void reset_results() { have = false; rows.clear(); nframes.clear(); dbg.clear(); }
+        bool have_dbg = false;                  // dbg belongs to a wh_align_tokens call: wh_get_alignment_debug serves it, wh_get_token_frames does not
+        void reset_results() { have = have_dbg = false; rows.clear(); nframes.clear(); dbg.clear(); }
     } al;
+    // Forced alignment of given transcripts (wh_align_tokens): no setting, its own buffers only — grown on demand by the calls,
+    // freed with the context.  No captured step holds them, and the call touches none of `al`'s device buffers.
+    struct ForcedAlign {
+        DevBuf<float> q;                        // [n_heads][G][Lmax][dk] f32: the listed heads' queries of a pass's hypotheses (k_align_gather)
+        DevBuf<> ws;                            // post-pass workspace of one chunk of hypotheses
+        DevBuf<int> ints;                       // carved into frames [G][Lmax], sb [G], n_out [G] (P + n_g) of a pass: 3 x max_batch ints
+        std::vector<std::array<hipEvent_t, 2>> ev_gather;   // WH_ALIGN_TIMING=1 (tools/forced_align_bench.py): events around every k_align_gather
+        double ms_gather = 0;
+        void reset_results() { wh_drain_events(ev_gather, nullptr); }
+    } fa;
     std::vector<int> enc_nframes;              // mel frames of each clip whose encoder states are resident (what alignment's S_b derives from)
     // Beam search (wh_ctx_set_beam_search): off unless on.  The logits scratch and the search state are allocated by the setter
     // (not part of the workspace carve) and freed when the option is cleared and with the context; the captured step is dropped before that.
@@ -464,7 +475,7 @@ struct wh_ctx {
         void collect_timing() { ms[0] = ms[1] = 0; wh_drain_events(ev_attn, &ms[0]); wh_drain_events(ev_finish, &ms[1]); }
         void reset_results() { wh_drain_events(ev_attn, nullptr); wh_drain_events(ev_finish, nullptr); }
     } sc;
-    void reset_option_results() { sc.reset_results(); ts.reset_results(); lp.reset_results(); lang.reset_results(); pfx.reset_results(); rep.reset_results(); al.reset_results(); bm.reset_results(); sm.reset_results(); }
+    void reset_option_results() { sc.reset_results(); fa.reset_results(); ts.reset_results(); lp.reset_results(); lang.reset_results(); pfx.reset_results(); rep.reset_results(); al.reset_results(); bm.reset_results(); sm.reset_results(); }
     // the captured step: one graph (element 0), or the four single-chain segments of the free-running halves (A1, A2, B1, B2)
     static constexpr int STEP_GRAPHS = 4;
     hipGraph_t step_graph[STEP_GRAPHS] = {nullptr, nullptr, nullptr, nullptr};

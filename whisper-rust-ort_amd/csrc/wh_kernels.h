@@ -372,12 +372,20 @@ struct AlignLayerHeads {
 // index *pos_p - first_emit (nothing outside 0 .. cap - 1)
 void wh_launch_align_copy(hipStream_t s, bool src_bf16, const void* src, long row_pitch, long head_pitch, int dk, const AlignLayerHeads& hs, const int* pos_p,
                           int first_emit, int cap, int nb, float* dst);
-// the post-pass over the clips clip0 .. clip0 + n_clips - 1 of a batch of nb (workspace slots 0 .. n_clips - 1)
+// the forced pass's copy (wh_align_tokens): the pass runs hypothesis g's T positions as the rows g * T .. g * T + T - 1; row
+// g * T + t, head h at src + row * row_pitch + h * head_pitch (dk values, bf16 or f32) -> dst [slot][G][Lmax][dk] f32 at index i = t - (P - 1),
+// only for 0 <= i < len[g].  One launch per layer over the `rows` = G * T rows, grid (row, listed head of the layer); nothing is read or
+// written for a prompt row before P - 1, a padded row of a shorter hypothesis, or a row >= rows.
+void wh_launch_align_gather(hipStream_t s, bool src_bf16, const void* src, long row_pitch, long head_pitch, int dk, const AlignLayerHeads& hs, int rows, int T,
+                            int P, int Lmax, const int* len, int G, float* dst);
+// the post-pass over the rows clip0 .. clip0 + n_clips - 1 of a batch of nb (workspace slots 0 .. n_clips - 1).  A row is a clip of a decode
+// call, or a hypothesis of a forced pass: its keys are those of clip k_clip0 + row / k_div (the identity for a decode call)
 constexpr int WH_ALIGN_KV_F32 = 0, WH_ALIGN_KV_BF16 = 1, WH_ALIGN_ES_BF16 = 2;
 struct AlignArgs {
-    const float* q = nullptr;        // [n_heads][nb][cap][dk] f32 (the token loop's copy)
+    const float* q = nullptr;        // [n_heads][nb][cap][dk] f32 (the token loop's copy, or the forced pass's gather)
     const void* k_base[WH_MAX_ALIGN_HEADS] = {nullptr};   // per listed head: its key rows of clip 0 (K plane + 64 h, or the encoder states)
     long k_clip_pitch = 0, k_row_pitch = 0;                // elements from clip to clip and from frame to frame
+    int k_div = 1, k_clip0 = 0;                            // key clip of row b = k_clip0 + b / k_div
     int dk = 0;
     const int* n_out = nullptr;      // [nb] tokens of each row, prompt included (DecodeState::n_out)
     int n_prompt = 0, cap = 0;       // rows of clip b: clamp(n_out[b] - n_prompt, 0, cap)

@@ -111,6 +111,32 @@ int options_check(wh_ctx* c, const wh_decode_params* p, int n_clips, bool longfo
         return rc;
     return WH_OK;
 }
+// the argument errors of a wh_alignment_opts, for the setter and for wh_align_tokens (`who`, for the message): WH_ERR_ARG, nothing changed
+int alignment_opts_check(wh_ctx* c, const wh_alignment_opts* o, const char* who) {
+    if (o->struct_size != sizeof(wh_alignment_opts)) return fail(c, WH_ERR_ARG, "%s: struct_size %zu, expected %zu", who, o->struct_size, sizeof(wh_alignment_opts));
+    const wh_dims& D = c->m->dims;
+    if (o->n_heads < 1 || o->n_heads > WH_MAX_ALIGN_HEADS || !o->heads) return fail(c, WH_ERR_ARG, "%s: n_heads %zu outside 1..%d (or a NULL list)", who, o->n_heads, WH_MAX_ALIGN_HEADS);
+    if (o->n_debug_rows > WH_MAX_ALIGN_DEBUG_ROWS || (o->n_debug_rows && !o->debug_rows)) return fail(c, WH_ERR_ARG, "%s: more than %d debug rows (or a NULL list)", who, WH_MAX_ALIGN_DEBUG_ROWS);
+    for (size_t i = 0; i < o->n_heads; i++) {
+        const int l = o->heads[2 * i], h = o->heads[2 * i + 1];
+        if (l < 0 || l >= D.dec_layers || h < 0 || h >= D.n_heads) return fail(c, WH_ERR_ARG, "%s: (layer %d, head %d) outside the model (%d layers, %d heads)", who, l, h, D.dec_layers, D.n_heads);
+        for (size_t j = 0; j < i; j++)
+            if (o->heads[2 * j] == l && o->heads[2 * j + 1] == h) return fail(c, WH_ERR_ARG, "%s: (layer %d, head %d) listed twice", who, l, h);
+    }
+    for (size_t i = 0; i < o->n_debug_rows; i++)
+        if (o->debug_rows[i] < 0) return fail(c, WH_ERR_ARG, "%s: negative debug row", who);
+    return WH_OK;
+}
+// the listed heads of each decoder layer, with their slots in the caller's list
+void alignment_layers(const wh_dims& D, const wh_alignment_opts* o, std::vector<AlignLayerHeads>& layer) {
+    layer.assign(D.dec_layers, AlignLayerHeads());
+    for (size_t i = 0; i < o->n_heads; i++) {
+        AlignLayerHeads& lh = layer[o->heads[2 * i]];
+        lh.slot[lh.n] = (unsigned char)i;
+        lh.head[lh.n] = (unsigned char)o->heads[2 * i + 1];
+        lh.n++;
+    }
+}
 // every temperature 0 and every row active: the plain kernels are launched
 bool sample_trivial(const wh_ctx* c) {
     for (size_t i = 0; i < c->sm.temp.size(); i++)
@@ -296,18 +322,8 @@ int wh_ctx_set_alignment(wh_ctx* c, const wh_alignment_opts* o) {
         c->al.on = false;
         return WH_OK;
     }
-    if (o->struct_size != sizeof(wh_alignment_opts)) return fail(c, WH_ERR_ARG, "wh_ctx_set_alignment: struct_size %zu, expected %zu", o->struct_size, sizeof(wh_alignment_opts));
+    if (int rc = alignment_opts_check(c, o, "wh_ctx_set_alignment")) return rc;
     const wh_dims& D = c->m->dims;
-    if (o->n_heads < 1 || o->n_heads > WH_MAX_ALIGN_HEADS || !o->heads) return fail(c, WH_ERR_ARG, "wh_ctx_set_alignment: n_heads %zu outside 1..%d (or a NULL list)", o->n_heads, WH_MAX_ALIGN_HEADS);
-    if (o->n_debug_rows > WH_MAX_ALIGN_DEBUG_ROWS || (o->n_debug_rows && !o->debug_rows)) return fail(c, WH_ERR_ARG, "wh_ctx_set_alignment: more than %d debug rows (or a NULL list)", WH_MAX_ALIGN_DEBUG_ROWS);
-    for (size_t i = 0; i < o->n_heads; i++) {
-        const int l = o->heads[2 * i], h = o->heads[2 * i + 1];
-        if (l < 0 || l >= D.dec_layers || h < 0 || h >= D.n_heads) return fail(c, WH_ERR_ARG, "wh_ctx_set_alignment: (layer %d, head %d) outside the model (%d layers, %d heads)", l, h, D.dec_layers, D.n_heads);
-        for (size_t j = 0; j < i; j++)
-            if (o->heads[2 * j] == l && o->heads[2 * j + 1] == h) return fail(c, WH_ERR_ARG, "wh_ctx_set_alignment: (layer %d, head %d) listed twice", l, h);
-    }
-    for (size_t i = 0; i < o->n_debug_rows; i++)
-        if (o->debug_rows[i] < 0) return fail(c, WH_ERR_ARG, "wh_ctx_set_alignment: negative debug row");
     if (!c->al.frames) {
         DevBuf<int> fr, sb;
         if (!setter_alloc(c, "wh_ctx_set_alignment", (size_t)c->max_batch * D.n_text_ctx * 4, fr) || !setter_alloc(c, "wh_ctx_set_alignment", (size_t)c->max_batch * 4, sb)) return WH_ERR_NOMEM;
@@ -315,13 +331,7 @@ int wh_ctx_set_alignment(wh_ctx* c, const wh_alignment_opts* o) {
     }
     c->al.heads.assign(o->heads, o->heads + 2 * o->n_heads);
     c->al.debug.assign(o->debug_rows, o->debug_rows + o->n_debug_rows);
-    c->al.layer.assign(D.dec_layers, AlignLayerHeads());
-    for (size_t i = 0; i < o->n_heads; i++) {
-        AlignLayerHeads& lh = c->al.layer[o->heads[2 * i]];
-        lh.slot[lh.n] = (unsigned char)i;
-        lh.head[lh.n] = (unsigned char)o->heads[2 * i + 1];
-        lh.n++;
-    }
+    alignment_layers(D, o, c->al.layer);
     c->al.gen++;
     c->al.on = true;
     return WH_OK;
@@ -478,7 +488,7 @@ int wh_get_token_frames(const wh_ctx* c, int32_t* frames, size_t cap_tokens, int
 
 int wh_get_alignment_debug(const wh_ctx* c, size_t k, float* probs, float* matrix, size_t cap_floats, int32_t* shape3) {
     if (!c) return WH_ERR_ARG;
-    if (!c->al.have || c->al.dbg.empty()) return WH_ERR_STATE;
+    if (!(c->al.have || c->al.have_dbg) || c->al.dbg.empty()) return WH_ERR_STATE;
     if (k >= c->al.dbg.size()) return WH_ERR_ARG;
     const wh_ctx::AlignDebug& d = c->al.dbg[k];
     if (shape3) { shape3[0] = d.n_heads; shape3[1] = d.n_gen; shape3[2] = d.sb; }

@@ -10,6 +10,15 @@ namespace wh {
 void pack_mask(const int64_t* a, size_t na, const int64_t* b, size_t nb, int vocab, std::vector<unsigned>& out);
 // the cross-attention operands of the nb resident clips: K / V of every decoder layer, or the encoder states' final LayerNorm
 int project_cross_kv(wh_ctx* c, int nb, const std::function<int()>& after_kv);
+// The alignment post-pass that a decode call (rows = clips) and a forced pass (rows = hypotheses) share.
+// align_keys: the listed heads' key rows among ncl resident clips, the key pitches and dk into `a`; returns the score kernels' form.
+// align_post_pass: scores + softmax, filter, DTW over a.nb rows, in chunks sized so that the workspace `ws` (P, M and the DTW steps of a chunk,
+// grown on demand) stays within 1 GiB; the caller has set everything in `a` but P, M, trace and clip0, and has zeroed a.frames.  debug[k] (a
+// row, or < 0: not in these rows) keeps that row's whole P and M slots in dbg[k]; the three kernels' times are added to c->al.ms under
+// WH_ALIGN_TIMING.
+int align_dk(const wh_ctx* c);
+int align_keys(const wh_ctx* c, const std::vector<int>& heads, int ncl, AlignArgs& a);
+int align_post_pass(wh_ctx* c, AlignArgs a, int form, DevBuf<>& ws, const std::vector<int>& debug, std::vector<wh_ctx::AlignDebug>& dbg);
 
 // LayerNorm never runs as a kernel in the decoder: the kernel that produces a residual-stream row also emits its raw copy in the
 // compute dtype (c->dxs, slab layout) and per-column-tile partial sums (c->lnpart); the GEMM that consumes LN(x) has γ folded into
@@ -45,7 +54,13 @@ struct StepBase {
     // the staggering of two branches (null in one chain): q_rec is recorded behind layer 0's cross-attention query — what the other branch's
     // first launch waits for, so that one branch's cross-attention stream runs beside the other's GEMM chain
     hipEvent_t q_rec = nullptr;
-    void after_query(int l) const { if (q_rec && l == 0) hipEventRecord(q_rec, s); }
+    // the forced-alignment pass (wh_score_host.cpp) takes the layer's query here; empty in a token-loop step, which launches
+    // what it launched without it
+    std::function<void(int)> query_hook;
+    void after_query(int l) const {
+        if (q_rec && l == 0) hipEventRecord(q_rec, s);
+        if (query_hook) query_hook(l);
+    }
 
     StepBase(wh_ctx* ctx, const wh_ctx::StepKey& key) : c(ctx), k(key), rpc(key.beam_k ? key.beam_k : 1), ncl(key.nb / rpc), clip0(0) {}
     StepBase(wh_ctx* ctx, const wh_ctx::StepKey& key, int rows_per_clip, int clips, int first_clip) : c(ctx), k(key), rpc(rows_per_clip), ncl(clips), clip0(first_clip) {}

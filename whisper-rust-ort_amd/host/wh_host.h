@@ -170,6 +170,7 @@ struct RowOut {
     double temperature = 0, compression_ratio = 0;
     bool has_prompt = false;  // --prompt-ids / --prompt-ids-dir: the length of the file's text context (<|startofprev|> included; 0: none)
     long long prompt_tokens = 0;
+    bool aligned = false;     // --align-ids-dir: the row's text is the given transcript, aligned; avg_logprob (above) is the transcript's own
     std::string windows;      // --sequential: JSON array of the file's windows {seek_s, frames, advance_s, skipped, temperature, tokens}; empty: no key
 };
 
@@ -244,6 +245,7 @@ inline std::string per_file_json(const std::vector<RowOut>& rows) {  // :1232 to
         if (rows[i].has_lang) { JVal v; v.raw = fmt_conf(rows[i].language_probability); r.set("language", JVal::str(rows[i].language)).set("language_probability", v); }
         if (rows[i].has_prompt) r.set("prompt_tokens", JVal::integer(rows[i].prompt_tokens));
         if (rows[i].has_conf) { JVal v; v.raw = fmt_conf(rows[i].avg_logprob); r.set("avg_logprob", v); v.raw = fmt_conf(rows[i].no_speech_prob); r.set("no_speech_prob", v); }
+        if (rows[i].aligned) { JVal v; v.raw = fmt_conf(rows[i].avg_logprob); r.set("avg_logprob", v).set("aligned", JVal::boolean(true)); }
         if (rows[i].has_ladder) { JVal v; v.raw = fmt_f32((float)rows[i].temperature); r.set("temperature", v); v.raw = fmt_conf(rows[i].compression_ratio); r.set("compression_ratio", v); }
         if (!rows[i].windows.empty()) { JVal w; w.raw = rows[i].windows; r.set("windows", w); }
         if (!rows[i].segments.empty()) { JVal sg; sg.raw = rows[i].segments; r.set("segments", sg); }

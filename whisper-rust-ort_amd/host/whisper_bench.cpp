@@ -61,6 +61,8 @@ struct Args {
     // additive: word-level timestamps (wh_ctx_set_alignment): words and token times in the per-file JSON; the alignment heads as "l:h,l:h,..."
     bool word_timestamps = false;
     std::string alignment_heads;
+    std::string align_ids_dir;   // --align-ids-dir: forced alignment of given transcripts (wh_align_tokens) instead of a decode
+    bool align() const { return !align_ids_dir.empty(); }
     // additive: beam search (wh_ctx_set_beam_search).  --beam-size 1 is the greedy path with the option not set
     int beam_size = 1, n_best = 1;
     float patience = 1.0f, length_penalty = -1.0f;
@@ -188,6 +190,9 @@ static bool parse_args(int argc, char** argv, Args& a) {
                    "  --word-timestamps        words [{word, start, end}] and token_times in every row of the per-file JSON (cross-attention alignment + DTW);\n"
                    "                           a one-window file's words concatenate to its text, a longer file's are its windows' words one after the other\n"
                    "                           (the overlap of two windows is not removed from them as it is from the stitched text)\n"
+                   "  --align-ids-dir DIR      forced alignment: DIR/<audio stem>.txt holds the token ids of the file's transcript (as --prompt-ids-dir's files);\n"
+                   "                           every batch is encoded and then aligned instead of decoded (wh_align_tokens): text = the given ids decoded, words,\n"
+                   "                           token_times, avg_logprob of the given ids and aligned: true in every row; one-window files only; heads as --word-timestamps\n"
                    "  --alignment-heads L      its heads as \"layer:head,layer:head,...\" (default: alignment_heads of the model directory's generation_config.json,\n"
                    "                           else every head of the upper half of the decoder layers, the topmost layers first, 32 heads at most)\n");
             exit(0);
@@ -239,6 +244,7 @@ static bool parse_args(int argc, char** argv, Args& a) {
             else if (k == "--prompt-ids") a.prompt_ids = v;
             else if (k == "--alignment-heads") a.alignment_heads = v;
             else if (k == "--prompt-ids-dir") a.prompt_ids_dir = v;
+            else if (k == "--align-ids-dir") a.align_ids_dir = v;
             else if (k == "--repetition-penalty") {   // what wh_ctx_set_repetition refuses is refused here, before any device is touched
                 char* end = nullptr;
                 a.rep_penalty = strtof(v.c_str(), &end);
@@ -292,6 +298,12 @@ static bool parse_args(int argc, char** argv, Args& a) {
     } else if (a.n_best > 1) {
         fprintf(stderr, "error: --n-best %d needs --beam-size 2 or more\n", a.n_best);
         return false;
+    }
+    if (a.align()) {   // forced alignment takes the transcript as given: nothing that chooses tokens, no per-row text context, no long-form walk
+        const char* clash = a.sequential ? "--sequential" : a.beam() ? "--beam-size" : a.ladder() ? "--temperature" : a.prompts() ? "--prompt-ids / --prompt-ids-dir"
+                            : a.language == "auto" ? "--language auto" : a.precision == "fp8" || a.precision == "f16x3" ? "--precision fp8 / f16x3"
+                            : a.timestamp_rules ? "--timestamp-rules" : a.have_rep_penalty || a.have_rep_ngram ? "--repetition-penalty / --no-repeat-ngram-size" : nullptr;
+        if (clash) { fprintf(stderr, "error: --align-ids-dir cannot be combined with %s\n", clash); return false; }
     }
     if (a.sequential) {
         if (a.language == "auto") {
@@ -752,7 +764,13 @@ int main(int argc, char** argv) {
             }
             for (int st = 0; st < a.streams_per_gpu; st++) {
                 wh_ctx* c = nullptr;
-                if (int rc = wh_ctx_create(m, a.max_batch, &c))
+                int rows = a.max_batch;
+                if (a.align()) {   // a pass holds whole files of prompt + transcript - 1 rows each: room for one of any length at least
+                    wh_dims dims{};
+                    wh_model_get_dims(m, &dims);
+                    rows = std::max(rows, dims.n_text_ctx);
+                }
+                if (int rc = wh_ctx_create(m, rows, &c))
                     throw std::runtime_error(std::string("wh_ctx_create: ") + std::to_string(rc) + ": " + wh_last_error(nullptr));
                 if (a.timestamp_rules) {   // Whisper's timestamp rules on every context (no reference counterpart)
                     WhisperSpecial sp = special_tokens(a.language, a.task, &tok);
@@ -837,6 +855,27 @@ int main(int argc, char** argv) {
             }
         }
 
+        // forced alignment: each file's transcript ids
+        std::vector<std::vector<int64_t>> file_align(files.size());
+        std::vector<int32_t> align_heads;
+        if (a.align()) {
+            wh_dims dims{};
+            wh_model_get_dims(models[0], &dims);
+            align_heads = alignment_heads(a, gen, dims);
+            for (size_t i = 0; i < files.size(); i++) {
+                const std::string path = a.align_ids_dir + "/" + files[i].substr(0, files[i].rfind('.')) + ".txt";
+                FILE* f = is_file(path) ? fopen(path.c_str(), "rb") : nullptr;
+                if (!f) throw std::runtime_error("--align-ids-dir: no transcript ids for " + files[i] + ": cannot read " + path);
+                std::string txt; char b[4096]; size_t n;
+                while ((n = fread(b, 1, sizeof b, f)) > 0) txt.append(b, n);
+                fclose(f);
+                file_align[i] = parse_ids(txt, path);
+                if (file_align[i].empty()) throw std::runtime_error("--align-ids-dir: " + path + " holds no id");
+                for (int64_t t : file_align[i])
+                    if (t >= dims.vocab) throw std::runtime_error("id " + std::to_string(t) + " of " + path + " is outside the vocabulary (" + std::to_string(dims.vocab) + ")");
+            }
+        }
+
         auto load = [&](size_t idx, std::vector<float>& audio, double& dur) {
             if (a.synthetic_clips) { audio = synthetic_clip(a.seed + idx); dur = (double)audio.size() / 16000.0; }
             else load_audio_16k_mono(a.audio_dir + "/" + files[idx], audio, &dur);
@@ -865,7 +904,8 @@ int main(int argc, char** argv) {
                         },
                         [](float* p) { (void)hipHostFree(p); });
         struct Result { std::string text; double dur = 0, load_s = 0; Timing t; bool ok = false; std::vector<Cue> cues; Conf conf; Lang lang; WordOut words; std::string hyps;
-                        bool has_ladder = false; double temperature = 0, compression_ratio = 0; std::string windows; };
+                        bool has_ladder = false; double temperature = 0, compression_ratio = 0; std::string windows;
+                        bool aligned = false; double aligned_avg_lp = 0; };
         const size_t nfiles = files.size();
         std::vector<Result> results(nfiles);
         const unsigned hc = std::thread::hardware_concurrency();
@@ -1044,6 +1084,10 @@ int main(int argc, char** argv) {
                 busy_s[wi] += now_s() - tb0;
                 return;
             }
+            if (a.align())
+                for (const PipeItem& it : batch)
+                    if (it.n() > (size_t)WH_CLIP_SAMPLES)
+                        throw std::runtime_error("--align-ids-dir: " + files[it.idx] + " is longer than one 30 s window; forced alignment is built for one-window files");
             if (batch.size() == 1 && batch[0].n() > (size_t)WH_CLIP_SAMPLES) {
                 // a file longer than one window goes alone through the long-form entry (which batches its windows)
                 Result& r = results[batch[0].idx];
@@ -1087,7 +1131,35 @@ int main(int argc, char** argv) {
                 std::vector<float> lps, nss;
                 std::vector<int> rung_of;
                 std::vector<WindowScore> scores;
-                if (!a.ladder()) {
+                std::vector<int32_t> frames;
+                size_t row_cap = a.max_new_tokens;   // entries per file of lps and frames
+                if (a.align()) {
+                    // the batch is encoded as usual (one position decoded: the entry that leaves the encoder states resident), then aligned: the
+                    // given ids take the place of the generated ones below
+                    p.max_new_tokens = 1;
+                    int rc = raw ? wh_transcribe_batch_raw_next(ctx, rclips.data(), rclips.size(), rnext.empty() ? nullptr : rnext.data(), rnext.size(), &p, toks.data(), ntok.data())
+                                 : wh_transcribe_batch_next(ctx, clips.data(), clips.size(), nclips.empty() ? nullptr : nclips.data(), nclips.size(), &p, toks.data(), ntok.data());
+                    if (rc) throw std::runtime_error(std::string("libwhisper_hip error ") + std::to_string(rc) + ": " + wh_last_error(ctx));
+                    wh_get_timings(ctx, &wt);
+                    std::vector<int64_t> ids;
+                    std::vector<size_t> offs(1, 0);
+                    row_cap = 1;
+                    for (size_t k = 0; k < batch.size(); k++) {
+                        const std::vector<int64_t>& t = file_align[batch[k].idx];
+                        ids.insert(ids.end(), t.begin(), t.end());
+                        offs.push_back(ids.size());
+                        row_cap = std::max(row_cap, t.size());
+                    }
+                    wh_score_input in{sizeof(wh_score_input), ids.data(), offs.data(), batch.size(), 1};
+                    wh_alignment_opts ao{sizeof(wh_alignment_opts), align_heads.data(), align_heads.size() / 2, nullptr, 0};
+                    frames.assign(batch.size() * row_cap, 0);
+                    lps.assign(batch.size() * row_cap, 0.0f);
+                    if ((rc = wh_align_tokens(ctx, &p, &in, &ao, frames.data(), nullptr, lps.data(), row_cap)))
+                        throw std::runtime_error(std::string("wh_align_tokens: ") + std::to_string(rc) + ": " + wh_last_error(ctx));
+                    wh_timing wa{};
+                    wh_get_timings(ctx, &wa);
+                    wt.decode_s += wa.decode_s;
+                } else if (!a.ladder()) {
                     // the next batch of this worker, if it is loaded already, is copied to the device beside this batch's work
                     int rc = raw ? wh_transcribe_batch_raw_next(ctx, rclips.data(), rclips.size(), rnext.empty() ? nullptr : rnext.data(), rnext.size(), &p, toks.data(), ntok.data())
                                  : wh_transcribe_batch_next(ctx, clips.data(), clips.size(), nclips.empty() ? nullptr : nclips.data(), nclips.size(), &p, toks.data(), ntok.data());
@@ -1144,8 +1216,7 @@ int main(int argc, char** argv) {
                 const double batch_s = now_s() - t0;
                 std::vector<Lang> langs;
                 if (lang_auto) langs = fetch_languages(ctx, batch.size(), lang_table);
-                std::vector<int32_t> frames;
-                if (a.word_timestamps) fetch_frames(ctx, batch.size(), a.max_new_tokens, frames);
+                if (a.word_timestamps && !a.align()) fetch_frames(ctx, batch.size(), a.max_new_tokens, frames);
                 if (a.beam()) {   // the n best hypotheses of every file of the batch
                     const std::vector<std::string> hy = fetch_hypotheses(ctx, batch.size(), a, sp, &tok, false);
                     for (size_t k = 0; k < batch.size(); k++) results[batch[k].idx].hyps = "[" + hy[k] + "]";
@@ -1155,12 +1226,16 @@ int main(int argc, char** argv) {
                     if (lang_auto) r.lang = langs[k];
                     const double td0 = now_s();
                     std::vector<int64_t> g;
-                    if (ntok[k] > prompt.size()) g.assign(toks.begin() + k * stride + prompt.size(), toks.begin() + k * stride + ntok[k]);
+                    if (a.align()) {
+                        g = file_align[batch[k].idx];
+                        r.aligned = true;
+                        r.aligned_avg_lp = avg_logprob(std::vector<float>(lps.begin() + k * row_cap, lps.begin() + k * row_cap + g.size()), g, sp.eot);
+                    } else if (ntok[k] > prompt.size()) g.assign(toks.begin() + k * stride + prompt.size(), toks.begin() + k * stride + ntok[k]);
                     double avg_lp = 0;
-                    const bool skip = a.logprobs && window_conf(a, g, lps.data() + k * a.max_new_tokens, nss[k], sp.eot, r.conf, avg_lp);
+                    const bool skip = !a.align() && a.logprobs && window_conf(a, g, lps.data() + k * a.max_new_tokens, nss[k], sp.eot, r.conf, avg_lp);
                     if (skip) g.clear();   // the silence rule: empty text, no segments
-                    if (a.word_timestamps) {
-                        window_words(a, g, frames.data() + k * a.max_new_tokens, sp, batch[k].dur, 0.0, &tok, r.words);
+                    if (a.word_timestamps || a.align()) {
+                        window_words(a, g, frames.data() + k * row_cap, sp, batch[k].dur, 0.0, &tok, r.words);
                         // a one-window file's text is trimmed: so are the ends of its words, which then concatenate to the text
                         if (!r.words.words.empty()) {
                             r.words.words.front().word = ltrim(r.words.words.front().word);
@@ -1210,7 +1285,8 @@ int main(int argc, char** argv) {
             const double end_to_end = r.load_s + r.t.end_to_end_s;   // :1190
             rows.push_back(make_row(files[i], r.dur, end_to_end, r.text));
             if (a.timestamp_rules) rows.back().segments = cues_json(r.cues);
-            if (a.word_timestamps) { rows.back().words = words_json(r.words.words); rows.back().token_times = times_json(r.words.token_times); }
+            if (a.word_timestamps || a.align()) { rows.back().words = words_json(r.words.words); rows.back().token_times = times_json(r.words.token_times); }
+            if (r.aligned) { rows.back().aligned = true; rows.back().avg_logprob = r.aligned_avg_lp; }
             if (!r.hyps.empty()) rows.back().hypotheses = r.hyps;
             if (a.sequential) rows.back().windows = r.windows;
             if (a.prompts()) { rows.back().has_prompt = true; rows.back().prompt_tokens = (long long)file_prefix[i].size(); }
